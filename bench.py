@@ -20,7 +20,20 @@ Multi-GPU (one process per GPU, RCCL counter all-reduce per step, no payload exc
   --scaling strong  ONE archive; the row cursor is split into per-rank ranges balanced by bytes
                     (znippy_amd.sharding.split_rows = decompress.rs:L104,L136 split over ranks)
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+A plain run sets up, warms up and times the headline read leg only, and prints the result line (metric, value, unit,
+higher_is_better, dtype, ms_per_step and the configuration).  --full adds everything else: the oracle parity checks of
+the write side, the decoded-bytes check of every read leg before timing, the own-archive and real-text read legs, the
+write leg, table-build and single-shot times, per-kernel times, the roofline and the CPU baseline.
+
+--dump-outputs DIR writes what the headline leg's last timed step returned to rank 0 (float32 / float64 .npy):
+  counters.npy              the run's counters, COUNTER_KEYS order
+  row_status.npy            per-row status (0 = verified)                    \\ all rows, or DUMP_ROWS of them drawn
+  row_digests.npy           per-row BLAKE3 digest of the decoded bytes       / with np.random.default_rng(0), sorted
+  decoded_bytes_sample.npy  decoded bytes at DUMP_BYTES positions: all of them, or sorted
+                            np.random.default_rng(1).integers(0, bytes_per_gpu, DUMP_BYTES)
+The inputs are generated from fixed seeds, so two builds run with the same arguments can be compared file for file.
+
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
@@ -38,6 +51,12 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 COUNTER_KEYS = ("total_chunks", "total_written_bytes", "verified_bytes", "corrupt_bytes", "corrupt_rows", "decode_errors")
+DUMP_ROWS = 1 << 17   # --dump-outputs: at most 64 MB in all (digests 16 MiB + status 0.5 MiB + bytes 16 MiB)
+DUMP_BYTES = 1 << 22
+# A plain run's headline leg starts straight out of the CPU-bound set-up, where a few warm-up steps leave the timed ones
+# ~9 % slow (--full times it after the other legs).  So its warm-up steps go on until this many seconds have passed; with
+# several ranks it stays W steps, because every rank must run the same number of steps.
+WARMUP_MIN_S = 0.25
 
 
 def measured_traffic(kernel, workload):
@@ -54,7 +73,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=3,
+                    help="untimed steps before the timed ones (a plain one-process run goes on until WARMUP_MIN_S has passed)")
     ap.add_argument("--workload", default="c2")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--archive", choices=("libzstd19", "own"), default=None,
@@ -64,7 +84,13 @@ def main():
     ap.add_argument("--headline-only", action="store_true",
                     help="run only the headline read leg and the write leg (a profiler's per-kernel averages then "
                          "describe the headline leg alone: the other read legs launch the same kernels)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline leg: parity checks, the other read legs, the write leg, table-build and "
+                         "single-shot times, per-kernel times, roofline, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline leg's last timed step's results to DIR/<name>.npy")
     args = ap.parse_args()
+    full = args.full
 
     import torch
     import torch.distributed as dist
@@ -114,38 +140,41 @@ def main():
     d_src, base = wl["d_src"], wl["base"]
     rel = (src_off - np.uint64(base)).astype(np.uint64)  # offsets into d_src (meaningful for this rank's rows)
 
-    # ---- write side: this rank's Rounds over the resident staging buffer ----
-    t0 = time.perf_counter()
-    rounds = hip.RoundTable(ctx, rel[r0:r1], lens[r0:r1], None if skip is None else skip[r0:r1])
-    round_table_ms = (time.perf_counter() - t0) * 1e3  # the context's first table: includes its device-memory pools
-    # warm = what a context that has built and released a table of this shape before pays (its pools hold the buffers: the
-    # host pipelines build and drop one table per hand-off); best of three
-    round_table_warm_ms = None
-    for _ in range(4):
+    # ---- write side: this rank's Rounds over the resident staging buffer (a plain run needs it only to make the
+    # archive of an "own" headline leg) ----
+    archives = {}
+    if full or archive_kind == "own":
         t0 = time.perf_counter()
-        _rt2 = hip.RoundTable(ctx, rel[r0:r1], lens[r0:r1], None if skip is None else skip[r0:r1])
-        dt_ = (time.perf_counter() - t0) * 1e3
-        _rt2.close()
-        if _ > 0:
-            round_table_warm_ms = dt_ if round_table_warm_ms is None else min(round_table_warm_ms, dt_)
-    d_blob = torch.zeros(rounds.blob_bound() + 64, dtype=torch.uint8, device="cuda")
-    enc = rounds.encode_hash(d_src, d_blob)
-    enc = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in enc.items()}
-    # parity spot checks against the oracle: digests and frames of a few rounds
-    for i in sorted({0, my_rows // 2, my_rows - 1}):
-        g = r0 + i
-        src_i = d_src[int(rel[g]):int(rel[g] + lens[g])].cpu().numpy()
-        assert enc["checksum"][i].tobytes() == O.blake3(src_i), "GPU write-side digest != oracle"
-        f = d_blob[int(enc["blob_offset"][i]):int(enc["blob_offset"][i] + enc["blob_size"][i])].cpu().numpy()
-        if enc["compressed"][i]:
-            assert O.zstd_decompress(f.tobytes()) == src_i.tobytes(), "GPU frame does not decode on the oracle"
-        else:
-            assert f.tobytes() == src_i.tobytes()
+        rounds = hip.RoundTable(ctx, rel[r0:r1], lens[r0:r1], None if skip is None else skip[r0:r1])
+        round_table_ms = (time.perf_counter() - t0) * 1e3  # the context's first table: includes its device-memory pools
+        # warm = what a context that has built and released a table of this shape before pays (its pools hold the buffers:
+        # the host pipelines build and drop one table per hand-off); best of three
+        round_table_warm_ms = None
+        for _ in range(4 if full else 0):
+            t0 = time.perf_counter()
+            _rt2 = hip.RoundTable(ctx, rel[r0:r1], lens[r0:r1], None if skip is None else skip[r0:r1])
+            dt_ = (time.perf_counter() - t0) * 1e3
+            _rt2.close()
+            if _ > 0:
+                round_table_warm_ms = dt_ if round_table_warm_ms is None else min(round_table_warm_ms, dt_)
+        d_blob = torch.zeros(rounds.blob_bound() + 64, dtype=torch.uint8, device="cuda")
+        enc = rounds.encode_hash(d_src, d_blob)
+        enc = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in enc.items()}
+        # parity spot checks against the oracle: digests and frames of a few rounds
+        for i in sorted({0, my_rows // 2, my_rows - 1}) if full else ():
+            g = r0 + i
+            src_i = d_src[int(rel[g]):int(rel[g] + lens[g])].cpu().numpy()
+            assert enc["checksum"][i].tobytes() == O.blake3(src_i), "GPU write-side digest != oracle"
+            f = d_blob[int(enc["blob_offset"][i]):int(enc["blob_offset"][i] + enc["blob_size"][i])].cpu().numpy()
+            if enc["compressed"][i]:
+                assert O.zstd_decompress(f.tobytes()) == src_i.tobytes(), "GPU frame does not decode on the oracle"
+            else:
+                assert f.tobytes() == src_i.tobytes()
 
-    # ---- the archives the read legs decode ----
-    own = dict(d_blobs=d_blob, bo=enc["blob_offset"], bs=enc["blob_size"], comp=enc["compressed"], ck=enc["checksum"],
-               label="gpu-encoded (this build's zstd frames)")
-    archives = {"own": own}
+        # ---- the archives the read legs decode ----
+        own = dict(d_blobs=d_blob, bo=enc["blob_offset"], bs=enc["blob_size"], comp=enc["compressed"], ck=enc["checksum"],
+                   label="gpu-encoded (this build's zstd frames)")
+        archives["own"] = own
     if archive_kind == "libzstd19":
         sz = int(lens[0])
         chunk = gen.text(sz)
@@ -211,7 +240,7 @@ def main():
         first = (time.perf_counter() - t0) * 1e3
         bm = np.packbits(a["comp"].astype(bool), bitorder="little")
         warm = None  # further tables of the same archive, each released before the next: the pools hold the buffers; best of three
-        for k in range(4):
+        for k in range(4 if full else 0):
             t0 = time.perf_counter()
             rt2 = hip.RowTable(ctx, a["bo"], a["bs"], my_lens, out_off, bm, a["ck"])
             dt_ = (time.perf_counter() - t0) * 1e3
@@ -286,10 +315,12 @@ def main():
     # (tools/ab_ktime.sh) — around every kernel otherwise (the dominant kernel of c3/c4store/c5 is not a decode_verify_* one)
     timed_level = 1 if args.workload in ("c2", "c2small") else 2
 
-    def timed(leg, steps, warmup):
+    def timed(leg, steps, warmup, after=None):
         ctx.set_kernel_timing(timed_level)
-        for _ in range(warmup):
+        t0, k = time.perf_counter(), 0
+        while k < warmup or (not full and world == 1 and time.perf_counter() - t0 < WARMUP_MIN_S):
             leg.step()
+            k += 1
         leg.drain()
         barrier()
         t0 = time.perf_counter()
@@ -298,11 +329,13 @@ def main():
         leg.drain()
         barrier()
         dt = time.perf_counter() - t0
+        if after is not None:  # before any further step overwrites what the last timed step returned
+            after(leg)
         # per-kernel durations (HIP events the library records around each launch on its own streams): read back in
         # a few extra, untimed steps so that the event queries are not part of the timed region
         ktimes = {}
         ctx.set_kernel_timing(2)
-        for _ in range(min(steps, 10)):
+        for _ in range(min(steps, 10) if full else 0):
             leg.step()
             leg.drain()
             for name, ms in ctx.kernel_times():
@@ -312,12 +345,29 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item()), {k: float(np.mean(v)) for k, v in ktimes.items()}
 
+    def dump_outputs(leg):
+        """--dump-outputs: the results the headline leg's last timed step handed this rank (see the module docstring)."""
+        if args.dump_outputs is None or rank != 0:
+            return
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        _c, _corrupt, status = leg.rows.results()
+        rows = np.arange(my_rows) if my_rows <= DUMP_ROWS else np.sort(
+            np.random.default_rng(0).choice(my_rows, DUMP_ROWS, replace=False))
+        pos = np.arange(my_bytes) if my_bytes <= DUMP_BYTES else np.sort(
+            np.random.default_rng(1).integers(0, my_bytes, DUMP_BYTES))
+        sample = d_out[torch.from_numpy(pos.astype(np.int64)).to(d_out.device)].cpu().numpy()
+        for name, a in (("counters", np.array([leg.last[k] for k in COUNTER_KEYS], np.float64)),
+                        ("row_status", status[rows].astype(np.float32)),
+                        ("row_digests", leg.rows.digests()[rows].astype(np.float32)),
+                        ("decoded_bytes_sample", sample.astype(np.float32))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+
     # ---- read side (the headline) ----
-    if args.headline_only:
+    if args.headline_only or not full:
         args.no_text_leg = True
         archives = {archive_kind: archives[archive_kind]}
     legs = {k: ReadLeg(a) for k, a in archives.items()}
-    for k, leg in legs.items():  # correctness of each archive's decode before anything is timed
+    for k, leg in legs.items() if full else ():  # correctness of each archive's decode before anything is timed
         d_out.zero_()
         leg.step()
         leg.drain()
@@ -344,10 +394,10 @@ def main():
     # ~4 % slow with W = 3 (the two archives decode at the same speed when their runs are interleaved in one process,
     # tools/ab_frames.py: 0.475 vs 0.480 ms) — the sustained rate is the one that describes the path.
     dt_own, k_own = timed(legs["own"], args.steps, args.warmup) if archive_kind != "own" and "own" in legs else (None, None)
-    dt_read, k_read = timed(head, args.steps, args.warmup)
+    dt_read, k_read = timed(head, args.steps, args.warmup, after=dump_outputs)
     if dt_own is None:
         dt_own, k_own = dt_read, k_read
-    dt_write, k_write = timed(WriteLeg(), args.steps, args.warmup)
+    dt_write, k_write = timed(WriteLeg(), args.steps, args.warmup) if full else (None, None)
     dt_text, k_text = timed(legs["text"], args.steps, args.warmup) if text is not None else (None, None)
     # single shot (an archive is decoded once): table construction + ONE run + its results, blobs resident, index columns
     # in host memory as the reader leaves them; best of three
@@ -378,8 +428,8 @@ def main():
             best = dt_ if best is None else min(best, dt_)
         return best
     ctx.set_kernel_timing(timed_level)  # as in the timed steps (the kernel-time collection above brackets every kernel)
-    ss_read = None if args.headline_only else single_shot_read(archives[archive_kind])
-    ss_write = single_shot_write()
+    ss_read = None if args.headline_only or not full else single_shot_read(archives[archive_kind])
+    ss_write = single_shot_write() if full else None
     for k, leg in legs.items():  # every step of every read leg (warmup, timed, kernel-time collection) verified every byte
         assert leg.bad_steps == 0, f"{leg.bad_steps} steps of the {k} read leg did not verify"
 
@@ -437,7 +487,7 @@ def main():
             except Exception as e:  # the hook is diagnostic: never fail the bench over it
                 roofline["valu"] = dict(error=str(e))
         cpu = None
-        if not args.no_cpu_baseline and world == 1:
+        if full and not args.no_cpu_baseline and world == 1:
             cpu = cpu_read_loop(A, my_rows, out_off, my_lens, my_bytes)
         text_leg = None
         if text is not None:
@@ -465,22 +515,25 @@ def main():
                        "bytes_per_gpu": my_bytes, "blob_bytes_per_gpu": blob_bytes, "archive": A["label"],
                        "parallelism": f"row-cursor ranges x{world}",
                        "pipelining": "step k+1 queued before step k's counters are read (two runs in flight)"},
-            "read_own_archive": {"archive": own["label"], "MBps": round(mbps(dt_own), 1),
-                                 "ms_per_step": round(dt_own / args.steps * 1e3, 4),
-                                 "blob_bytes_per_gpu": int(own["bs"].sum()),
-                                 "kernel_ms": {k: round(v, 4) for k, v in k_own.items()}},
-            "compress_level": int(ctx.level),  # CONFIG.compression_level = 19 unless ZNIPPY_LEVEL says otherwise: the higher effort tier
-            "compress_MBps": round(mbps(dt_write), 1),
-            "compress_ms_per_step": round(dt_write / args.steps * 1e3, 4),
-            "compress_kernel_ms": {k: round(v, 4) for k, v in k_write.items()},
-            "table_build_ms": {"row_table": round(head.table_ms[1], 3), "round_table": round(round_table_warm_ms, 3),
-                               "row_table_first": round(head.table_ms[0], 3), "round_table_first": round(round_table_ms, 3),
-                               "note": "host passes + H2D of the index columns / Rounds (the encoder plan is built on the device), outside the timed steps; best of three with the context's pools warm (a table of this shape was built and released before); *_first = the context's first table (its memory pools are created)"},
-            "single_shot_ms": {"read": None if ss_read is None else round(ss_read, 3), "write": round(ss_write, 3),
-                               "note": "table construction + one run + its results (synchronous), blobs / staging buffer resident, index columns / Rounds in host memory; best of three"},
-            "read_text_archive": text_leg,
-            "roofline": roofline, "cpu_baseline": cpu,
         }
+        if full:
+            line.update({
+                "read_own_archive": {"archive": own["label"], "MBps": round(mbps(dt_own), 1),
+                                     "ms_per_step": round(dt_own / args.steps * 1e3, 4),
+                                     "blob_bytes_per_gpu": int(own["bs"].sum()),
+                                     "kernel_ms": {k: round(v, 4) for k, v in k_own.items()}},
+                "compress_level": int(ctx.level),  # CONFIG.compression_level = 19 unless ZNIPPY_LEVEL says otherwise: the higher effort tier
+                "compress_MBps": round(mbps(dt_write), 1),
+                "compress_ms_per_step": round(dt_write / args.steps * 1e3, 4),
+                "compress_kernel_ms": {k: round(v, 4) for k, v in k_write.items()},
+                "table_build_ms": {"row_table": round(head.table_ms[1], 3), "round_table": round(round_table_warm_ms, 3),
+                                   "row_table_first": round(head.table_ms[0], 3), "round_table_first": round(round_table_ms, 3),
+                                   "note": "host passes + H2D of the index columns / Rounds (the encoder plan is built on the device), outside the timed steps; best of three with the context's pools warm (a table of this shape was built and released before); *_first = the context's first table (its memory pools are created)"},
+                "single_shot_ms": {"read": None if ss_read is None else round(ss_read, 3), "write": round(ss_write, 3),
+                                   "note": "table construction + one run + its results (synchronous), blobs / staging buffer resident, index columns / Rounds in host memory; best of three"},
+                "read_text_archive": text_leg,
+                "roofline": roofline, "cpu_baseline": cpu,
+            })
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

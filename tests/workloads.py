@@ -186,4 +186,18 @@ def image_corpus(kind, cap, whole_files=True):
                     return out
             if tot >= cap:
                 return out
+    if not whole_files:  # an image without enough such files: seeded stand-ins make up the rest, so callers still get cap bytes
+        k = 0
+        while tot < cap:
+            n = int(min(cap - tot, 1 << 20))
+            if kind == "text":
+                b = gen.pseudo_text(n, seed=100 + k)
+            else:  # object-file-like: runs of zeros, small integers, word soup and random bytes
+                rng = np.random.default_rng(100 + k)
+                parts = [bytes(4096), gen.binary(16384), gen.pseudo_text(16384, seed=200 + k),
+                         rng.integers(0, 256, size=32768, dtype=np.uint8).tobytes()]
+                b = (b"".join(parts) * (n // 69632 + 1))[:n]
+            out.append(b)
+            tot += n
+            k += 1
     return out

@@ -1,17 +1,18 @@
 # Run on the GPU box (gpurun): FETCH_SIZE / WRITE_SIZE passes of bench.py for one workload; per-kernel means.
 # Usage: bash tools/pmc_workload.sh WORKLOAD TAG
 R=${GRAFT_REPO_ROOT:-/root/repo}
+OUT=${OUT:-$R/tool_out}; mkdir -p $OUT
 WL=${1:-c2store}
 TAG=${2:-x}
 cd /tmp && export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $R/gpurun_out/pmcw_${TAG}_$c -- python3 $R/bench.py --workload $WL --steps 4 --warmup 1 --no-cpu-baseline > $R/gpurun_out/pmcw_${TAG}_$c.log 2>&1
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d $OUT/pmcw_${TAG}_$c -- python3 $R/bench.py --workload $WL --steps 4 --warmup 1 --full --no-cpu-baseline > $OUT/pmcw_${TAG}_$c.log 2>&1
 done
 python3 - <<PY
 import csv, glob, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for c in ("FETCH_SIZE", "WRITE_SIZE"):
-    for f in glob.glob("$R/gpurun_out/pmcw_${TAG}_%s/**/*counter_collection.csv" % c, recursive=True):
+    for f in glob.glob("$OUT/pmcw_${TAG}_%s/**/*counter_collection.csv" % c, recursive=True):
         for r in csv.DictReader(open(f)):
             k = r["Kernel_Name"].split("(")[0].replace("void ", "")
             if "zn::" in k: acc[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
