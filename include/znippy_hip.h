@@ -130,8 +130,13 @@ int znippy_rows_set_blob_cap(znippy_rows *rows, uint64_t blob_cap);
  * znippy_rows_results_lagged, znippy_rows_digests — the synchronous call ends in one): a table whose previous run needed
  * nothing behind its main kernel is run without the kernels that stand behind it, and a run that turns out to have needed
  * them after all (the blobs changed) is repeated in full, with the arguments it was given, inside the first results call
- * that looks at it.  d_blobs / d_out of a queued run must therefore stay valid until its results have been read
- * (ZNIPPY_NO_LEAN=1 in the environment of znippy_ctx_create: every run is a full one). */
+ * that looks at it.  A repeat is invisible in the run sequence: znippy_rows_results_lagged still returns each queued run's
+ * own counters, once its d_out is complete.  When the repeated run is not the latest one, the latest run is repeated in
+ * full after it, so that a flagged run queued behind it is complete as well and the table's status column, corrupt list
+ * and digests (znippy_rows_results, znippy_rows_digests) again describe the latest run.  d_blobs / d_out of a queued run
+ * must therefore stay valid until its results have been read, and those of the latest run until the run before it has
+ * been read as well (ZNIPPY_NO_LEAN=1 in the environment of znippy_ctx_create: every run is a full one).  A failed
+ * queueing call that had already queued work leaves the table with no readable run. */
 int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs,
                               uint64_t blob_base, void *d_out, uint64_t out_cap,
                               znippy_verify_counters *counters, uint64_t *corrupt_rows,

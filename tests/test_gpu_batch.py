@@ -10,40 +10,9 @@ import pytest
 
 import gen
 import workloads
-from test_gpu_foreign import _py_corpus, _mixed
+from gpu_cases import decode_table as _decode, frame_table as _table, fuzz_run, mixed as _mixed, py_corpus as _py_corpus
 
 pytestmark = pytest.mark.gpu
-
-
-def _table(oracle, entries, frames):
-    bs = np.array([len(f) for f in frames], np.uint64)
-    bo = np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64)
-    us = np.array([len(e) for e in entries], np.uint64)
-    oo = np.concatenate([[0], np.cumsum(us)[:-1]]).astype(np.uint64)
-    dig = {}
-    for e in entries:
-        if e not in dig:
-            dig[e] = np.frombuffer(oracle.blake3(e), dtype=np.uint8)
-    ck = np.stack([dig[e] for e in entries])
-    blobs = np.frombuffer(b"".join(frames) + bytes(64), dtype=np.uint8)
-    return dict(blobs=blobs, bo=bo, bs=bs, us=us, oo=oo, ck=ck)
-
-
-def _decode(ctx, A, reps=2):
-    import torch
-    from znippy_amd import hip
-    d_blobs = torch.from_numpy(A["blobs"].copy()).cuda()
-    total = int(A["us"].sum())
-    d_out = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
-    rt = hip.RowTable(ctx, A["bo"], A["bs"], A["us"], A["oo"], None, A["ck"])
-    outs = []
-    for _ in range(reps):  # work lists are filled in a different order every run: every run must agree
-        d_out.zero_()
-        c, corrupt, status = rt.decode_verify(d_blobs, d_out)
-        outs.append((dict(c), status.copy(), d_out[:total].cpu().numpy().copy()))
-    for o in outs[1:]:
-        assert o[0] == outs[0][0] and (o[1] == outs[0][1]).all() and (o[2] == outs[0][2]).all()
-    return outs[0] + (rt.foreign_stats(), dict(ctx.kernel_times()))
 
 
 @pytest.mark.parametrize("level", [1, 3, 19])
@@ -120,7 +89,6 @@ def test_damaged_small_frames_agree_with_oracle(gpu_ctx, oracle):
     """Small text frames damaged anywhere (bit flips, random bytes, truncation, bursts, swaps), hundreds of rows in one
     table so that they share the batch kernels' waves with intact frames: the oracle's verdict is the GPU's, accepted
     mutants decode to the oracle's bytes, nothing is reported verified with different bytes, intact rows are untouched."""
-    from test_gpu_fuzz import _run as fuzz_run
     data = _py_corpus(1 << 20)
     bases = [(data[i * 9000:i * 9000 + 10240], (19, 3, 1)[i % 3]) for i in range(12)]
     fuzz_run(gpu_ctx, oracle, bases, 40, 2024, 10, 100)

@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 
 import gen
+from gpu_cases import (build_archive, check_random_archive_run, mixed_archive_entries, oracle_rows, random_archive,
+                       run_gpu)
 
 pytestmark = pytest.mark.gpu
 
@@ -47,55 +49,12 @@ def test_shim_vs_libzstd_frames(gpu_ctx, oracle, gname, n, level):
     assert gpu_ctx.decompress(frame) == data
 
 
-def _build_archive(oracle, entries, level=19, skip=None):
-    """entries: list of bytes; returns dict of index columns + blob region (oracle write loop)."""
-    src = np.frombuffer(b"".join(entries) + b"\0" * 16, dtype=np.uint8)
-    lens = np.array([len(e) for e in entries], dtype=np.uint64)
-    offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
-    skip = np.zeros(len(entries), dtype=np.uint8) if skip is None else np.asarray(skip, dtype=np.uint8)
-    r = oracle.compress_rounds(src, offs, lens, skip, level=level, n_threads=1)
-    r["usize"] = lens
-    r["out_off"] = offs
-    r["src"] = src
-    return r
-
-
-def _run_gpu(gpu_ctx, arch, pad_blobs=0):
-    import torch
-    from znippy_amd import hip
-    blobs = np.concatenate([np.zeros(pad_blobs, np.uint8), arch["blobs"], np.zeros(32, np.uint8)])
-    d_blobs = torch.from_numpy(blobs).cuda()
-    total = int(arch["usize"].sum())
-    d_out = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
-    bitmap = np.packbits(arch["compressed"].astype(bool), bitorder="little")
-    rt = hip.RowTable(gpu_ctx, arch["blob_offset"] + np.uint64(pad_blobs), arch["blob_size"], arch["usize"],
-                      arch["out_off"], bitmap, arch["checksum"])
-    counters, corrupt, status = rt.decode_verify(d_blobs, d_out)
-    return counters, corrupt, status, d_out.cpu().numpy()[:total], rt
-
-
 def test_rows_mixed_archive_matches_oracle_loop(gpu_ctx, oracle):
     """Mixed archive: compressed text/binary/pseudo-text rows of ragged sizes, stored (skip) rows,
     an empty row — GPU counters, bytes and digests equal the restated CPU read loop."""
-    rng = np.random.default_rng(11)
-    entries, skip = [], []
-    for i in range(300):
-        kind = i % 6
-        n = int(rng.integers(0, 40000))
-        if kind == 0: e = gen.text(n)
-        elif kind == 1: e = gen.binary(n)
-        elif kind == 2: e = gen.pseudo_text(n, seed=i)
-        elif kind == 3: e = gen.incompressible(i, n)
-        elif kind == 4: e = b""
-        else: e = gen.pseudo_text(n * 4, seed=i)
-        entries.append(e)
-        skip.append(1 if kind == 3 and i % 2 else 0)
-    entries.append(gen.pseudo_text(2 << 20, seed=77))   # multi-block frame, > 64 leaves
-    skip.append(0)
-    entries.append(gen.incompressible(5, 3 << 20))      # big stored row
-    skip.append(1)
-    arch = _build_archive(oracle, entries, level=3, skip=skip)
-    counters, corrupt, status, out, rt = _run_gpu(gpu_ctx, arch, pad_blobs=5)
+    entries, skip = mixed_archive_entries()
+    arch = build_archive(oracle, entries, level=3, skip=skip)
+    counters, corrupt, status, out, rt = run_gpu(gpu_ctx, arch, pad_blobs=5)
     n = len(entries)
     bitmap = np.packbits(arch["compressed"].astype(bool), bitorder="little")
     want_out = np.zeros(int(arch["usize"].sum()), dtype=np.uint8)
@@ -113,7 +72,7 @@ def test_rows_corruption_is_counted_not_fatal(gpu_ctx, oracle):
     """decompress.rs:L159-162,L175-189: a checksum mismatch is counted and the bytes are still
     written; a frame that fails to decode is counted in chunks only."""
     entries = [gen.text(10240) for _ in range(20)] + [gen.pseudo_text(30000, seed=3)]
-    arch = _build_archive(oracle, entries, level=19)
+    arch = build_archive(oracle, entries, level=19)
     arch["checksum"] = arch["checksum"].copy()
     arch["checksum"][3, 0] ^= 0xFF           # wrong expected digest -> corrupt row 3
     arch["checksum"][17, 31] ^= 0x01
@@ -121,7 +80,7 @@ def test_rows_corruption_is_counted_not_fatal(gpu_ctx, oracle):
     o = int(arch["blob_offset"][20])
     blobs[o + 1] ^= 0xFF                     # break the magic of row 20 -> decode error
     arch["blobs"] = blobs
-    counters, corrupt, status, out, rt = _run_gpu(gpu_ctx, arch)
+    counters, corrupt, status, out, rt = run_gpu(gpu_ctx, arch)
     bitmap = np.packbits(arch["compressed"].astype(bool), bitorder="little")
     want, want_corrupt = oracle.decompress_rows(arch["blobs"], arch["blob_offset"], arch["blob_size"], arch["usize"],
                                                 arch["out_off"], bitmap, arch["checksum"], 0, len(entries))
@@ -261,8 +220,8 @@ def test_periodic_rows_every_period_and_alignment(gpu_ctx, oracle, level):
         n = int(rng.integers(1, 40)) * 1024 if i % 3 else int(rng.integers(70, 40000))
         entries.append(_periodic(period, n, i))
     entries += [gen.text(10240)] * 40 + [gen.text(10239), gen.text(10241), gen.text(65536), gen.text(65), gen.text(64)]
-    arch = _build_archive(oracle, entries, level=level)
-    counters, corrupt, status, out, rt = _run_gpu(gpu_ctx, arch, pad_blobs=3)
+    arch = build_archive(oracle, entries, level=level)
+    counters, corrupt, status, out, rt = run_gpu(gpu_ctx, arch, pad_blobs=3)
     assert (status == 0).all()
     assert len(corrupt) == 0 and counters["verified_bytes"] == sum(len(e) for e in entries)
     assert out.tobytes() == b"".join(entries)
@@ -492,45 +451,9 @@ def test_random_archives_every_path_every_time(gpu_ctx, gpu_ctx_roles, oracle, s
     compressed, runs of equal rows and single ones, a few big rows, ~1 in 40 rows damaged — through the default context and
     through one that sends every table to the role-split kernel first, three runs each: counters, verdicts, bytes and
     digests equal the oracle's read loop every time."""
-    rng = np.random.default_rng(1000 + seed)
-    entries, skip = [], []
-    while len(entries) < 2500:
-        kind = int(rng.integers(0, 8))
-        run = int(rng.integers(1, 30)) if rng.random() < 0.5 else 1
-        n = int(rng.choice([0, 1, 1023, 1024, 1025, 4096, 10240, 10240, 10240, 20480, 30720, 65536, int(rng.integers(2, 50000))]))
-        if kind <= 1: e = gen.text(n)
-        elif kind == 2: e = gen.binary(n)
-        elif kind == 3: e = gen.pseudo_text(min(n, 20000), seed=len(entries))
-        elif kind == 4: e = gen.incompressible(len(entries), min(n, 30000))
-        elif kind == 5: e = bytes(n)
-        else: e = gen.text(n)
-        for _ in range(run):
-            entries.append(e)
-            skip.append(1 if kind == 4 and len(entries) % 3 == 0 else 0)
-    for big, sk in ((gen.text(700_000), 0), (gen.incompressible(9, 400_000), 1), (gen.pseudo_text(300_000, seed=5), 0)):
-        at = int(rng.integers(0, len(entries)))
-        entries.insert(at, big); skip.insert(at, sk)
-    arch = _build_archive(oracle, entries, level=3, skip=skip)
-    n = len(entries)
-    blobs = arch["blobs"].copy()
-    for i in rng.choice(n, size=n // 40, replace=False):       # damage: one byte somewhere in the row's blob
-        if arch["blob_size"][i] > 0:
-            at = int(arch["blob_offset"][i]) + int(rng.integers(0, int(arch["blob_size"][i])))
-            blobs[at] ^= 1 << int(rng.integers(0, 8))
-    arch["blobs"] = blobs
-    bitmap = np.packbits(arch["compressed"].astype(bool), bitorder="little")
-    want_out = np.zeros(int(arch["usize"].sum()), dtype=np.uint8)
-    want, want_corrupt = oracle.decompress_rows(arch["blobs"], arch["blob_offset"], arch["blob_size"], arch["usize"],
-                                                arch["out_off"], bitmap, arch["checksum"], 0, n, out=want_out)
+    arch = random_archive(oracle, seed)
+    want, want_corrupt, want_out = oracle_rows(oracle, arch)
     for ctx in (gpu_ctx, gpu_ctx_roles):
         for rep in range(3):
-            counters, corrupt, status, out, rt = _run_gpu(ctx, arch, pad_blobs=3)
-            assert counters == want, (rep, counters, want)
-            assert sorted(int(x) for x in corrupt) == sorted(int(x) for x in want_corrupt), rep
-            okrows = status >= 0
-            assert int((~okrows).sum()) == want["decode_errors"]
-            for i in np.nonzero(okrows)[0][:: max(1, n // 400)]:    # bytes of a sample of the decoded rows (all digests below)
-                a, b = int(arch["out_off"][i]), int(arch["out_off"][i] + arch["usize"][i])
-                assert np.array_equal(out[a:b], want_out[a:b]), (rep, int(i))
-            good = okrows.copy(); good[[int(x) for x in want_corrupt]] = False
-            assert np.array_equal(rt.digests()[good], arch["checksum"][good]), rep
+            counters, corrupt, status, out, rt = run_gpu(ctx, arch, pad_blobs=3)
+            check_random_archive_run(arch, want, want_corrupt, want_out, counters, corrupt, status, out, rt, rep)

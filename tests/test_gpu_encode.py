@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gen
+from gpu_cases import random_round_entries
 
 pytestmark = pytest.mark.gpu
 
@@ -300,20 +301,7 @@ def test_random_round_tables_encode_decode_and_repeat(gpu_ctx, oracle, seed):
     and this library's read side gets every byte back."""
     import torch
     from znippy_amd import hip
-    rng = np.random.default_rng(seed)
-    entries, skip = [], []
-    while len(entries) < 500:
-        kind = int(rng.integers(0, 7))
-        run = int(rng.integers(1, 12)) if rng.random() < 0.4 else 1
-        n = int(rng.choice([0, 1, 63, 1024, 4096, 10240, 10240, 16384, 16385, 20480, 131072, 131073, int(rng.integers(2, 300000))]))
-        if kind <= 1: e = gen.text(n)
-        elif kind == 2: e = gen.binary(n)
-        elif kind == 3: e = gen.pseudo_text(min(n, 60000), seed=len(entries) + seed * 1000)
-        elif kind == 4: e = gen.incompressible(len(entries) + seed, min(n, 200000))
-        elif kind == 5: e = bytes(n)
-        else: e = (gen.pseudo_text(min(n, 30000) // 2 + 1, seed=seed) + gen.incompressible(seed, min(n, 30000) // 2))[:n]
-        for _ in range(run):
-            entries.append(e); skip.append(1 if kind == 4 and len(entries) % 4 == 0 else 0)
+    entries, skip = random_round_entries(seed)
     lens = np.array([len(e) for e in entries], np.uint64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)
     total = int(lens.sum())

@@ -3,7 +3,6 @@ tables reused across blocks, matches reaching into earlier blocks) through the t
 decoded by its own workgroup, sequences executed frame by frame — against the source bytes, the oracle's digests and
 the serial decoder's verdicts.  Replaces codec::decompress_into (codec.rs:L67-78) for the frames a reference archive
 holds (level 19, common_config.rs:L37) when a chunk is larger than one 128 KiB block."""
-import glob
 import os
 
 import numpy as np
@@ -11,75 +10,9 @@ import pytest
 
 import gen
 import workloads
+from gpu_cases import foreign_archive as _archive, fuzz_run, mixed as _mixed, py_corpus as _py_corpus, run_foreign as _run
 
 pytestmark = pytest.mark.gpu
-
-
-def _py_corpus(cap):
-    """Real text: python sources of the image, in sorted order (deterministic on a given image)."""
-    out, tot = [], 0
-    for f in sorted(glob.glob("/usr/lib/python3.10/*.py")):
-        try:
-            b = open(f, "rb").read()
-        except OSError:
-            continue
-        out.append(b)
-        tot += len(b)
-        if tot >= cap:
-            break
-    data = b"".join(out)
-    if len(data) < cap:  # a bare image: fall back to the seeded word stream
-        data += gen.pseudo_text(cap - len(data), seed=5)
-    return data[:cap]
-
-
-def _mixed(n, seed):
-    """Text with incompressible and constant stretches: raw and RLE blocks between compressed ones."""
-    rng = np.random.default_rng(seed)
-    parts, tot = [], 0
-    while tot < n:
-        k = int(rng.integers(0, 4))
-        m = int(rng.integers(20000, 400000))
-        if k == 0:
-            p = rng.integers(0, 256, size=m, dtype=np.uint8).tobytes()
-        elif k == 1:
-            p = bytes([int(rng.integers(0, 256))]) * m
-        else:
-            p = gen.pseudo_text(m, seed=int(rng.integers(0, 1 << 30)))
-        parts.append(p)
-        tot += m
-    return b"".join(parts)[:n]
-
-
-def _archive(oracle, entries, level):
-    frames = [workloads.libzstd_compress(e, level) for e in entries]
-    bs = np.array([len(f) for f in frames], np.uint64)
-    bo = np.concatenate([[0], np.cumsum(bs)[:-1]]).astype(np.uint64)
-    us = np.array([len(e) for e in entries], np.uint64)
-    oo = np.concatenate([[0], np.cumsum(us)[:-1]]).astype(np.uint64)
-    ck = np.stack([np.frombuffer(oracle.blake3(e), dtype=np.uint8) for e in entries])
-    blobs = np.frombuffer(b"".join(frames) + bytes(64), dtype=np.uint8)
-    return dict(blobs=blobs, bo=bo, bs=bs, us=us, oo=oo, ck=ck, frames=frames)
-
-
-def _run(ctx, A):
-    import torch
-    from znippy_amd import hip
-    d_blobs = torch.from_numpy(A["blobs"].copy()).cuda()
-    total = int(A["us"].sum())
-    d_out = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
-    rt = hip.RowTable(ctx, A["bo"], A["bs"], A["us"], A["oo"], None, A["ck"])
-    first = None
-    for rep in range(3):  # the work lists of the two-phase path are filled in a different order every run: every run must agree
-        d_out.zero_()
-        c, corrupt, status = rt.decode_verify(d_blobs, d_out)
-        got = (dict(c), sorted(int(x) for x in corrupt), status.copy(), rt.digests()[status >= 0].copy(), d_out.cpu().numpy()[:total].copy())
-        if first is None:
-            first = got
-        else:
-            assert got[0] == first[0] and got[1] == first[1] and (got[2] == first[2]).all(), rep
-            assert (got[3] == first[3]).all() and (got[4] == first[4]).all(), rep
-    return c, corrupt, status, first[4], dict(ctx.kernel_times())
 
 
 @pytest.mark.parametrize("level", [1, 3, 19])
@@ -172,7 +105,6 @@ def test_mutated_real_text_frames_agree_with_oracle(gpu_ctx, oracle):
     """Real-text multi-block frames at level 19 (Treeless literals, Repeat_Mode tables, repeat offsets across blocks),
     damaged anywhere: the oracle's verdict is the GPU's, accepted mutants decode to the oracle's bytes, and nothing is
     ever reported verified with different bytes (the harness of test_gpu_fuzz.py)."""
-    from test_gpu_fuzz import _run as fuzz_run
     data = _py_corpus(1 << 20)
     bases = [(data[:400_000], 19), (data[400_000:400_000 + 262_145], 19), (data[700_000:1_000_000], 3)]
     fuzz_run(gpu_ctx, oracle, bases, 60, 4242, 10, 60)

@@ -10,8 +10,7 @@ import pytest
 
 import gen
 import workloads
-from test_gpu_batch import _table
-from test_gpu_foreign import _py_corpus, _mixed
+from gpu_cases import frame_table as _table, fuzz_run, mixed as _mixed, py_corpus as _py_corpus
 
 pytestmark = pytest.mark.gpu
 
@@ -95,7 +94,6 @@ def test_damaged_big_frames_agree_with_oracle(gpu_ctx, oracle):
     """Big frames damaged anywhere — sequence sections, literals, block headers: the words are written from whatever the
     entropy stages decoded, so offsets are checked when they are written; the oracle's verdict is the GPU's, nothing is
     reported verified with other bytes, and the run ends."""
-    from test_gpu_fuzz import _run as fuzz_run
     data = _py_corpus(2 << 20)
     bases = [(data[:400_000], 3), (data[300_000:300_000 + 280_000], 19), (_mixed(300_000, 8), 1)]
     fuzz_run(gpu_ctx, oracle, bases, 40, 99, 5, 40)

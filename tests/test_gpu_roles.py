@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import gen
-from test_gpu_decode import _build_archive, _run_gpu
+from gpu_cases import build_archive, run_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -18,10 +18,10 @@ def _period(p, n, seed=0):
 
 
 def _check(oracle, ctx, entries, level=19, skip=None, pad=0, mutate=None):
-    arch = _build_archive(oracle, entries, level=level, skip=skip)
+    arch = build_archive(oracle, entries, level=level, skip=skip)
     if mutate:
         mutate(arch)
-    counters, corrupt, status, out, rt = _run_gpu(ctx, arch, pad_blobs=pad)
+    counters, corrupt, status, out, rt = run_gpu(ctx, arch, pad_blobs=pad)
     n = len(entries)
     bitmap = np.packbits(arch["compressed"].astype(bool), bitorder="little")
     want_out = np.zeros(int(arch["usize"].sum()), dtype=np.uint8)
@@ -111,7 +111,7 @@ def test_roles_kernel_respects_host_verdicts_and_out_cap(gpu_ctx_roles, oracle):
     from znippy_amd import _lib, hip
     n, sz = 120, 10240
     entries = [gen.text(sz)] * n
-    arch = _build_archive(oracle, entries, level=19)
+    arch = build_archive(oracle, entries, level=19)
     bo = arch["blob_offset"].copy()
     bo[10] = np.uint64(len(arch["blobs"]) + 999)
     bo[77] = np.uint64(2**63)

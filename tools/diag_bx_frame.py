@@ -3,7 +3,7 @@ import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..")); sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..", "tests"))
 import numpy as np, torch
 import workloads, gen
-from test_gpu_foreign import _mixed
+from gpu_cases import mixed as _mixed
 from znippy_amd import hip
 
 level = int(sys.argv[1]) if len(sys.argv) > 1 else 1

@@ -393,7 +393,7 @@ struct znippy_rows {
     uint32_t *all_rows = nullptr;
     int lean_hint2 = -1;
     bool last_lean = false;
-    struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0; } run_args[2];  // per mirror slot: what the run was given
+    struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; } run_args[2];  // per mirror slot: what the run was given
     hipEvent_t ev_done[2] = {nullptr, nullptr};
     uint64_t run_seq = 0;  // async runs queued so far
     // Host copies of the columns a run is validated against (one pass per distinct (blob_base, blob_cap, out_cap)):
@@ -1347,12 +1347,12 @@ static void rows_note_hint(znippy_rows *r, unsigned slot) {
     if (r->small_off) r->bx_hint = 1;
 }
 
-int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs,
-                                    uint64_t blob_base, void *d_out, uint64_t out_cap) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
-    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
-    if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+// Queues one run of the table with the given arguments; its counters land in mirror slot `slot` and ev_done[slot] marks its
+// end.  run_seq is the caller's (znippy_decode_verify_rows_async advances it, a repeat inside rows_settle does not).  Every
+// allocation the run needs is made before its first stream operation on the table (*queued): an error return after that
+// point is a HIP runtime error, which the caller turns into a table without a readable run (rows_abandon).
+static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap,
+                       unsigned slot, bool *queued = nullptr) {
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
     { const int rc0 = ensure_decoder(ctx); if (rc0) return rc0; }
@@ -1364,6 +1364,7 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
         if (!rc0 && r->rx_base && r->bx_hint != 0) rc0 = ensure_rx_pool(ctx, r->rx_words);
         if (rc0) return rc0;
     }
+    if (r->n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
     if (r->run_seq && r->bx_hint < 0 && r->n) {  // a run of this table has finished meanwhile?
         const unsigned slot = (unsigned)((r->run_seq - 1) & 1);
         if (hipEventQuery(r->ev_done[slot]) == hipSuccess) rows_note_hint(r, slot);
@@ -1376,12 +1377,13 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
         hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, s, r->all_rows, r->n);
     }
     const int preset = r->n_bad ? 1 : 0;
-    { auto &ra = r->run_args[r->run_seq & 1]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = d_out; ra.cap = out_cap; }
+    { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = d_out; ra.cap = out_cap; ra.blob_cap = r->blob_cap; }
     bool lean = false, lean_blocks = false, lean_mixed = false;
     // counters, hand-over counts, work cursors and the status column: one stream operation
+    if (queued) *queued = true;
     if (preset) HIPCHK(ctx, hipMemcpyAsync(r->ctl, r->status_init, r->ctl_bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(r->ctl, 0, r->ctl_bytes, s));
-    if (!r->n) { r->run_seq++; return ZNIPPY_OK; }
+    if (!r->n) return ZNIPPY_OK;
     // (the second hash pass looks at small tiles only when rows were handed over: word 0 of the hand-over counts)
     if (small_off) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)(r->ctl + 64), (int)r->n, 1, s));
     // 1) fused small-row kernel: decode simple frames + hash (+ copy stored rows), one wave per tile
@@ -1473,7 +1475,6 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
     // of small rows leaves out what stands behind the roles kernel: k_verify looks at the lists, a flagged run is repeated.
     lean_blocks = one_stream && r->lean_blocks_ok && r->lean_hint2 == 1 && !preset && !r->force_full && r->n_bt && !ctx->sw.ddbg && !r->fz_total;
     if (r->n_cand) {
-        if (!ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
         b.cand_row = r->cand_row; b.cand_base = r->cand_base; b.cand_nblocks = r->cand_nblocks; b.n_cand = r->n_cand;
         b.blobs = (const uint8_t *)d_blobs; b.blob_base = blob_base;
         b.blob_off = r->blob_off; b.blob_size = r->blob_size; b.usize = r->usize; b.out_off = r->out_off; b.out_cap = out_cap;
@@ -1779,35 +1780,66 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
     launch_verify(r->digests, r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt,
                   r->corrupt_cap, s, (lean || lean_blocks || lean_mixed) ? r->pending_count : nullptr, (lean || lean_mixed) ? 0x2Bu : 0x27u);
     ktime_end(ctx);
-    {
-        const unsigned slot = (unsigned)(r->run_seq & 1);
-        HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * slot, r->counters, 128, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipEventRecord(r->ev_done[slot], s));
-        r->run_seq++;
-    }
+    HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * slot, r->counters, 128, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipEventRecord(r->ev_done[slot], s));
     HIPCHK(ctx, hipGetLastError());
     return ZNIPPY_OK;
 }
 
-// A lean run whose lists were not empty after all (counters[7] set by k_verify): the run of mirror slot `slot` is done again
-// in full with the arguments IT was given (a caller that alternates buffers gets the right buffer completed), and the slot
-// gets the full run's counters.  The repeat is run k + 2 when another run is queued behind the flagged one — the same slot
-// — or run k + 1 otherwise; a flagged run k + 1 is settled when its own results are read.  Called by everything that hands
-// a run's results to the caller.
+// A run that failed after its first stream operation: whatever it queued on the auxiliary stream is joined back into the
+// main one and waited for, and the table forgets its runs (the control block, the status column and one mirror slot may hold
+// a part of the failed run): results calls see no run until the next one is queued, and that one runs in full.
+static void rows_abandon(znippy_ctx *ctx, znippy_rows *r) {
+    if (hipEventRecord(ctx->ev_join, ctx->aux) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipGetLastError();
+    r->run_seq = 0;
+    r->force_full = true;
+    r->lean_hint = 0; r->lean_hint2 = 0;
+}
+
+int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs,
+                                    uint64_t blob_base, void *d_out, uint64_t out_cap) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    bool queued = false;
+    const int rc = rows_launch(ctx, r, d_blobs, blob_base, d_out, out_cap, (unsigned)(r->run_seq & 1), &queued);
+    if (rc && queued) rows_abandon(ctx, r);
+    if (rc) return rc;
+    r->run_seq++;
+    return ZNIPPY_OK;
+}
+
+// A lean run whose lists were not empty after all (counters[7] set by k_verify) is run again in full with the arguments IT was
+// given (run_args[slot]: a caller that alternates buffers gets the right buffer completed), its counters into its own mirror
+// slot; run_seq does not move, so the caller's lagged reads keep counting the runs it queued.  When a later run stands behind
+// it (run k read with lag 1 while run k + 1 was queued), that later run — the latest — is run again in full as well, after the
+// first: whatever it was (lean and flagged too, lean and clean, or sharing d_out with run k), its bytes and counters are
+// complete before any results call hands them out, and the table's own outputs (status column, corrupt list, digests) once
+// more describe the latest run, as znippy_rows_results and znippy_rows_digests report them.  A full run leaves counters[7]
+// clear: no slot is repeated twice.  Only runs over changed blobs get here, so the cost of the second repeat does not matter.
+// Called by everything that hands a run's results to the caller.
 static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
     if (!r->n || !r->run_seq || !(r->h_counters[16 * slot + 7])) return ZNIPPY_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     r->force_full = true;
     r->lean_hint = 0; r->lean_hint2 = 0;
-    const znippy_rows::RunArgs ra = r->run_args[slot];
-    const int rc = znippy_decode_verify_rows_async(ctx, r, ra.blobs, ra.base, ra.out, ra.cap);
-    if (rc) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    const unsigned now = (unsigned)((r->run_seq - 1) & 1);
-    if (now != slot) {
-        memcpy(r->h_counters + 16 * slot, r->h_counters + 16 * now, 128);
-        r->run_args[slot] = ra;
+    const unsigned latest = (unsigned)((r->run_seq - 1) & 1);
+    const unsigned order[2] = {slot, latest};
+    for (int i = 0; i < (slot == latest ? 1 : 2); i++) {
+        const znippy_rows::RunArgs ra = r->run_args[order[i]];
+        r->blob_cap = ra.blob_cap;
+        bool queued = false;
+        const int rc = rows_launch(ctx, r, ra.blobs, ra.base, ra.out, ra.cap, order[i], &queued);
+        if (rc) {
+            if (queued) rows_abandon(ctx, r);
+            return rc;
+        }
     }
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     return ZNIPPY_OK;
 }
 

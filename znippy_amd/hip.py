@@ -157,12 +157,17 @@ class RowTable:
         self.n = row_end - row_begin
         self._corrupt, self._k1 = _pinned((max(self.n, 1),), np.uint64)
         self._status, self._k2 = _pinned((max(self.n, 1),), np.int32)
+        # The library may run a queued run again, with the pointers it was given, inside a later results call (a lean run
+        # over changed blobs; znippy_hip.h): the tensors of the last two runs stay referenced here until they are read.
+        self._runs = {}  # run number -> [d_blobs, d_out, read]
+        self._seq = 0
 
     def close(self):
         if getattr(self, "h", None):
             if getattr(self.ctx, "h", None):
                 self.ctx.L.znippy_rows_destroy(self.h)
             self.h = None
+        self._runs = {}
 
     __del__ = close
 
@@ -175,12 +180,27 @@ class RowTable:
         self.ctx._chk(self.ctx.L.znippy_decode_verify_rows_async(self.ctx.h, self.h, _dptr(d_blobs), blob_base,
                                                                  _dptr(d_out), out_cap),
                       "znippy_decode_verify_rows_async")
+        self._runs[self._seq] = [d_blobs, d_out, False]
+        self._seq += 1
+        self._runs.pop(self._seq - 3, None)  # the library keeps two runs
+
+    def _read(self, lag):
+        """Run `lag` before the latest has been read.  A run's buffers go once it has been read and no older run is left
+        unread: reading that one may repeat the latest run as well."""
+        run = self._runs.get(self._seq - 1 - lag)
+        if run is not None:
+            run[2] = True
+        for k in sorted(self._runs):
+            if not self._runs[k][2]:
+                break
+            del self._runs[k]
 
     def results(self, want_status=True):
         c = VerifyCounters()
         corrupt, status = self._corrupt, self._status
         self.ctx._chk(self.ctx.L.znippy_rows_results(self.ctx.h, self.h, C.byref(c), np_ptr(corrupt), corrupt.size,
                                                      np_ptr(status) if want_status else None), "znippy_rows_results")
+        self._read(0)
         return c.as_dict(), corrupt[:min(c.corrupt_rows, corrupt.size)].copy(), status[:self.n]
 
     def results_lagged(self, lag=1):
@@ -188,6 +208,7 @@ class RowTable:
         c = VerifyCounters()
         self.ctx._chk(self.ctx.L.znippy_rows_results_lagged(self.ctx.h, self.h, lag, C.byref(c)),
                       "znippy_rows_results_lagged")
+        self._read(lag)
         return c.as_dict()
 
     def foreign_stats(self):
@@ -204,6 +225,7 @@ class RowTable:
     def digests(self):
         out = np.zeros((max(self.n, 1), 32), dtype=np.uint8)
         self.ctx._chk(self.ctx.L.znippy_rows_digests(self.ctx.h, self.h, np_ptr(out)), "znippy_rows_digests")
+        self._read(0)
         return out[:self.n]
 
 
