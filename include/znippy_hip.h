@@ -61,6 +61,20 @@ void znippy_ctx_destroy(znippy_ctx *ctx);
  * per-block entropy tables).  Frames of both tiers are plain RFC 8878.  znippy_ctx_level returns the level. */
 int znippy_ctx_set_level(znippy_ctx *ctx, int level);
 int znippy_ctx_level(const znippy_ctx *ctx);
+/* Opt-in cross-block match window of every later encode call of this context (znippy_compress,
+ * znippy_encode_hash_rounds[_async]).  0 (the default): every 128 KiB block of a frame is self-contained, and frames
+ * of several blocks end with an empty raw block that says so.  17..27: a match reaches up to 2^window_log bytes back,
+ * never in front of the first byte of its own round (rounds stay independent frames): the 64 KiB in front of a block
+ * through the block matcher, farther back through long-distance matches found by a per-round index.  Such frames
+ * are smaller on big rounds, carry no closing empty block and go through the slower foreign-frame read paths.
+ * Blocks are still encoded in parallel (repeat offsets start unknown in every block, no table is shared) and frames
+ * are plain single-segment RFC 8878, deterministic, and the same whatever else is in the batch.  Only levels 4-22 use
+ * the window; at levels 1-3 the value is kept but frames do not change.  Rounds of at most one block are identical
+ * with the window on or off.  znippy_compress_bound / znippy_rounds_blob_bound hold as before.  Other values, and a
+ * closed context, give ZNIPPY_E_INVAL.  ZNIPPY_WINDOW_LOG in the environment of znippy_ctx_create sets the initial
+ * value.  znippy_ctx_window_log returns it. */
+int znippy_ctx_set_window_log(znippy_ctx *ctx, int window_log);
+int znippy_ctx_window_log(const znippy_ctx *ctx);
 const char *znippy_last_error(const znippy_ctx *ctx);
 /* Block until everything queued on the context's stream has finished. */
 int znippy_ctx_sync(znippy_ctx *ctx);

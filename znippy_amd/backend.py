@@ -19,6 +19,10 @@ class HipBackend:
         """CompressCtx::new(compression_level), codec.rs:L16-28."""
         self.ctx.set_level(level)
 
+    def set_window_log(self, window_log):
+        """Cross-block match window of later encode calls (0 = off, 17..27; znippy_ctx_set_window_log)."""
+        self.ctx.set_window_log(window_log)
+
     def _to_dev(self, a):
         t = self.torch.from_numpy(np.ascontiguousarray(a))
         return t.to(f"cuda:{self.device}", non_blocking=False)
@@ -53,6 +57,15 @@ class HipBackend:
         out = d_out[:out_total].cpu().numpy()
         rt.close()
         return counters, corrupt, status, out
+
+
+def apply_window_log(backend, window_log):
+    """The pipelines' window_log keyword: set on every backend that has the setting (the CPU test double has not, and
+    takes only 0)."""
+    if hasattr(backend, "set_window_log"):
+        backend.set_window_log(window_log)
+    elif window_log:
+        raise ValueError(f"backend {type(backend).__name__} has no cross-block window")
 
 
 _default = None

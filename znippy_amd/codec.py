@@ -7,7 +7,8 @@ Same names, argument meaning and error behaviour as the reference:
   decompress_frame(frame)       codec.rs:L58-62
   decompress_into(frame, out)   codec.rs:L67-78
 Errors raise ZnippyError (the reference returns anyhow::Error).  The compression level selects the
-encoder's effort tier (znippy_ctx_set_level: 1-3 fast, 4-22 higher effort).
+encoder's effort tier (znippy_ctx_set_level: 1-3 fast, 4-22 higher effort).  window_log (0, or
+17..27) opts into the cross-block match window of the higher effort tier (znippy_ctx_set_window_log).
 """
 from . import hip
 from ._lib import ZnippyError  # noqa: F401
@@ -24,8 +25,9 @@ def default_context():
 
 
 class CompressCtx:
-    def __init__(self, compression_level: int = 19, ctx=None):
+    def __init__(self, compression_level: int = 19, ctx=None, window_log: int = 0):
         self.level = compression_level
+        self.window_log = window_log
         self.ctx = ctx or default_context()
 
     def _apply_level(self):
@@ -33,6 +35,8 @@ class CompressCtx:
             raise ZnippyError(-1, f"compression level {self.level} outside 1..22")
         if self.ctx.level != self.level:  # the HIP context may be shared between CompressCtx objects
             self.ctx.set_level(self.level)
+        if self.ctx.window_log != self.window_log:  # (so is the window)
+            self.ctx.set_window_log(self.window_log)
 
     def compress(self, data) -> bytes:
         self._apply_level()

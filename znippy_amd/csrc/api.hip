@@ -75,6 +75,9 @@ struct znippy_ctx {
     int encode_grid = 0, encode_grid_small = 0;
     int gen_share = 3;  // workgroups per CU the general decoder takes while block items / foreign frames run beside it (4 = the whole register file)
     int level = 19;  // CompressCtx::new(compression_level), codec.rs:L16-28; CONFIG.compression_level is 19 (common_config.rs:L37)
+    int window_log = 0;  // cross-block window of the higher effort tier (znippy_ctx_set_window_log); 0 = self-contained blocks
+    uint32_t *ldm = nullptr;  // far window index (grow-only, entries)
+    size_t ldm_cap = 0;
     uint8_t *enc_prov = nullptr;
     size_t enc_prov_cap = 0;
     uint32_t *enc_seq = nullptr;
@@ -157,6 +160,7 @@ static void read_switches(znippy_ctx *ctx) {
     ctx->sw.no_bx = on("ZNIPPY_NO_BX");
     if (const char *e = getenv("ZNIPPY_BX_BIG")) { ctx->sw.bx_big = (unsigned)atoi(e); ctx->sw.bx_big_set = true; }  // A/B: foreign frames through the round-2 paths (serial decoder + wave-per-block two-phase path)
     if (const char *lv = getenv("ZNIPPY_LEVEL")) { const int v = atoi(lv); if (v >= 1 && v <= 22) ctx->level = v; }  // initial level of every context (tests, A/B runs)
+    if (const char *wl = getenv("ZNIPPY_WINDOW_LOG")) { const int v = atoi(wl); if (v == 0 || (v >= WINDOW_LOG_MIN && v <= WINDOW_LOG_MAX)) ctx->window_log = v; }  // initial window of every context (host layer, tools)
     if (const char *gs = getenv("ZNIPPY_GEN_SHARE")) { const int v = atoi(gs); if (v >= 1 && v <= 4) ctx->gen_share = v; }  // A/B
     ctx->sw.fz_only = on("ZNIPPY_FZ_ONLY");  // test hook: no serial fallback behind the two-phase path (what it leaves shows up as corrupt rows)
     if (const char *e = getenv("ZNIPPY_ROLES_MIN")) ctx->sw.roles_min = (unsigned)atoi(e);
@@ -490,6 +494,13 @@ struct znippy_rounds {
     uint8_t *stored = nullptr, *h_stored = nullptr;  // per round: turned into a raw payload by the opt-in pass
     uint64_t *blob_offset = nullptr, *blob_size = nullptr, *total = nullptr;
     uint32_t *overflow = nullptr;
+    // far window: the rounds longer than one block and their regions of the index (found at creation; the device copies
+    // are made by the first windowed encode call)
+    std::vector<LdmRound> h_ldm;
+    uint64_t ldm_entries = 0;
+    uint32_t ldm_chunks = 0;
+    LdmRound *d_ldm = nullptr;
+    uint64_t *d_ldm_desc = nullptr;  // per round: its region (LDM_NONE: not indexed)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -867,6 +878,7 @@ static void ctx_teardown(znippy_ctx *ctx) {
     if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
     if (ctx->enc_seq) (void)hipFree(ctx->enc_seq);
     if (ctx->enc_tabs) (void)hipFree(ctx->enc_tabs);
+    if (ctx->ldm) (void)hipFree(ctx->ldm);
     if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }
     if (ctx->copy) { (void)hipStreamSynchronize(ctx->copy); (void)hipStreamDestroy(ctx->copy); }
     for (auto &e : ctx->pinned_pool) (void)hipHostFree(e.second);
@@ -919,6 +931,15 @@ int znippy_ctx_set_level(znippy_ctx *ctx, int level) {
 }
 
 int znippy_ctx_level(const znippy_ctx *ctx) { return ctx ? ctx->level : ZNIPPY_E_INVAL; }
+
+int znippy_ctx_set_window_log(znippy_ctx *ctx, int window_log) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || (window_log != 0 && (window_log < WINDOW_LOG_MIN || window_log > WINDOW_LOG_MAX))) return ZNIPPY_E_INVAL;
+    ctx->window_log = window_log;
+    return ZNIPPY_OK;
+}
+
+int znippy_ctx_window_log(const znippy_ctx *ctx) { return ctx && !ctx->closing ? ctx->window_log : ZNIPPY_E_INVAL; }
 
 int znippy_ctx_set_kernel_timing(znippy_ctx *ctx, int level) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
@@ -1936,7 +1957,7 @@ void znippy_rounds_destroy(znippy_rounds *r) {
     }
     void *ptrs[] = {r->src_off, r->len, r->skip, r->res_m[0], r->res_m[1], r->items, r->piece_len, r->piece_len_init,
                     r->piece_start, r->local_excl, r->block_tot, r->first_item, r->stored, r->order_small, r->order_wide, r->retry_list, r->retry_count,
-                    r->plan_scratch[0], r->plan_scratch[1], r->plan_scratch[2]};
+                    r->plan_scratch[0], r->plan_scratch[1], r->plan_scratch[2], r->d_ldm, r->d_ldm_desc};
     pinned_give(r->ctx, r->h_stored, r->h_stored_cap);
     for (void *p : ptrs)
         tfree(r->ctx, p);
@@ -1995,6 +2016,18 @@ int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint
         if (const char *e = getenv("ZNIPPY_FUSE_TILES")) { const int v = atoi(e); if (v >= 1 && v * (int)max_units <= 64) r->fuse_tiles = v; }  // A/B
     }
     td.mark("hash_plan");
+    // far window: regions of the index for the encoded rounds longer than one block (rounds of 4 GiB and more are not
+    // indexed: the index holds 32-bit positions).  Every round has at least one piece: with no more pieces than rounds
+    // there is no such round, and the pass is skipped (100k small rounds: no host pass of its own)
+    if (r->n_items > n) {
+        for (uint64_t i = 0; i < n; i++)
+            if (len[i] > BLOCK_BYTES && len[i] < (1ull << 32) && !(skip && skip[i])) {
+                const uint32_t lg = ldm_log2(len[i]);
+                r->h_ldm.push_back(LdmRound{(uint32_t)i, r->ldm_chunks, r->ldm_entries | ((uint64_t)lg << 48)});
+                r->ldm_entries += 1ull << lg;
+                r->ldm_chunks += (uint32_t)((len[i] + LDM_CHUNK - 1) / LDM_CHUNK);
+            }
+    }
     // encoder plan: one item per output piece, in round order — counted, scanned and filled on the device
     const size_t ni = std::max<size_t>(r->n_items, 1), nsb = (ni + 255) / 256;
     RoundSums *sums = nullptr;
@@ -2154,6 +2187,37 @@ __global__ __launch_bounds__(256) void k_results_out(uint4 *dst, const uint4 *sr
 }
 
 // ---- write side ------------------------------------------------------------------------------------
+// Far window of a windowed encode call: the context's index (grow-only) and the table's region list and per-round
+// descriptors (once per table).  Any failure leaves the far window off for the call — the near window still works.
+static bool ensure_ldm(znippy_ctx *ctx, znippy_rounds *r) {
+    if (!r->ldm_entries || r->ldm_entries > LDM_MAX_ENTRIES) return false;
+    if (r->ldm_entries > ctx->ldm_cap) {
+        if (ctx->ldm) {
+            if (hipStreamSynchronize(ctx->stream) != hipSuccess) return false;  // an earlier call may still read it
+            (void)hipFree(ctx->ldm);
+        }
+        ctx->ldm = nullptr; ctx->ldm_cap = 0;
+        if (hipMalloc(&ctx->ldm, 4 * r->ldm_entries) != hipSuccess) { (void)hipGetLastError(); ctx->ldm = nullptr; return false; }
+        ctx->ldm_cap = r->ldm_entries;
+    }
+    if (!r->d_ldm) {
+        std::vector<uint64_t> desc(r->n, LDM_NONE);
+        for (const LdmRound &e : r->h_ldm) desc[e.round] = e.desc;
+        LdmRound *dl = nullptr;
+        uint64_t *dd = nullptr;
+        if (tmalloc(ctx, &dl, sizeof(LdmRound) * r->h_ldm.size()) != hipSuccess || tmalloc(ctx, &dd, 8 * (size_t)r->n) != hipSuccess ||
+            hipMemcpy(dl, r->h_ldm.data(), sizeof(LdmRound) * r->h_ldm.size(), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(dd, desc.data(), 8 * (size_t)r->n, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError();
+            tfree(ctx, dl);
+            tfree(ctx, dd);
+            return false;
+        }
+        r->d_ldm = dl; r->d_ldm_desc = dd;
+    }
+    return true;
+}
+
 extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out,
                                                uint64_t blob_cap) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
@@ -2163,6 +2227,9 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     ctx->n_ktimes = 0;
     if (!r->n) return ZNIPPY_OK;
     { const int rc0 = ensure_encoder(ctx); if (rc0) return rc0; }
+    const bool high = ctx->level >= HIGH_TIER_LEVEL;
+    const int window_log = high ? ctx->window_log : 0;  // (the fast tier keeps its frames)
+    const bool far = window_log && ensure_ldm(ctx, r);  // allocations before the first stream operation of the call
     if (r->prov_bytes + 64 > ctx->enc_prov_cap) {
         HIPCHK(ctx, hipStreamSynchronize(s));
         if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
@@ -2184,7 +2251,16 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     a.src = (const uint8_t *)d_src; a.src_off = r->src_off; a.len = r->len;
     a.prov = ctx->enc_prov; a.seq_scratch = ctx->enc_seq;
     a.piece_len = r->piece_len; a.piece_start = r->piece_start; a.tabs = ctx->enc_tabs;
-    a.tail_mark = a.high = ctx->level >= HIGH_TIER_LEVEL;
+    a.high = high;
+    a.tail_mark = high && !window_log;  // the empty closing block says every block stands alone: not with a window
+    a.window_log = window_log;
+    if (far) {
+        a.ldm = ctx->ldm; a.ldm_desc = r->d_ldm_desc;
+        ktime_begin(ctx, "ldm_index");
+        HIPCHK(ctx, hipMemsetAsync(ctx->ldm, 0xFF, 4 * r->ldm_entries, s));
+        launch_ldm_index(r->d_ldm, (uint32_t)r->h_ldm.size(), r->ldm_chunks, (const uint8_t *)d_src, r->src_off, r->len, ctx->ldm, s);
+        ktime_end(ctx);
+    }
     if (ctx->sw.edbg) {  // diagnostic: phase shares of the previous run's wide-variant blocks
         static unsigned long long *dbg = nullptr;
         if (!dbg) { (void)hipMalloc(&dbg, 64); (void)hipMemset(dbg, 0, 64); }
@@ -2217,7 +2293,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
             a.h.digests = r->digests; a.h.tile_cv = r->plan.tile_cv;
             grid = std::min<int>(g, (int)((r->plan.n_tiles + r->fuse_tiles - 1) / r->fuse_tiles));
         }
-        launch_encode(a, grid, !wide, ctx->level >= HIGH_TIER_LEVEL, s);
+        launch_encode(a, grid, !wide, high, s);
         a.fuse_tiles = 0;
     }
     if (r->n_small) {  // second wide launch: whatever the small variant handed over (count on the device)
@@ -2225,7 +2301,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
         a.retry_list = nullptr; a.retry_count = nullptr;
         a.cursor = ctx->cursor + 12;
         a.batch = 1;
-        launch_encode(a, std::min<int>(ctx->encode_grid, (int)r->n_small), false, ctx->level >= HIGH_TIER_LEVEL, s);
+        launch_encode(a, std::min<int>(ctx->encode_grid, (int)r->n_small), false, high, s);
     }
     ktime_end(ctx);
     // checksum over the ORIGINAL bytes (stream_packer.rs:L219): VALU-bound, submitted to the

@@ -61,7 +61,32 @@ struct EncodeArgs {
     // then encodes them; the cursor counts tiles.  fuse_tiles == 0: items as usual, the hash is a kernel of its own.
     int fuse_tiles;
     HashArgs h;
+    // Cross-block window (higher effort tier, wide variant; 0 = every block self-contained): a match reaches up to
+    // 2^window_log bytes back, never in front of its round.  ldm / ldm_desc: the far window's index (k_ldm_index) and
+    // each round's region of it (LDM_NONE: no far window for the round); NULL = near window only.
+    int window_log;
+    const uint32_t *ldm;
+    const uint64_t *ldm_desc;
 };
+
+// Far window (long-distance matches).  Every round longer than one block owns a region of the index: 2^log2 buckets
+// (one per 64 bytes of the round, a power of two, at most 2^LDM_MAX_LOG) at bucket `slot`.  desc = slot | log2 << 48.
+// Regions are per round, so a round's frame does not depend on the other rounds of its table.
+constexpr uint64_t LDM_NONE = 0;
+constexpr uint32_t LDM_MIN_LOG = 11, LDM_MAX_LOG = 22;
+constexpr uint64_t LDM_MAX_ENTRIES = 1ull << 27;  // the whole index of one call (512 MiB); beyond it the far window is off
+constexpr uint32_t LDM_CHUNK = 16384;             // positions per workgroup of k_ldm_index
+constexpr int WINDOW_LOG_MIN = 17, WINDOW_LOG_MAX = 27;
+struct LdmRound {  // one indexed round
+    uint32_t round;
+    uint32_t first_chunk;  // its first workgroup of k_ldm_index
+    uint64_t desc;
+};
+__host__ __device__ inline uint32_t ldm_log2(uint64_t len) {
+    uint32_t l = LDM_MIN_LOG;
+    while (l < LDM_MAX_LOG && (1ull << l) * 64 < len) l++;
+    return l;
+}
 
 struct GatherArgs {
     const EncItem *items;
@@ -82,6 +107,8 @@ struct GatherArgs {
 
 void launch_encode(const EncodeArgs &a, int grid, bool small_blocks, bool high, hipStream_t s);
 constexpr int HIGH_TIER_LEVEL = 4;  // compression levels from here up use the higher effort tier of the wide encoder
+void launch_ldm_index(const LdmRound *rl, uint32_t n_rl, uint32_t n_chunks, const uint8_t *src, const uint64_t *src_off,
+                      const uint64_t *len, uint32_t *ldm, hipStream_t s);
 void launch_piece_scan(const uint32_t *piece_len, uint32_t n, uint64_t *local_excl, uint64_t *block_tot, hipStream_t s);
 void launch_gather(const GatherArgs &g, hipStream_t s);
 void launch_store_decide(const uint32_t *first_item, const EncItem *items, const uint64_t *len, const uint8_t *skip,

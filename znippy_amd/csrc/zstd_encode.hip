@@ -32,6 +32,21 @@ template <uint32_t HASH_LOG>
 __device__ __forceinline__ uint32_t hash4(uint32_t v) { return (v * 2654435761u) >> (32 - HASH_LOG); }
 __device__ __forceinline__ int hib(uint32_t v) { return 31 - __clz(v); }
 
+// Far window: content-defined anchors (about one position in 64) and the key of the 32 bytes at an anchor.  k_ldm_index
+// and the matcher must agree on both.
+__device__ __forceinline__ bool ldm_anchor(uint32_t v) { return (hash4<22>(v) & 63u) == 0; }
+__device__ __forceinline__ uint32_t ldm_key(const uint8_t *p) {
+    uint64_t h = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        uint64_t x;
+        __builtin_memcpy(&x, p + 8 * i, 8);
+        h = (h ^ x) * 0x9E3779B97F4A7C15ull;
+        h ^= h >> 29;
+    }
+    return (uint32_t)(h >> 32);
+}
+
 __constant__ uint8_t c_ll_code[64] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15,
                                       16, 16, 17, 17, 18, 18, 19, 19, 20, 20, 20, 20, 21, 21, 21, 21,
                                       22, 22, 22, 22, 22, 22, 22, 22, 23, 23, 23, 23, 23, 23, 23, 23,
@@ -1002,7 +1017,9 @@ __device__ __forceinline__ uint32_t huf_literals_any(SH &S, const uint8_t *lits,
 // resident waves) serves batches of small rounds, 13 serves 128 KiB blocks.
 // HIGH (with HASH_LOG 13 only) is the higher effort tier (levels >= HIGH_TIER_LEVEL): 8-way buckets, one-step lazy
 // choice, a cost gate on short far matches, in-block repeat offsets.
-template <uint32_t HASH_LOG, bool HIGH = false>
+// WIN (with HIGH only) adds the cross-block window of EncodeArgs::window_log: the near window (the 64 KiB in front of the
+// block go into the bucket table before the scan) and the far window (anchors looked up in the index of k_ldm_index).
+template <uint32_t HASH_LOG, bool HIGH = false, bool WIN = false>
 __global__ __launch_bounds__(64) void k_zstd_encode(EncodeArgs a) {
     constexpr uint32_t HASH_SIZE = 1u << HASH_LOG;
     __shared__ __attribute__((aligned(16))) EncShared<HASH_LOG> S;
@@ -1102,15 +1119,17 @@ __global__ __launch_bounds__(64) void k_zstd_encode(EncodeArgs a) {
         __syncthreads();
         ESTAMP(1);
         // Every block is self-contained: no match reaches in front of the block and no repeat-offset code is
-        // used, so the blocks of a frame can be decoded independently (zstd_decode.hip, block items).  PRE > 0
-        // would seed the block with the bytes in front of it (saves one literal run per block on periodic data).
-        constexpr uint32_t PRE = 0;
+        // used, so the blocks of a frame can be decoded independently (zstd_decode.hip, block items).  With the
+        // window (WIN) the PRE bytes in front of the block — back to the round's start, at most 2^window_log — are
+        // addressable: positions count from inb, the scan starts at PRE, and every read stops at inb, never in
+        // front of the round.
+        const uint32_t PRE = WIN ? suni((uint32_t)(boff < (1ull << a.window_log) ? boff : (1ull << a.window_log))) : 0u;
         const uint8_t *const inb = in - PRE;
         const uint32_t nq = n + PRE;
         uint32_t nseq = 0, lit_total = 0;
         uint32_t anchor = PRE;  // first byte not yet covered by a sequence
         uint32_t emitted = PRE; // wide variant: literal bytes [anchor, emitted) are already written
-        uint32_t base = 0, misses = 0;
+        uint32_t base = PRE, misses = 0;
         bool gave_up = false;  // wide variant: incompressible block recognised early
         const uint32_t scan_end = nq >= 8 ? nq - 7 : 0;  // positions with >= 8 bytes ahead
         if constexpr (HIGH) {
@@ -1126,6 +1145,31 @@ __global__ __launch_bounds__(64) void k_zstd_encode(EncodeArgs a) {
             constexpr uint32_t LMAX = 64;
             uint4 *const B = reinterpret_cast<uint4 *>(S.table);
             uint32_t r0 = 0, r1 = 0, r2 = 0;
+            // far window: this round's region of the index (none: near window only)
+            uint64_t ldm_slot = 0;
+            uint32_t ldm_mask = 0, far_dmax = 0;
+            bool far_on = false;
+            if constexpr (WIN) {
+                constexpr uint32_t NEAR = 64u << 10;  // what the buckets' 16-bit positions reach
+                // near window: the (up to) 64 KiB in front of the block go into the buckets first, oldest first, every 4th
+                // position.  Every position would be 64 Ki insertions for the table's 8 Ki ways: only the newest ~8 KiB
+                // would survive.  A quarter of them keeps most of the prefix reachable, and a repeat of more than a few
+                // bytes still meets an inserted position within its first 4.
+                const uint32_t p0 = PRE > NEAR ? PRE - NEAR : 0u;
+                for (uint32_t b0 = p0; b0 < PRE; b0 += 256) {  // uniform bounds, no early exit
+                    const uint32_t p = b0 + 4 * lane;
+                    if (p < PRE && p + 4 <= nq) {
+                        const uint32_t h = hash4<10>(ld32(inb + p));
+                        const uint4 b = B[h];
+                        B[h] = make_uint4((b.x << 16) | (p & 0xFFFFu), (b.y << 16) | (b.x >> 16), (b.z << 16) | (b.y >> 16), (b.w << 16) | (b.z >> 16));
+                    }
+                }
+                const uint64_t desc = a.ldm ? a.ldm_desc[it.round] : LDM_NONE;
+                far_on = desc != LDM_NONE;
+                ldm_slot = desc & ((1ull << 48) - 1);
+                ldm_mask = (1u << (uint32_t)(desc >> 48)) - 1u;
+                far_dmax = 1u << a.window_log;
+            }
             while (base < scan_end && nseq < max_seq) {
                 const uint32_t pos = base + lane;
                 uint32_t cand = 0, mlen = 0, v = 0, back = 0;
@@ -1247,8 +1291,37 @@ __global__ __launch_bounds__(64) void k_zstd_encode(EncodeArgs a) {
                                 if (k + 1 > score || (i == 0 && k + 1 >= score)) { score = k + 1; mlen = k; cand = cc[8 + i]; pick = 8 + i; }
                             }
                     }
+                    if constexpr (WIN) {
+                        // far window: an anchor looks up the earliest position of its key in the round; a candidate more than
+                        // 64 KiB back (nearer ones are the buckets' job), inside the window and with 32 bytes verified competes
+                        // on length alone
+                        if (far_on && pos + 32 <= nq && ldm_anchor(v)) {
+                            const uint32_t shift = (uint32_t)boff - PRE;  // inb's offset in the round (rounds < 4 GiB)
+                            const uint32_t apos = pos + shift;
+                            const uint32_t F = a.ldm[ldm_slot + (ldm_key(inb + pos) & ldm_mask)];
+                            if (F < apos && apos - F > (64u << 10) && apos - F <= far_dmax && F >= shift) {
+                                const uint32_t fc = F - shift;
+                                const uint32_t lim = nq - pos < LMAX ? nq - pos : LMAX;
+                                uint32_t fl = 0;
+                                bool same = true;
+#pragma unroll
+                                for (uint32_t k = 0; k < LMAX; k += 8)
+                                    if (same && k + 8 <= lim) {
+                                        uint64_t x, y;
+                                        __builtin_memcpy(&x, inb + pos + k, 8);
+                                        __builtin_memcpy(&y, inb + fc + k, 8);
+                                        const uint64_t d = x ^ y;
+                                        if (d) { fl = k + ((uint32_t)(__ffsll((long long)d) - 1) >> 3); same = false; }
+                                        else fl = k + 8;
+                                    }
+                                if (same)
+                                    while (fl < lim && inb[pos + fl] == inb[fc + fl]) fl++;
+                                if (fl >= 32 && fl > mlen) { mlen = fl; cand = fc; pick = 12; }
+                            }
+                        }
+                    }
                     if (mlen && cand >= 8) {  // bytes in front of the match that agree too (up to 8): literals it can take over
-                        if (misses < 8 && pos >= 8 && pos + 16 <= nq) {
+                        if (misses < 8 && pos >= 8 && pos + 16 <= nq && (!WIN || pick != 12)) {
 #pragma unroll
                             for (int w = 0; w < 11; w++)
                                 if (pick == (uint32_t)w) back = bk[w];
@@ -1823,8 +1896,38 @@ __global__ __launch_bounds__(256) void k_gather(GatherArgs g) {
 void launch_encode(const EncodeArgs &a, int grid, bool small_blocks, bool high, hipStream_t s) {
     if (!a.n_items) return;
     if (small_blocks) hipLaunchKernelGGL(k_zstd_encode<11>, dim3(grid), dim3(64), 0, s, a);
+    else if (high && a.window_log) hipLaunchKernelGGL((k_zstd_encode<13, true, true>), dim3(grid), dim3(64), 0, s, a);
     else if (high) hipLaunchKernelGGL((k_zstd_encode<13, true>), dim3(grid), dim3(64), 0, s, a);
     else hipLaunchKernelGGL(k_zstd_encode<13>, dim3(grid), dim3(64), 0, s, a);
+}
+
+// Far window index: every anchor of an indexed round puts its position into its key's bucket of the round's region; the
+// bucket keeps the EARLIEST one (atomicMin), whatever order the workgroups run in.  One workgroup per LDM_CHUNK positions.
+__global__ __launch_bounds__(256) void k_ldm_index(const LdmRound *rl, uint32_t n_rl, const uint8_t *src, const uint64_t *src_off,
+                                                   const uint64_t *len, uint32_t *ldm) {
+    const uint32_t b = blockIdx.x;
+    uint32_t lo = 0, hi = n_rl;  // the last entry whose first chunk is <= b (uniform)
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (rl[mid].first_chunk <= b) lo = mid;
+        else hi = mid;
+    }
+    const LdmRound e = rl[lo];
+    const uint64_t L = len[e.round];
+    const uint8_t *const r = src + src_off[e.round];
+    uint32_t *const region = ldm + (e.desc & ((1ull << 48) - 1));
+    const uint32_t mask = (1u << (uint32_t)(e.desc >> 48)) - 1u;
+    const uint64_t c0 = (uint64_t)(b - e.first_chunk) * LDM_CHUNK;
+    for (uint32_t i = threadIdx.x; i < LDM_CHUNK; i += 256) {  // static stride: every thread runs the same trip count
+        const uint64_t p = c0 + i;
+        if (p + 32 <= L && ldm_anchor(ld32(r + p))) atomicMin(&region[ldm_key(r + p) & mask], (uint32_t)p);
+    }
+}
+
+void launch_ldm_index(const LdmRound *rl, uint32_t n_rl, uint32_t n_chunks, const uint8_t *src, const uint64_t *src_off,
+                      const uint64_t *len, uint32_t *ldm, hipStream_t s) {
+    if (!n_rl || !n_chunks) return;
+    hipLaunchKernelGGL(k_ldm_index, dim3(n_chunks), dim3(256), 0, s, rl, n_rl, src, src_off, len, ldm);
 }
 
 void launch_piece_scan(const uint32_t *piece_len, uint32_t n, uint64_t *local_excl, uint64_t *block_tot, hipStream_t s) {

@@ -79,6 +79,15 @@ class Context:
     def level(self):
         return int(self.L.znippy_ctx_level(self.h))
 
+    def set_window_log(self, window_log):
+        """Opt-in cross-block match window of later encode calls: 0 (default, self-contained blocks) or 17..27
+        (matches up to 2^window_log bytes back inside their round; levels 4-22 only).  See znippy_hip.h."""
+        self._chk(self.L.znippy_ctx_set_window_log(self.h, int(window_log)), "znippy_ctx_set_window_log")
+
+    @property
+    def window_log(self):
+        return int(self.L.znippy_ctx_window_log(self.h))
+
     def set_kernel_timing(self, level):
         """2 = HIP events around every kernel (default), 1 = around the dominant read kernels only, 0 = none."""
         self._chk(self.L.znippy_ctx_set_kernel_timing(self.h, int(level)), "znippy_ctx_set_kernel_timing")

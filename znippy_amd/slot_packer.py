@@ -21,13 +21,15 @@ NUM_SLOTS = 8                  # slot_packer.rs:L31
 
 
 def compress_dir(input_dir, output, no_skip: bool = False, plugin=None, repo: Optional[str] = None, backend=None,
-                 config=None) -> ix.CompressionReport:
+                 config=None, window_log: int = 0) -> ix.CompressionReport:
+    """window_log: 0 (default) or 17..27, the encoder's opt-in cross-block match window (znippy_ctx_set_window_log)."""
     if plugin is not None:
         raise NotImplementedError("metadata plugins are outside the hot path (SURVEY §2 #12)")
-    from .backend import default_backend
+    from .backend import apply_window_log, default_backend
     backend = backend or default_backend()
     config = config or ix.CONFIG
     backend.set_level(config.compression_level)  # CompressCtx::new(CONFIG.compression_level), stream_packer.rs:L217 / slot_packer.rs:L551
+    apply_window_log(backend, window_log)
     input_dir = str(input_dir)
     total_dirs = 0
     all_files = []

@@ -37,11 +37,12 @@ class _Sender:
 
 
 class StreamCompressor:  # stream_packer.rs:L58-76
-    def __init__(self, output: str, no_skip: bool, backend=None, config=None):
+    def __init__(self, output: str, no_skip: bool, backend=None, config=None, window_log: int = 0):
         self._output = output
         self._no_skip = no_skip
         self._backend = backend
         self._config = config or ix.CONFIG
+        self._window_log = window_log
         self._entries: List[ArchiveEntry] = []
         self._finished = False
 
@@ -52,11 +53,13 @@ class StreamCompressor:  # stream_packer.rs:L58-76
         if self._finished:
             raise RuntimeError("already finished")
         self._finished = True
-        return run_pipeline(self._entries, self._output, self._no_skip, self._backend, self._config)
+        return run_pipeline(self._entries, self._output, self._no_skip, self._backend, self._config,
+                            window_log=self._window_log)
 
 
-def compress_stream(output: str, no_skip: bool = False, backend=None, config=None) -> StreamCompressor:
-    return StreamCompressor(str(output), no_skip, backend, config)
+def compress_stream(output: str, no_skip: bool = False, backend=None, config=None, window_log: int = 0) -> StreamCompressor:
+    """window_log: 0 (default) or 17..27, the encoder's opt-in cross-block match window (znippy_ctx_set_window_log)."""
+    return StreamCompressor(str(output), no_skip, backend, config, window_log)
 
 
 def with_extension(path: str, ext: str) -> str:
@@ -124,16 +127,17 @@ def encode_round_range(rounds, entries, backend, lo, hi):
     return cols, b"".join(parts)
 
 
-def run_pipeline(entries, output, no_skip, backend=None, config=None) -> ix.CompressionReport:
+def run_pipeline(entries, output, no_skip, backend=None, config=None, window_log: int = 0) -> ix.CompressionReport:
     """Single process: all rounds.  Inside an initialised torch.distributed group every rank encodes a contiguous
     range of the rounds balanced by bytes (its GPU's share), rank 0 concatenates the payload regions in rank order —
     blob offsets are a running sum, so rebasing a region is one addition — and writes the archive; the
     report is the same on every rank.  Every rank is handed the same entries."""
-    from .backend import default_backend
+    from .backend import apply_window_log, default_backend
     from .sharding import split_rows
     backend = backend or default_backend()
     config = config or ix.CONFIG
     backend.set_level(config.compression_level)  # CompressCtx::new(CONFIG.compression_level), stream_packer.rs:L217 / slot_packer.rs:L551
+    apply_window_log(backend, window_log)
     output_path = with_extension(output, "znippy")  # L132
     rounds, (uf, ub, cf, cb) = plan_rounds(entries, no_skip)
     rank, world = 0, 1
