@@ -6,7 +6,7 @@ mixed archive, foreign frames of the batch and resolve paths with damaged ones a
 a random write-side round table, and four lagged runs over two output buffers.  Expected results come from the oracle's read
 and write loops (decompress.rs:L135-190, stream_packer.rs:L217-284) and do not depend on the switch.
 
-Left out on purpose: ZNIPPY_FZ_ONLY (changes verdicts by design), NOHASH, the diagnostics (DBG, DDBG, EDBG, TDBG, TRACE),
+Left out on purpose: ZNIPPY_FZ_ONLY (changes verdicts by design), NOHASH, the diagnostics (DBG, EDBG, TDBG, TRACE),
 KTIME and LDS_PAD."""
 import numpy as np
 import pytest
@@ -39,6 +39,7 @@ SWITCH_SETS = [
     ("no_fuse_hash", {"ZNIPPY_NO_FUSE_HASH": "1"}),
     ("gen_share_1", {"ZNIPPY_GEN_SHARE": "1"}),
     ("gen_share_4", {"ZNIPPY_GEN_SHARE": "4"}),
+    ("ddbg", {"ZNIPPY_DDBG": "1"}),
 ]
 
 

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <vector>
 #include <unordered_map>
@@ -135,6 +136,10 @@ struct znippy_ctx {
     int live_tables = 0;
     bool closing = false;
     unsigned long long *clk_buf = nullptr;  // diagnostic (ZNIPPY_DBG & 32768): shader cycles / 100 MHz ticks of one wave
+    // diagnostic (ZNIPPY_DBG & 8, ZNIPPY_DDBG, ZNIPPY_EDBG): phase stamps of the previous launch of a kernel, one buffer per
+    // kind, allocated at first use on this context's device (diag_cycle)
+    enum Diag { DIAG_FUSED, DIAG_ITEMS, DIAG_FZ, DIAG_GENERAL, DIAG_BX, DIAG_ENCODE, DIAG_N };
+    unsigned long long *diag[DIAG_N] = {};
 };
 
 static void read_switches(znippy_ctx *ctx) {
@@ -354,6 +359,35 @@ static void free_plan(znippy_ctx *ctx, DevPlan &d) {
     d = DevPlan();
 }
 
+// The control block of a row table (znippy_rows::ctl): ONE allocation, cleared (or preset from status_init) by ONE stream
+// operation per run.  The regions below, then from CTL_HEAD on the status column (n x i32).  The first CTL_MIRROR bytes
+// travel to the host mirror (h_counters) behind every run.
+struct CtlRegion { size_t at, bytes; };
+constexpr CtlRegion CTL_COUNTERS{0, 8 * 8};    // u64: k_verify's counters; [CTL_FLAG] != 0: a lean run left something on a list (rows_settle)
+constexpr CtlRegion CTL_HAND{64, 16 * 4};      // u32: hand-over counts, indexed by Hand
+constexpr CtlRegion CTL_CURSORS{128, 16 * 4};  // u32: work cursors, indexed by Cursor
+constexpr CtlRegion CTL_FZ_POOL{192, 8 * 8};   // u64: pool counters of the two-phase path (FzArgs::pool_used)
+constexpr CtlRegion CTL_BX_POOL{256, 16 * 8};  // u64: pool counters of the batch path (BxArgs::pool_used)
+constexpr CtlRegion CTL_BX_CTR{384, 16 * 4};   // u32: its work counters (BxArgs::ctr)
+constexpr CtlRegion CTL_RX{448, 16 * 4};       // u32: words left after each resolve round (BxArgs::rx_pending, RX_ROUNDS of them); [RX_ZERO] is never written
+constexpr size_t CTL_HEAD = 512, CTL_MIRROR = 128, CTL_FLAG = 7;
+constexpr uint32_t RX_ZERO = 15;
+enum Hand : uint32_t {  // length of a list one kernel leaves to another; the mirror tells the next run's plan which were empty
+    H_FUSED = 0,    // rows handed over by the fused kernels (pending)
+    H_SERIAL = 1,   // rows for the serial decoder (pending2)
+    H_ITEMS = 2,    // block items left by the fused block kernel (todo)
+    H_TILES = 3,    // tiles left by the role-split kernel (slow_list)
+    H_FLAGGED = 5,  // block candidates left flagged for the batch path: k_finish_blocks counts them at ITS pending_count (H_SERIAL) + 4
+};
+enum Cursor : uint32_t { CUR_GENERAL = 0, CUR_ROLES = 2, CUR_ITEMS = 4, CUR_FALLBACK = 8, CUR_FZ = 12, CUR_FZ_WORK = 13 };  // CUR_FZ_WORK: the two-phase path's work count
+// the lists a lean run must have left empty (k_verify's mask over the hand-over counts): small rows / big multi-block rows
+constexpr uint32_t LEAN_ANY = 1u << H_FUSED | 1u << H_SERIAL | 1u << H_FLAGGED, LEAN_SMALL = LEAN_ANY | 1u << H_TILES, LEAN_BLOCKS = LEAN_ANY | 1u << H_ITEMS;
+constexpr bool ctl_before(CtlRegion a, CtlRegion b) { return a.at + a.bytes <= b.at; }
+static_assert(ctl_before(CTL_COUNTERS, CTL_HAND) && ctl_before(CTL_HAND, CTL_CURSORS) && ctl_before(CTL_CURSORS, CTL_FZ_POOL) && ctl_before(CTL_FZ_POOL, CTL_BX_POOL) &&
+              ctl_before(CTL_BX_POOL, CTL_BX_CTR) && ctl_before(CTL_BX_CTR, CTL_RX) && CTL_RX.at + CTL_RX.bytes <= CTL_HEAD, "control block: regions overlap or pass the head");
+static_assert(CTL_COUNTERS.at == 0 && CTL_HAND.at == CTL_COUNTERS.bytes && CTL_MIRROR == CTL_HAND.at + CTL_HAND.bytes, "the mirror is exactly counters + hand-over counts");
+static_assert(CTL_FLAG < 8 && H_FLAGGED == H_SERIAL + 4 && H_FLAGGED < 8 && CUR_FZ_WORK < 16 && zn::RX_ROUNDS <= RX_ZERO && RX_ZERO < 16, "control block: a word outside its region");
+
 struct znippy_rows {
     znippy_ctx *ctx = nullptr;
     uint64_t row_begin = 0;
@@ -364,25 +398,24 @@ struct znippy_rows {
     uint32_t *h_pack = nullptr, *d_pack = nullptr;  // front-to-back tables: the two size columns as 32-bit values (page-locked / device)
     size_t h_pack_cap = 0;
     unsigned long long *d_pack_sums = nullptr;
-    // One allocation, cleared (or preset) by ONE stream operation per run: [counters 8 x u64][hand-over counts 16 x u32]
-    // [work cursors 16 x u32][pad 64 B][status n x i32]
-    uint8_t *ctl = nullptr;
-    static constexpr size_t CTL_HEAD = 512;  // [256, 384): pool counters of the batch path (16 x u64), [384, 448): its work counters (16 x u32)
+    uint8_t *ctl = nullptr;  // the control block (layout: CtlRegion above)
     size_t ctl_bytes = 0;
+    template <class T> T *ctl_at(CtlRegion g, size_t i = 0) const { return reinterpret_cast<T *>(ctl + g.at) + i; }
+    uint32_t *hand(Hand h) const { return ctl_at<uint32_t>(CTL_HAND, h); }
+    uint32_t *cur(Cursor c) const { return ctl_at<uint32_t>(CTL_CURSORS, c); }
     int32_t *status = nullptr;
     uint32_t *digests = nullptr;
     uint64_t *counters = nullptr;
-    uint32_t *cursor = nullptr;
     // pinned mirror of the counters, filled by the run's own D2H copy.  Two slots + one event each: run k uses slot
     // k & 1, so the counters of run k can be read while run k + 1 is already executing (znippy_rows_results_lagged)
-    uint64_t *h_counters = nullptr;  // per slot 16 x u64: the counters, then the 16 hand-over counts (u32)
+    uint64_t *h_counters = nullptr;  // per slot CTL_MIRROR bytes (16 x u64): the counters, then the 16 hand-over counts (u32)
+    const uint32_t *mirror_hand(unsigned slot) const { return reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(h_counters + 16 * slot) + CTL_HAND.at); }
     size_t h_counters_cap = 0;
     // Does the batch path have anything to do?  Its six launches cost ~0.1 ms even when every list is empty (the BASELINE
     // archives: every row is taken by the fused kernels), so a table remembers what its last finished run found: -1 not
     // known yet (launch it), 0 nothing handed over (the serial decoder alone stands behind the fused kernels, as a
     // safety net), 1 something was.
     int bx_hint = -1;
-    uint64_t hint_seq = 0;  // runs whose mirror has been looked at
     // Lean runs.  A table of small rows whose last finished run left nothing behind the role-split kernel — no tile on its
     // list, no row handed over — is run as memset + that kernel + verify: the three launches behind it (left-over tiles,
     // serial decoder, second hash pass) cost ~25 us of a 0.5 ms step for looking at empty lists.  The verify kernel checks
@@ -396,7 +429,6 @@ struct znippy_rows {
     bool small_ok = false, small_off = false;  // the fused kernels handed over every row: later runs skip them (all_rows = the batch path's list)
     uint32_t *all_rows = nullptr;
     int lean_hint2 = -1;
-    bool last_lean = false;
     struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; } run_args[2];  // per mirror slot: what the run was given
     hipEvent_t ev_done[2] = {nullptr, nullptr};
     uint64_t run_seq = 0;  // async runs queued so far
@@ -420,8 +452,7 @@ struct znippy_rows {
     uint32_t *list_a = nullptr;   // compressed rows with > 64 leaves: general decoder
     uint32_t n_list_a = 0;
     bool wide_rows = false;       // big rows average >= 1 MiB: 1024-thread workgroups
-    uint32_t *pending = nullptr;  // rows the fused kernel hands over (+ its counter)
-    uint32_t *pending_count = nullptr;
+    uint32_t *pending = nullptr;  // rows the fused kernel hands over (count: H_FUSED)
     // block items: compressed rows of >= 2 blocks are tried block by block first
     uint32_t n_cand = 0, n_items = 0;
     uint32_t *cand_row = nullptr, *cand_base = nullptr, *cand_nblocks = nullptr, *pending2 = nullptr;
@@ -449,9 +480,9 @@ struct znippy_rows {
     uint32_t *bt_tile = nullptr, *bt_item = nullptr;
     uint8_t *tile_done = nullptr, *item_done = nullptr;  // one allocation (item_done lies behind tile_done)
     size_t done_bytes = 0;
-    uint32_t *todo = nullptr;  // items left to the block decoder (count: third word of the control block)
+    uint32_t *todo = nullptr;  // items left to the block decoder (count: H_ITEMS)
     uint32_t n_small_tiles = 0;     // tiles of whole small rows (the fused kernels' work)
-    uint32_t *slow_list = nullptr;  // tiles the role-split kernel leaves to k_fused_small (count: fourth word of the control block)
+    uint32_t *slow_list = nullptr;  // tiles the role-split kernel leaves to k_fused_small (count: H_TILES)
     DevPlan plan;
 };
 
@@ -529,6 +560,42 @@ static void ktime_end(znippy_ctx *ctx, hipStream_t on = nullptr) {
     if (!ctx->ktime_open) return;
     (void)hipEventRecord(ctx->ktimes[ctx->n_ktimes].t1, on ? on : ctx->stream);
     ctx->n_ktimes++;
+}
+
+// one bracketed launch (the callable is inlined: no allocation, nothing virtual on the 0.5 ms step)
+template <class F>
+static inline void timed(znippy_ctx *ctx, const char *name, hipStream_t on, F &&launch) {
+    ktime_begin(ctx, name, on);
+    launch();
+    ktime_end(ctx, on);
+}
+// Diagnostic stamps of a kernel kind (N words, in the context: allocated at first use on ITS device, freed with it).  Waits for
+// the given streams (s1 may be null), hands the previous launch's stamps to `print`, clears them and returns the device buffer
+// for the next launch's argument struct.
+template <size_t N, class Print>
+static unsigned long long *diag_cycle(znippy_ctx *ctx, znippy_ctx::Diag which, hipStream_t s0, hipStream_t s1, Print print) {
+    unsigned long long *&d = ctx->diag[which];
+    if (!d) { (void)hipMalloc(&d, 8 * N); (void)hipMemset(d, 0, 8 * N); }
+    unsigned long long h[N];
+    (void)hipStreamSynchronize(s0);
+    if (s1) (void)hipStreamSynchronize(s1);
+    (void)hipMemcpy(h, d, 8 * N, hipMemcpyDeviceToHost);
+    print(h);
+    (void)hipMemset(d, 0, 8 * N);
+    return d;
+}
+
+// what the caller gave a run; preset != 0: the status column starts as the host's verdicts (rows_validate found bad rows); slot: its mirror slot and event
+struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; };
+// the ten row columns every decode path's argument struct has under the same names (BlockScanArgs: all but `out`)
+static void set_out(BlockScanArgs &, uint8_t *) {}
+template <class A> static void set_out(A &a, uint8_t *out) { a.out = out; }
+template <class A>
+static void fill_row_args(A &a, const znippy_rows *r, const RowsRun &run) {
+    a.blobs = (const uint8_t *)run.d_blobs; a.blob_base = run.blob_base;
+    a.blob_off = r->blob_off; a.blob_size = r->blob_size; a.usize = r->usize; a.out_off = r->out_off;
+    a.out_cap = run.out_cap; a.status = r->status; a.preset = run.preset;
+    set_out(a, (uint8_t *)run.d_out);
 }
 
 template <class T>
@@ -863,22 +930,10 @@ static void ctx_teardown(znippy_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &k : ctx->ktimes) { (void)hipEventDestroy(k.t0); (void)hipEventDestroy(k.t1); }
-    if (ctx->lit_scratch) (void)hipFree(ctx->lit_scratch);
-    if (ctx->lit_scratch_b) (void)hipFree(ctx->lit_scratch_b);
-    if (ctx->fz_lit_pool) (void)hipFree(ctx->fz_lit_pool);
-    if (ctx->fz_seq_pool) (void)hipFree(ctx->fz_seq_pool);
-    if (ctx->bx_fse_pool) (void)hipFree(ctx->bx_fse_pool);
-    if (ctx->bx_huf_pool) (void)hipFree(ctx->bx_huf_pool);
-    if (ctx->rx_pool) (void)hipFree(ctx->rx_pool);
-    if (ctx->rx_chunk) (void)hipFree(ctx->rx_chunk);
-    if (ctx->rx_cdone) (void)hipFree(ctx->rx_cdone);
-    if (ctx->cursor) (void)hipFree(ctx->cursor);
-    if (ctx->shim_in) (void)hipFree(ctx->shim_in);
-    if (ctx->shim_out) (void)hipFree(ctx->shim_out);
-    if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
-    if (ctx->enc_seq) (void)hipFree(ctx->enc_seq);
-    if (ctx->enc_tabs) (void)hipFree(ctx->enc_tabs);
-    if (ctx->ldm) (void)hipFree(ctx->ldm);
+    void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor,
+                   ctx->clk_buf, ctx->shim_in, ctx->shim_out, ctx->enc_prov, ctx->enc_seq, ctx->enc_tabs, ctx->ldm};
+    for (void *p : dev) if (p) (void)hipFree(p);
+    for (unsigned long long *d : ctx->diag) if (d) (void)hipFree(d);
     if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }
     if (ctx->copy) { (void)hipStreamSynchronize(ctx->copy); (void)hipStreamDestroy(ctx->copy); }
     for (auto &e : ctx->pinned_pool) (void)hipHostFree(e.second);
@@ -918,8 +973,8 @@ int znippy_rows_foreign_stats(znippy_ctx *ctx, znippy_rows *r, uint64_t stats[8]
     if (!ctx || !r || r->ctx != ctx || !stats) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    // the path that ran for this table: the batch path's counters sit at +256, the round-2 two-phase path's at +192
-    HIPCHK(ctx, hipMemcpy(stats, r->ctl + (r->bx_slots ? 256 : 192), 64, hipMemcpyDeviceToHost));
+    // the pool counters of the path that ran for this table: the batch path's or the round-2 two-phase path's
+    HIPCHK(ctx, hipMemcpy(stats, r->ctl + (r->bx_slots ? CTL_BX_POOL : CTL_FZ_POOL).at, 64, hipMemcpyDeviceToHost));
     return ZNIPPY_OK;
 }
 
@@ -1041,6 +1096,180 @@ void znippy_rows_destroy(znippy_rows *r) {
     table_released(c);
 }
 
+struct RowCols {  // the caller's columns from row_begin on (host memory)
+    const uint64_t *bo, *bs, *us, *oo;
+    const uint8_t *bitmap;
+    uint64_t row_begin, row_end;
+    bool allc;  // every row compressed (the usual archive): the per-row passes skip the bit column
+    uint32_t comp(uint32_t i) const { if (allc) return 1u; const uint64_t row = row_begin + i; return (bitmap[row >> 3] >> (row & 7)) & 1u; }
+};
+struct RowClasses {  // what the pass over the columns finds about the compressed rows above 64 KiB (rows_classify)
+    std::vector<uint32_t> la, cand_row, cand_base, cand_nb, item_row, item_k, fz_base, fz_cap, fz_it_cand;
+    uint64_t big_bytes = 0, big_blob = 0, n_big = 0, nblk = 0;
+};
+
+// the columns as they are (the device derives the byte-per-row flags and the stored rows' lengths), then the checksums
+static int rows_columns_h2d(znippy_ctx *ctx, znippy_rows *r, const RowCols &c, const uint8_t *checksum, TDbg &td) {
+    const uint32_t n = r->n;
+    int rc = ZNIPPY_OK;
+    const uint64_t bm0 = c.row_begin >> 3, bm1 = (c.row_end + 7) >> 3;  // (d_bitmap is kept until the table goes: k_rows_fixup reads it on the stream, uploads are not stream-ordered)
+    // A table written front to back is its two size columns (zn_rows_pack32): 8 bytes per row go to the device, from
+    // page-locked memory, and three small kernels make the four 64-bit columns there.  (The four pageable copies of 0.8 MB
+    // each were 0.18 of the 0.36 ms a table of 100k rows took to build.)
+    bool packed = false;
+    if (n >= 64 && !ctx->sw.no_pack) {
+        r->h_pack = (uint32_t *)pinned_take(ctx, 8 * (size_t)n, &r->h_pack_cap);
+        if (r->h_pack && zn_rows_pack32(c.bo, c.bs, c.oo, c.us, n, r->h_pack)) {
+            const uint32_t nblk = (n + 1023) / 1024;
+            if (tmalloc(ctx, &r->d_pack, 8 * (size_t)n) != hipSuccess || tmalloc(ctx, &r->d_pack_sums, 16 * (size_t)nblk) != hipSuccess ||
+                tmalloc(ctx, &r->blob_off, 8 * (size_t)n) != hipSuccess || tmalloc(ctx, &r->blob_size, 8 * (size_t)n) != hipSuccess ||
+                tmalloc(ctx, &r->usize, 8 * (size_t)n) != hipSuccess || tmalloc(ctx, &r->out_off, 8 * (size_t)n) != hipSuccess ||
+                hipMemcpyAsync(r->d_pack, r->h_pack, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+                return ZNIPPY_E_NOMEM;
+            hipLaunchKernelGGL(k_rows_unpack_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->d_pack, r->d_pack + n, n, r->d_pack_sums);
+            hipLaunchKernelGGL(k_rows_unpack_scan, dim3(1), dim3(256), 0, ctx->stream, r->d_pack_sums, nblk);
+            hipLaunchKernelGGL(k_rows_unpack_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->d_pack, r->d_pack + n, n, r->d_pack_sums, c.bo[0], c.oo[0],
+                               r->blob_off, r->blob_size, r->out_off, r->usize);
+            packed = true;
+        }
+    }
+    if ((!packed && ((rc = dev_upload(ctx, &r->blob_off, c.bo, n)) || (rc = dev_upload(ctx, &r->blob_size, c.bs, n)) ||
+                     (rc = dev_upload(ctx, &r->usize, c.us, n)) || (rc = dev_upload(ctx, &r->out_off, c.oo, n)))) ||
+        (c.bitmap && (rc = dev_upload(ctx, &r->d_bitmap, c.bitmap + bm0, (size_t)(bm1 - bm0)))) ||
+        tmalloc(ctx, &r->compressed, std::max<size_t>(n, 16)) != hipSuccess)
+        return rc ? rc : ZNIPPY_E_NOMEM;
+    if (n) hipLaunchKernelGGL(k_rows_fixup, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, r->d_bitmap, c.row_begin - 8 * bm0, n, r->compressed, r->usize, r->blob_size);
+    td.mark("columns_h2d");
+    if (checksum && (rc = dev_upload(ctx, &r->checksum, checksum + 32 * c.row_begin, (size_t)32 * n))) return rc;
+    td.mark("checksum_h2d");
+    return ZNIPPY_OK;
+}
+
+// ONE pass over the caller's columns: the flags the runs need, the extents a run is validated against (rows_validate: a
+// table whose extents fit the run's regions has no bad row — the per-row pass is for the others), and the big rows.
+// Compressed rows above 64 KiB: frames of >= 2 blocks (and < 4 GiB) are tried block by block (each block a work item),
+// the others go straight to the general decoder.
+static void rows_classify(const znippy_ctx *ctx, znippy_rows *r, const RowCols &c, RowClasses &k) {
+    constexpr uint64_t BLK = 128 * 1024;
+    const uint32_t n = r->n;
+    if (c.allc) {  // the vectorised pass; the row-by-row one below only if the table has big rows
+        uint64_t e[8];
+        zn_rows_extents(c.bo, c.bs, c.oo, c.us, n, e);
+        if (e[6] == 0) {
+            r->ext_min_bo = e[0]; r->ext_max_bend = e[1]; r->ext_max_oend = e[2]; r->ext_wrap = e[3] != 0;
+            r->n_compressed = n; r->bx_bytes = e[4]; k.nblk = e[5];
+            return;
+        }
+    }
+    uint64_t min_bo = ~0ull, max_bend = 0, max_oend = 0;
+    bool wrap = false;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t comp = c.comp(i);
+        const uint64_t bo = c.bo[i], bs = c.bs[i], oo = c.oo[i], us = comp ? c.us[i] : bs;
+        r->n_compressed += comp;
+        if (!comp && (oo & 15)) r->odd_out = true;
+        min_bo = std::min(min_bo, bo);
+        wrap |= bo + bs < bo || oo + us < oo;
+        max_bend = std::max(max_bend, bo + bs);
+        max_oend = std::max(max_oend, oo + us);
+        if (!comp) continue;
+        k.nblk += us ? (us + BLK - 1) / BLK : 1;
+        r->bx_bytes += us;
+        if (us > 65536 && us < (1ull << 30)) r->rx_words_small += (us + 1023) & ~1023ull;
+        if (us >= zn::RX_MIN && us < (1ull << 30)) r->rx_words += (us + 1023) & ~1023ull;
+        if (us <= 64 * 1024) continue;
+        k.big_bytes += us;
+        k.big_blob += bs;
+        k.n_big++;
+        const uint64_t nb = (us + BLK - 1) / BLK;
+        if (nb >= 2 && us < 0xFFFFFFFFull && k.item_row.size() + nb < 0x7FFFFFFFull && !ctx->sw.no_block_items) {
+            k.cand_row.push_back(i);
+            k.cand_base.push_back((uint32_t)k.item_row.size());
+            k.cand_nb.push_back((uint32_t)nb);
+            for (uint32_t b = 0; b < nb; b++) { k.item_row.push_back(i); k.item_k.push_back(b); }
+            if (!ctx->sw.no_fz && ctx->sw.no_bx && k.fz_it_cand.size() + 2 * nb + 8 < 0x7FFFFFFFull) {
+                const uint32_t cap = (uint32_t)(2 * nb + 8);
+                k.fz_base.push_back((uint32_t)k.fz_it_cand.size());
+                k.fz_cap.push_back(cap);
+                k.fz_it_cand.insert(k.fz_it_cand.end(), cap, (uint32_t)k.cand_row.size() - 1);
+                r->fz_bytes += us;
+            } else { k.fz_base.push_back(0); k.fz_cap.push_back(0); }
+        } else k.la.push_back(i);
+    }
+    r->ext_min_bo = min_bo; r->ext_max_bend = max_bend; r->ext_max_oend = max_oend; r->ext_wrap = wrap;
+}
+
+// what the block-item path, the batch path and the serial decoder tell each other about a row, the serial decoder's list,
+// and the batch / resolve paths' per-table buffers
+static int rows_batch_buffers(znippy_ctx *ctx, znippy_rows *r, uint64_t nblk) {
+    if (tmalloc(ctx, &r->row_flag, std::max<size_t>(4 * (size_t)r->n, 16)) != hipSuccess ||
+        tmalloc(ctx, &r->pending2, std::max<size_t>(4 * (size_t)r->n_compressed, 16)) != hipSuccess)
+        return ZNIPPY_E_NOMEM;
+    if (ctx->sw.no_bx) return ZNIPPY_OK;
+    // a writer may split blocks (libzstd's high levels cut a 128 KiB block into 2-5; runs of equal bytes come as
+    // strings of small RLE blocks): half as many again + up to 64k more, shared by all frames.  Frames that find no
+    // slot stay with the serial decoder.
+    r->bx_nblk = nblk;
+    if (r->rx_words_small && r->rx_words_small <= (256ull << 20)) { r->rx_min = 65537; r->rx_words = r->rx_words_small; }
+    const uint64_t cap = nblk + nblk / 2 + std::min<uint64_t>(3 * nblk, 65536) + 1024;
+    if (cap >= 0x7FFFFFFFull) return ZNIPPY_OK;
+    r->bx_slots = r->n_compressed;
+    r->bx_item_cap = (uint32_t)cap;
+    if (tmalloc(ctx, &r->bx_cand_row, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_cand_base, 4 * (size_t)r->bx_slots) != hipSuccess ||
+        tmalloc(ctx, &r->bx_cand_nb, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_huf_list, 4 * (size_t)cap) != hipSuccess ||
+        tmalloc(ctx, &r->bx_seq_list, 4 * 4 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->bx_sort_tmp, 5 * 4 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->bx_items, sizeof(zn::FzItem) * (size_t)cap) != hipSuccess ||
+        tmalloc(ctx, &r->bx_prep, sizeof(zn::BxPrep) * (size_t)cap) != hipSuccess ||
+        ((r->rx_words || r->rx_words_small) && !ctx->sw.no_rx &&
+         (tmalloc(ctx, &r->rx_base, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->rx_fail, 4 * (size_t)r->bx_slots) != hipSuccess ||
+          tmalloc(ctx, &r->rx_blk, 16 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->rx_list, 4 * (size_t)cap) != hipSuccess)))
+        return ZNIPPY_E_NOMEM;
+    return ZNIPPY_OK;
+}
+// block items: the candidates, their items, and the round-2 two-phase path's item slots
+static int rows_item_buffers(znippy_ctx *ctx, znippy_rows *r, const RowClasses &k) {
+    int rc;
+    if ((rc = dev_upload(ctx, &r->cand_row, k.cand_row.data(), k.cand_row.size())) ||
+        (rc = dev_upload(ctx, &r->cand_base, k.cand_base.data(), k.cand_base.size())) ||
+        (rc = dev_upload(ctx, &r->cand_nblocks, k.cand_nb.data(), k.cand_nb.size())) ||
+        (rc = dev_upload(ctx, &r->item_row, k.item_row.data(), k.item_row.size())) ||
+        (rc = dev_upload(ctx, &r->item_k, k.item_k.data(), k.item_k.size())))
+        return rc;
+    if (tmalloc(ctx, &r->item_src, 4 * (size_t)r->n_items) != hipSuccess) return ZNIPPY_E_NOMEM;
+    r->fz_total = (uint32_t)k.fz_it_cand.size();
+    if (!r->fz_total) return ZNIPPY_OK;
+    if ((rc = dev_upload(ctx, &r->fz_base, k.fz_base.data(), k.fz_base.size())) ||
+        (rc = dev_upload(ctx, &r->fz_cap, k.fz_cap.data(), k.fz_cap.size())) ||
+        (rc = dev_upload(ctx, &r->fz_it_cand, k.fz_it_cand.data(), k.fz_it_cand.size())))
+        return rc;
+    if (tmalloc(ctx, &r->fz_nb, 4 * (size_t)r->n_cand) != hipSuccess || tmalloc(ctx, &r->fz_work, 4 * (size_t)r->fz_total) != hipSuccess ||
+        tmalloc(ctx, &r->fz_items, sizeof(zn::FzItem) * (size_t)r->fz_total) != hipSuccess)
+        return ZNIPPY_E_NOMEM;
+    return ZNIPPY_OK;
+}
+// fused block kernel: the big-slice tiles of the candidate rows and the item each belongs to
+static int rows_fused_block_buffers(znippy_ctx *ctx, znippy_rows *r, const RowClasses &k, const PlanBuf &p) {
+    std::vector<uint32_t> row_base(r->n, 0xFFFFFFFFu), bt_tile, bt_item;
+    for (size_t c = 0; c < k.cand_row.size(); c++) row_base[k.cand_row[c]] = k.cand_base[c];
+    for (uint32_t ti = 0; ti < (uint32_t)p.tiles.size(); ti++) {
+        const Tile &t = p.tiles[ti];
+        if (t.n_units == 0 && row_base[t.first_unit] != 0xFFFFFFFFu) {
+            bt_tile.push_back(ti);
+            bt_item.push_back(row_base[t.first_unit] + (t.first_leaf >> 7));
+        }
+    }
+    r->n_bt = (uint32_t)bt_tile.size();
+    int rc;
+    if ((rc = dev_upload(ctx, &r->bt_tile, bt_tile.data(), bt_tile.size())) || (rc = dev_upload(ctx, &r->bt_item, bt_item.data(), bt_item.size()))) return rc;
+    // (the two arrays of done flags in one allocation: one clear per run instead of two)
+    const size_t td_bytes = (std::max<size_t>(p.tiles.size(), 16) + 15) & ~(size_t)15;
+    r->done_bytes = td_bytes + std::max<size_t>(r->n_items, 16);
+    if (tmalloc(ctx, &r->tile_done, r->done_bytes) != hipSuccess ||
+        tmalloc(ctx, &r->todo, std::max<size_t>(4 * (size_t)r->n_items, 16)) != hipSuccess)
+        return ZNIPPY_E_NOMEM;
+    r->item_done = r->tile_done + td_bytes;
+    return ZNIPPY_OK;
+}
+
 int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint64_t *blob_size,
                        const uint8_t *compressed_bitmap, const uint64_t *uncompressed_size,
                        const uint64_t *out_offset, const uint8_t *checksum, uint64_t row_begin,
@@ -1051,258 +1280,66 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
     if (row_end - row_begin >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TDbg td(ctx->sw.tdbg, "rows_create");
-    znippy_rows *r = new znippy_rows();
+    std::unique_ptr<znippy_rows, void (*)(znippy_rows *)> guard(new znippy_rows(), znippy_rows_destroy);  // every failure below: return
+    znippy_rows *const r = guard.get();
     r->ctx = ctx;
     ctx->live_tables++;
     r->row_begin = row_begin;
     r->n = (uint32_t)(row_end - row_begin);
     const uint32_t n = r->n;
-    const uint64_t *const bo_in = blob_offset + row_begin, *const bs_in = blob_size + row_begin, *const us_in = uncompressed_size + row_begin,
-                   *const oo_in = out_offset + row_begin;
-    bool allc = true;  // every row compressed (the usual archive): the per-row passes skip the bit column
+    bool allc = true;
     if (compressed_bitmap) {
         uint64_t row = row_begin;
         for (; row < row_end && (row & 7); row++) allc &= (compressed_bitmap[row >> 3] >> (row & 7)) & 1;
         for (; row + 8 <= row_end && allc; row += 8) allc &= compressed_bitmap[row >> 3] == 0xFF;
         for (; row < row_end && allc; row++) allc &= (compressed_bitmap[row >> 3] >> (row & 7)) & 1;
     }
-    auto comp_of = [&](uint32_t i) -> uint32_t { if (allc) return 1u; const uint64_t row = row_begin + i; return (compressed_bitmap[row >> 3] >> (row & 7)) & 1u; };
-    // a stored row IS its blob (see k_rows_fixup): its effective length is blob_size
-    auto len_of = [&](uint32_t i) -> uint64_t { return comp_of(i) ? us_in[i] : bs_in[i]; };
-    int rc = ZNIPPY_OK;
-    // the columns as they are (the device derives the byte-per-row flags and the stored rows' lengths)
-    uint8_t *&d_bitmap = r->d_bitmap;  // (kept until the table goes: k_rows_fixup reads it on the stream, uploads are not stream-ordered)
-    const uint64_t bm0 = row_begin >> 3, bm1 = (row_end + 7) >> 3;
-    // A table written front to back is its two size columns (zn_rows_pack32): 8 bytes per row go to the device, from
-    // page-locked memory, and three small kernels make the four 64-bit columns there.  (The four pageable copies of 0.8 MB
-    // each were 0.18 of the 0.36 ms a table of 100k rows took to build.)
-    bool packed = false;
-    if (n >= 64 && !ctx->sw.no_pack) {
-        r->h_pack = (uint32_t *)pinned_take(ctx, 8 * (size_t)n, &r->h_pack_cap);
-        if (r->h_pack && zn_rows_pack32(bo_in, bs_in, oo_in, us_in, n, r->h_pack)) {
-            const uint32_t nblk = (n + 1023) / 1024;
-            if (tmalloc(ctx, &r->d_pack, 8 * (size_t)n) == hipSuccess && tmalloc(ctx, &r->d_pack_sums, 16 * (size_t)nblk) == hipSuccess &&
-                tmalloc(ctx, &r->blob_off, 8 * (size_t)n) == hipSuccess && tmalloc(ctx, &r->blob_size, 8 * (size_t)n) == hipSuccess &&
-                tmalloc(ctx, &r->usize, 8 * (size_t)n) == hipSuccess && tmalloc(ctx, &r->out_off, 8 * (size_t)n) == hipSuccess &&
-                hipMemcpyAsync(r->d_pack, r->h_pack, 8 * (size_t)n, hipMemcpyHostToDevice, ctx->stream) == hipSuccess) {
-                hipLaunchKernelGGL(k_rows_unpack_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->d_pack, r->d_pack + n, n, r->d_pack_sums);
-                hipLaunchKernelGGL(k_rows_unpack_scan, dim3(1), dim3(256), 0, ctx->stream, r->d_pack_sums, nblk);
-                hipLaunchKernelGGL(k_rows_unpack_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->d_pack, r->d_pack + n, n, r->d_pack_sums, bo_in[0], oo_in[0],
-                                   r->blob_off, r->blob_size, r->out_off, r->usize);
-                packed = true;
-            } else {
-                znippy_rows_destroy(r);
-                return ZNIPPY_E_NOMEM;
-            }
-        }
-    }
-    if ((!packed && ((rc = dev_upload(ctx, &r->blob_off, bo_in, n)) || (rc = dev_upload(ctx, &r->blob_size, bs_in, n)) ||
-                     (rc = dev_upload(ctx, &r->usize, us_in, n)) || (rc = dev_upload(ctx, &r->out_off, oo_in, n)))) ||
-        (compressed_bitmap && (rc = dev_upload(ctx, &d_bitmap, compressed_bitmap + bm0, (size_t)(bm1 - bm0)))) ||
-        tmalloc(ctx, &r->compressed, std::max<size_t>(n, 16)) != hipSuccess) {
-        znippy_rows_destroy(r);
-        return rc ? rc : ZNIPPY_E_NOMEM;
-    }
-    if (n) hipLaunchKernelGGL(k_rows_fixup, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_bitmap, row_begin - 8 * bm0, n, r->compressed, r->usize, r->blob_size);
-    td.mark("columns_h2d");
-    if (checksum && (rc = dev_upload(ctx, &r->checksum, checksum + 32 * row_begin, (size_t)32 * n))) {
-        znippy_rows_destroy(r);
-        return rc;
-    }
-    td.mark("checksum_h2d");
+    const RowCols c{blob_offset + row_begin, blob_size + row_begin, uncompressed_size + row_begin, out_offset + row_begin, compressed_bitmap, row_begin, row_end, allc};
+    int rc = rows_columns_h2d(ctx, r, c, checksum, td);
+    if (rc) return rc;
     r->corrupt_cap = std::max<uint32_t>(n, 1);
-    r->ctl_bytes = znippy_rows::CTL_HEAD + std::max<size_t>(4 * (size_t)n, 16);
+    r->ctl_bytes = CTL_HEAD + std::max<size_t>(4 * (size_t)n, 16);
     if (tmalloc(ctx, &r->ctl, r->ctl_bytes) != hipSuccess ||
         tmalloc(ctx, &r->digests, std::max<size_t>(32 * (size_t)n, 32)) != hipSuccess ||
         !(r->h_counters = (uint64_t *)pinned_take(ctx, 256, &r->h_counters_cap)) ||
         !(r->ev_done[0] = event_take(ctx)) || !(r->ev_done[1] = event_take(ctx)) ||
-        tmalloc(ctx, &r->corrupt, 8 * (size_t)r->corrupt_cap) != hipSuccess) {
-        znippy_rows_destroy(r);
+        tmalloc(ctx, &r->corrupt, 8 * (size_t)r->corrupt_cap) != hipSuccess)
         return ZNIPPY_E_NOMEM;
-    }
-    r->counters = reinterpret_cast<uint64_t *>(r->ctl);
-    r->pending_count = reinterpret_cast<uint32_t *>(r->ctl + 64);
-    r->cursor = reinterpret_cast<uint32_t *>(r->ctl + 128);
-    r->status = reinterpret_cast<int32_t *>(r->ctl + znippy_rows::CTL_HEAD);
+    r->counters = r->ctl_at<uint64_t>(CTL_COUNTERS);
+    r->status = reinterpret_cast<int32_t *>(r->ctl + CTL_HEAD);
     td.mark("allocs");
     PlanBuf p;
-    build_plan(len_of, n, p);
+    // a stored row IS its blob (see k_rows_fixup): its effective length is blob_size.  (allc and the column pointers by value: the pass over
+    // 100k rows keeps them in registers, which it cannot with members of `c`, whose address has left this function)
+    build_plan([=, us = c.us, bs = c.bs, &c](uint32_t i) -> uint64_t { return (allc || c.comp(i)) ? us[i] : bs[i]; }, n, p);
     td.mark("plan");
-    if ((rc = upload_plan(ctx, p, r->plan))) {
-        znippy_rows_destroy(r);
-        return rc;
-    }
+    if ((rc = upload_plan(ctx, p, r->plan))) return rc;
     td.mark("plan_h2d");
     for (const Tile &t : p.tiles) r->n_small_tiles += t.n_units != 0;
-    if (r->n_small_tiles && tmalloc(ctx, &r->slow_list, 4 * (size_t)p.tiles.size()) != hipSuccess) {
-        znippy_rows_destroy(r);
-        return ZNIPPY_E_NOMEM;
-    }
-    // compressed rows above 64 KiB: frames of >= 2 blocks (and < 4 GiB) are tried block by block (each block a work
-    // item), the others go straight to the general decoder
-    constexpr uint64_t BLK = 128 * 1024;
-    std::vector<uint32_t> la, cand_row, cand_base, cand_nb, item_row, item_k, fz_base, fz_cap, fz_it_cand;
-    uint64_t big_bytes = 0, big_blob = 0, n_big = 0, nblk = 0;
-    // ONE pass over the caller's columns: the flags the runs need, the extents a run is validated against (rows_validate:
-    // a table whose extents fit the run's regions has no bad row — the per-row pass is for the others), and the big rows
-    bool scan_rows = true;
-    if (allc) {  // the vectorised pass; the row-by-row one below only if the table has big rows
-        uint64_t e[8];
-        zn_rows_extents(bo_in, bs_in, oo_in, us_in, n, e);
-        if (e[6] == 0) {
-            scan_rows = false;
-            r->ext_min_bo = e[0]; r->ext_max_bend = e[1]; r->ext_max_oend = e[2]; r->ext_wrap = e[3] != 0;
-            r->n_compressed = n; r->bx_bytes = e[4]; nblk = e[5];
-        }
-    }
-    if (scan_rows) {
-        uint64_t min_bo = ~0ull, max_bend = 0, max_oend = 0;
-        bool wrap = false;
-        for (uint32_t i = 0; i < n; i++) {
-            const uint32_t c = comp_of(i);
-            const uint64_t bo = bo_in[i], bs = bs_in[i], oo = oo_in[i], us = c ? us_in[i] : bs;
-            r->n_compressed += c;
-            if (!c && (oo & 15)) r->odd_out = true;
-            min_bo = std::min(min_bo, bo);
-            wrap |= bo + bs < bo || oo + us < oo;
-            max_bend = std::max(max_bend, bo + bs);
-            max_oend = std::max(max_oend, oo + us);
-            if (!c) continue;
-            nblk += us ? (us + BLK - 1) / BLK : 1;
-            r->bx_bytes += us;
-            if (us > 65536 && us < (1ull << 30)) r->rx_words_small += (us + 1023) & ~1023ull;
-            if (us >= zn::RX_MIN && us < (1ull << 30)) r->rx_words += (us + 1023) & ~1023ull;
-            if (us <= 64 * 1024) continue;
-            big_bytes += us;
-            big_blob += bs;
-            n_big++;
-            const uint64_t nb = (us + BLK - 1) / BLK;
-            if (nb >= 2 && us < 0xFFFFFFFFull && item_row.size() + nb < 0x7FFFFFFFull && !ctx->sw.no_block_items) {
-                cand_row.push_back(i);
-                cand_base.push_back((uint32_t)item_row.size());
-                cand_nb.push_back((uint32_t)nb);
-                for (uint32_t k = 0; k < nb; k++) { item_row.push_back(i); item_k.push_back(k); }
-                if (!ctx->sw.no_fz && ctx->sw.no_bx && fz_it_cand.size() + 2 * nb + 8 < 0x7FFFFFFFull) {
-                    const uint32_t cap = (uint32_t)(2 * nb + 8);
-                    fz_base.push_back((uint32_t)fz_it_cand.size());
-                    fz_cap.push_back(cap);
-                    fz_it_cand.insert(fz_it_cand.end(), cap, (uint32_t)cand_row.size() - 1);
-                    r->fz_bytes += us;
-                } else { fz_base.push_back(0); fz_cap.push_back(0); }
-            } else la.push_back(i);
-        }
-        r->ext_min_bo = min_bo; r->ext_max_bend = max_bend; r->ext_max_oend = max_oend; r->ext_wrap = wrap;
-    }
-    r->n_list_a = (uint32_t)la.size();
+    if (r->n_small_tiles && tmalloc(ctx, &r->slow_list, 4 * (size_t)p.tiles.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+    RowClasses k;
+    rows_classify(ctx, r, c, k);
+    r->n_list_a = (uint32_t)k.la.size();
     td.mark("big_rows");
-    if (r->n_compressed) {
-        // what the block-item path, the batch path and the serial decoder tell each other about a row, and the serial
-        // decoder's list
-        if (tmalloc(ctx, &r->row_flag, std::max<size_t>(4 * (size_t)n, 16)) != hipSuccess ||
-            tmalloc(ctx, &r->pending2, std::max<size_t>(4 * (size_t)r->n_compressed, 16)) != hipSuccess) {
-            znippy_rows_destroy(r);
-            return ZNIPPY_E_NOMEM;
-        }
-        if (!ctx->sw.no_bx) {
-            // a writer may split blocks (libzstd's high levels cut a 128 KiB block into 2-5; runs of equal bytes come as
-            // strings of small RLE blocks): half as many again + up to 64k more, shared by all frames.  Frames that find no
-            // slot stay with the serial decoder.
-            r->bx_nblk = nblk;
-            if (r->rx_words_small && r->rx_words_small <= (256ull << 20)) { r->rx_min = 65537; r->rx_words = r->rx_words_small; }
-            const uint64_t cap = nblk + nblk / 2 + std::min<uint64_t>(3 * nblk, 65536) + 1024;
-            if (cap < 0x7FFFFFFFull) {
-                r->bx_slots = r->n_compressed;
-                r->bx_item_cap = (uint32_t)cap;
-                if (tmalloc(ctx, &r->bx_cand_row, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_cand_base, 4 * (size_t)r->bx_slots) != hipSuccess ||
-                    tmalloc(ctx, &r->bx_cand_nb, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_huf_list, 4 * (size_t)cap) != hipSuccess ||
-                    tmalloc(ctx, &r->bx_seq_list, 4 * 4 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->bx_sort_tmp, 5 * 4 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->bx_items, sizeof(zn::FzItem) * (size_t)cap) != hipSuccess ||
-                    tmalloc(ctx, &r->bx_prep, sizeof(zn::BxPrep) * (size_t)cap) != hipSuccess ||
-                    ((r->rx_words || r->rx_words_small) && !ctx->sw.no_rx &&
-                     (tmalloc(ctx, &r->rx_base, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->rx_fail, 4 * (size_t)r->bx_slots) != hipSuccess ||
-                      tmalloc(ctx, &r->rx_blk, 16 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->rx_list, 4 * (size_t)cap) != hipSuccess))) {
-                    znippy_rows_destroy(r);
-                    return ZNIPPY_E_NOMEM;
-                }
-            }
-        }
-    }
+    if (r->n_compressed && (rc = rows_batch_buffers(ctx, r, k.nblk))) return rc;
     // 1024-thread workgroups pay off where a few very long copies dominate (multi-MiB frames of periodic or stored
     // data: a frame that is < 2 % of its content); entropy-coded frames are a serial bitstream and want the narrow
     // variant's window execution instead, whatever their size
-    r->wide_rows = n_big && big_bytes / n_big >= (1u << 20) && big_blob * 50 < big_bytes;
-    r->n_cand = (uint32_t)cand_row.size();
-    r->n_items = (uint32_t)item_row.size();
-    r->small_ok = allc && !ctx->sw.no_lean && !ctx->sw.no_bx && r->n_list_a == 0 && r->n_cand == 0 && r->n_small_tiles == (uint32_t)p.tiles.size() &&
-                  r->n_small_tiles > 0 && r->bx_slots;
-    r->lean_mixed_ok = !ctx->sw.no_lean && r->n_list_a == 0 && r->n_cand == 0 && r->n_small_tiles > 0 && r->n_small_tiles < (uint32_t)p.tiles.size();
-    r->lean_blocks_ok = allc && !ctx->sw.no_lean && r->n_list_a == 0 && r->n_cand > 0 && r->n_small_tiles == 0;
-    r->lean_ok = allc && !ctx->sw.no_lean && r->n_list_a == 0 && r->n_cand == 0 && p.big.empty() && r->n_small_tiles == (uint32_t)p.tiles.size() &&
-                 r->n_small_tiles > 0;
-    if (r->n_cand) {
-        if ((rc = dev_upload(ctx, &r->cand_row, cand_row.data(), cand_row.size())) ||
-            (rc = dev_upload(ctx, &r->cand_base, cand_base.data(), cand_base.size())) ||
-            (rc = dev_upload(ctx, &r->cand_nblocks, cand_nb.data(), cand_nb.size())) ||
-            (rc = dev_upload(ctx, &r->item_row, item_row.data(), item_row.size())) ||
-            (rc = dev_upload(ctx, &r->item_k, item_k.data(), item_k.size()))) {
-            znippy_rows_destroy(r);
-            return rc;
-        }
-        if (tmalloc(ctx, &r->item_src, 4 * (size_t)r->n_items) != hipSuccess) {
-            znippy_rows_destroy(r);
-            return ZNIPPY_E_NOMEM;
-        }
-        r->fz_total = (uint32_t)fz_it_cand.size();
-        if (r->fz_total) {
-            if ((rc = dev_upload(ctx, &r->fz_base, fz_base.data(), fz_base.size())) ||
-                (rc = dev_upload(ctx, &r->fz_cap, fz_cap.data(), fz_cap.size())) ||
-                (rc = dev_upload(ctx, &r->fz_it_cand, fz_it_cand.data(), fz_it_cand.size()))) {
-                znippy_rows_destroy(r);
-                return rc;
-            }
-            if (tmalloc(ctx, &r->fz_nb, 4 * (size_t)r->n_cand) != hipSuccess || tmalloc(ctx, &r->fz_work, 4 * (size_t)r->fz_total) != hipSuccess ||
-                tmalloc(ctx, &r->fz_items, sizeof(zn::FzItem) * (size_t)r->fz_total) != hipSuccess) {
-                znippy_rows_destroy(r);
-                return ZNIPPY_E_NOMEM;
-            }
-        }
-    }
-    if (r->n_cand && !ctx->sw.no_fused_blocks) {
-        std::vector<uint32_t> row_base(n, 0xFFFFFFFFu), bt_tile, bt_item;
-        for (size_t c = 0; c < cand_row.size(); c++) row_base[cand_row[c]] = cand_base[c];
-        for (uint32_t ti = 0; ti < (uint32_t)p.tiles.size(); ti++) {
-            const Tile &t = p.tiles[ti];
-            if (t.n_units == 0 && row_base[t.first_unit] != 0xFFFFFFFFu) {
-                bt_tile.push_back(ti);
-                bt_item.push_back(row_base[t.first_unit] + (t.first_leaf >> 7));
-            }
-        }
-        r->n_bt = (uint32_t)bt_tile.size();
-        if ((rc = dev_upload(ctx, &r->bt_tile, bt_tile.data(), bt_tile.size())) ||
-            (rc = dev_upload(ctx, &r->bt_item, bt_item.data(), bt_item.size()))) {
-            znippy_rows_destroy(r);
-            return rc;
-        }
-        // (the two arrays of done flags in one allocation: one clear per run instead of two)
-        const size_t td_bytes = (std::max<size_t>(p.tiles.size(), 16) + 15) & ~(size_t)15;
-        r->done_bytes = td_bytes + std::max<size_t>(r->n_items, 16);
-        if (tmalloc(ctx, &r->tile_done, r->done_bytes) != hipSuccess ||
-            tmalloc(ctx, &r->todo, std::max<size_t>(4 * (size_t)r->n_items, 16)) != hipSuccess) {
-            znippy_rows_destroy(r);
-            return ZNIPPY_E_NOMEM;
-        }
-        r->item_done = r->tile_done + td_bytes;
-    }
-    if ((rc = dev_upload(ctx, &r->list_a, la.data(), la.size()))) {
-        znippy_rows_destroy(r);
-        return rc;
-    }
-    if (tmalloc(ctx, &r->pending, std::max<size_t>(4 * (size_t)n, 16)) != hipSuccess ||
-        false) {
-        znippy_rows_destroy(r);
-        return ZNIPPY_E_NOMEM;
-    }
+    r->wide_rows = k.n_big && k.big_bytes / k.n_big >= (1u << 20) && k.big_blob * 50 < k.big_bytes;
+    r->n_cand = (uint32_t)k.cand_row.size();
+    r->n_items = (uint32_t)k.item_row.size();
+    const bool hints = !ctx->sw.no_lean && r->n_list_a == 0;  // what the lean forms of a run have in common
+    const uint32_t n_tiles = (uint32_t)p.tiles.size();
+    r->small_ok = allc && hints && !ctx->sw.no_bx && r->n_cand == 0 && r->n_small_tiles == n_tiles && r->n_small_tiles > 0 && r->bx_slots;
+    r->lean_mixed_ok = hints && r->n_cand == 0 && r->n_small_tiles > 0 && r->n_small_tiles < n_tiles;
+    r->lean_blocks_ok = allc && hints && r->n_cand > 0 && r->n_small_tiles == 0;
+    r->lean_ok = allc && hints && r->n_cand == 0 && p.big.empty() && r->n_small_tiles == n_tiles && r->n_small_tiles > 0;
+    if (r->n_cand && (rc = rows_item_buffers(ctx, r, k))) return rc;
+    if (r->n_cand && !ctx->sw.no_fused_blocks && (rc = rows_fused_block_buffers(ctx, r, k, p))) return rc;
+    if ((rc = dev_upload(ctx, &r->list_a, k.la.data(), k.la.size()))) return rc;
+    if (tmalloc(ctx, &r->pending, std::max<size_t>(4 * (size_t)n, 16)) != hipSuccess) return ZNIPPY_E_NOMEM;
     td.mark("rest");
-    *out = r;
+    *out = guard.release();
     return ZNIPPY_OK;
 }
 
@@ -1346,7 +1383,7 @@ static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, ui
             if (tmalloc(ctx, &r->status_init, r->ctl_bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
             HIPCHK(ctx, hipMemset(r->status_init, 0, r->ctl_bytes));
         }
-        HIPCHK(ctx, hipMemcpy(r->status_init + znippy_rows::CTL_HEAD, init.data(), 4 * (size_t)r->n, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(r->status_init + CTL_HEAD, init.data(), 4 * (size_t)r->n, hipMemcpyHostToDevice));
     }
     r->n_bad = bad;
     r->val_base = blob_base; r->val_bcap = r->blob_cap; r->val_ocap = out_cap;
@@ -1354,18 +1391,409 @@ static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, ui
     return ZNIPPY_OK;
 }
 
-// what a finished run's mirror says about the batch path's work: rows the fused kernel handed over ([0]) + block
-// candidates left flagged ([5]) + the host's own list of big single-block rows
+// what a finished run's mirror says about the batch path's work: rows the fused kernel handed over + block candidates left
+// flagged + the host's own list of big single-block rows
 static void rows_note_hint(znippy_rows *r, unsigned slot) {
-    const uint32_t *pc = reinterpret_cast<const uint32_t *>(r->h_counters + 16 * slot + 8);
-    r->bx_hint = (pc[0] || pc[1] || pc[5] || r->n_list_a) ? 1 : 0;  // ([1]: what went to the serial decoder)
-    r->lean_hint = (pc[0] || pc[1] || pc[3] || pc[5]) ? 0 : 1;       // ([3]: tiles the role-split kernel left on its list)
-    r->lean_hint2 = (pc[0] || pc[1] || pc[2] || pc[5]) ? 0 : 1;      // ([2]: block items the fused block kernel left)
-    if (r->n_small_tiles && pc[3] >= r->n_small_tiles) r->roles_off = true;  // the role-split kernel took not one tile: not this table's kernel
+    const uint32_t *left = r->mirror_hand(slot);
+    const bool handed = left[H_FUSED] || left[H_SERIAL] || left[H_FLAGGED];
+    r->bx_hint = (handed || r->n_list_a) ? 1 : 0;
+    r->lean_hint = (handed || left[H_TILES]) ? 0 : 1;
+    r->lean_hint2 = (handed || left[H_ITEMS]) ? 0 : 1;
+    if (r->n_small_tiles && left[H_TILES] >= r->n_small_tiles) r->roles_off = true;  // the role-split kernel took not one tile: not this table's kernel
     // ... and when the fused kernels handed over every row of a table of small compressed rows, the next runs give the rows to the
     // batch path themselves (100k rows of real text: 0.26 ms of parsing each frame only to pass it on)
-    if (r->small_ok && pc[0] >= r->n) r->small_off = true;
+    if (r->small_ok && left[H_FUSED] >= r->n) r->small_off = true;
     if (r->small_off) r->bx_hint = 1;
+}
+
+// ---- one run of a row table: the plan, then the stages in the order rows_launch queues them -----------------------
+// Which kernels a run launches and on which streams.  Everything here is known before the run's first launch — the context's
+// switches and pools, the table's shape, the hints of its last finished run — and nothing in rows_plan calls HIP.
+struct RunPlan {
+    bool bx;           // the batch path takes the undecoded frames (its pools exist, the last run did not find its lists empty)
+    bool small_off;    // ... every row of the table: the fused small-row kernels are left out, all_rows is its list
+    bool stored_only;  // no compressed row: one pass of the store path kernel over ALL tiles instead of stages 1 and 2
+    bool roles;        // the role-split persistent kernel in front of k_fused_small
+    bool lean;         // nothing behind the roles kernel but the verify, which checks the lists (rows_settle repeats a flagged run)
+    bool lean_mixed;   // small rows beside big stored units: the small rows' kernels on the auxiliary stream beside the second hash pass
+    bool decode;       // stage 2 runs: block items and the decoders behind the fused kernels
+    bool one_stream;   // block items on the main stream: nothing else is expected there
+    bool lean_blocks;  // ... and neither the block decoder nor the serial decoders behind the fused block kernel
+    bool behind;       // round-2 flow: the general decoder behind the block items instead of beside them
+    bool rx;           // batch path: big frames through the resolve stages
+    bool third;        // batch path: the lane-per-block sequence kernel on a third stream beside the Huffman streams
+};
+static RunPlan rows_plan(const znippy_ctx *ctx, const znippy_rows *r, int preset) {
+    const auto &sw = ctx->sw;
+    RunPlan p{};
+    p.bx = r->bx_slots && ctx->fz_lit_pool && ctx->fz_seq_pool && ctx->bx_fse_pool && ctx->bx_huf_pool && r->bx_hint != 0;
+    p.small_off = p.bx && r->small_off && !r->n_bad && !r->force_full && !sw.dbg;
+    // (a repository of small files the reference stores as they are — png, jpg, gz —, or one big jar.  The fused small-row kernel
+    // copies a stored row with each lane's own 64-byte stores: 100k x 10 KiB stored rows 0.85 ms there, 0.63 through the store path kernel)
+    p.stored_only = r->n_compressed == 0 && !preset && !sw.dbg && !sw.no_stored_only && !r->force_full;
+    const bool may_skip = !preset && !r->force_full;  // a run may leave out what the table's last finished run had no use for
+    if (!p.small_off && !p.stored_only) {
+        // Tables with enough small tiles go to the role-split persistent kernel first (loader + hasher waves: tiles whose rows are all whole-leaf rows of
+        // the recognised periodic shape); what it leaves on its list — and small tables, where a persistent grid only adds start-up latency — is k_fused_small's.
+        p.roles = !sw.no_roles && sw.roles_min != 0 && r->n_small_tiles >= sw.roles_min && r->n_small_tiles > 0 && !(sw.dbg & (1 | 2 | 4 | 8 | 128)) && !r->roles_off;
+        // A table of small rows AND big stored / hashed units (BASELINE configs[4]: 3,500 small files beside 6 GB of jars) whose
+        // last run handed nothing over: nothing of the small rows' kernel and the second hash pass depends on the other (C5:
+        // 0.28 ms of a 3.45 ms step ran in front of the pass).
+        p.lean_mixed = r->lean_mixed_ok && r->lean_hint == 1 && r->bx_hint == 0 && may_skip && !sw.dbg && !sw.ddbg;
+        p.lean = p.roles && r->lean_ok && r->lean_hint == 1 && r->bx_hint == 0 && may_skip && !sw.dbg;
+    }
+    p.decode = !p.lean && !p.lean_mixed && !p.stored_only;
+    if (!p.decode) return p;
+    // a table of big rows only whose last run handed nothing over: the main stream has nothing for the block items to run beside, and
+    // the fork and the join between two streams were ~0.1 ms of C3's 1.09 ms step
+    p.one_stream = r->n_cand && r->bx_hint == 0 && r->n_small_tiles == 0;
+    // ... and when its last run needed neither the serial block decoder nor the serial decoder behind it (every block item was written and hashed by the
+    // fused block kernel), those three launches are left out, the way a lean run of a table of small rows leaves out what stands behind the roles kernel.
+    p.lean_blocks = p.one_stream && r->lean_blocks_ok && r->lean_hint2 == 1 && may_skip && r->n_bt && !sw.ddbg && !r->fz_total;
+    if (!r->n_compressed) return p;
+    // (the serial decoder's launch then returns at once instead of waiting for CUs next to the block kernels: C3's 0.25 ms that only waited)
+    p.behind = !p.bx && r->n_cand && r->bx_hint == 0;
+    p.rx = p.bx && r->rx_base && ctx->rx_pool && r->rx_words;
+    // (only where the chip is not full of blocks anyway: 100k blocks, both kernels chip-wide: 2.98 ms together against 1.85 + 0.96 in a row)
+    p.third = p.bx && r->bx_nblk <= 32768;
+    return p;
+}
+
+static HashArgs rows_hash_args(const znippy_ctx *ctx, const znippy_rows *r, const RowsRun &run) {
+    HashArgs h{};
+    h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
+    h.len = r->usize;
+    h.srcA = (const uint8_t *)run.d_blobs; h.offA = r->blob_off; h.baseA = run.blob_base;
+    h.srcB = (uint8_t *)run.d_out; h.offB = r->out_off;
+    h.sel = r->compressed; h.status = r->status; h.pending_count = r->hand(H_FUSED);
+    h.copy_to_B = 1;
+    h.store_tiles = ctx->sw.store_g;
+    h.misaligned_dst = r->odd_out || ((uintptr_t)run.d_out & 15) != 0;
+    h.digests = r->digests; h.tile_cv = r->plan.tile_cv;
+    return h;
+}
+static BlockScanArgs rows_scan_args(const znippy_rows *r, const RowsRun &run) {
+    BlockScanArgs b{};
+    b.cand_row = r->cand_row; b.cand_base = r->cand_base; b.cand_nblocks = r->cand_nblocks; b.n_cand = r->n_cand;
+    fill_row_args(b, r, run);
+    b.item_src = r->item_src; b.row_flag = r->row_flag;
+    b.pending = r->pending2; b.pending_count = r->hand(H_SERIAL);  // its own hand-over list
+    return b;
+}
+// the serial decoder over the host's list and what the fused kernels handed over; decode_rest turns it to what everything left
+static DecodeArgs rows_decode_args(znippy_ctx *ctx, const znippy_rows *r, const RowsRun &run) {
+    DecodeArgs a{};
+    fill_row_args(a, r, run);
+    a.list_a = r->list_a; a.n_list_a = r->n_list_a;
+    a.pending = r->pending; a.pending_count = r->hand(H_FUSED);
+    a.compressed = r->compressed;
+    a.n_rows = r->n; a.cursor = r->cur(CUR_GENERAL);
+    a.lit_scratch = ctx->lit_scratch;
+    if (ctx->sw.ddbg)  // diagnostic: phase shares of the previous general-decoder launch
+        a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_GENERAL, ctx->stream, nullptr, [](const unsigned long long *h) {
+            if (h[0]) fprintf(stderr, "[znippy ddbg] general decoder frames=%llu  kcycles per frame: headers+tree=%.1f huffman-table=%.1f literal-streams=%.1f seq-tables=%.1f first-batch=%.1f decode+execute=%.1f tail=%.1f\n", h[0],
+                              h[6] / 1e3 / h[0], h[7] / 1e3 / h[0], h[1] / 1e3 / h[0], h[2] / 1e3 / h[0], h[3] / 1e3 / h[0], h[4] / 1e3 / h[0], h[5] / 1e3 / h[0]);
+        });
+    return a;
+}
+static void decode_rest(znippy_ctx *ctx, const znippy_rows *r, DecodeArgs a, uint32_t rows) {  // what every path left: pending2
+    a.list_a = nullptr; a.n_list_a = 0;
+    a.pending = r->pending2; a.pending_count = r->hand(H_SERIAL);
+    a.cursor = r->cur(CUR_FALLBACK);
+    timed(ctx, "zstd_decode_fallback", ctx->stream, [&] {
+        if (!ctx->sw.fz_only) launch_decode(a, std::min<int>(ctx->decode_grid, (int)rows), r->wide_rows, ctx->stream);
+    });
+}
+
+// counters, hand-over counts, work cursors and the status column: one stream operation
+static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    if (run.preset) HIPCHK(ctx, hipMemcpyAsync(r->ctl, r->status_init, r->ctl_bytes, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(ctx, hipMemsetAsync(r->ctl, 0, r->ctl_bytes, s));
+    // (the second hash pass looks at small tiles only when rows were handed over)
+    if (p.small_off) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)r->hand(H_FUSED), (int)r->n, 1, s));
+    return ZNIPPY_OK;
+}
+
+// 1) small rows: decode simple frames + hash (+ copy stored rows), one wave per tile; the role-split kernel in front
+static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    FusedArgs f{};
+    f.h = rows_hash_args(ctx, r, run);
+    f.h.pass = 1;  // PASS_FUSED
+    f.blob_size = r->blob_size; f.out_cap = run.out_cap; f.status = r->status;
+    f.preset = run.preset;
+    f.pending = r->pending; f.pending_count = r->hand(H_FUSED);
+    f.dbg = ctx->sw.dbg;
+    if (f.dbg & 8) {  // diagnostic: print the previous launch's phase stamps, then reset them
+        f.dbg_buf = diag_cycle<8>(ctx, znippy_ctx::DIAG_FUSED, s, nullptr, [](const unsigned long long *h4) {
+            if (h4[3]) fprintf(stderr, "[znippy dbg] waves=%llu prologue=%.0f decode=%.0f hash=%.0f | parse+lits=%.0f expand-build=%.0f stream-out=%.0f after-match=%.0f cycles/wave\n", h4[3],
+                               (double)h4[0] / h4[3], (double)h4[1] / h4[3], (double)h4[2] / h4[3], (double)h4[6] / h4[3], (double)h4[4] / h4[3], (double)h4[5] / h4[3], (double)h4[7] / h4[3]);
+        });
+        set_fused_dbg(f.dbg_buf);
+    }
+    if (f.dbg & 32768) {
+        if (!ctx->clk_buf) { (void)hipMalloc(&ctx->clk_buf, 64); (void)hipMemset(ctx->clk_buf, 0, 64); }
+        f.dbg_buf = ctx->clk_buf;
+    }
+    if (f.dbg & (16 | 32 | 64)) set_fused_abl(f.dbg);
+    f.lds_pad = ctx->sw.lds_pad;
+    const hipStream_t fs = p.lean_mixed ? ctx->aux : s;
+    if (p.lean_mixed) {
+        HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
+    }
+    if (p.roles) {
+        f.cursor = r->cur(CUR_ROLES);
+        f.tile_list = r->slow_list;
+        f.tile_count = r->hand(H_TILES);
+        timed(ctx, "decode_verify_roles", fs, [&] { launch_fused_roles(f, ctx->cus, fs); });
+    }
+    if (r->n_small_tiles && !p.lean) timed(ctx, "decode_verify_fused", fs, [&] { launch_fused_small(f, fs, p.roles ? ctx->cus * 5 : 0); });
+    if (p.lean_mixed) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));  // (joined in front of the verify)
+    return ZNIPPY_OK;
+}
+
+// Round-2 two-phase path for foreign frames (what the block items gave up on): entropy-decode every block at once, then
+// execute frame by frame.  Behind the block items and BESIDE the general decoder on the main stream: both are a few
+// long-lived waves per frame, neither fills the chip (real text, libzstd -19 frames: the two used to run back to back,
+// 7.0 + 10.6 ms).
+static void run_two_phase(znippy_ctx *ctx, znippy_rows *r, const RowsRun &run, hipStream_t ba) {
+    FzArgs z{};
+    z.cand_row = r->cand_row; z.cand_fzbase = r->fz_base; z.cand_fzcap = r->fz_cap; z.n_cand = r->n_cand;
+    z.it_cand = r->fz_it_cand; z.total_items = r->fz_total; z.cand_nb = r->fz_nb; z.items = r->fz_items;
+    fill_row_args(z, r, run);
+    z.row_flag = r->row_flag;
+    z.lit_pool = ctx->fz_lit_pool; z.lit_cap = ctx->fz_lit_cap; z.seq_pool = ctx->fz_seq_pool; z.seq_cap = ctx->fz_seq_cap;
+    z.pool_used = r->ctl_at<unsigned long long>(CTL_FZ_POOL);  // [lit bytes, seq records], zeroed with the control block
+    z.cursor = r->cur(CUR_FZ);
+    if (ctx->sw.ddbg)  // diagnostic: where the previous run's execute kernel spent its cycles
+        z.dbg = diag_cycle<32>(ctx, znippy_ctx::DIAG_FZ, ctx->stream, ba, [](const unsigned long long *h) {
+            if (h[0]) fprintf(stderr, "[znippy ddbg] fz exec: frames=%llu groups=%llu seqs=%llu big=%llu rounds=%llu flushes=%llu histreads=%llu rep_groups=%llu | kcycles/frame: total=%.0f records=%.0f rep+scan=%.0f big=%.0f flush=%.0f histread=%.0f lits=%.0f matches=%.0f tail=%.0f\n",
+                              h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8] / 1e3 / h[0], h[9] / 1e3 / h[0], h[10] / 1e3 / h[0], h[11] / 1e3 / h[0],
+                              h[12] / 1e3 / h[0], h[13] / 1e3 / h[0], h[14] / 1e3 / h[0], h[15] / 1e3 / h[0], h[16] / 1e3 / h[0]);
+            if (h[20]) fprintf(stderr, "[znippy ddbg] fz entropy: blocks=%llu seqs=%llu | kcycles/block: literal tree=%.0f literal table+streams=%.0f sequence tables=%.0f sequence decode=%.0f\n",
+                               h[20], h[25], h[21] / 1e3 / h[20], h[22] / 1e3 / h[20], h[23] / 1e3 / h[20], h[24] / 1e3 / h[20]);
+        });
+    launch_fz_scan(z, r->fz_work, r->cur(CUR_FZ_WORK), ba);
+    timed(ctx, "zstd_foreign_entropy", ba, [&] { launch_fz_entropy(z, ctx->cus, r->fz_work, r->cur(CUR_FZ_WORK), ba); });
+    timed(ctx, "zstd_foreign_execute", ba, [&] { launch_fz_exec(z, ba); });
+}
+
+// 2a) block items: frames of >= 2 blocks, every block a work item, on the auxiliary stream beside the decoders of 2b (each
+//     is latency-bound on its own and leaves most of the chip idle) — or in front of them on the main stream (one_stream)
+static int run_block_items(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    const hipStream_t ba = p.one_stream ? s : ctx->aux;
+    const BlockScanArgs b = rows_scan_args(r, run);
+    if (!p.one_stream) {
+        HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
+        HIPCHK(ctx, hipStreamWaitEvent(ba, ctx->ev_fork, 0));
+    }
+    timed(ctx, "zstd_block_scan", ba, [&] { launch_scan_blocks(b, ba); });
+    if (r->n_bt) {  // blocks of the common shape: written and hashed in one go, skipped by the block decoder and the second hash pass
+        HIPCHK(ctx, hipMemsetAsync(r->tile_done, 0, r->done_bytes, ba));
+        FusedBlocksArgs fb{};
+        fb.h = rows_hash_args(ctx, r, run);
+        fb.h.pass = 0;  // PASS_ALL
+        fb.blob_size = r->blob_size;
+        fb.bt_tile = r->bt_tile; fb.bt_item = r->bt_item; fb.n_bt = r->n_bt;
+        fb.item_src = r->item_src; fb.row_flag = r->row_flag;
+        fb.tile_done = r->tile_done; fb.item_done = r->item_done;
+        fb.dbg = ctx->sw.dbg;
+        timed(ctx, "decode_verify_fused_blocks", ba, [&] { launch_fused_blocks(fb, ba); });
+        launch_compact_items(r->item_done, r->n_items, r->todo, r->hand(H_ITEMS), ba);
+    }
+    DecodeArgs a{};
+    fill_row_args(a, r, run);
+    a.block_mode = 1;
+    a.item_row = r->item_row; a.item_k = r->item_k; a.item_src = r->item_src; a.n_items = r->n_items; a.row_flag = r->row_flag;
+    a.item_done = r->n_bt ? r->item_done : nullptr;
+    a.todo = r->n_bt ? r->todo : nullptr; a.n_todo = r->hand(H_ITEMS);
+    a.pending_count = r->hand(H_FUSED);
+    a.compressed = r->compressed;
+    a.n_rows = r->n; a.cursor = r->cur(CUR_ITEMS);
+    a.lit_scratch = ctx->lit_scratch_b;
+    if (ctx->sw.ddbg)  // diagnostic: phase shares of the previous block-item launch
+        a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_ITEMS, s, ba, [](const unsigned long long *h) {
+            if (h[0]) fprintf(stderr, "[znippy ddbg] block items=%llu  cycles per item: literals=%.0f seq-tables=%.0f seq-decode=%.0f execute=%.0f tail=%.0f\n", h[0],
+                              (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0], (double)h[5] / h[0]);
+        });
+    if (!p.lean_blocks) timed(ctx, "zstd_decode_blocks", ba, [&] { launch_decode(a, std::min<int>(ctx->decode_grid, (int)r->n_items), false, ba); });
+    if (r->fz_total) run_two_phase(ctx, r, run, ba);
+    if (!p.one_stream) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
+    return ZNIPPY_OK;
+}
+
+static BxArgs rows_bx_args(znippy_ctx *ctx, const znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    BxArgs x{};
+    x.list_a = r->list_a; x.n_list_a = r->n_list_a;
+    x.pending = r->pending; x.pending_count = r->hand(H_FUSED);
+    if (p.small_off) {  // every row is the batch path's: its list is all rows, nothing was handed over (a word that stays zero)
+        x.list_a = r->all_rows; x.n_list_a = r->n;
+        x.pending_count = r->ctl_at<uint32_t>(CTL_RX, RX_ZERO);
+    }
+    x.bc_row = r->cand_row; x.n_bc = r->n_cand;
+    fill_row_args(x, r, run);
+    x.row_flag = r->row_flag;
+    x.cand_row = r->bx_cand_row; x.cand_base = r->bx_cand_base; x.cand_nb = r->bx_cand_nb; x.slot_cap = r->bx_slots;
+    x.items = r->bx_items; x.prep = r->bx_prep; x.item_cap = r->bx_item_cap;
+    x.ctr = r->ctl_at<uint32_t>(CTL_BX_CTR);
+    x.huf_list = r->bx_huf_list; x.seq_list = r->bx_seq_list; x.sort_tmp = r->bx_sort_tmp;
+    x.lit_pool = ctx->fz_lit_pool; x.lit_cap = ctx->fz_lit_cap; x.seq_pool = ctx->fz_seq_pool; x.seq_cap = ctx->fz_seq_cap;
+    x.fse_pool = ctx->bx_fse_pool; x.fse_cap = ctx->bx_fse_cap; x.huf_pool = ctx->bx_huf_pool; x.huf_cap = ctx->bx_huf_cap;
+    x.pool_used = r->ctl_at<unsigned long long>(CTL_BX_POOL);
+    x.pending2 = r->pending2; x.pending2_count = r->hand(H_SERIAL);
+    // 0: the blocks that get a wave of their own are picked from the table's histogram (k_bx_split: one workgroup per
+    // list, worth its ~0.1-0.4 ms where the chip is not full of blocks anyway); big tables keep the fixed threshold
+    x.big_seq = ctx->sw.bx_big_set || r->bx_nblk > 32768 ? ctx->sw.bx_big : 0u;
+    if (p.rx) {
+        x.rx_ptr = ctx->rx_pool; x.rx_cap = ctx->rx_cap; x.rx_chunk = ctx->rx_chunk; x.rx_cdone = ctx->rx_cdone;
+        x.rx_base = r->rx_base; x.rx_fail = r->rx_fail; x.rx_blk = r->rx_blk; x.rx_list = r->rx_list;
+        x.rx_pending = r->ctl_at<uint32_t>(CTL_RX);
+        x.rx_bound = std::min<uint64_t>(r->rx_words, ctx->rx_cap);
+        x.rx_min = r->rx_min;
+    }
+    x.small_frames = r->n_compressed && r->bx_bytes / r->n_compressed <= 65536;
+    if (ctx->sw.ddbg)  // diagnostic: where the previous run's table kernel spent its waves' time
+        x.dbg = diag_cycle<128>(ctx, znippy_ctx::DIAG_BX, ctx->stream, nullptr, [](const unsigned long long *h) {
+            if (h[64]) {
+                const unsigned long long *e = h + 64;
+                fprintf(stderr, "[znippy ddbg] batch execute: frames=%llu groups=%llu seqs=%llu big=%llu rounds=%llu flushes=%llu histreads=%llu | kcycles/frame: total=%.1f records=%.1f rep+scan=%.1f big=%.1f flush=%.1f histread=%.1f lits=%.1f matches=%.1f tail=%.1f\n",
+                        e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[8] / 1e3 / e[0], e[9] / 1e3 / e[0], e[10] / 1e3 / e[0], e[11] / 1e3 / e[0], e[12] / 1e3 / e[0], e[13] / 1e3 / e[0],
+                        e[14] / 1e3 / e[0], e[15] / 1e3 / e[0], e[16] / 1e3 / e[0]);
+            }
+            if (h[32]) fprintf(stderr, "[znippy ddbg] batch tables: wave passes=%llu  kcycles per pass: literals header + weights=%.1f sequences header=%.1f huffman table=%.1f sequence tables=%.1f\n", h[32],
+                               h[33] / 1e3 / h[32], h[34] / 1e3 / h[32], h[35] / 1e3 / h[32], h[36] / 1e3 / h[32]);
+        });
+    return x;
+}
+static void bx_stage(znippy_ctx *ctx, const BxArgs &x, BxStage st, hipStream_t on) {
+    static const char *const names[10] = {"zstd_batch_scan", "zstd_batch_tables", "zstd_batch_huffman", "zstd_batch_sequences", "zstd_batch_execute", "zstd_batch_finish",
+                                          "zstd_batch_sequences_long", "zstd_batch_sort", "zstd_resolve_plan", "zstd_resolve_expand"};
+    timed(ctx, names[st], on, [&] { launch_bx_stage(x, ctx->cus, st, on); });
+}
+// big frames of the batch path: resolved in parallel (every byte a word, pointer jumping) instead of executed by a wave each;
+// the frames the plan did not take are executed by a wave each, beside the resolve stages (they share nothing)
+static int run_resolve(znippy_ctx *ctx, znippy_rows *r, const BxArgs &x) {
+    hipStream_t s = ctx->stream;
+    bx_stage(ctx, x, BX_RX_PLAN, s);
+    if (ctx->sw.trace) {
+        uint32_t g[16];
+        unsigned long long pu[16];
+        (void)hipMemcpy(g, r->ctl + CTL_BX_CTR.at, CTL_BX_CTR.bytes, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(pu, r->ctl + CTL_BX_POOL.at, CTL_BX_POOL.bytes, hipMemcpyDeviceToHost);
+        fprintf(stderr, "[znippy trace] resolve plan: slots %u items %u list %u frames %u words %llu extent %llu cap %llu item_cap %u\n", g[0], g[1], g[9], g[11], pu[10], pu[11],
+                (unsigned long long)ctx->rx_cap, r->bx_item_cap);
+    }
+    HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
+    bx_stage(ctx, x, BX_EXEC, ctx->aux);
+    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
+    bx_stage(ctx, x, BX_RX_EXPAND, s);
+    static const char *const jump_names[12] = {"zstd_resolve_jump_0", "zstd_resolve_jump_1", "zstd_resolve_jump_2", "zstd_resolve_jump_3", "zstd_resolve_jump_4", "zstd_resolve_jump_5",
+                                               "zstd_resolve_jump_6", "zstd_resolve_jump_7", "zstd_resolve_jump_8", "zstd_resolve_jump_9", "zstd_resolve_jump_10", "zstd_resolve_jump_11"};
+    static_assert(zn::RX_ROUNDS <= 12, "names");
+    if (!ctx->sw.ddbg) ktime_begin(ctx, "zstd_resolve_jump", s);
+    for (int rd = 0; rd < (int)zn::RX_ROUNDS; rd++) {
+        if (ctx->sw.ddbg) ktime_begin(ctx, jump_names[rd], s);  // diagnostic: every round by itself
+        launch_bx_stage(x, ctx->cus, BX_RX_JUMP + rd, s);
+        if (ctx->sw.ddbg) ktime_end(ctx, s);
+    }
+    if (!ctx->sw.ddbg) ktime_end(ctx, s);
+    timed(ctx, "zstd_resolve_store", s, [&] { launch_bx_stage(x, ctx->cus, BX_RX_STORE, s); });
+    HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+    return ZNIPPY_OK;
+}
+// 2b) batch path: every frame that is still undecoded — big single-block rows, what the fused kernel handed over, block
+//     candidates the block-item path flagged — goes through the lane-per-block kernels in ONE pass (the more blocks, the
+//     fuller their waves), behind the block items; the serial decoder takes what they leave.
+static int run_batch_path(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    const DecodeArgs a = rows_decode_args(ctx, r, run);
+    if (r->n_cand) {
+        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+        launch_finish_blocks(rows_scan_args(r, run), s, true);  // unflagged candidates are done; flagged ones wait for the batch path's verdict
+    }
+    const BxArgs x = rows_bx_args(ctx, r, p, run);
+    bx_stage(ctx, x, BX_SCAN, s);
+    bx_stage(ctx, x, BX_PREP, s);
+    bx_stage(ctx, x, BX_SORT, s);
+    // the long chains (blocks of >= BX_BIG_SEQ sequences, a wave each) run on the auxiliary stream beside the Huffman
+    // streams and the lane-per-block sequence kernel: each is a few hundred long-lived waves at most
+    HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
+    bx_stage(ctx, x, BX_FSE_WAVE, ctx->aux);
+    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
+    // ... and the lane-per-block sequence kernel beside the Huffman streams on a third stream (the write side's copy
+    // stream, idle here): the two touch different pools and different fields of a block's record.  A small table is
+    // its longest chains: the image's source text had Huffman 2.5 + sequences 1.8 ms in a row beside 3.5 ms of long chains.
+    if (p.third) {
+        HIPCHK(ctx, hipStreamWaitEvent(ctx->copy, ctx->ev_fork, 0));
+        bx_stage(ctx, x, BX_FSE, ctx->copy);
+        HIPCHK(ctx, hipEventRecord(ctx->ev_join2, ctx->copy));
+    }
+    bx_stage(ctx, x, BX_HUF, s);
+    if (!p.third) bx_stage(ctx, x, BX_FSE, s);
+    HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+    if (p.third) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join2, 0));
+    if (p.rx) { const int rc = run_resolve(ctx, r, x); if (rc) return rc; }
+    else bx_stage(ctx, x, BX_EXEC, s);
+    bx_stage(ctx, x, BX_FINISH, s);
+    decode_rest(ctx, r, a, r->n_compressed);
+    return ZNIPPY_OK;
+}
+// 2b') round-2 flow (no batch path: ZNIPPY_NO_BX, no pools, or a table whose last run handed nothing over): the serial
+//      decoder takes the host's list and what the fused kernel hands over, beside the block items on the auxiliary stream —
+//      or behind them when nothing is expected; frames the block path gives up on are decoded by a second launch afterwards.
+static int run_serial_flow(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    const DecodeArgs a = rows_decode_args(ctx, r, run);
+    if (p.behind) {
+        if (!p.one_stream) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+        launch_finish_blocks(rows_scan_args(r, run), s, false);
+    }
+    if (p.lean_blocks) return ZNIPPY_OK;
+    // A full grid of this kernel (4 workgroups per CU at 128 VGPRs) is the whole register file: whatever the auxiliary
+    // stream launches then waits until workgroups run out of rows.  With candidates for the block / foreign-frame
+    // paths it leaves them a quarter.
+    const int gen_grid = r->n_cand && !p.behind ? ctx->decode_grid / 4 * ctx->gen_share : ctx->decode_grid;
+    timed(ctx, "zstd_decode_general", s, [&] { launch_decode(a, std::min<int>(gen_grid, (int)r->n_compressed), r->wide_rows, s); });
+    if (!r->n_cand) return ZNIPPY_OK;
+    if (!p.behind) {  // join (block items and the foreign-frame path on the auxiliary stream), then what both gave up on
+        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+        launch_finish_blocks(rows_scan_args(r, run), s, false);
+    }
+    decode_rest(ctx, r, a, r->n_cand);
+    return ZNIPPY_OK;
+}
+
+// 3) second hash pass: slices of big rows + rows the decoders finished (stored_only: every tile), then the big rows' trees
+static void run_second_hash(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    HashArgs h = rows_hash_args(ctx, r, run);
+    h.pass = p.stored_only ? 0 : 2;  // PASS_ALL : PASS_SECOND
+    h.tile_done = r->n_bt && !p.stored_only ? r->tile_done : nullptr;
+    timed(ctx, "blake3_second_pass", s, [&] { launch_hash_tiles(h, s); });
+    if (r->plan.n_big)
+        timed(ctx, "blake3_merge_big", s, [&] {
+            launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, r->digests, r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, r->plan.max_cvs, s);
+        });
+}
+
+// 4) verify (a run that left stages out: its lists must be empty, or the counters come back flagged), mirror copy, event
+static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    hipStream_t s = ctx->stream;
+    if (p.lean_mixed) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
+    const bool skipped = p.lean || p.lean_blocks || p.lean_mixed;
+    timed(ctx, "verify", s, [&] {
+        launch_verify(r->digests, r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt, r->corrupt_cap, s,
+                      skipped ? r->ctl_at<uint32_t>(CTL_HAND) : nullptr, (p.lean || p.lean_mixed) ? LEAN_SMALL : LEAN_BLOCKS);
+    });
+    HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * run.slot, r->counters, CTL_MIRROR, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipEventRecord(r->ev_done[run.slot], s));
+    HIPCHK(ctx, hipGetLastError());
+    return ZNIPPY_OK;
 }
 
 // Queues one run of the table with the given arguments; its counters land in mirror slot `slot` and ev_done[slot] marks its
@@ -1374,437 +1802,36 @@ static void rows_note_hint(znippy_rows *r, unsigned slot) {
 // point is a HIP runtime error, which the caller turns into a table without a readable run (rows_abandon).
 static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap,
                        unsigned slot, bool *queued = nullptr) {
-    hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
-    { const int rc0 = ensure_decoder(ctx); if (rc0) return rc0; }
-    { const int rc0 = rows_validate(ctx, r, blob_base, out_cap); if (rc0) return rc0; }
-    if (r->fz_total) { const int rc0 = ensure_fz_pools(ctx, r->fz_bytes, r->fz_total); if (rc0) return rc0; }
-    if (r->bx_slots) {
-        int rc0 = ensure_fz_pools(ctx, r->bx_bytes, r->bx_item_cap);
-        if (!rc0) rc0 = ensure_bx_pools(ctx, r->bx_bytes, r->bx_item_cap);
-        if (!rc0 && r->rx_base && r->bx_hint != 0) rc0 = ensure_rx_pool(ctx, r->rx_words);
-        if (rc0) return rc0;
+    int rc = ensure_decoder(ctx);
+    if (!rc) rc = rows_validate(ctx, r, blob_base, out_cap);
+    if (!rc && r->fz_total) rc = ensure_fz_pools(ctx, r->fz_bytes, r->fz_total);
+    if (!rc && r->bx_slots) {
+        rc = ensure_fz_pools(ctx, r->bx_bytes, r->bx_item_cap);
+        if (!rc) rc = ensure_bx_pools(ctx, r->bx_bytes, r->bx_item_cap);
+        if (!rc && r->rx_base && r->bx_hint != 0) rc = ensure_rx_pool(ctx, r->rx_words);
     }
+    if (rc) return rc;
     if (r->n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
     if (r->run_seq && r->bx_hint < 0 && r->n) {  // a run of this table has finished meanwhile?
-        const unsigned slot = (unsigned)((r->run_seq - 1) & 1);
-        if (hipEventQuery(r->ev_done[slot]) == hipSuccess) rows_note_hint(r, slot);
+        const unsigned last = (unsigned)((r->run_seq - 1) & 1);
+        if (hipEventQuery(r->ev_done[last]) == hipSuccess) rows_note_hint(r, last);
         else (void)hipGetLastError();
     }
-    const bool bx = r->bx_slots && ctx->fz_lit_pool && ctx->fz_seq_pool && ctx->bx_fse_pool && ctx->bx_huf_pool && r->bx_hint != 0;
-    const bool small_off = bx && r->small_off && !r->n_bad && !r->force_full && !ctx->sw.dbg;
-    if (small_off && !r->all_rows) {
+    const RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot};
+    const RunPlan p = rows_plan(ctx, r, run.preset);
+    if (p.small_off && !r->all_rows) {
         if (tmalloc(ctx, &r->all_rows, 4 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
-        hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, s, r->all_rows, r->n);
+        hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, ctx->stream, r->all_rows, r->n);
     }
-    const int preset = r->n_bad ? 1 : 0;
     { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = d_out; ra.cap = out_cap; ra.blob_cap = r->blob_cap; }
-    bool lean = false, lean_blocks = false, lean_mixed = false;
-    // counters, hand-over counts, work cursors and the status column: one stream operation
     if (queued) *queued = true;
-    if (preset) HIPCHK(ctx, hipMemcpyAsync(r->ctl, r->status_init, r->ctl_bytes, hipMemcpyDeviceToDevice, s));
-    else HIPCHK(ctx, hipMemsetAsync(r->ctl, 0, r->ctl_bytes, s));
-    if (!r->n) return ZNIPPY_OK;
-    // (the second hash pass looks at small tiles only when rows were handed over: word 0 of the hand-over counts)
-    if (small_off) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)(r->ctl + 64), (int)r->n, 1, s));
-    // 1) fused small-row kernel: decode simple frames + hash (+ copy stored rows), one wave per tile
-    HashArgs h{};
-    h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
-    h.len = r->usize;
-    h.srcA = (const uint8_t *)d_blobs; h.offA = r->blob_off; h.baseA = blob_base;
-    h.srcB = (uint8_t *)d_out; h.offB = r->out_off;
-    h.sel = r->compressed; h.status = r->status; h.pending_count = r->pending_count;
-    h.copy_to_B = 1;
-    h.store_tiles = ctx->sw.store_g;
-    h.misaligned_dst = r->odd_out || ((uintptr_t)d_out & 15) != 0;
-    h.digests = r->digests; h.tile_cv = r->plan.tile_cv;
-    // A table without a single compressed row (a repository of small files the reference stores as they are — png, jpg, gz —,
-    // or one big jar): nothing to recognise, nothing to decode — one pass of the store path kernel over ALL tiles (hash + copy,
-    // small tiles 64 bytes per leaf per step through the stage), the merge, the verify.  (The fused small-row kernel copies a
-    // stored row with each lane's own 64-byte stores: 100k x 10 KiB stored rows 0.85 ms there, 0.63 here.)
-    const bool stored_only = r->n_compressed == 0 && !preset && !ctx->sw.dbg && !ctx->sw.no_stored_only && !r->force_full;
-    if (!small_off && !stored_only) {
-        FusedArgs f{};
-        f.h = h;
-        f.h.pass = 1;  // PASS_FUSED
-        f.blob_size = r->blob_size; f.out_cap = out_cap; f.status = r->status;
-        f.preset = preset;
-        f.pending = r->pending; f.pending_count = r->pending_count;
-        f.dbg = ctx->sw.dbg;
-        if (f.dbg & 8) {  // diagnostic: print the previous launch's phase stamps, then reset them
-            static unsigned long long *dbg = nullptr;
-            if (!dbg) { (void)hipMalloc(&dbg, 64); (void)hipMemset(dbg, 0, 64); }
-            unsigned long long h4[8];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(h4, dbg, 64, hipMemcpyDeviceToHost);
-            if (h4[3]) fprintf(stderr, "[znippy dbg] waves=%llu prologue=%.0f decode=%.0f hash=%.0f | parse+lits=%.0f expand-build=%.0f stream-out=%.0f after-match=%.0f cycles/wave\n", h4[3],
-                               (double)h4[0] / h4[3], (double)h4[1] / h4[3], (double)h4[2] / h4[3], (double)h4[6] / h4[3], (double)h4[4] / h4[3], (double)h4[5] / h4[3], (double)h4[7] / h4[3]);
-            set_fused_dbg(dbg);
-            (void)hipMemset(dbg, 0, 64);
-            f.dbg_buf = dbg;
-        }
-        if (f.dbg & 32768) {
-            if (!ctx->clk_buf) { (void)hipMalloc(&ctx->clk_buf, 64); (void)hipMemset(ctx->clk_buf, 0, 64); }
-            f.dbg_buf = ctx->clk_buf;
-        }
-        if (f.dbg & (16 | 32 | 64)) set_fused_abl(f.dbg);
-        f.lds_pad = ctx->sw.lds_pad;
-        // Tables with enough small tiles go to the role-split persistent kernel first (loader + hasher waves: tiles whose
-        // rows are all whole-leaf rows of the recognised periodic shape); what it leaves on its list — and small
-        // tables, where a persistent grid only adds start-up latency — is k_fused_small's.
-        const bool roles = !ctx->sw.no_roles && ctx->sw.roles_min != 0 && r->n_small_tiles >= ctx->sw.roles_min && r->n_small_tiles > 0 &&
-                           !(f.dbg & (1 | 2 | 4 | 8 | 128)) && !r->roles_off;
-        // A table of small rows AND big stored / hashed units (BASELINE configs[4]: 3,500 small files beside 6 GB of jars) whose
-        // last run handed nothing over: the small rows' kernel runs on the auxiliary stream beside the second hash pass, which
-        // then has only the big units' slices to do — nothing of the one depends on the other (C5: 0.28 ms of a 3.45 ms
-        // step ran in front of the pass).  k_verify checks the hand-over lists as in a lean run.
-        lean_mixed = r->lean_mixed_ok && r->lean_hint == 1 && r->bx_hint == 0 && !preset && !r->force_full && !f.dbg && !ctx->sw.ddbg;
-        const hipStream_t fs = lean_mixed ? ctx->aux : s;
-        if (lean_mixed) {
-            HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-        }
-        if (roles) {
-            f.cursor = r->cursor + 2;
-            f.tile_list = r->slow_list;
-            f.tile_count = r->pending_count + 3;
-            ktime_begin(ctx, "decode_verify_roles", fs);
-            launch_fused_roles(f, ctx->cus, fs);
-            ktime_end(ctx, fs);
-            lean = r->lean_ok && r->lean_hint == 1 && r->bx_hint == 0 && !preset && !r->force_full && !f.dbg;
-        }
-        if (r->n_small_tiles && !lean) {
-            ktime_begin(ctx, "decode_verify_fused", fs);
-            launch_fused_small(f, fs, roles ? ctx->cus * 5 : 0);
-            ktime_end(ctx, fs);
-        }
-        if (lean_mixed) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-    }
-    // 2) the two decode paths run side by side: block items (frames of >= 2 blocks, every block a work item) on the
-    //    auxiliary stream, the general decoder (single-block big rows + whatever the fused kernel handed over) on the
-    //    main one — each is latency-bound on its own and leaves most of the chip idle.  Frames the block path gives up
-    //    on are decoded by a second general launch afterwards.
-    if (!lean && !lean_mixed && !stored_only) {  // (a lean run: nothing is expected behind the fused kernels; k_verify checks that — rows_settle)
-    BlockScanArgs b{};
-    // The block items run on the auxiliary stream beside whatever the main stream has — unless it has nothing: a table of big
-    // rows only whose last run handed nothing over (`behind` below: the serial decoder is launched after the join anyway).
-    // Then everything goes down one stream: the fork and the join between two streams were ~0.1 ms of C3's 1.09 ms step.
-    const bool one_stream = r->n_cand && r->bx_hint == 0 && r->n_small_tiles == 0;
-    const hipStream_t ba = one_stream ? s : ctx->aux;
-    // ... and when its last run needed neither the serial block decoder nor the serial decoder behind it (every block item
-    // was written and hashed by the fused block kernel), those three launches are left out, the way a lean run of a table
-    // of small rows leaves out what stands behind the roles kernel: k_verify looks at the lists, a flagged run is repeated.
-    lean_blocks = one_stream && r->lean_blocks_ok && r->lean_hint2 == 1 && !preset && !r->force_full && r->n_bt && !ctx->sw.ddbg && !r->fz_total;
-    if (r->n_cand) {
-        b.cand_row = r->cand_row; b.cand_base = r->cand_base; b.cand_nblocks = r->cand_nblocks; b.n_cand = r->n_cand;
-        b.blobs = (const uint8_t *)d_blobs; b.blob_base = blob_base;
-        b.blob_off = r->blob_off; b.blob_size = r->blob_size; b.usize = r->usize; b.out_off = r->out_off; b.out_cap = out_cap;
-        b.item_src = r->item_src; b.row_flag = r->row_flag; b.status = r->status;
-        b.preset = preset;
-        b.pending = r->pending2; b.pending_count = r->pending_count + 1;  // its own hand-over list (count: second word of the control block)
-        if (!one_stream) {
-            HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
-            HIPCHK(ctx, hipStreamWaitEvent(ba, ctx->ev_fork, 0));
-        }
-        ktime_begin(ctx, "zstd_block_scan", ba);
-        launch_scan_blocks(b, ba);
-        ktime_end(ctx, ba);
-        if (r->n_bt) {  // blocks of the common shape: written and hashed in one go, skipped by the two passes below
-            HIPCHK(ctx, hipMemsetAsync(r->tile_done, 0, r->done_bytes, ba));
-            FusedBlocksArgs fb{};
-            fb.h = h;
-            fb.h.pass = 0;  // PASS_ALL
-            fb.blob_size = r->blob_size;
-            fb.bt_tile = r->bt_tile; fb.bt_item = r->bt_item; fb.n_bt = r->n_bt;
-            fb.item_src = r->item_src; fb.row_flag = r->row_flag;
-            fb.tile_done = r->tile_done; fb.item_done = r->item_done;
-            fb.dbg = ctx->sw.dbg;
-            ktime_begin(ctx, "decode_verify_fused_blocks", ba);
-            launch_fused_blocks(fb, ba);
-            ktime_end(ctx, ba);
-            launch_compact_items(r->item_done, r->n_items, r->todo, r->pending_count + 2, ba);
-        }
-        DecodeArgs a{};
-        a.preset = preset;
-        a.block_mode = 1;
-        a.item_row = r->item_row; a.item_k = r->item_k; a.item_src = r->item_src; a.n_items = r->n_items; a.row_flag = r->row_flag;
-        a.item_done = r->n_bt ? r->item_done : nullptr;
-        a.todo = r->n_bt ? r->todo : nullptr; a.n_todo = r->pending_count + 2;
-        a.pending_count = r->pending_count;
-        a.blobs = (const uint8_t *)d_blobs;
-        a.blob_base = blob_base;
-        a.blob_off = r->blob_off; a.blob_size = r->blob_size; a.usize = r->usize; a.out_off = r->out_off;
-        a.compressed = r->compressed;
-        a.out = (uint8_t *)d_out; a.out_cap = out_cap;
-        a.status = r->status; a.n_rows = r->n; a.cursor = r->cursor + 4;
-        a.lit_scratch = ctx->lit_scratch_b;
-        if (ctx->sw.ddbg) {  // diagnostic: phase shares of the previous block-item launch
-            static unsigned long long *dbg = nullptr;
-            if (!dbg) { (void)hipMalloc(&dbg, 64); (void)hipMemset(dbg, 0, 64); }
-            unsigned long long h[8];
-            (void)hipStreamSynchronize(s);
-            (void)hipStreamSynchronize(ba);
-            (void)hipMemcpy(h, dbg, 64, hipMemcpyDeviceToHost);
-            if (h[0]) fprintf(stderr, "[znippy ddbg] block items=%llu  cycles per item: literals=%.0f seq-tables=%.0f seq-decode=%.0f execute=%.0f tail=%.0f\n", h[0],
-                              (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0], (double)h[5] / h[0]);
-            (void)hipMemset(dbg, 0, 64);
-            a.dbg = dbg;
-        }
-        if (!lean_blocks) {
-            ktime_begin(ctx, "zstd_decode_blocks", ba);
-            launch_decode(a, std::min<int>(ctx->decode_grid, (int)r->n_items), false, ba);
-            ktime_end(ctx, ba);
-        }
-        if (r->fz_total) {
-            // Foreign frames (what the block items gave up on): entropy-decode every block at once, then execute frame by
-            // frame.  On the auxiliary stream, behind the block items and BESIDE the general decoder on the main stream:
-            // both are a few long-lived waves per frame, neither fills the chip (real text, libzstd -19 frames: the two
-            // used to run back to back, 7.0 + 10.6 ms).
-            FzArgs z{};
-            z.cand_row = r->cand_row; z.cand_fzbase = r->fz_base; z.cand_fzcap = r->fz_cap; z.n_cand = r->n_cand;
-            z.it_cand = r->fz_it_cand; z.total_items = r->fz_total; z.cand_nb = r->fz_nb; z.items = r->fz_items;
-            z.blobs = (const uint8_t *)d_blobs; z.blob_base = blob_base;
-            z.blob_off = r->blob_off; z.blob_size = r->blob_size; z.usize = r->usize; z.out_off = r->out_off; z.out_cap = out_cap;
-            z.out = (uint8_t *)d_out;
-            z.row_flag = r->row_flag; z.status = r->status; z.preset = preset;
-            z.lit_pool = ctx->fz_lit_pool; z.lit_cap = ctx->fz_lit_cap; z.seq_pool = ctx->fz_seq_pool; z.seq_cap = ctx->fz_seq_cap;
-            z.pool_used = reinterpret_cast<unsigned long long *>(r->ctl + 192);  // [lit bytes, seq records], zeroed with the control block
-            z.cursor = r->cursor + 12;
-            if (ctx->sw.ddbg) {  // diagnostic: where the previous run's execute kernel spent its cycles
-                static unsigned long long *dbg = nullptr;
-                if (!dbg) { (void)hipMalloc(&dbg, 256); (void)hipMemset(dbg, 0, 256); }
-                unsigned long long h[32];
-                (void)hipStreamSynchronize(s);
-                (void)hipStreamSynchronize(ba);
-                (void)hipMemcpy(h, dbg, 256, hipMemcpyDeviceToHost);
-                if (h[0]) fprintf(stderr, "[znippy ddbg] fz exec: frames=%llu groups=%llu seqs=%llu big=%llu rounds=%llu flushes=%llu histreads=%llu rep_groups=%llu | kcycles/frame: total=%.0f records=%.0f rep+scan=%.0f big=%.0f flush=%.0f histread=%.0f lits=%.0f matches=%.0f tail=%.0f\n",
-                                  h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8] / 1e3 / h[0], h[9] / 1e3 / h[0], h[10] / 1e3 / h[0], h[11] / 1e3 / h[0],
-                                  h[12] / 1e3 / h[0], h[13] / 1e3 / h[0], h[14] / 1e3 / h[0], h[15] / 1e3 / h[0], h[16] / 1e3 / h[0]);
-                if (h[20]) fprintf(stderr, "[znippy ddbg] fz entropy: blocks=%llu seqs=%llu | kcycles/block: literal tree=%.0f literal table+streams=%.0f sequence tables=%.0f sequence decode=%.0f\n",
-                                   h[20], h[25], h[21] / 1e3 / h[20], h[22] / 1e3 / h[20], h[23] / 1e3 / h[20], h[24] / 1e3 / h[20]);
-                (void)hipMemset(dbg, 0, 256);
-                z.dbg = dbg;
-            }
-            launch_fz_scan(z, r->fz_work, r->cursor + 13, ba);
-            ktime_begin(ctx, "zstd_foreign_entropy", ba);
-            launch_fz_entropy(z, ctx->cus, r->fz_work, r->cursor + 13, ba);
-            ktime_end(ctx, ba);
-            ktime_begin(ctx, "zstd_foreign_execute", ba);
-            launch_fz_exec(z, ba);
-            ktime_end(ctx, ba);
-        }
-        if (!one_stream) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-    }
-    if (r->n_compressed) {
-        DecodeArgs a{};
-        a.preset = preset;
-        a.list_a = r->list_a; a.n_list_a = r->n_list_a;
-        a.pending = r->pending; a.pending_count = r->pending_count;
-        a.blobs = (const uint8_t *)d_blobs;
-        a.blob_base = blob_base;
-        a.blob_off = r->blob_off; a.blob_size = r->blob_size; a.usize = r->usize; a.out_off = r->out_off;
-        a.compressed = r->compressed;
-        a.out = (uint8_t *)d_out; a.out_cap = out_cap;
-        a.status = r->status; a.n_rows = r->n; a.cursor = r->cursor;
-        a.lit_scratch = ctx->lit_scratch;
-        if (ctx->sw.ddbg) {  // diagnostic: phase shares of the previous general-decoder launch
-            static unsigned long long *dbg = nullptr;
-            if (!dbg) { (void)hipMalloc(&dbg, 64); (void)hipMemset(dbg, 0, 64); }
-            unsigned long long h[8];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(h, dbg, 64, hipMemcpyDeviceToHost);
-            if (h[0]) fprintf(stderr, "[znippy ddbg] general decoder frames=%llu  kcycles per frame: headers+tree=%.1f huffman-table=%.1f literal-streams=%.1f seq-tables=%.1f first-batch=%.1f decode+execute=%.1f tail=%.1f\n", h[0],
-                              h[6] / 1e3 / h[0], h[7] / 1e3 / h[0], h[1] / 1e3 / h[0], h[2] / 1e3 / h[0], h[3] / 1e3 / h[0], h[4] / 1e3 / h[0], h[5] / 1e3 / h[0]);
-            (void)hipMemset(dbg, 0, 64);
-            a.dbg = dbg;
-        }
-        if (bx) {
-            // Batch path: every frame that is still undecoded — big single-block rows, what the fused kernel handed over,
-            // block candidates the block-item path flagged — goes through the lane-per-block kernels in ONE pass (the
-            // more blocks, the fuller their waves), behind the block items; the serial decoder takes what they leave.
-            if (r->n_cand) {
-                HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-                launch_finish_blocks(b, s, true);  // unflagged candidates are done; flagged ones wait for the batch path's verdict
-            }
-            BxArgs x{};
-            x.list_a = r->list_a; x.n_list_a = r->n_list_a;
-            x.pending = r->pending; x.pending_count = r->pending_count;
-            if (small_off) {  // every row is the batch path's: its list is all rows, nothing was handed over (a word that stays zero)
-                x.list_a = r->all_rows; x.n_list_a = r->n;
-                x.pending_count = reinterpret_cast<uint32_t *>(r->ctl + 448) + 15;
-            }
-            x.bc_row = r->cand_row; x.n_bc = r->n_cand;
-            x.blobs = (const uint8_t *)d_blobs; x.blob_base = blob_base;
-            x.blob_off = r->blob_off; x.blob_size = r->blob_size; x.usize = r->usize; x.out_off = r->out_off; x.out_cap = out_cap;
-            x.out = (uint8_t *)d_out;
-            x.status = r->status; x.preset = preset; x.row_flag = r->row_flag;
-            x.cand_row = r->bx_cand_row; x.cand_base = r->bx_cand_base; x.cand_nb = r->bx_cand_nb; x.slot_cap = r->bx_slots;
-            x.items = r->bx_items; x.prep = r->bx_prep; x.item_cap = r->bx_item_cap;
-            x.ctr = reinterpret_cast<uint32_t *>(r->ctl + 384);
-            x.huf_list = r->bx_huf_list; x.seq_list = r->bx_seq_list; x.sort_tmp = r->bx_sort_tmp;
-            x.lit_pool = ctx->fz_lit_pool; x.lit_cap = ctx->fz_lit_cap; x.seq_pool = ctx->fz_seq_pool; x.seq_cap = ctx->fz_seq_cap;
-            x.fse_pool = ctx->bx_fse_pool; x.fse_cap = ctx->bx_fse_cap; x.huf_pool = ctx->bx_huf_pool; x.huf_cap = ctx->bx_huf_cap;
-            x.pool_used = reinterpret_cast<unsigned long long *>(r->ctl + 256);
-            x.pending2 = r->pending2; x.pending2_count = r->pending_count + 1;
-            // 0: the blocks that get a wave of their own are picked from the table's histogram (k_bx_split: one workgroup per
-            // list, worth its ~0.1-0.4 ms where the chip is not full of blocks anyway); big tables keep the fixed threshold
-            x.big_seq = ctx->sw.bx_big_set || r->bx_nblk > 32768 ? ctx->sw.bx_big : 0u;
-            const bool rx = r->rx_base && ctx->rx_pool && r->rx_words;
-            if (rx) {
-                x.rx_ptr = ctx->rx_pool; x.rx_cap = ctx->rx_cap; x.rx_chunk = ctx->rx_chunk; x.rx_cdone = ctx->rx_cdone;
-                x.rx_base = r->rx_base; x.rx_fail = r->rx_fail; x.rx_blk = r->rx_blk; x.rx_list = r->rx_list;
-                x.rx_pending = reinterpret_cast<uint32_t *>(r->ctl + 448);
-                x.rx_bound = std::min<uint64_t>(r->rx_words, ctx->rx_cap);
-                x.rx_min = r->rx_min;
-            }
-            x.small_frames = r->n_compressed && r->bx_bytes / r->n_compressed <= 65536;
-            if (ctx->sw.ddbg) {  // diagnostic: where the previous run's table kernel spent its waves' time
-                static unsigned long long *dbg = nullptr;
-                if (!dbg) { (void)hipMalloc(&dbg, 1024); (void)hipMemset(dbg, 0, 1024); }
-                unsigned long long h[128];
-                (void)hipStreamSynchronize(s);
-                (void)hipMemcpy(h, dbg, 1024, hipMemcpyDeviceToHost);
-                if (h[64]) {
-                    const unsigned long long *e = h + 64;
-                    fprintf(stderr, "[znippy ddbg] batch execute: frames=%llu groups=%llu seqs=%llu big=%llu rounds=%llu flushes=%llu histreads=%llu | kcycles/frame: total=%.1f records=%.1f rep+scan=%.1f big=%.1f flush=%.1f histread=%.1f lits=%.1f matches=%.1f tail=%.1f\n",
-                            e[0], e[1], e[2], e[3], e[4], e[5], e[6], e[8] / 1e3 / e[0], e[9] / 1e3 / e[0], e[10] / 1e3 / e[0], e[11] / 1e3 / e[0], e[12] / 1e3 / e[0], e[13] / 1e3 / e[0],
-                            e[14] / 1e3 / e[0], e[15] / 1e3 / e[0], e[16] / 1e3 / e[0]);
-                }
-                if (h[32]) fprintf(stderr, "[znippy ddbg] batch tables: wave passes=%llu  kcycles per pass: literals header + weights=%.1f sequences header=%.1f huffman table=%.1f sequence tables=%.1f\n", h[32],
-                                   h[33] / 1e3 / h[32], h[34] / 1e3 / h[32], h[35] / 1e3 / h[32], h[36] / 1e3 / h[32]);
-                (void)hipMemset(dbg, 0, 1024);
-                x.dbg = dbg;
-            }
-            static const char *const bx_names[10] = {"zstd_batch_scan", "zstd_batch_tables", "zstd_batch_huffman", "zstd_batch_sequences", "zstd_batch_execute", "zstd_batch_finish",
-                                                     "zstd_batch_sequences_long", "zstd_batch_sort", "zstd_resolve_plan", "zstd_resolve_expand"};
-            auto stage = [&](int st, hipStream_t on) {
-                ktime_begin(ctx, bx_names[st], on);
-                launch_bx_stage(x, ctx->cus, st, on);
-                ktime_end(ctx, on);
-            };
-            stage(0, s);
-            stage(1, s);
-            stage(7, s);
-            // the long chains (blocks of >= BX_BIG_SEQ sequences, a wave each) run on the auxiliary stream beside the Huffman
-            // streams and the lane-per-block sequence kernel: each is a few hundred long-lived waves at most
-            HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
-            HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-            stage(6, ctx->aux);
-            HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-            // ... and the lane-per-block sequence kernel beside the Huffman streams on a third stream (the write side's copy
-            // stream, idle here): the two touch different pools and different fields of a block's record.  A small table is
-            // its longest chains: the image's source text had Huffman 2.5 + sequences 1.8 ms in a row beside 3.5 ms of long chains.
-            // (Only where the chip is not full of blocks anyway: 100k blocks, both kernels chip-wide: 2.98 ms together against
-            // 1.85 + 0.96 one after the other.)
-            const bool third = r->bx_nblk <= 32768;
-            if (third) {
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->copy, ctx->ev_fork, 0));
-                stage(3, ctx->copy);
-                HIPCHK(ctx, hipEventRecord(ctx->ev_join2, ctx->copy));
-            }
-            stage(2, s);
-            if (!third) stage(3, s);
-            HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-            if (third) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join2, 0));
-            if (rx) {  // big frames: resolved in parallel (every byte a word, pointer jumping) instead of executed by a wave each
-                stage(8, s);
-                if (ctx->sw.trace) {
-                    uint32_t g[16];
-                    unsigned long long pu[16];
-                    (void)hipMemcpy(g, r->ctl + 384, 64, hipMemcpyDeviceToHost);
-                    (void)hipMemcpy(pu, r->ctl + 256, 128, hipMemcpyDeviceToHost);
-                    fprintf(stderr, "[znippy trace] resolve plan: slots %u items %u list %u frames %u words %llu extent %llu cap %llu item_cap %u\n", g[0], g[1], g[9], g[11], pu[10], pu[11],
-                            (unsigned long long)ctx->rx_cap, r->bx_item_cap);
-                }
-                // the frames the plan did not take are executed by a wave each, beside the resolve stages (they share nothing)
-                HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
-                HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-                stage(4, ctx->aux);
-                HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-                stage(9, s);
-                static const char *const jump_names[12] = {"zstd_resolve_jump_0", "zstd_resolve_jump_1", "zstd_resolve_jump_2", "zstd_resolve_jump_3", "zstd_resolve_jump_4", "zstd_resolve_jump_5",
-                                                           "zstd_resolve_jump_6", "zstd_resolve_jump_7", "zstd_resolve_jump_8", "zstd_resolve_jump_9", "zstd_resolve_jump_10", "zstd_resolve_jump_11"};
-                static_assert(zn::RX_ROUNDS <= 12, "names");
-                if (!ctx->sw.ddbg) ktime_begin(ctx, "zstd_resolve_jump", s);
-                for (int rd = 0; rd < (int)zn::RX_ROUNDS; rd++) {
-                    if (ctx->sw.ddbg) ktime_begin(ctx, jump_names[rd], s);  // diagnostic: every round by itself
-                    launch_bx_stage(x, ctx->cus, 10 + rd, s);
-                    if (ctx->sw.ddbg) ktime_end(ctx, s);
-                }
-                if (!ctx->sw.ddbg) ktime_end(ctx, s);
-                ktime_begin(ctx, "zstd_resolve_store", s);
-                launch_bx_stage(x, ctx->cus, 30, s);
-                ktime_end(ctx, s);
-                HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-            } else stage(4, s);
-            stage(5, s);
-            a.list_a = nullptr; a.n_list_a = 0;
-            a.pending = r->pending2; a.pending_count = r->pending_count + 1;
-            a.cursor = r->cursor + 8;
-            ktime_begin(ctx, "zstd_decode_fallback");
-            if (!ctx->sw.fz_only)
-                launch_decode(a, std::min<int>(ctx->decode_grid, (int)r->n_compressed), r->wide_rows, s);
-            ktime_end(ctx);
-        } else {
-            // Round-2 flow (no batch path: ZNIPPY_NO_BX, no pools, or a table whose last run handed nothing over): the
-            // serial decoder takes the host's list and what the fused kernel hands over, beside the block items on the
-            // auxiliary stream — or behind them when nothing is expected (its launch then returns at once instead of
-            // waiting for CUs next to the block kernels: C3's 0.25 ms "general decoder" that only waited).
-            const bool behind = r->n_cand && r->bx_hint == 0;
-            if (behind) {
-                if (!one_stream) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-                launch_finish_blocks(b, s, false);
-            }
-            if (!lean_blocks) {
-            ktime_begin(ctx, "zstd_decode_general");
-            // A full grid of this kernel (4 workgroups per CU at 128 VGPRs) is the whole register file: whatever the auxiliary
-            // stream launches then waits until workgroups run out of rows.  With candidates for the block / foreign-frame
-            // paths it leaves them a quarter.
-            const int gen_grid = r->n_cand && !behind ? ctx->decode_grid / 4 * ctx->gen_share : ctx->decode_grid;
-            launch_decode(a, std::min<int>(gen_grid, (int)r->n_compressed), r->wide_rows, s);
-            ktime_end(ctx);
-            }
-            if (r->n_cand && !lean_blocks) {  // join (block items and the foreign-frame path on the auxiliary stream), then what both gave up on
-                if (!behind) {
-                    HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-                    launch_finish_blocks(b, s, false);
-                }
-                a.list_a = nullptr; a.n_list_a = 0;
-                a.pending = r->pending2; a.pending_count = r->pending_count + 1;
-                a.cursor = r->cursor + 8;
-                ktime_begin(ctx, "zstd_decode_fallback");
-                if (!ctx->sw.fz_only)
-                    launch_decode(a, std::min<int>(ctx->decode_grid, (int)r->n_cand), r->wide_rows, s);
-                ktime_end(ctx);
-            }
-        }
-    }
-    }
-    if (!lean) {
-    // 3) second hash pass: slices of big rows + rows the general decoder finished
-    h.pass = stored_only ? 0 : 2;  // PASS_ALL : PASS_SECOND
-    h.tile_done = r->n_bt && !stored_only ? r->tile_done : nullptr;
-    ktime_begin(ctx, "blake3_second_pass");
-    launch_hash_tiles(h, s);
-    ktime_end(ctx);
-    if (r->plan.n_big) {
-        ktime_begin(ctx, "blake3_merge_big");
-        launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, r->digests, r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, r->plan.max_cvs, s);
-        ktime_end(ctx);
-    }
-    }  // !lean
-    if (lean_mixed) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-    r->last_lean = lean || lean_blocks || lean_mixed;
-    ktime_begin(ctx, "verify");
-    // the lists a lean run must have left empty: [0] rows handed over by the fused kernels, [1] rows for the serial decoder, [5]
-    // flagged candidates; [3] tiles the roles kernel left (small rows), [2] block items the fused block kernel left (big rows)
-    launch_verify(r->digests, r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt,
-                  r->corrupt_cap, s, (lean || lean_blocks || lean_mixed) ? r->pending_count : nullptr, (lean || lean_mixed) ? 0x2Bu : 0x27u);
-    ktime_end(ctx);
-    HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * slot, r->counters, 128, hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipEventRecord(r->ev_done[slot], s));
-    HIPCHK(ctx, hipGetLastError());
-    return ZNIPPY_OK;
+    if ((rc = run_clear(ctx, r, p, run)) || !r->n) return rc;
+    if (!p.small_off && !p.stored_only && (rc = run_small_rows(ctx, r, p, run))) return rc;
+    if (p.decode && r->n_cand && (rc = run_block_items(ctx, r, p, run))) return rc;
+    if (p.decode && r->n_compressed && (rc = p.bx ? run_batch_path(ctx, r, p, run) : run_serial_flow(ctx, r, p, run))) return rc;
+    if (!p.lean) run_second_hash(ctx, r, p, run);
+    return run_verify(ctx, r, p, run);
 }
 
 // A run that failed after its first stream operation: whatever it queued on the auxiliary stream is joined back into the
@@ -1972,43 +1999,37 @@ int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
     if (!ctx || !out || (n && (!src_offset || !len)) || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    znippy_rounds *r = new znippy_rounds();
+    TDbg td(ctx->sw.tdbg, "rounds_create");
+    std::unique_ptr<znippy_rounds, void (*)(znippy_rounds *)> guard(new znippy_rounds(), znippy_rounds_destroy);  // every failure below: return
+    znippy_rounds *const r = guard.get();
     r->ctx = ctx;
     ctx->live_tables++;
     r->n = (uint32_t)n;
-    TDbg td(ctx->sw.tdbg, "rounds_create");
     if (skip) r->h_skip.assign(skip, skip + n);  // (results: which rounds are stored; empty = none)
     uint64_t tot[8];
     zn_rounds_totals(len, skip, n, tot);  // sizes of the device arrays; the arrays themselves are filled on the device
     r->blob_bound = tot[4]; r->in_bytes = tot[5]; r->enc_bytes = tot[6];
     r->all_stored_aligned = n > 0 && r->enc_bytes == 0 && !tot[7];
-    if (tot[0] >= 0xFFFFFFF0ull) { znippy_rounds_destroy(r); return ZNIPPY_E_INVAL; }
+    if (tot[0] >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
     r->n_items = (uint32_t)tot[0]; r->prov_bytes = tot[1]; r->n_small = (uint32_t)tot[2]; r->n_wide = (uint32_t)tot[3];
     td.mark("totals");
     int rc;
     if ((rc = dev_upload(ctx, &r->src_off, src_offset, n)) || (rc = dev_upload(ctx, &r->len, len, n)) ||
-        (skip ? (rc = dev_upload(ctx, &r->skip, skip, n)) : (tmalloc(ctx, &r->skip, std::max<size_t>(n, 16)) != hipSuccess ? (rc = ZNIPPY_E_NOMEM) : 0))) {
-        znippy_rounds_destroy(r);
+        (skip ? (rc = dev_upload(ctx, &r->skip, skip, n)) : (tmalloc(ctx, &r->skip, std::max<size_t>(n, 16)) != hipSuccess ? (rc = ZNIPPY_E_NOMEM) : 0)))
         return rc;
-    }
     if (!skip && n) HIPCHK(ctx, hipMemsetAsync(r->skip, 0, n, ctx->stream));
     td.mark("columns_h2d");
     r->res_bytes = 16 + (size_t)n * (8 + 8 + 32);
     for (int k = 0; k < 2; k++)
         if (tmalloc(ctx, &r->res_m[k], r->res_bytes) != hipSuccess ||
             !(r->h_res_m[k] = (uint8_t *)pinned_take(ctx, r->res_bytes, &r->h_res_cap_m[k])) ||
-            !(r->ev_enc[k] = event_take(ctx)) || !(r->ev_res[k] = event_take(ctx))) {
-            znippy_rounds_destroy(r);
+            !(r->ev_enc[k] = event_take(ctx)) || !(r->ev_res[k] = event_take(ctx)))
             return ZNIPPY_E_NOMEM;
-        }
     rounds_select(r, 0);
     td.mark("slabs");
     PlanBuf p;
     build_plan([&](uint32_t u) { return len[u]; }, (uint32_t)n, p);
-    if ((rc = upload_plan(ctx, p, r->plan))) {
-        znippy_rounds_destroy(r);
-        return rc;
-    }
+    if ((rc = upload_plan(ctx, p, r->plan))) return rc;
     if (r->n_items == n && r->n_wide == 0 && r->enc_bytes == r->in_bytes && n) {
         uint32_t max_units = 0;
         for (const Tile &t : p.tiles) max_units = std::max(max_units, t.n_units);
@@ -2042,7 +2063,6 @@ int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint
         tmalloc(ctx, &r->piece_len, 4 * ni) != hipSuccess || tmalloc(ctx, &r->piece_start, 8 * ni) != hipSuccess ||
         tmalloc(ctx, &r->local_excl, 8 * ni) != hipSuccess || tmalloc(ctx, &r->block_tot, 8 * nsb) != hipSuccess) {
         tfree(ctx, sums);
-        znippy_rounds_destroy(r);
         return ZNIPPY_E_NOMEM;
     }
     if (n) {
@@ -2058,7 +2078,7 @@ int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint
     // the encoder on every run, so one copy at creation is enough
     if (r->n_items) HIPCHK(ctx, hipMemcpyAsync(r->piece_len, r->piece_len_init, 4 * (size_t)r->n_items, hipMemcpyDeviceToDevice, ctx->stream));
     td.mark("rest");
-    *out = r;
+    *out = guard.release();
     return ZNIPPY_OK;
 }
 
@@ -2261,17 +2281,11 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
         launch_ldm_index(r->d_ldm, (uint32_t)r->h_ldm.size(), r->ldm_chunks, (const uint8_t *)d_src, r->src_off, r->len, ctx->ldm, s);
         ktime_end(ctx);
     }
-    if (ctx->sw.edbg) {  // diagnostic: phase shares of the previous run's wide-variant blocks
-        static unsigned long long *dbg = nullptr;
-        if (!dbg) { (void)hipMalloc(&dbg, 64); (void)hipMemset(dbg, 0, 64); }
-        unsigned long long h[8];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, dbg, 64, hipMemcpyDeviceToHost);
-        if (h[0]) fprintf(stderr, "[znippy edbg] wide blocks=%llu  cycles per block: setup=%.0f matching=%.0f literals=%.0f sequences=%.0f\n", h[0],
-                          (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0]);
-        (void)hipMemset(dbg, 0, 64);
-        a.dbg = dbg;
-    }
+    if (ctx->sw.edbg)  // diagnostic: phase shares of the previous run's wide-variant blocks
+        a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_ENCODE, s, nullptr, [](const unsigned long long *h) {
+            if (h[0]) fprintf(stderr, "[znippy edbg] wide blocks=%llu  cycles per block: setup=%.0f matching=%.0f literals=%.0f sequences=%.0f\n", h[0],
+                              (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0]);
+        });
     // Tables of small encoded rounds only: the encoder's waves hash the rounds they are about to encode (EncodeArgs::fuse_tiles)
     const bool fuse_hash = r->fuse_tiles && !r->store_incompressible && !ctx->sw.nohash && !ctx->sw.no_fuse_hash;
     ktime_begin(ctx, fuse_hash ? "zstd_encode_hash" : "zstd_encode");

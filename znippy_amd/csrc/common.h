@@ -264,7 +264,11 @@ struct BxArgs {
     uint32_t rx_min;                    // frames of at least this many bytes are resolved (RX_MIN; less for tables with few rows above 64 KiB)
 };
 constexpr uint32_t RX_NONE = 0xFFFFFFFFu, RX_DONE = 0x80000000u, RX_MIN = 256u << 10, RX_ROUNDS = 12, RX_JUMPS = 6;
-void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s);  // 0 scan, 1 prep, 7 sort the work lists, 2 huf, 3 fse (lane = block), 4 exec, 5 finish, 6 fse (wave = block), 8 resolve: plan, 9 expand, 10 + r jump round r, 30 store
+// the batch path's launches, in the order of a run: scan, prep (the tables), sort the work lists, fse (wave = block) beside huf
+// and fse (lane = block), then exec — or the resolve path: plan, exec beside expand, jump round r, store —, finish
+enum BxStage : int { BX_SCAN = 0, BX_PREP = 1, BX_HUF = 2, BX_FSE = 3, BX_EXEC = 4, BX_FINISH = 5, BX_FSE_WAVE = 6, BX_SORT = 7, BX_RX_PLAN = 8, BX_RX_EXPAND = 9,
+                     BX_RX_JUMP = 10 /* + r */, BX_RX_STORE = 30 };
+void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s);  // stage: a BxStage
 void bx_predefined_tables(uint16_t cells[160]);  // host: the three predefined tables as pool cells
 
 }  // namespace zn

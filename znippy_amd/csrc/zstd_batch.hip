@@ -2174,38 +2174,38 @@ __global__ __launch_bounds__(64) void k_bx_finish(BxArgs a) {
     }
 }
 
-// stage 0..5 = scan, prep, huf, fse (lane = block), exec, finish; 6 = fse (wave = block, the long chains: beside stages 2 and 3 on
-// another stream) — launched one by one so that each can be timed
+// the stages of a run (BxStage, common.h; BX_FSE_WAVE: the long chains, beside BX_HUF and BX_FSE on another stream) — launched one
+// by one so that each can be timed
 void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s) {
     const uint32_t slots = a.slot_cap, lane_grid = std::max(std::min<uint32_t>((slots + 63) / 64, (uint32_t)cus * 8), 1u);
     if (!slots) return;
     auto cap = [&](uint32_t want, uint32_t per_cu) { return dim3(std::max(std::min<uint32_t>(want, (uint32_t)cus * per_cu), 1u)); };
     switch (stage) {
-    case 0: hipLaunchKernelGGL(k_bx_scan, dim3(lane_grid), dim3(64), 0, s, a); break;
-    case 1: hipLaunchKernelGGL(k_bx_prep, cap((a.item_cap + 63) / 64, 3), dim3(64), 0, s, a); break;
-    case 7:
+    case BX_SCAN: hipLaunchKernelGGL(k_bx_scan, dim3(lane_grid), dim3(64), 0, s, a); break;
+    case BX_PREP: hipLaunchKernelGGL(k_bx_prep, cap((a.item_cap + 63) / 64, 3), dim3(64), 0, s, a); break;
+    case BX_SORT:
         if (!a.big_seq) hipLaunchKernelGGL(k_bx_split, dim3(3), dim3(1024), 0, s, a);
         hipLaunchKernelGGL(k_bx_sort, dim3(5), dim3(1024), 0, s, a, a.sort_tmp);
         break;
-    case 2: hipLaunchKernelGGL(k_bx_huf, cap((a.item_cap + BX_HUF_BLOCKS - 1) / BX_HUF_BLOCKS, 2), dim3(64), 0, s, a); break;
-    case 3:
+    case BX_HUF: hipLaunchKernelGGL(k_bx_huf, cap((a.item_cap + BX_HUF_BLOCKS - 1) / BX_HUF_BLOCKS, 2), dim3(64), 0, s, a); break;
+    case BX_FSE:
         hipLaunchKernelGGL(k_bx_fse, cap((a.item_cap + 63) / 64, 3), dim3(64), 0, s, a, a.seq_list, a.ctr + 3, 64u);
         hipLaunchKernelGGL(k_bx_fse, cap((a.item_cap + 31) / 32, 3), dim3(64), 0, s, a, a.seq_list + a.item_cap, a.ctr + 5, 32u);
         hipLaunchKernelGGL(k_bx_fse, cap((a.item_cap + 15) / 16, 3), dim3(64), 0, s, a, a.seq_list + 2 * (size_t)a.item_cap, a.ctr + 6, 16u);
         break;
-    case 6: hipLaunchKernelGGL(k_bx_fse_wave, cap(a.item_cap, 16), dim3(64), 0, s, a, a.seq_list + 3 * (size_t)a.item_cap, a.ctr + 7); break;  // 10 KB of LDS per wave: 16 per CU
-    case 4:
+    case BX_FSE_WAVE: hipLaunchKernelGGL(k_bx_fse_wave, cap(a.item_cap, 16), dim3(64), 0, s, a, a.seq_list + 3 * (size_t)a.item_cap, a.ctr + 7); break;  // 10 KB of LDS per wave: 16 per CU
+    case BX_EXEC:
         if (a.dbg) hipLaunchKernelGGL((k_bx_exec<true, WIN_HIST, WIN_CAP, 1>), cap(slots, 12), dim3(64), 0, s, a);
         else if (a.small_frames) hipLaunchKernelGGL((k_bx_exec<false, BX_SMALL_HIST, BX_SMALL_CAP, BX_SMALL_WAVES>), cap(slots, 4 * BX_SMALL_WAVES), dim3(64), 0, s, a);
         else hipLaunchKernelGGL((k_bx_exec<false, WIN_HIST, WIN_CAP, 1>), cap(slots, 12), dim3(64), 0, s, a);
         break;
-    case 8: hipLaunchKernelGGL(k_rx_plan, cap(slots, 8), dim3(64), 0, s, a); break;
-    case 9: hipLaunchKernelGGL(k_rx_expand, cap(a.item_cap, 32), dim3(64), 0, s, a); break;  // (static stride over the list; lone chains: the more the better, 54 VGPRs, no LDS)
-    case 30: hipLaunchKernelGGL(k_rx_store, cap((uint32_t)std::min<uint64_t>((a.rx_bound + 1023) / 1024, 1u << 30), 64), dim3(256), 0, s, a); break;
-    case 5: hipLaunchKernelGGL(k_bx_finish, dim3(lane_grid), dim3(64), 0, s, a); break;
+    case BX_RX_PLAN: hipLaunchKernelGGL(k_rx_plan, cap(slots, 8), dim3(64), 0, s, a); break;
+    case BX_RX_EXPAND: hipLaunchKernelGGL(k_rx_expand, cap(a.item_cap, 32), dim3(64), 0, s, a); break;  // (static stride over the list; lone chains: the more the better, 54 VGPRs, no LDS)
+    case BX_RX_STORE: hipLaunchKernelGGL(k_rx_store, cap((uint32_t)std::min<uint64_t>((a.rx_bound + 1023) / 1024, 1u << 30), 64), dim3(256), 0, s, a); break;
+    case BX_FINISH: hipLaunchKernelGGL(k_bx_finish, dim3(lane_grid), dim3(64), 0, s, a); break;
     default:
-        if (stage >= 10 && stage < 10 + (int)RX_ROUNDS)
-            hipLaunchKernelGGL(k_rx_jump, cap((uint32_t)std::min<uint64_t>((a.rx_bound + 1023) / 1024, 1u << 30), 32), dim3(256), 0, s, a, (uint32_t)(stage - 10));
+        if (stage >= BX_RX_JUMP && stage < BX_RX_JUMP + (int)RX_ROUNDS)
+            hipLaunchKernelGGL(k_rx_jump, cap((uint32_t)std::min<uint64_t>((a.rx_bound + 1023) / 1024, 1u << 30), 32), dim3(256), 0, s, a, (uint32_t)(stage - BX_RX_JUMP));
         break;
     }
 }
