@@ -14,6 +14,8 @@
  *   znippy_rows_* + znippy_decode_verify_rows
  *                                body of the read worker loop  znippy-common/src/decompress.rs:L135-190
  *                                (+ stats merge L195-221)      over index columns (index.rs:L43-54)
+ *   znippy_verify_rows[_async]   the same loop, save_data=false  znippy-common/src/decompress.rs:L186-189 (the write is
+ *                                (`verify`)                     skipped), called from index.rs:L550-553
  *   znippy_rounds_* + znippy_encode_hash_rounds
  *                                barrel + writer bodies        znippy-compress/src/stream_packer.rs:L217-284,
  *                                                              znippy-compress/src/slot_packer.rs:L551-609
@@ -110,7 +112,10 @@ typedef struct {
  *   checksum                                  : 32 bytes per row (NULL = no verification)
  *   out_offset                                : u64 per row, byte position of the row's decoded
  *                                               bytes in the caller's flat output region
- *                                               (stands for (file, fdata_offset), L186-189)
+ *                                               (stands for (file, fdata_offset), L186-189).
+ *                                               NULL = a table that can only be verified
+ *                                               (znippy_verify_rows; a decode call on it
+ *                                               returns ZNIPPY_E_INVAL)
  * Also builds the work plan (tiles of <=64 BLAKE3 leaves) that drives the kernels' cursor. */
 int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint64_t *blob_size,
                        const uint8_t *compressed_bitmap, const uint64_t *uncompressed_size,
@@ -157,6 +162,25 @@ int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_
                               uint64_t corrupt_cap, int32_t *row_status);
 int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs,
                                     uint64_t blob_base, void *d_out, uint64_t out_cap);
+/* Verify only: the read loop with save_data=false (decompress.rs:L186-189; `verify`, index.rs:L550-553) — every blob is
+ * read, decoded as far as hashing it needs, hashed and compared, and no output is written.  It takes the place of a
+ * znippy_decode_verify_rows[_async] call whose d_out is thrown away.  The results are read with the same three calls
+ * (znippy_rows_results, _results_lagged, znippy_rows_digests) and are what a decode run of the same table over the same
+ * blobs reports — total_written_bytes included, which the reference counts whatever save_data is (decompress.rs:L168-169).
+ * A verify run is a run like any other in the table's sequence: it takes a slot of the two-run ring, uses and updates what
+ * the table remembers of its last run (it may be a lean run, and is then repeated as a verify run if it comes back
+ * flagged), and may be queued between decode runs on the same table; it never writes into a d_out an earlier decode run
+ * was given.  Rows outside the declared blob region report ZNIPPY_E_CORRUPT as before; there is no output side to check.
+ * Rows of the periodic shape the fused kernels recognise, the periodic and raw blocks of big multi-block frames and stored
+ * rows are hashed where they are (on chip, or in the blob region).  Only rows that go through a decoder need their bytes
+ * in memory: those land in a scratch region the CONTEXT owns — one 16-byte aligned slot per compressed row with bytes,
+ * sized by the table's compressed rows (a table without one takes none), grow-only, kept until the context goes, capped at
+ * 16 GiB: a table that needs more returns ZNIPPY_E_NOMEM and queues nothing.  Runs of one context are ordered on its stream
+ * and the auxiliary streams join before a run ends, so runs in flight — of one table or several — share the region. */
+int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base,
+                       znippy_verify_counters *counters, uint64_t *corrupt_rows, uint64_t corrupt_cap,
+                       int32_t *row_status);
+int znippy_verify_rows_async(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base);
 int znippy_rows_results(znippy_ctx *ctx, znippy_rows *rows, znippy_verify_counters *counters,
                         uint64_t *corrupt_rows, uint64_t corrupt_cap, int32_t *row_status);
 /* Counters of the run `lag` (0 or 1) runs before the latest one queued on this table: waits for THAT run only,
@@ -233,6 +257,14 @@ int znippy_measure_blake3_pass_ns(znippy_ctx *ctx, float *ns_per_pass_per_simd, 
 /* Shader clock (GHz) one wave of the read side's small-row kernel saw during the last run of a context created with
  * ZNIPPY_DBG bit 32768 set: its life in shader cycles / in 100 MHz ticks.  0 if nothing was recorded. */
 int znippy_last_shader_ghz(znippy_ctx *ctx, float *ghz);
+
+/* Where a verify-only run (znippy_verify_rows) keeps the rows it has to materialise: the context's scratch region as it
+ * is now (*d_base, DEVICE; NULL when the table needs none), the extent of this table's slots in it (*bytes) and, when
+ * row_offset is not NULL, every row's slot (HOST, one entry per row of the table, UINT64_MAX = the row has no slot: a
+ * stored or an empty row).  Builds the slots and the region if no verify run has yet.  For tests and measurements — the
+ * region's contents are no contract for consumers, and the pointer moves when the region grows. */
+int znippy_rows_verify_scratch(znippy_ctx *ctx, znippy_rows *rows, const void **d_base, uint64_t *bytes,
+                               uint64_t *row_offset);
 
 #ifdef __cplusplus
 }

@@ -74,7 +74,11 @@ int znippy_compress_dir(const char *input_dir, const char *output, int no_skip, 
 /* ---- read side ---- */
 /* rank/world split the row cursor into contiguous ranges balanced by uncompressed bytes (world = 1:
  * everything).  Counters are this rank's share; total_files is global.  corrupt_rows receives the
- * absolute row numbers with a checksum mismatch (ascending). */
+ * absolute row numbers with a checksum mismatch (ascending).
+ * save_data = 0 is the reference's `verify` (index.rs:L550-553): rows are checked by verify-only runs
+ * (znippy_verify_rows), no output region exists on the device and a range is cut by its blob bytes plus the
+ * scratch of its compressed rows.  ZNIPPY_NO_VERIFY_ONLY=1 in the environment: every row is decoded into a
+ * region that is thrown away, as before (A/B); the report and the corrupt rows are the same either way. */
 int znippy_decompress_archive(const char *index_path, int save_data, const char *out_dir, int device,
                               uint32_t rank, uint32_t world, znippy_verify_report *report,
                               uint64_t *corrupt_rows, uint64_t corrupt_cap, uint64_t *n_corrupt);

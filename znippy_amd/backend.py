@@ -58,6 +58,21 @@ class HipBackend:
         rt.close()
         return counters, corrupt, status, out
 
+    # read side, verify only (decompress.rs save_data=false): counters, corrupt rows and status, no bytes — nothing is
+    # allocated for an output and nothing comes back over the bus
+    def verify(self, blobs, blob_base, blob_offset, blob_size, usize, compressed, checksum):
+        n = len(blob_offset)
+        if n == 0:
+            return dict(total_chunks=0, total_written_bytes=0, verified_bytes=0, corrupt_bytes=0, corrupt_rows=0,
+                        decode_errors=0), np.zeros(0, np.uint64), np.zeros(0, np.int32)
+        d_blobs = self._to_dev(np.concatenate([blobs, np.zeros(64, np.uint8)]))
+        bitmap = np.packbits(np.asarray(compressed, dtype=bool), bitorder="little")
+        rt = self.hip.RowTable(self.ctx, blob_offset, blob_size, usize, None, bitmap, checksum)
+        counters, corrupt, status = rt.verify(d_blobs, blob_base=blob_base, blob_cap=len(blobs))
+        corrupt, status = corrupt.copy(), status.copy()  # (views of the table's host buffers)
+        rt.close()
+        return counters, corrupt, status
+
 
 def apply_window_log(backend, window_log):
     """The pipelines' window_log keyword: set on every backend that has the setting (the CPU test double has not, and

@@ -101,6 +101,10 @@ struct znippy_ctx {
     uint32_t *rx_pool = nullptr, *rx_chunk = nullptr;
     uint8_t *rx_cdone = nullptr;
     uint64_t rx_cap = 0;  // words
+    // verify-only runs (znippy_verify_rows): the region the rows that need bytes in memory are decoded into instead of a caller's
+    // output (grow-only, ensure_verify_scratch); shared by every table and run of the context — runs are ordered on its stream
+    uint8_t *vs_pool = nullptr;
+    uint64_t vs_cap = 0;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     // kernel timing
     std::vector<KTime> ktimes;
@@ -429,7 +433,13 @@ struct znippy_rows {
     bool small_ok = false, small_off = false;  // the fused kernels handed over every row: later runs skip them (all_rows = the batch path's list)
     uint32_t *all_rows = nullptr;
     int lean_hint2 = -1;
-    struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; } run_args[2];  // per mirror slot: what the run was given
+    struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; bool verify = false; } run_args[2];  // per mirror slot: what the run was given, and its mode
+    // verify-only runs: the second output column — a 16-byte aligned slot in the context's scratch for every compressed row with bytes
+    // (stored rows and empty rows: none) — built on the device at the table's first verify run; vs_bytes = the slots' extent
+    uint64_t *vs_off = nullptr;
+    uint64_t vs_bytes = 0;
+    bool vs_built = false;
+    bool no_out = false;  // created without output offsets: the table can only be verified
     hipEvent_t ev_done[2] = {nullptr, nullptr};
     uint64_t run_seq = 0;  // async runs queued so far
     // Host copies of the columns a run is validated against (one pass per distinct (blob_base, blob_cap, out_cap)):
@@ -442,7 +452,7 @@ struct znippy_rows {
     std::vector<uint64_t> h_blob_off, h_blob_size, h_len, h_out_off;
     uint64_t blob_cap = ~0ull;  // size of the caller's blob region (znippy_rows_set_blob_cap); ~0 = not declared
     uint64_t val_base = 0, val_bcap = 0, val_ocap = 0;
-    bool val_done = false;
+    bool val_done = false, val_verify = false;
     uint32_t n_bad = 0;
     bool force_full = false;  // a lean run came back flagged: this table runs in full from now on
     uint8_t *status_init = nullptr;  // image of ctl with the host-decided statuses (rows_validate)
@@ -536,7 +546,7 @@ struct znippy_rounds {
 
 // ------------------------------------------------------------------------------------------------
 static bool ktime_on(const znippy_ctx *ctx, const char *name) {
-    return ctx->sw.ktime >= 2 || (ctx->sw.ktime == 1 && !strncmp(name, "decode_verify_", 14));
+    return ctx->sw.ktime >= 2 || (ctx->sw.ktime == 1 && (!strncmp(name, "decode_verify_", 14) || !strncmp(name, "verify_", 7)));
 }
 static void ktime_begin(znippy_ctx *ctx, const char *name, hipStream_t on = nullptr) {
     if (ctx->sw.trace) { fprintf(stderr, "[znippy trace] %s ...", name); fflush(stderr); }
@@ -586,14 +596,15 @@ static unsigned long long *diag_cycle(znippy_ctx *ctx, znippy_ctx::Diag which, h
 }
 
 // what the caller gave a run; preset != 0: the status column starts as the host's verdicts (rows_validate found bad rows); slot: its mirror slot and event
-struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; };
+// verify: a verify-only run — d_out / out_cap are the context's scratch and the extent of the table's slots in it, and the output column is vs_off
+struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; bool verify; };
 // the ten row columns every decode path's argument struct has under the same names (BlockScanArgs: all but `out`)
 static void set_out(BlockScanArgs &, uint8_t *) {}
 template <class A> static void set_out(A &a, uint8_t *out) { a.out = out; }
 template <class A>
 static void fill_row_args(A &a, const znippy_rows *r, const RowsRun &run) {
     a.blobs = (const uint8_t *)run.d_blobs; a.blob_base = run.blob_base;
-    a.blob_off = r->blob_off; a.blob_size = r->blob_size; a.usize = r->usize; a.out_off = r->out_off;
+    a.blob_off = r->blob_off; a.blob_size = r->blob_size; a.usize = r->usize; a.out_off = run.verify ? r->vs_off : r->out_off;
     a.out_cap = run.out_cap; a.status = r->status; a.preset = run.preset;
     set_out(a, (uint8_t *)run.d_out);
 }
@@ -684,6 +695,21 @@ static int ensure_rx_pool(znippy_ctx *ctx, uint64_t words) {
     ctx->rx_cap = words;
     return ZNIPPY_OK;
 }
+// Scratch of the verify-only runs: the slots of one table (+ slack for 16-byte reads behind the last one).  Unlike the pools above it is
+// not optional — the rows that need it have nowhere else to go — and it is capped like them: above the cap the run is refused.
+static int ensure_verify_scratch(znippy_ctx *ctx, uint64_t bytes) {
+    constexpr uint64_t CAP = 16ull << 30;
+    if (!bytes) return ZNIPPY_OK;
+    if (bytes > CAP) return ZNIPPY_E_NOMEM;
+    bytes += 4096;
+    if (bytes <= ctx->vs_cap) return ZNIPPY_OK;
+    (void)hipStreamSynchronize(ctx->stream);  // (runs in flight use the region: the auxiliary streams have joined by the end of a run)
+    if (ctx->vs_pool) (void)hipFree(ctx->vs_pool);
+    ctx->vs_pool = nullptr; ctx->vs_cap = 0;
+    if (hipMalloc(&ctx->vs_pool, bytes) != hipSuccess) { (void)hipGetLastError(); ctx->vs_pool = nullptr; return ZNIPPY_E_NOMEM; }
+    ctx->vs_cap = bytes;
+    return ZNIPPY_OK;
+}
 static int ensure_encoder(znippy_ctx *ctx) {
     if (ctx->enc_tabs) return ZNIPPY_OK;
     EncTables t;
@@ -748,6 +774,35 @@ __global__ __launch_bounds__(256) void k_rows_unpack_fill(const uint32_t *bs32, 
         bo[lo + k] = pb; bs[lo + k] = vb[k]; oo[lo + k] = po; us[lo + k] = vu[k];
         pb += vb[k]; po += vu[k];
     }
+}
+
+// verify-only runs: the scratch slot of every row (compressed rows with bytes: their length rounded up to 16; the others take nothing
+// and get the position of the next slot), the same three steps per 1,024 rows; sums[2 nblk] = the slots' extent.  A crafted index
+// cannot wrap the sums: a row counts for at most VS_ROW_MAX and a group of 1,024 rows for at most VS_GROUP_MAX, both above the
+// pool's cap, so such a table comes out with an extent the pool refuses (its offsets are then never used).
+constexpr unsigned long long VS_ROW_MAX = (16ull << 30) + 16, VS_GROUP_MAX = 32ull << 30;
+__device__ __forceinline__ unsigned long long vs_slot_bytes(const uint8_t *comp, const uint64_t *usize, uint32_t i) {
+    if (!comp[i]) return 0ull;
+    const unsigned long long u = usize[i];
+    return u >= VS_ROW_MAX ? VS_ROW_MAX : (u + 15) & ~15ull;
+}
+__global__ __launch_bounds__(256) void k_rows_slot_sums(const uint8_t *comp, const uint64_t *usize, uint32_t n, unsigned long long *sums) {
+    __shared__ unsigned long long sa[256], sb[256];
+    const uint32_t lo = blockIdx.x * 1024 + threadIdx.x * 4;
+    unsigned long long a = 0, b = 0, ta, tb;
+    for (uint32_t k = 0; k < 4; k++) if (lo + k < n) a += vs_slot_bytes(comp, usize, lo + k);
+    block_excl_scan2(a, b, sa, sb, &ta, &tb);
+    if (threadIdx.x == 0) { sums[2 * blockIdx.x] = ta < VS_GROUP_MAX ? ta : VS_GROUP_MAX; sums[2 * blockIdx.x + 1] = 0; }
+}
+__global__ __launch_bounds__(256) void k_rows_slot_fill(const uint8_t *comp, const uint64_t *usize, uint32_t n, unsigned long long *sums, uint32_t nblk, uint64_t *slot_off) {
+    __shared__ unsigned long long sa[256], sb[256];
+    const uint32_t lo = blockIdx.x * 1024 + threadIdx.x * 4;
+    unsigned long long v[4] = {0, 0, 0, 0}, a = 0, b = 0, ta, tb;
+    for (uint32_t k = 0; k < 4; k++) if (lo + k < n) { v[k] = vs_slot_bytes(comp, usize, lo + k); a += v[k]; }
+    block_excl_scan2(a, b, sa, sb, &ta, &tb);
+    unsigned long long at = sums[2 * blockIdx.x] + a;
+    for (uint32_t k = 0; k < 4; k++) if (lo + k < n) { slot_off[lo + k] = at; at += v[k]; }
+    if (blockIdx.x == nblk - 1 && threadIdx.x == 0) sums[2 * nblk] = sums[2 * blockIdx.x] + (ta < VS_GROUP_MAX ? ta : VS_GROUP_MAX);
 }
 
 __global__ void k_iota32(uint32_t *p, uint32_t n) {
@@ -930,7 +985,7 @@ static void ctx_teardown(znippy_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &k : ctx->ktimes) { (void)hipEventDestroy(k.t0); (void)hipEventDestroy(k.t1); }
-    void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor,
+    void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor, ctx->vs_pool,
                    ctx->clk_buf, ctx->shim_in, ctx->shim_out, ctx->enc_prov, ctx->enc_seq, ctx->enc_tabs, ctx->ldm};
     for (void *p : dev) if (p) (void)hipFree(p);
     for (unsigned long long *d : ctx->diag) if (d) (void)hipFree(d);
@@ -1078,7 +1133,7 @@ void znippy_rows_destroy(znippy_rows *r) {
                     r->cand_row, r->cand_base, r->cand_nblocks, r->fz_base, r->fz_cap, r->fz_it_cand, r->fz_nb, r->fz_work, r->fz_items, r->item_row, r->item_k, r->item_src, r->row_flag, r->pending2,
                     r->bt_tile, r->bt_item, r->tile_done, r->todo, r->status_init, r->slow_list,
                     r->bx_cand_row, r->bx_cand_base, r->bx_cand_nb, r->bx_huf_list, r->bx_seq_list, r->bx_items, r->bx_prep, r->d_bitmap, r->bx_sort_tmp,
-                    r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows};
+                    r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off};
     for (void *p : ptrs)
         tfree(r->ctx, p);
     if (r->h_counters) {
@@ -1275,7 +1330,7 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
                        const uint64_t *out_offset, const uint8_t *checksum, uint64_t row_begin,
                        uint64_t row_end, znippy_rows **out) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
-    if (!ctx || !out || row_end < row_begin || !blob_offset || !blob_size || !uncompressed_size || !out_offset)
+    if (!ctx || !out || row_end < row_begin || !blob_offset || !blob_size || !uncompressed_size)
         return ZNIPPY_E_INVAL;
     if (row_end - row_begin >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1294,7 +1349,16 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
         for (; row + 8 <= row_end && allc; row += 8) allc &= compressed_bitmap[row >> 3] == 0xFF;
         for (; row < row_end && allc; row++) allc &= (compressed_bitmap[row >> 3] >> (row & 7)) & 1;
     }
-    const RowCols c{blob_offset + row_begin, blob_size + row_begin, uncompressed_size + row_begin, out_offset + row_begin, compressed_bitmap, row_begin, row_end, allc};
+    // a table without output offsets can only be verified (znippy_verify_rows): its output column is a packed layout of its own, so that
+    // everything below that looks at the column finds a consistent one
+    std::vector<uint64_t> own_oo;
+    if (!out_offset) {
+        r->no_out = true;
+        own_oo.resize(n);
+        uint64_t at = 0;
+        for (uint32_t i = 0; i < n; i++) { own_oo[i] = at; at += uncompressed_size[row_begin + i]; }
+    }
+    const RowCols c{blob_offset + row_begin, blob_size + row_begin, uncompressed_size + row_begin, out_offset ? out_offset + row_begin : own_oo.data(), compressed_bitmap, row_begin, row_end, allc};
     int rc = rows_columns_h2d(ctx, r, c, checksum, td);
     if (rc) return rc;
     r->corrupt_cap = std::max<uint32_t>(n, 1);
@@ -1351,22 +1415,28 @@ int znippy_rows_set_blob_cap(znippy_rows *r, uint64_t blob_cap) {
 
 // Every row's source range against the declared blob region and its output range against out_cap, overflow-safe,
 // once per distinct triple.  Bad rows (normally none) get their status from the host.
-static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, uint64_t out_cap) {
-    if (r->val_done && r->val_base == blob_base && r->val_bcap == r->blob_cap && r->val_ocap == out_cap) return ZNIPPY_OK;
+// (verify-only runs: the output side is the table's own slots in the scratch, which fit by construction — only the blob side is looked at)
+static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, uint64_t out_cap, bool verify) {
+    if (verify) out_cap = ~0ull;
+    if (r->val_done && r->val_verify == verify && r->val_base == blob_base && r->val_bcap == r->blob_cap && r->val_ocap == out_cap) return ZNIPPY_OK;
     std::vector<int32_t> init;
     uint32_t bad = 0;
     const uint64_t bcap = r->blob_cap;
-    const bool fits = !r->ext_wrap && (r->n == 0 || (r->ext_min_bo >= blob_base && (bcap == ~0ull || r->ext_max_bend - blob_base <= bcap) && r->ext_max_oend <= out_cap));
+    const bool fits = !r->ext_wrap && (r->n == 0 || (r->ext_min_bo >= blob_base && (bcap == ~0ull || r->ext_max_bend - blob_base <= bcap) && (verify || r->ext_max_oend <= out_cap)));
     if (!fits && r->h_blob_off.empty() && r->n) {  // the columns, for the per-row verdicts (the device copies hold the effective lengths)
-        r->h_blob_off.resize(r->n); r->h_blob_size.resize(r->n); r->h_len.resize(r->n); r->h_out_off.resize(r->n);
+        r->h_blob_off.resize(r->n); r->h_blob_size.resize(r->n); r->h_len.resize(r->n);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipMemcpy(r->h_blob_off.data(), r->blob_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
         HIPCHK(ctx, hipMemcpy(r->h_blob_size.data(), r->blob_size, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
         HIPCHK(ctx, hipMemcpy(r->h_len.data(), r->usize, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+    }
+    if (!fits && !verify && r->h_out_off.empty() && r->n) {
+        r->h_out_off.resize(r->n);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipMemcpy(r->h_out_off.data(), r->out_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
     }
     for (uint32_t i = 0; i < (fits ? 0u : r->n); i++) {
-        const uint64_t bo = r->h_blob_off[i], bs = r->h_blob_size[i], len = r->h_len[i], oo = r->h_out_off[i];
+        const uint64_t bo = r->h_blob_off[i], bs = r->h_blob_size[i], len = verify ? 0 : r->h_len[i], oo = verify ? 0 : r->h_out_off[i];
         int code = 0;
         if (bo < blob_base) code = ZNIPPY_E_CORRUPT;
         else if (bcap != ~0ull && (bs > bcap || bo - blob_base > bcap - bs)) code = ZNIPPY_E_CORRUPT;
@@ -1387,7 +1457,33 @@ static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, ui
     }
     r->n_bad = bad;
     r->val_base = blob_base; r->val_bcap = r->blob_cap; r->val_ocap = out_cap;
-    r->val_done = true;
+    r->val_done = true; r->val_verify = verify;
+    return ZNIPPY_OK;
+}
+
+// The table's slots in the verify scratch, once (the first verify-only run, or the hook): built on the device from the columns the kernels
+// read — a stored row's length there is its blob, and it gets no slot — and the extent comes back for the pool.
+static int rows_verify_slots(znippy_ctx *ctx, znippy_rows *r) {
+    if (r->vs_built) return ZNIPPY_OK;
+    if (r->n && r->n_compressed) {
+        const uint32_t nblk = (r->n + 1023) / 1024;
+        unsigned long long *sums = nullptr;
+        if (tmalloc(ctx, &r->vs_off, 8 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
+        if (tmalloc(ctx, &sums, 16 * ((size_t)nblk + 1)) != hipSuccess) return ZNIPPY_E_NOMEM;
+        hipLaunchKernelGGL(k_rows_slot_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->compressed, r->usize, r->n, sums);
+        hipLaunchKernelGGL(k_rows_unpack_scan, dim3(1), dim3(256), 0, ctx->stream, sums, nblk);
+        hipLaunchKernelGGL(k_rows_slot_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->compressed, r->usize, r->n, sums, nblk, r->vs_off);
+        unsigned long long total = 0;
+        const hipError_t e1 = hipStreamSynchronize(ctx->stream), e2 = hipMemcpy(&total, sums + 2 * (size_t)nblk, 8, hipMemcpyDeviceToHost);
+        tfree(ctx, sums);
+        HIPCHK(ctx, e1);
+        HIPCHK(ctx, e2);
+        r->vs_bytes = total;
+    } else if (r->n) {  // no compressed row: no slot, no scratch — the column exists (every row: position 0) because the kernels load it
+        if (tmalloc(ctx, &r->vs_off, 8 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, hipMemsetAsync(r->vs_off, 0, 8 * (size_t)r->n, ctx->stream));
+    }
+    r->vs_built = true;
     return ZNIPPY_OK;
 }
 
@@ -1464,11 +1560,13 @@ static HashArgs rows_hash_args(const znippy_ctx *ctx, const znippy_rows *r, cons
     h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
     h.len = r->usize;
     h.srcA = (const uint8_t *)run.d_blobs; h.offA = r->blob_off; h.baseA = run.blob_base;
-    h.srcB = (uint8_t *)run.d_out; h.offB = r->out_off;
+    h.srcB = (uint8_t *)run.d_out; h.offB = run.verify ? r->vs_off : r->out_off;
     h.sel = r->compressed; h.status = r->status; h.pending_count = r->hand(H_FUSED);
-    h.copy_to_B = 1;
+    // (verify-only: stored rows are hashed where they lie by the hash-only kernel, nothing is copied.  The store path's staged loads with
+    // the stores left out were measured in its place: equal on big slices, 8 % slower on C5 and on tables of small stored rows.)
+    h.copy_to_B = run.verify ? 0 : 1;
     h.store_tiles = ctx->sw.store_g;
-    h.misaligned_dst = r->odd_out || ((uintptr_t)run.d_out & 15) != 0;
+    h.misaligned_dst = !run.verify && (r->odd_out || ((uintptr_t)run.d_out & 15) != 0);
     h.digests = r->digests; h.tile_cv = r->plan.tile_cv;
     return h;
 }
@@ -1547,9 +1645,9 @@ static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
         f.cursor = r->cur(CUR_ROLES);
         f.tile_list = r->slow_list;
         f.tile_count = r->hand(H_TILES);
-        timed(ctx, "decode_verify_roles", fs, [&] { launch_fused_roles(f, ctx->cus, fs); });
+        timed(ctx, run.verify ? "verify_roles" : "decode_verify_roles", fs, [&] { launch_fused_roles(f, ctx->cus, fs, run.verify); });
     }
-    if (r->n_small_tiles && !p.lean) timed(ctx, "decode_verify_fused", fs, [&] { launch_fused_small(f, fs, p.roles ? ctx->cus * 5 : 0); });
+    if (r->n_small_tiles && !p.lean) timed(ctx, run.verify ? "verify_small" : "decode_verify_fused", fs, [&] { launch_fused_small(f, fs, p.roles ? ctx->cus * 5 : 0, run.verify); });
     if (p.lean_mixed) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));  // (joined in front of the verify)
     return ZNIPPY_OK;
 }
@@ -1601,7 +1699,7 @@ static int run_block_items(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, co
         fb.item_src = r->item_src; fb.row_flag = r->row_flag;
         fb.tile_done = r->tile_done; fb.item_done = r->item_done;
         fb.dbg = ctx->sw.dbg;
-        timed(ctx, "decode_verify_fused_blocks", ba, [&] { launch_fused_blocks(fb, ba); });
+        timed(ctx, run.verify ? "verify_blocks" : "decode_verify_fused_blocks", ba, [&] { launch_fused_blocks(fb, ba, run.verify); });
         launch_compact_items(r->item_done, r->n_items, r->todo, r->hand(H_ITEMS), ba);
     }
     DecodeArgs a{};
@@ -1774,7 +1872,7 @@ static void run_second_hash(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, c
     HashArgs h = rows_hash_args(ctx, r, run);
     h.pass = p.stored_only ? 0 : 2;  // PASS_ALL : PASS_SECOND
     h.tile_done = r->n_bt && !p.stored_only ? r->tile_done : nullptr;
-    timed(ctx, "blake3_second_pass", s, [&] { launch_hash_tiles(h, s); });
+    timed(ctx, run.verify ? "blake3_hash_only" : "blake3_second_pass", s, [&] { launch_hash_tiles(h, s); });
     if (r->plan.n_big)
         timed(ctx, "blake3_merge_big", s, [&] {
             launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, r->digests, r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, r->plan.max_cvs, s);
@@ -1800,11 +1898,18 @@ static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const R
 // end.  run_seq is the caller's (znippy_decode_verify_rows_async advances it, a repeat inside rows_settle does not).  Every
 // allocation the run needs is made before its first stream operation on the table (*queued): an error return after that
 // point is a HIP runtime error, which the caller turns into a table without a readable run (rows_abandon).
+// verify: a verify-only run (d_out / out_cap are not looked at: the run's output region is the context's scratch as it is NOW — a repeat
+// inside rows_settle finds the region wherever a later run of another table has moved it).
 static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap,
-                       unsigned slot, bool *queued = nullptr) {
+                       unsigned slot, bool verify, bool *queued = nullptr) {
     ctx->n_ktimes = 0;
     int rc = ensure_decoder(ctx);
-    if (!rc) rc = rows_validate(ctx, r, blob_base, out_cap);
+    if (!rc && verify) {
+        rc = rows_verify_slots(ctx, r);
+        if (!rc) rc = ensure_verify_scratch(ctx, r->vs_bytes);
+        d_out = ctx->vs_pool; out_cap = r->vs_bytes;
+    }
+    if (!rc) rc = rows_validate(ctx, r, blob_base, out_cap, verify);
     if (!rc && r->fz_total) rc = ensure_fz_pools(ctx, r->fz_bytes, r->fz_total);
     if (!rc && r->bx_slots) {
         rc = ensure_fz_pools(ctx, r->bx_bytes, r->bx_item_cap);
@@ -1818,13 +1923,13 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         if (hipEventQuery(r->ev_done[last]) == hipSuccess) rows_note_hint(r, last);
         else (void)hipGetLastError();
     }
-    const RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot};
+    const RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot, verify};
     const RunPlan p = rows_plan(ctx, r, run.preset);
     if (p.small_off && !r->all_rows) {
         if (tmalloc(ctx, &r->all_rows, 4 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
         hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, ctx->stream, r->all_rows, r->n);
     }
-    { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = d_out; ra.cap = out_cap; ra.blob_cap = r->blob_cap; }
+    { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = verify ? nullptr : d_out; ra.cap = verify ? 0 : out_cap; ra.blob_cap = r->blob_cap; ra.verify = verify; }
     if (queued) *queued = true;
     if ((rc = run_clear(ctx, r, p, run)) || !r->n) return rc;
     if (!p.small_off && !p.stored_only && (rc = run_small_rows(ctx, r, p, run))) return rc;
@@ -1837,6 +1942,16 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
 // A run that failed after its first stream operation: whatever it queued on the auxiliary stream is joined back into the
 // main one and waited for, and the table forgets its runs (the control block, the status column and one mirror slot may hold
 // a part of the failed run): results calls see no run until the next one is queued, and that one runs in full.
+static void rows_abandon(znippy_ctx *ctx, znippy_rows *r);
+static int rows_queue(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap, bool verify) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    bool queued = false;
+    const int rc = rows_launch(ctx, r, d_blobs, blob_base, d_out, out_cap, (unsigned)(r->run_seq & 1), verify, &queued);
+    if (rc && queued) rows_abandon(ctx, r);
+    if (rc) return rc;
+    r->run_seq++;
+    return ZNIPPY_OK;
+}
 static void rows_abandon(znippy_ctx *ctx, znippy_rows *r) {
     if (hipEventRecord(ctx->ev_join, ctx->aux) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
     (void)hipStreamSynchronize(ctx->stream);
@@ -1850,13 +1965,39 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
                                     uint64_t blob_base, void *d_out, uint64_t out_cap) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
     if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
+    return rows_queue(ctx, r, d_blobs, blob_base, d_out, out_cap, false);
+}
+
+// The same run without an output: every row is decoded as far as hashing it needs, hashed and compared, and nothing is written
+// that no kernel reads back (znippy_hip.h).  A run like any other in the table's sequence.
+int znippy_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (r->n && !d_blobs) return ZNIPPY_E_INVAL;
+    return rows_queue(ctx, r, d_blobs, blob_base, nullptr, 0, true);
+}
+
+int znippy_rows_verify_scratch(znippy_ctx *ctx, znippy_rows *r, const void **d_base, uint64_t *bytes, uint64_t *row_offset) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx || !d_base || !bytes) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    bool queued = false;
-    const int rc = rows_launch(ctx, r, d_blobs, blob_base, d_out, out_cap, (unsigned)(r->run_seq & 1), &queued);
-    if (rc && queued) rows_abandon(ctx, r);
+    int rc = rows_verify_slots(ctx, r);
+    if (!rc) rc = ensure_verify_scratch(ctx, r->vs_bytes);
     if (rc) return rc;
-    r->run_seq++;
+    *d_base = r->vs_bytes ? ctx->vs_pool : nullptr;
+    *bytes = r->vs_bytes;
+    if (row_offset && r->n) {
+        std::vector<uint8_t> comp(r->n);
+        std::vector<uint64_t> len(r->n);
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        HIPCHK(ctx, hipMemcpy(row_offset, r->vs_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(comp.data(), r->compressed, r->n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(len.data(), r->usize, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < r->n; i++)
+            if (!comp[i] || !len[i]) row_offset[i] = ~0ull;
+    }
     return ZNIPPY_OK;
 }
 
@@ -1881,7 +2022,7 @@ static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
         const znippy_rows::RunArgs ra = r->run_args[order[i]];
         r->blob_cap = ra.blob_cap;
         bool queued = false;
-        const int rc = rows_launch(ctx, r, ra.blobs, ra.base, ra.out, ra.cap, order[i], &queued);
+        const int rc = rows_launch(ctx, r, ra.blobs, ra.base, ra.out, ra.cap, order[i], ra.verify, &queued);
         if (rc) {
             if (queued) rows_abandon(ctx, r);
             return rc;
@@ -1947,6 +2088,14 @@ int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_
                               uint64_t corrupt_cap, int32_t *row_status) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
     int rc = znippy_decode_verify_rows_async(ctx, rows, d_blobs, blob_base, d_out, out_cap);
+    if (rc) return rc;
+    return znippy_rows_results(ctx, rows, counters, corrupt_rows, corrupt_cap, row_status);
+}
+
+int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base,
+                       znippy_verify_counters *counters, uint64_t *corrupt_rows, uint64_t corrupt_cap, int32_t *row_status) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    int rc = znippy_verify_rows_async(ctx, rows, d_blobs, blob_base);
     if (rc) return rc;
     return znippy_rows_results(ctx, rows, counters, corrupt_rows, corrupt_cap, row_status);
 }

@@ -124,11 +124,12 @@ struct FusedBlocksArgs {
     uint8_t *tile_done, *item_done;  // zeroed before the launch
     int dbg;
 };
-void launch_fused_blocks(const FusedBlocksArgs &a, hipStream_t s);
+// verify (here and below): the no-store instantiation of the kernel (verify-only runs: rows are hashed, not written)
+void launch_fused_blocks(const FusedBlocksArgs &a, hipStream_t s, bool verify = false);
 
 void launch_hash_tiles(const HashArgs &a, hipStream_t s);
-void launch_fused_small(const FusedArgs &a, hipStream_t s, int grid_cap = 0);
-void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s);
+void launch_fused_small(const FusedArgs &a, hipStream_t s, int grid_cap = 0, bool verify = false);
+void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify = false);
 void init_fused_tables();
 void launch_merge_big(const BigUnit *big, uint32_t n_big, uint32_t *tile_cv, uint32_t *digests, const uint32_t *grp_big,
                       const uint32_t *grp_k, uint32_t n_grp, uint32_t max_cvs, hipStream_t s);

@@ -829,6 +829,12 @@ struct BlockFold {
 };
 constexpr uint32_t FOLD_UNITS = 16;  // tiles with more units fold on the spot
 
+// STORE = false (verify-only runs): rows hashed from their windows and stored rows are not written at all — the hash lanes
+// keep their message registers to themselves (in a tile with a ragged leaf the generic leaf path reads the windows too),
+// stored rows are hashed where they lie in the blob region; rows that go through decode_simple or the pre-pass of tiles
+// with more than WROWS rows are hashed from memory and land in their scratch slots (a.h.srcB / offB are then the
+// scratch columns).
+template <bool STORE>
 __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wave, const BlockFold &bf) {
     __shared__ __attribute__((aligned(16))) uint8_t s_W[4][WROWS * WSTRIDE];
     const uint32_t lane = threadIdx.x & 63;
@@ -990,7 +996,9 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
     // a tile with any ragged leaf is hashed by the generic leaf path, which reads every row from the output and has
     // no room for side work: write the recognised rows before the hash
     const bool early = __ballot(lane < t.n_units && (c_len == 0 || ((uint32_t)c_len & 1023) != 0)) != 0ull || (a.dbg & (1 | 4));
-    if (early && fmask) { em.drain(); need_reread = 1; }
+    // (verify-only: such a tile's recognised rows are hashed from their windows by the generic leaf path as well — nothing to write;
+    //  under the diagnostic that hashes recognised rows from memory they go to their scratch slots like any decoded row)
+    if (early && fmask && (STORE || (a.dbg & 4))) { em.drain(); need_reread = 1; }
     // otherwise every leaf of the tile is full and the recognised rows are written by the lanes that hash them
     if (stamp) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); t1 = __builtin_amdgcn_s_memtime(); }
     // decode = short bursts of scalar parsing + store issue: let it issue ahead of SIMD-mates that are in
@@ -1034,9 +1042,9 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
     if (need_reread) fwave_mem_sync();
     if (stamp) t2 = __builtin_amdgcn_s_memtime();
     if (!(a.dbg & 1)) {
-        LdsSrc ls{WL, d_y, d_B, d_off, WROWS, l_st, c_len, c_src, c_oo, c_sel, (early || (g_abl & 16)) ? 0u : fmask};
+        LdsSrc ls{WL, d_y, d_B, d_off, WROWS, l_st, c_len, c_src, c_oo, c_sel, (!STORE || early || (g_abl & 16)) ? 0u : fmask};
         LeafOut lo;
-        hash_tile_leaves<true, true>(a.h, t, &ls, lo);
+        hash_tile_leaves<STORE, true>(a.h, t, &ls, lo);
         if (t.n_units <= FOLD_UNITS && !(a.dbg & 256)) {
             const uint32_t w = threadIdx.x >> 6;
             if (lo.active) {
@@ -1070,6 +1078,7 @@ __device__ __forceinline__ void lds_barrier() {  // workgroup barrier that order
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+template <bool STORE>
 __global__ __launch_bounds__(256, 5) void k_fused_small(FusedArgs a) {
     __shared__ __attribute__((aligned(16))) uint32_t s_nodes[4 * 64 * 8];
     __shared__ uint32_t s_tab[3][4 * FOLD_UNITS];
@@ -1083,7 +1092,7 @@ __global__ __launch_bounds__(256, 5) void k_fused_small(FusedArgs a) {
     for (uint32_t base = blockIdx.x * 4, it = 0; base < n_work; base += gridDim.x * 4, it++) {
         if (lane < FOLD_UNITS) bf.tab_n[w * FOLD_UNITS + lane] = 0;
         const uint32_t idx = base + w;
-        if (idx < n_work) fused_tile(a, a.tile_list ? a.tile_list[idx] : idx, bf);
+        if (idx < n_work) fused_tile<STORE>(a, a.tile_list ? a.tile_list[idx] : idx, bf);
         lds_barrier();
         // the folding wave changes from block to block, so that over the blocks resident on a CU the extra passes
         // spread over its four SIMDs
@@ -1222,6 +1231,8 @@ __device__ __forceinline__ void emit_periodic_row(uint8_t *Y, uint32_t L0, uint3
     }
 }
 
+// STORE = false (verify-only runs): no output column is loaded, tested or published (RolesShared::oo stays unused)
+template <bool STORE>
 __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S) {
     const uint32_t lane = threadIdx.x & 63, j = lane >> 4, u = lane & 15;  // 16 lanes per tile, lane u = row u of tile j
     FastTabs T;
@@ -1265,12 +1276,12 @@ __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S)
             c_sel = a.h.sel[row];
             c_len = a.h.len[row];
             c_src = a.h.offA[row] - a.h.baseA;
-            c_oo = a.h.offB[row];
+            if (STORE) c_oo = a.h.offB[row];
             const uint64_t bs = a.blob_size[row];
             c_bs = bs > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)bs;
         }
         const bool want = rowv && c_sel && c_st == 0 && c_len != 0 && (c_len & 1023) == 0 && c_len <= 0x10000 &&
-                          c_oo + c_len <= a.out_cap && c_bs >= 12 && c_bs <= WIN;
+                          (!STORE || c_oo + c_len <= a.out_cap) && c_bs >= 12 && c_bs <= WIN;
         while (lds_ld(&S.gen[grp]) != use) __builtin_amdgcn_s_sleep(4);  // the group's previous use has been folded
         asm volatile("" ::: "memory");  // (volatile accesses order only against one another: pin the window stores below)
         // ---- the frames, lane = row: 16 bytes per step into the row's window (the last partial piece bytewise: the
@@ -1301,13 +1312,13 @@ __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S)
         const bool mine = fast && rowv;
         if (mine) {
             S.len[slot][u] = (uint32_t)c_len;
-            S.oo[slot][u] = c_oo;
+            if (STORE) S.oo[slot][u] = c_oo;
             S.dy[slot][u] = (uint16_t)(u * WSTRIDE + fr.lit_at);
             S.dB[slot][u] = (uint16_t)(fr.L0 - fr.off);
             S.doff[slot][u] = (uint16_t)fr.off;
         }
         lds_fence();
-        if (R_LOADER_EMITS) {  // (off by default: see the measurements at the top)
+        if (R_LOADER_EMITS && STORE) {  // (off by default: see the measurements at the top)
             const float inv_l = 1.0f / (float)(mine ? fr.off : 1u);
             for (uint64_t m = __ballot(mine); m && !(a.dbg & 16); m &= m - 1) {
                 const uint32_t l = (uint32_t)__builtin_ctzll(m);
@@ -1362,6 +1373,7 @@ __device__ __forceinline__ bool tree_op_6x10(uint32_t n, uint32_t &l, uint32_t &
 //   root,    passes 13..14   row = 4(b-13) + s:     10 row | + 8  -> digest    320 s (+1280), gap 224
 // A result goes over its left child (the address just read).  What is left per pass for the parent lanes is the reset of
 // their chaining value, one select for the flags and the result's two stores.
+template <bool STORE>
 __device__ __forceinline__ void roles_hash_6x10(const FusedArgs &a, RolesShared &S, uint32_t slot, uint32_t *tree, bool have_prev,
                                                    uint32_t prev_first, uint32_t cv[8]) {
     typedef __attribute__((address_space(3))) uint8_t lds8b;
@@ -1375,11 +1387,11 @@ __device__ __forceinline__ void roles_hash_6x10(const FusedArgs &a, RolesShared 
     const uint32_t p1 = (kk << 10) > yB + yoff ? (kk << 10) : (((yB + yoff) >> 6) + 1) << 6;  // first block read through the period
     uint32_t r = (p1 - yB) % yoff;
     const uint32_t step64 = 64 % yoff;
-    uint8_t *const dst = a.h.srcB + S.oo[slot][row] + (kk << 10);
+    uint8_t *const dst = STORE ? a.h.srcB + S.oo[slot][row] + (kk << 10) : nullptr;
     uint32_t *const dig = a.h.digests + (size_t)(prev_first + ps) * 8;
     // passes in which this parent lane has an operation: all of 0..14, less the last pass of levels 1, 3 and 4 for lanes 2, 3
     const uint32_t vmask = (leaf || !have_prev) ? 0u : (ps < 2 ? 0x7FFFu : 0x7FFFu & ~((1u << 7) | (1u << 12) | (1u << 14)));
-    const bool store = leaf && !(a.dbg & 16);
+    const bool store = STORE && leaf && !(a.dbg & 16);  // (verify-only: loads from LDS, compression and the tree ride, nothing else)
     b3::set_iv(cv);
     uint4 n0, n1, n2, n3;
     uint32_t wq = 0, wq_next = 0;  // where the pass's result goes: the offset its message was read from
@@ -1469,6 +1481,7 @@ __device__ __forceinline__ void roles_flush_tree_6x10(const FusedArgs &a, uint32
     }
 }
 
+template <bool STORE>
 __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S) {
     const uint32_t lane = threadIdx.x & 63;
     HashArgs h = a.h;
@@ -1517,7 +1530,7 @@ __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S)
                                   __ballot(lane < 6 && S.len[slot][lu] != 10240u) == 0ull;
             if (shape610) {
                 uint32_t cv[8];
-                roles_hash_6x10(a, S, slot, tree, have_prev, prev_first, cv);
+                roles_hash_6x10<STORE>(a, S, slot, tree, have_prev, prev_first, cv);
                 if (lane < 60) {  // the previous tree is done (its last node ran in pass 14): this tile's leaves take its place
                     lds_u4a *o = (lds_u4a *)(tree + lane * 8);
                     o[0] = u4v{cv[0], cv[1], cv[2], cv[3]};
@@ -1529,15 +1542,15 @@ __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S)
             } else {
             // the rows are stored by the lanes that hash them (their message registers) unless the loader wrote them
             LdsSrc ls{S.slots[slot], S.dy[slot], S.dB[slot], S.doff[slot], WROWS, nullptr,
-                      lane < nu ? (uint64_t)S.len[slot][lu] : 0ull, 0ull, S.oo[slot][lu], 1u,
-                      (R_LOADER_EMITS || (a.dbg & 16)) ? 0u : 0x3Fu, 0ull};
+                      lane < nu ? (uint64_t)S.len[slot][lu] : 0ull, 0ull, STORE ? S.oo[slot][lu] : 0ull, 1u,
+                      (R_LOADER_EMITS || !STORE || (a.dbg & 16)) ? 0u : 0x3Fu, 0ull};
             LeafOut lo;
             if (a.dbg & 8192) {  // ablation: no hashing (the loaders' pace alone)
                 lo.active = false; lo.u_cnt = 0; lo.u_head = 0;
 #pragma unroll
                 for (int q = 0; q < 8; q++) lo.cv[q] = 0;
             } else
-                hash_tile_leaves<!R_LOADER_EMITS, true>(h, t, &ls, lo);
+                hash_tile_leaves<STORE && !R_LOADER_EMITS, true>(h, t, &ls, lo);
             // the windows are dead (every lane has read its last block): the leaf CVs take their place
             if (lo.active) {
                 uint4 *d = reinterpret_cast<uint4 *>(S.slots[slot] + lane * 32);
@@ -1582,6 +1595,7 @@ __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S)
     }
 }
 
+template <bool STORE>
 __global__ __launch_bounds__(R_WAVES * 64) void k_fused_roles(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_roles_raw[];  // dynamic: more than the 64 KiB a static array may take
     RolesShared &S = *reinterpret_cast<RolesShared *>(s_roles_raw);
@@ -1594,23 +1608,25 @@ __global__ __launch_bounds__(R_WAVES * 64) void k_fused_roles(FusedArgs a) {
         // the loader's instruction stream is one long dependent chain with little VALU in it: at top priority it
         // issues whenever it is ready and costs the hashers a few per cent of the issue slots
         if (!(a.dbg & 64)) __builtin_amdgcn_s_setprio(3);
-        roles_loader(a, S);
-    } else roles_hasher(a, S);
+        roles_loader<STORE>(a, S);
+    } else roles_hasher<STORE>(a, S);
     if (clk) { a.dbg_buf[0] = __builtin_amdgcn_s_memtime() - c0; a.dbg_buf[1] = __builtin_amdgcn_s_memrealtime() - r0; }
 }
 
-void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s) {
+void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify) {
     if (!a.h.n_tiles) return;
-    static bool attr_set = false;
-    if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_fused_roles), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RolesShared));
-        attr_set = true;
+    static bool attr_set[2] = {false, false};
+    if (!attr_set[verify]) {
+        (void)hipFuncSetAttribute(verify ? reinterpret_cast<const void *>(k_fused_roles<false>) : reinterpret_cast<const void *>(k_fused_roles<true>),
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(RolesShared));
+        attr_set[verify] = true;
     }
     const uint32_t want = (a.h.n_tiles + R_GROUP - 1) / R_GROUP;  // one group per workgroup at least
     const uint32_t per_cu = sizeof(RolesShared) > 80 * 1024 ? 1u : 2u;
     uint32_t grid = std::min<uint32_t>((uint32_t)cus * per_cu, want);
     if (a.lds_pad) grid = std::min<uint32_t>(grid, a.lds_pad);  // diagnostic: ZNIPPY_LDS_PAD caps the grid (one workgroup = a deterministic ring)
-    hipLaunchKernelGGL(k_fused_roles, dim3(grid), dim3(R_WAVES * 64), sizeof(RolesShared), s, a);
+    if (verify) hipLaunchKernelGGL(k_fused_roles<false>, dim3(grid), dim3(R_WAVES * 64), sizeof(RolesShared), s, a);
+    else hipLaunchKernelGGL(k_fused_roles<true>, dim3(grid), dim3(R_WAVES * 64), sizeof(RolesShared), s, a);
 }
 
 // ---- big rows: block items of the common shape --------------------------------------------------------
@@ -1622,6 +1638,10 @@ void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s) {
 // this way is skipped by the block decoder and its two tiles by the second hash pass, so the row's bytes are
 // written once and never read back.  Anything else about the block (another shape, a short last block, a frame the
 // scan gave up on) leaves it to those kernels, untouched.
+// STORE = false (verify-only runs): both shapes are hashed without a store — the periodic block from its window, the raw
+// block from src + 3 where it lies, through the stage (the store path's loads without its stores) — and tile_done / item_done are set all the same, so the block decoder and the second
+// hash pass skip what this kernel verified and the row's scratch slot is never touched for those blocks.
+template <bool STORE>
 __global__ __launch_bounds__(256, 4) void k_fused_blocks(FusedBlocksArgs a) {
     // one 9 KiB area per wave: the copy stage of a raw block's leaf loop (whole lines), and afterwards — the first
     // 2 KiB of it — the wave's 64 leaf CVs for the workgroup's fold (node index = byte offset / 32)
@@ -1670,7 +1690,7 @@ __global__ __launch_bounds__(256, 4) void k_fused_blocks(FusedBlocksArgs a) {
             if (avail >= 3 && ((bh >> 1) & 3) == 0 && (bh >> 3) == 128 * 1024 && src_pos + 3 + 128 * 1024ull <= n) {
                 // raw block: its bytes sit in the frame — hash them while they are copied out (store-path loop)
                 LeafOut lo;
-                hash_tile_leaves<true, false, true>(a.h, t, nullptr, lo, s_area[w], src + 3 - origin);
+                hash_tile_leaves<true, false, STORE, false, !STORE>(a.h, t, nullptr, lo, s_area[w], src + 3 - origin);  // (verify-only: staged loads, no stores)
                 uint4 *d = reinterpret_cast<uint4 *>(s_nodes + (size_t)(w * AREA_NODES + lane) * 8);
                 d[0] = make_uint4(lo.cv[0], lo.cv[1], lo.cv[2], lo.cv[3]);
                 d[1] = make_uint4(lo.cv[4], lo.cv[5], lo.cv[6], lo.cv[7]);
@@ -1688,9 +1708,9 @@ __global__ __launch_bounds__(256, 4) void k_fused_blocks(FusedBlocksArgs a) {
                 uint8_t *y = WL + lit_at;
                 y[L0 + lane] = y[L0 - off + lmod(lane, off, 1.0f / (float)off)];
                 if (lane == 0) { s_d[w][0] = (uint16_t)lit_at; s_d[w][1] = (uint16_t)(L0 - off); s_d[w][2] = (uint16_t)off; }
-                LdsSrc ls{WL, &s_d[w][0], &s_d[w][1], &s_d[w][2], 1, nullptr, 0, 0, 0, 0, (a.dbg & 16) ? 0u : 1u, origin};
+                LdsSrc ls{WL, &s_d[w][0], &s_d[w][1], &s_d[w][2], 1, nullptr, 0, 0, 0, 0, (!STORE || (a.dbg & 16)) ? 0u : 1u, origin};
                 LeafOut lo;
-                hash_tile_leaves<true, true, true>(a.h, t, &ls, lo, s_area[w]);  // row stores leave as whole lines through the stage
+                hash_tile_leaves<STORE, true, STORE>(a.h, t, &ls, lo, STORE ? s_area[w] : nullptr);  // row stores leave as whole lines through the stage
                 uint4 *d = reinterpret_cast<uint4 *>(s_nodes + (size_t)(w * AREA_NODES + lane) * 8);
                 d[0] = make_uint4(lo.cv[0], lo.cv[1], lo.cv[2], lo.cv[3]);
                 d[1] = make_uint4(lo.cv[4], lo.cv[5], lo.cv[6], lo.cv[7]);
@@ -1716,19 +1736,21 @@ __global__ __launch_bounds__(256, 4) void k_fused_blocks(FusedBlocksArgs a) {
     fq.fold_and_write(s_nodes, a.h);
 }
 
-void launch_fused_blocks(const FusedBlocksArgs &a, hipStream_t s) {
+void launch_fused_blocks(const FusedBlocksArgs &a, hipStream_t s, bool verify) {
     if (!a.n_bt) return;
-    hipLaunchKernelGGL(k_fused_blocks, dim3((a.n_bt + 3) / 4), dim3(256), 0, s, a);
+    if (verify) hipLaunchKernelGGL(k_fused_blocks<false>, dim3((a.n_bt + 3) / 4), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_fused_blocks<true>, dim3((a.n_bt + 3) / 4), dim3(256), 0, s, a);
 }
 
 void set_fused_dbg(unsigned long long *) {}
 void set_fused_abl(int v) { (void)hipMemcpyToSymbol(HIP_SYMBOL(g_abl), &v, sizeof v); }
 
-void launch_fused_small(const FusedArgs &a, hipStream_t s, int grid_cap) {
+void launch_fused_small(const FusedArgs &a, hipStream_t s, int grid_cap, bool verify) {
     if (!a.h.n_tiles) return;
     uint32_t grid = (a.h.n_tiles + 3) / 4;
     if (grid_cap > 0 && grid > (uint32_t)grid_cap) grid = (uint32_t)grid_cap;
-    hipLaunchKernelGGL(k_fused_small, dim3(grid), dim3(256), a.lds_pad, s, a);
+    if (verify) hipLaunchKernelGGL(k_fused_small<false>, dim3(grid), dim3(256), a.lds_pad, s, a);
+    else hipLaunchKernelGGL(k_fused_small<true>, dim3(grid), dim3(256), a.lds_pad, s, a);
 }
 
 }  // namespace zn

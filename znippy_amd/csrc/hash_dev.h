@@ -149,8 +149,9 @@ constexpr uint32_t STAGE_FULL_BYTES = 64 * STAGE_FULL_SLOT;
 // lanes that write one slot's eight pieces still write its 128 contiguous bytes.
 constexpr uint32_t STAGE_SWZ_BYTES = 64 * 128;
 
-// `raw_src` (big-slice tiles, fused block kernel): the tile's bytes are copied from raw_src + leaf offset instead of
-// the unit's own source column (a raw block of a compressed frame: blob -> output while hashing).
+// `raw_src` (big-slice tiles, fused block kernel): the tile's bytes are read from raw_src + leaf offset instead of
+// the unit's own source column (a raw block of a compressed frame: blob -> output while hashing; without COPY they are
+// hashed where they lie).
 constexpr uint32_t STAGE_SHIFT_SLOT = 160;  // 16 (tail of the previous 128 bytes) + 128 + 16
 constexpr uint32_t STAGE_SHIFT_BYTES = 64 * STAGE_SHIFT_SLOT;
 
@@ -281,7 +282,11 @@ __device__ __noinline__ Cv8 hash_ragged_through_stage(const uint8_t *src, uint8_
     return r;
 }
 
-template <bool COPY, bool LDSRC = false, bool STAGE_FULL = false, bool STAGE_SHIFT = false>
+// NOSTORE (with COPY; the fused block kernel's verify-only form, raw blocks): the store path's leaf loops with the stores left
+// out — the bytes still come through the stage, 16 leaves x 64 contiguous bytes per load instruction instead of every lane's
+// own 64 bytes 1 KiB from its neighbour's (a raw block starts at an odd address inside its frame: 0.267 against 0.289 ms for
+// C4's 500 MiB).  No destination exists: nothing can be written.
+template <bool COPY, bool LDSRC = false, bool STAGE_FULL = false, bool STAGE_SHIFT = false, bool NOSTORE = false>
 __device__ __forceinline__ void hash_tile_leaves(const HashArgs &a, const Tile &t, const LdsSrc *ls, LeafOut &out,
                                                  uint8_t *stage = nullptr, const uint8_t *raw_src = nullptr) {
     const uint32_t lane = threadIdx.x & 63;
@@ -350,10 +355,11 @@ __device__ __forceinline__ void hash_tile_leaves(const HashArgs &a, const Tile &
         dst = (COPY && !from_b && a.srcB) ? a.srcB + a.offB[unit] : nullptr;
         if (COPY && dst && a.copy_mask && (!a.copy_mask[unit] || a.offB[unit] + ulen > a.copy_cap)) dst = nullptr;
     }
-    if (!LDSRC && COPY && raw_src) {
+    if (!LDSRC && raw_src) {  // (the hash-only form reads a raw block where it lies as well: verify-only runs)
         src = raw_src;
-        dst = a.srcB + a.offB[unit];
+        if (COPY && !NOSTORE) dst = a.srcB + a.offB[unit];
     }
+    if (NOSTORE) dst = nullptr;
     const uint64_t leaf_off = (uint64_t)k << 10;
     uint32_t leaf_len = 0;
     if (active && ulen > leaf_off) leaf_len = (uint32_t)((ulen - leaf_off) < 1024 ? (ulen - leaf_off) : 1024);
@@ -728,11 +734,35 @@ __device__ __forceinline__ void hash_tile_leaves(const HashArgs &a, const Tile &
             maxblk = o > maxblk ? o : maxblk;
         }
         maxblk = __builtin_amdgcn_readfirstlane(maxblk);
+        // Hash-only with an on-chip source (verify-only runs): a recognised row of a tile with a ragged leaf is read from its
+        // window here as well, so it is never written — any 64 bytes of the row are 64 CONTIGUOUS window bytes, at the
+        // position itself (up to L0 + 64) or inside the period's copy; a partial block is cut to its length afterwards.
+        const uint8_t *Yg = nullptr;
+        uint32_t gB = 0, goff = 1, gL0 = 0;
+        if constexpr (LDSRC && !COPY) {
+            if (t.n_units && active && local < ls->rows && ls->ybase[local] != 0xFFFF) {
+                Yg = ls->wl + ls->ybase[local];
+                gB = ls->pB[local];
+                goff = ls->poff[local];
+                gL0 = gB + goff;
+            }
+        }
         for (uint32_t b = 0; b < maxblk; b++) {
             if (active && b < nblk) {
                 uint32_t m[16];
                 uint32_t rem = leaf_len - b * 64;
                 uint32_t bl = leaf_len == 0 ? 0 : (rem < 64 ? rem : 64);
+                if (LDSRC && !COPY && Yg) {
+                    const uint32_t pos = (uint32_t)leaf_off + b * 64;
+                    const lds_u4 *q = (const lds_u4 *)(pos > gL0 ? Yg + gB + (pos - gB) % goff : Yg + pos);
+                    const u4v a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
+                    const uint32_t w[16] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w, a3.x, a3.y, a3.z, a3.w};
+#pragma unroll
+                    for (uint32_t i = 0; i < 16; i++) {
+                        const uint32_t have = bl > 4 * i ? bl - 4 * i : 0u;  // bytes of word i inside the block
+                        m[i] = have >= 4 ? w[i] : (have ? w[i] & ((1u << (8 * have)) - 1u) : 0u);
+                    }
+                } else
                 load_block(src + b * 64, bl, m);
                 if (COPY && dst) store_block(dst + b * 64, bl, m);
                 uint32_t flags = (b == 0 ? b3::CHUNK_START : 0u) |

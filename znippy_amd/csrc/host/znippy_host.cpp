@@ -66,7 +66,8 @@ unsigned reader_threads() { return env_threads("ZNIPPY_HOST_READERS", 16); }
 unsigned writer_threads() { return env_threads("ZNIPPY_HOST_WRITERS", 4); }
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-bool trace_on() { const char *v = getenv("ZNIPPY_HOST_TRACE"); return v && *v && *v != '0'; }
+bool env_on(const char *name) { const char *v = getenv(name); return v && *v && *v != '0'; }
+bool trace_on() { return env_on("ZNIPPY_HOST_TRACE"); }
 const char MAGIC[8] = {'Z', 'N', 'P', 'Y', 'M', 'I', 'D', 'X'};  // index.rs:L245
 
 // is_probably_compressed, index.rs:L470-484 — last extension, case-insensitive
@@ -923,9 +924,10 @@ struct ReadBufs {
 };
 
 // Blob bytes -> HBM -> decode+verify kernels; the decoded rows stay in bufs.d_out (the caller decides whether
-// they cross PCIe at all).  Stands for the worker loop body, decompress.rs:L135-190.
+// they cross PCIe at all).  Stands for the worker loop body, decompress.rs:L135-190.  keep_out = false (save_data=false,
+// L186-189): no output region at all — the rows are checked by a verify-only run (znippy_verify_rows) and bufs.d_out is not touched.
 int decode_range(znippy_ctx *ctx, int arc_fd, const znippy_index &ix, const uint64_t *row_ids, size_t n, bool verify, ReadBufs &bufs,
-                 DecodedRange *dr) {
+                 DecodedRange *dr, bool keep_out = true) {
     std::vector<uint64_t> bo(n), bs(n), us(n);
     std::vector<uint8_t> bitmap((n + 7) / 8, 0), ck(verify ? 32 * n : 0);
     dr->out_off.assign(n, 0);
@@ -967,15 +969,16 @@ int decode_range(znippy_ctx *ctx, int arc_fd, const znippy_index &ix, const uint
         if (nblob && !pread_all(arc_fd, bufs.blob_pin.p, nblob, lo)) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
     }
     bufs.t_read += now_s() - t; t = now_s();
-    if (!bufs.d_blobs.reserve(nblob + 64) || !bufs.d_out.reserve(dr->total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+    if (!bufs.d_blobs.reserve(nblob + 64) || (keep_out && !bufs.d_out.reserve(dr->total + 64))) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
     if (nblob && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, nblob, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
     bufs.t_h2d += now_s() - t; t = now_s();
     znippy_rows *rt = nullptr;
-    int rc = znippy_rows_create(ctx, bo.data(), bs.data(), bitmap.data(), us.data(), dr->out_off.data(), verify ? ck.data() : nullptr, 0, n, &rt);
+    int rc = znippy_rows_create(ctx, bo.data(), bs.data(), bitmap.data(), us.data(), keep_out ? dr->out_off.data() : nullptr, verify ? ck.data() : nullptr, 0, n, &rt);
     if (rc) return fail(rc, "znippy_rows_create failed");
     znippy_rows_set_blob_cap(rt, nblob);  // a row pointing outside what was read is an error code, not a device fault
     std::vector<uint64_t> cr(n);
-    rc = znippy_decode_verify_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, cr.data(), n, dr->status.data());
+    if (keep_out) rc = znippy_decode_verify_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, cr.data(), n, dr->status.data());
+    else rc = znippy_verify_rows(ctx, rt, bufs.d_blobs.p, base, &dr->cnt, cr.data(), n, dr->status.data());
     znippy_rows_destroy(rt);
     if (rc) return fail(rc, std::string("decode failed: ") + znippy_last_error(ctx));
     bufs.t_kern += now_s() - t;
@@ -1104,13 +1107,18 @@ static int znippy_decompress_archive_impl(const char *index_path, int save_data,
     const RowWriter writer{&ix, out_dir, &first_touch, world == 1, world > 1 ? &final_size : nullptr, &werr};
     const unsigned n_writers = adjacent ? writer_threads() : 1;
     const uint64_t batch_bytes = range_bytes(save_data != 0);
+    // save_data=false: rows are verified without being written (ZNIPPY_NO_VERIFY_ONLY=1 in the environment: decoded into a region
+    // that is thrown away, as before — for A/B).  What such a range takes on the device is its blobs and the scratch of its
+    // compressed rows, so that is what a range is cut by.
+    const bool verify_only = !save_data && !env_on("ZNIPPY_NO_VERIFY_ONLY");
     double t_d2h = 0, t_wjoin = 0;
     int which = 0, n_ranges = 0;
     uint64_t i = range.first;
     std::vector<uint64_t> ids;
     while (i < range.second && rc == ZNIPPY_OK && !werr.load()) {
         uint64_t j = i, nbytes = 0;
-        while (j < range.second && (j == i || nbytes + ix.rows.cols[4].u64[j] <= batch_bytes)) nbytes += ix.rows.cols[4].u64[j++];
+        const auto row_cost = [&](uint64_t r) { return verify_only ? ix.rows.cols[6].u64[r] + (ix.rows.cols[3].u8[r] ? ix.rows.cols[4].u64[r] : 0) : ix.rows.cols[4].u64[r]; };
+        while (j < range.second && (j == i || nbytes + row_cost(j) <= batch_bytes)) nbytes += row_cost(j++);
         ids.resize(j - i);
         for (uint64_t k = i; k < j; k++) ids[k - i] = k;
         OutSlab &sl = slabs[which];
@@ -1121,7 +1129,7 @@ static int znippy_decompress_archive_impl(const char *index_path, int save_data,
         if (!other.writers.empty() && i && paths[i] == paths[i - 1]) other.join();
         t_wjoin += now_s() - t;
         sl.dr.corrupt.clear();
-        rc = decode_range(ctx, arc, ix, ids.data(), ids.size(), true, bufs, &sl.dr);
+        rc = decode_range(ctx, arc, ix, ids.data(), ids.size(), true, bufs, &sl.dr, !verify_only);
         if (rc) break;
         n_ranges++;
         const znippy_verify_counters &c = sl.dr.cnt;

@@ -140,6 +140,9 @@ def decompress_archive(index_path, save_data: bool, out_dir, backend=None, group
     counters = dict(total_chunks=0, total_written_bytes=0, verified_bytes=0, corrupt_bytes=0, corrupt_rows=0,
                     decode_errors=0)
     corrupt_all = []
+    # verify only (save_data=False): a backend that can check rows without writing them does (HipBackend.verify); one that
+    # cannot — or ZNIPPY_NO_VERIFY_ONLY=1 in the environment, for A/B — decodes and the bytes are thrown away
+    verify_only = not save_data and hasattr(backend, "verify") and os.environ.get("ZNIPPY_NO_VERIFY_ONLY", "0") in ("", "0")
     with open(index_path, "rb") as arc:
         i = r0
         while i < r1:
@@ -151,8 +154,11 @@ def decompress_archive(index_path, save_data: bool, out_dir, backend=None, group
             blobs, bo = read_spans(arc, file_size, c["blob_offset"][i:j], bs)  # the preads of L148-153, coalesced
             usz = rlen[i:j]
             out_off = np.concatenate([[0], np.cumsum(usz)[:-1]]).astype(np.uint64)
-            cnt, corrupt, status, out = backend.decode_verify(blobs, 0, bo, bs, usz, out_off, c["compressed"][i:j],
-                                                              c["checksum"][i:j], int(usz.sum()))
+            if verify_only:
+                cnt, corrupt, status = backend.verify(blobs, 0, bo, bs, usz, c["compressed"][i:j], c["checksum"][i:j])
+            else:
+                cnt, corrupt, status, out = backend.decode_verify(blobs, 0, bo, bs, usz, out_off, c["compressed"][i:j],
+                                                                  c["checksum"][i:j], int(usz.sum()))
             for k in counters:
                 counters[k] += int(cnt[k])
             corrupt_all.extend(int(i + r) for r in corrupt)

@@ -143,7 +143,8 @@ def get_decompressed_size(frame) -> int:
 
 
 class RowTable:
-    """Device-resident slice [row_begin,row_end) of the index columns + its work plan."""
+    """Device-resident slice [row_begin,row_end) of the index columns + its work plan.  out_offset=None: a table that
+    can only be verified (verify / verify_async)."""
 
     def __init__(self, ctx, blob_offset, blob_size, uncompressed_size, out_offset, compressed_bitmap=None,
                  checksum=None, row_begin=0, row_end=None):
@@ -151,14 +152,14 @@ class RowTable:
         bo = as_np(blob_offset, np.uint64)
         bs = as_np(blob_size, np.uint64)
         us = as_np(uncompressed_size, np.uint64)
-        oo = as_np(out_offset, np.uint64)
+        oo = as_np(out_offset, np.uint64) if out_offset is not None else None
         n = len(bo)
         row_end = n if row_end is None else row_end
         bm = as_np(compressed_bitmap, np.uint8) if compressed_bitmap is not None else None
         ck = as_np(checksum, np.uint8).reshape(-1) if checksum is not None else None
         h = vp()
         ctx._chk(ctx.L.znippy_rows_create(ctx.h, np_ptr(bo), np_ptr(bs), np_ptr(bm) if bm is not None else None,
-                                          np_ptr(us), np_ptr(oo), np_ptr(ck) if ck is not None else None,
+                                          np_ptr(us), np_ptr(oo) if oo is not None else None, np_ptr(ck) if ck is not None else None,
                                           row_begin, row_end, C.byref(h)), "znippy_rows_create")
         self.h = h
         ctx._tables.add(self)
@@ -192,6 +193,32 @@ class RowTable:
         self._runs[self._seq] = [d_blobs, d_out, False]
         self._seq += 1
         self._runs.pop(self._seq - 3, None)  # the library keeps two runs
+
+    def verify_async(self, d_blobs, blob_base=0, blob_cap=None):
+        """Queue a verify-only run (the read loop with save_data=false, decompress.rs:L186-189): same results calls, same
+        counters, corrupt list, status and digests as a decode run over these blobs, and no output."""
+        if blob_cap is None and not isinstance(d_blobs, int):
+            blob_cap = d_blobs.numel()
+        if blob_cap is not None:
+            self.ctx._chk(self.ctx.L.znippy_rows_set_blob_cap(self.h, int(blob_cap)), "znippy_rows_set_blob_cap")
+        self.ctx._chk(self.ctx.L.znippy_verify_rows_async(self.ctx.h, self.h, _dptr(d_blobs), blob_base),
+                      "znippy_verify_rows_async")
+        self._runs[self._seq] = [d_blobs, None, False]  # (a flagged lean run is repeated over these blobs)
+        self._seq += 1
+        self._runs.pop(self._seq - 3, None)
+
+    def verify(self, d_blobs, blob_base=0, blob_cap=None):
+        self.verify_async(d_blobs, blob_base, blob_cap)
+        return self.results()
+
+    def verify_scratch(self):
+        """Test / measurement hook: (device address of the context's verify scratch or 0, bytes of this table's slots in
+        it, per-row slot offsets with 2**64 - 1 for rows without one).  No contract for consumers."""
+        base, nbytes = vp(), C.c_uint64()
+        off = np.zeros(max(self.n, 1), dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.znippy_rows_verify_scratch(self.ctx.h, self.h, C.byref(base), C.byref(nbytes), np_ptr(off)),
+                      "znippy_rows_verify_scratch")
+        return int(base.value or 0), int(nbytes.value), off[:self.n]
 
     def _read(self, lag):
         """Run `lag` before the latest has been read.  A run's buffers go once it has been read and no older run is left
