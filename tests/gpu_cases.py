@@ -238,21 +238,27 @@ def frame_table(oracle, entries, frames):
     return dict(blobs=blobs, bo=bo, bs=bs, us=us, oo=oo, ck=ck)
 
 
-def decode_table(ctx, A, reps=2):
+def decode_table(ctx, A, reps=2, full=False):
+    """full: the corrupt list and the digests of the last run are returned too."""
     import torch
     from znippy_amd import hip
     d_blobs = torch.from_numpy(A["blobs"].copy()).cuda()
     total = int(A["us"].sum())
     d_out = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
     rt = hip.RowTable(ctx, A["bo"], A["bs"], A["us"], A["oo"], None, A["ck"])
-    outs = []
+    outs, lists = [], []
     for _ in range(reps):  # work lists are filled in a different order every run: every run must agree
         d_out.zero_()
         c, corrupt, status = rt.decode_verify(d_blobs, d_out)
         outs.append((dict(c), status.copy(), d_out[:total].cpu().numpy().copy()))
+        lists.append(sorted(int(x) for x in corrupt))
     for o in outs[1:]:
         assert o[0] == outs[0][0] and (o[1] == outs[0][1]).all() and (o[2] == outs[0][2]).all()
-    return outs[0] + (rt.foreign_stats(), dict(ctx.kernel_times()))
+    res = outs[0] + (rt.foreign_stats(), dict(ctx.kernel_times()))
+    if full:
+        assert all(x == lists[0] for x in lists[1:])
+        res += (lists[0], rt.digests().copy())
+    return res
 
 
 # ---- mutated frames -------------------------------------------------------------------------------------------------

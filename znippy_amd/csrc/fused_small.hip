@@ -394,6 +394,7 @@ __device__ int decode_simple(const uint8_t *src, uint32_t n, uint8_t *out, uint6
     }
     if (n < 5) return F_E_CORRUPT;
     uint64_t h = W.fwd(0);
+    if (((uint32_t)h & 0xFFFFFFF0u) == 0x184D2A50u) return F_NOT_SIMPLE;  // a skippable frame in front: the general decoder steps over it
     if ((uint32_t)h != 0xFD2FB528u) return F_E_CORRUPT;
     const uint32_t fhd = (uint32_t)(h >> 32) & 0xFF;
     const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did_flag = fhd & 3;

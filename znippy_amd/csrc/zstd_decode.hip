@@ -98,18 +98,26 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 4 ? 4 : 1) void k_zstd_decod
             S.blk_base = 0;
             S.huf_valid = 0; S.valid[0] = S.valid[1] = S.valid[2] = 0;
             S.rep[0] = 1; S.rep[1] = 4; S.rep[2] = 8;
-            if (src_n < 5) err = E_TRUNC;
+            // leading skippable frames (RFC 8878 3.1.2) carry no content: the frame starts behind them
+            uint64_t f0 = 0;
+            while (src_n - f0 >= 8 && ((src[f0] | (src[f0 + 1] << 8) | (src[f0 + 2] << 16) | ((uint32_t)src[f0 + 3] << 24)) & 0xFFFFFFF0u) == 0x184D2A50u) {
+                const uint64_t sz = src[f0 + 4] | (src[f0 + 5] << 8) | (src[f0 + 6] << 16) | ((uint64_t)src[f0 + 7] << 24);
+                if (8 + sz > src_n - f0) { err = E_TRUNC; break; }
+                f0 += 8 + sz;
+            }
+            if (err) {}
+            else if (src_n - f0 < 5) err = E_TRUNC;
             else {
-                uint32_t magic = src[0] | (src[1] << 8) | (src[2] << 16) | ((uint32_t)src[3] << 24);
+                uint32_t magic = src[f0] | (src[f0 + 1] << 8) | (src[f0 + 2] << 16) | ((uint32_t)src[f0 + 3] << 24);
                 if (magic != 0xFD2FB528u) err = E_CORRUPT;
                 else {
-                    uint32_t fhd = src[4];
+                    uint32_t fhd = src[f0 + 4];
                     uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did_flag = fhd & 3;
                     if (fhd & 8) err = E_CORRUPT;
                     S.has_cksum = (fhd >> 2) & 1;
                     uint32_t fcs_bytes = fcs_flag == 0 ? single : (1u << fcs_flag);
                     uint32_t did_bytes = did_flag == 3 ? 4 : did_flag;
-                    pos = 5;
+                    pos = f0 + 5;
                     if (src_n < pos + (single ? 0 : 1) + did_bytes + fcs_bytes) err = E_TRUNC;
                     if (!err) {
                         if (!single) pos++;  // window descriptor: matches are bounded by the frame start below
@@ -159,7 +167,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 4 ? 4 : 1) void k_zstd_decod
             __syncthreads();
             if (S.err) break;
             const uint32_t btype = S.blk_type, bsize = S.blk_size;
-            const uint64_t bpos = S.src_pos;
+            const uint64_t bpos = S.src_pos, blk_out0 = S.out_pos;
             if (btype == 0) {
                 coop_copy(out + S.out_pos, src + bpos, bsize, tid, NT);
                 __syncthreads();
@@ -736,6 +744,9 @@ linc = wave_incl_scan(linc); pinc = wave_incl_scan(pinc);
                 }
         
             }
+            // Block_Maximum_Size (RFC 8878 3.1.1.2.4) bounds what a compressed block regenerates, not only its payload
+            if (tid == 0 && !S.err && S.out_pos - blk_out0 > BLOCK_MAX) S.err = E_CORRUPT;
+            __syncthreads();
         }
         DSTAMP(5);
         __syncthreads();  // every wave's output stores have landed (same CU)
