@@ -16,6 +16,7 @@
  *                                (+ stats merge L195-221)      over index columns (index.rs:L43-54)
  *   znippy_verify_rows[_async]   the same loop, save_data=false  znippy-common/src/decompress.rs:L186-189 (the write is
  *                                (`verify`)                     skipped), called from index.rs:L550-553
+ *   znippy_decode_rows[_async]   ZnippyArchive::extract_file(s)  znippy-common/src/archive.rs:L144-168 (decode, no checksum)
  *   znippy_rounds_* + znippy_encode_hash_rounds
  *                                barrel + writer bodies        znippy-compress/src/stream_packer.rs:L217-284,
  *                                                              znippy-compress/src/slot_packer.rs:L551-609
@@ -181,6 +182,25 @@ int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, 
                        znippy_verify_counters *counters, uint64_t *corrupt_rows, uint64_t corrupt_cap,
                        int32_t *row_status);
 int znippy_verify_rows_async(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base);
+/* Decode only: the extract path, which never looks at the checksum column (ZnippyArchive::extract_file / extract_files,
+ * znippy-common/src/archive.rs:L144-168) — every row is decoded (or, if stored, copied) to d_out + out_offset[r], exactly where and
+ * as a decode run places it, and nothing is hashed: no digest is computed and the checksum column, if the table has one, is not read.
+ * It takes the place of a znippy_decode_verify_rows[_async] call on a table created with checksum = NULL, without the hash that
+ * call still pays for.  Counters, status column and the bytes in d_out are what that call reports for a table built from the same
+ * columns with checksum = NULL over the same blobs: verified_bytes == total_written_bytes, corrupt_bytes == corrupt_rows == 0,
+ * decode_errors and every row's ZNIPPY_E_* are identical.  The results are read with znippy_rows_results / _results_lagged;
+ * znippy_rows_digests returns ZNIPPY_E_INVAL while the latest run of the table is a decode-only run (there are no digests), and
+ * works again after the next decode or verify-only run.  A table without out_offset returns ZNIPPY_E_INVAL; the host's validation of
+ * every row against the blob region and out_cap is the decode run's.  A decode-only run is a run like any other in the table's
+ * sequence: it takes a slot of the two-run ring and may be queued between decode and verify-only runs of the same table with two
+ * runs in flight.  It is never a lean run, never comes back flagged, and neither uses up nor updates what the table remembers of
+ * its last run; when an earlier flagged run forces the latest run to be repeated, a decode-only run is repeated as one.  It writes
+ * only into the d_out it was given.  Every allocation it needs is made before its first stream operation; a failed queueing call
+ * that had already queued work leaves the table with no readable run, as for a decode run. */
+int znippy_decode_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base, void *d_out,
+                       uint64_t out_cap, znippy_verify_counters *counters, int32_t *row_status);
+int znippy_decode_rows_async(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base, void *d_out,
+                             uint64_t out_cap);
 int znippy_rows_results(znippy_ctx *ctx, znippy_rows *rows, znippy_verify_counters *counters,
                         uint64_t *corrupt_rows, uint64_t corrupt_cap, int32_t *row_status);
 /* Counters of the run `lag` (0 or 1) runs before the latest one queued on this table: waits for THAT run only,

@@ -46,6 +46,7 @@ EXPORTS = [
     "znippy_rounds_results_view", "znippy_rows_results_lagged", "znippy_rows_set_blob_cap", "znippy_rounds_results_lagged", "znippy_rounds_set_store_incompressible", "znippy_hash_rounds", "znippy_last_kernel_times", "znippy_measure_blake3_pass_ns", "znippy_last_shader_ghz", "znippy_ctx_set_kernel_timing", "znippy_rows_foreign_stats", "znippy_ctx_set_level", "znippy_ctx_level",
     "znippy_ctx_set_window_log", "znippy_ctx_window_log",
     "znippy_verify_rows", "znippy_verify_rows_async", "znippy_rows_verify_scratch",
+    "znippy_decode_rows", "znippy_decode_rows_async",
 ]
 
 
@@ -117,6 +118,9 @@ def lib():
         L.znippy_verify_rows.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(VerifyCounters), vp, C.c_uint64, vp]
         L.znippy_verify_rows_async.argtypes = [vp, vp, vp, C.c_uint64]
         L.znippy_rows_verify_scratch.argtypes = [vp, vp, C.POINTER(vp), C.POINTER(C.c_uint64), vp]
+    if hasattr(L, "znippy_decode_rows"):  # (likewise)
+        L.znippy_decode_rows.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(VerifyCounters), vp]
+        L.znippy_decode_rows_async.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64]
     _lib = L
     return L
 

@@ -69,8 +69,13 @@ class ZnippyArchive:
                 blobs, bo = read_spans(f, os.path.getsize(self.path), c["blob_offset"][rows_np], bs)
             out_off = np.concatenate([[0], np.cumsum(usz)[:-1]]).astype(np.uint64)
             backend = self._backend or default_backend()
-            _, corrupt, status, out = backend.decode_verify(blobs, 0, bo, bs, usz, out_off, c["compressed"][rows_np],
-                                                            c["checksum"][rows_np] if verify else None, int(usz.sum()))
+            # an unverified extract never looks at the checksum column (archive.rs:L144-168): a decode-only run, which does not hash
+            # (ZNIPPY_NO_DECODE_ONLY=1 in the environment: the decode + verify run without a checksum, as before — for A/B runs)
+            if not verify and hasattr(backend, "decode") and os.environ.get("ZNIPPY_NO_DECODE_ONLY", "0") in ("", "0"):
+                _, corrupt, status, out = backend.decode(blobs, 0, bo, bs, usz, out_off, c["compressed"][rows_np], int(usz.sum()))
+            else:
+                _, corrupt, status, out = backend.decode_verify(blobs, 0, bo, bs, usz, out_off, c["compressed"][rows_np],
+                                                                c["checksum"][rows_np] if verify else None, int(usz.sum()))
             corrupt = set(int(x) for x in corrupt)
         for p, sp in zip(paths, spans):
             if sp is None:

@@ -58,6 +58,22 @@ class HipBackend:
         rt.close()
         return counters, corrupt, status, out
 
+    # read side, decode only (the extract path, archive.rs:L144-168): the bytes, counters and status — nothing is hashed
+    def decode(self, blobs, blob_base, blob_offset, blob_size, usize, out_offset, compressed, out_total):
+        n = len(blob_offset)
+        if n == 0:
+            return dict(total_chunks=0, total_written_bytes=0, verified_bytes=0, corrupt_bytes=0, corrupt_rows=0,
+                        decode_errors=0), np.zeros(0, np.uint64), np.zeros(0, np.int32), np.zeros(0, np.uint8)
+        d_blobs = self._to_dev(np.concatenate([blobs, np.zeros(64, np.uint8)]))
+        d_out = self.torch.empty(out_total + 64, dtype=self.torch.uint8, device=f"cuda:{self.device}")
+        bitmap = np.packbits(np.asarray(compressed, dtype=bool), bitorder="little")
+        rt = self.hip.RowTable(self.ctx, blob_offset, blob_size, usize, out_offset, bitmap, None)
+        counters, status = rt.decode(d_blobs, d_out, blob_base=blob_base, out_cap=out_total, blob_cap=len(blobs))
+        status = status.copy()  # (a view of the table's host buffer)
+        out = d_out[:out_total].cpu().numpy()
+        rt.close()
+        return counters, np.zeros(0, np.uint64), status, out
+
     # read side, verify only (decompress.rs save_data=false): counters, corrupt rows and status, no bytes — nothing is
     # allocated for an output and nothing comes back over the bus
     def verify(self, blobs, blob_base, blob_offset, blob_size, usize, compressed, checksum):

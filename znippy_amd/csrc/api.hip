@@ -433,7 +433,12 @@ struct znippy_rows {
     bool small_ok = false, small_off = false;  // the fused kernels handed over every row: later runs skip them (all_rows = the batch path's list)
     uint32_t *all_rows = nullptr;
     int lean_hint2 = -1;
-    struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; bool verify = false; } run_args[2];  // per mirror slot: what the run was given, and its mode
+    // Decode-only runs neither use up nor update the hints above (they cannot be flagged, so nothing they skip may be something a row
+    // needs).  What they do keep is their own answer to bx_hint's question — did the last finished decode-only run hand anything to the
+    // decoders behind the store kernels? — which only ROUTES the undecoded frames (batch path, or the serial decoders alone, which take
+    // whatever is handed over): a wrong answer costs time, never a row.  -1: not known (the table's bx_hint is consulted)
+    int plain_hint = -1;
+    struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; bool verify = false, plain = false; } run_args[2];  // per mirror slot: what the run was given, and its kind (plain: decode-only)
     // verify-only runs: the second output column — a 16-byte aligned slot in the context's scratch for every compressed row with bytes
     // (stored rows and empty rows: none) — built on the device at the table's first verify run; vs_bytes = the slots' extent
     uint64_t *vs_off = nullptr;
@@ -597,7 +602,8 @@ static unsigned long long *diag_cycle(znippy_ctx *ctx, znippy_ctx::Diag which, h
 
 // what the caller gave a run; preset != 0: the status column starts as the host's verdicts (rows_validate found bad rows); slot: its mirror slot and event
 // verify: a verify-only run — d_out / out_cap are the context's scratch and the extent of the table's slots in it, and the output column is vs_off
-struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; bool verify; };
+// plain: a decode-only run (znippy_decode_rows) — rows are written as in a decode run and nothing is hashed
+struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; bool verify; bool plain; };
 // the ten row columns every decode path's argument struct has under the same names (BlockScanArgs: all but `out`)
 static void set_out(BlockScanArgs &, uint8_t *) {}
 template <class A> static void set_out(A &a, uint8_t *out) { a.out = out; }
@@ -1502,6 +1508,13 @@ static void rows_note_hint(znippy_rows *r, unsigned slot) {
     if (r->small_off) r->bx_hint = 1;
 }
 
+static void rows_note_plain(znippy_rows *r, unsigned slot) {  // the same reading of a decode-only run's mirror, into its own field
+    const uint32_t *left = r->mirror_hand(slot);
+    r->plain_hint = (left[H_FUSED] || left[H_SERIAL] || left[H_FLAGGED] || r->n_list_a) ? 1 : 0;
+}
+// the routing hint a run goes by: a decode-only run's own once it has one
+static int rows_route_hint(const znippy_rows *r, bool plain) { return plain && r->plain_hint >= 0 ? r->plain_hint : r->bx_hint; }
+
 // ---- one run of a row table: the plan, then the stages in the order rows_launch queues them -----------------------
 // Which kernels a run launches and on which streams.  Everything here is known before the run's first launch — the context's
 // switches and pools, the table's shape, the hints of its last finished run — and nothing in rows_plan calls HIP.
@@ -1519,19 +1532,22 @@ struct RunPlan {
     bool rx;           // batch path: big frames through the resolve stages
     bool third;        // batch path: the lane-per-block sequence kernel on a third stream beside the Huffman streams
 };
-static RunPlan rows_plan(const znippy_ctx *ctx, const znippy_rows *r, int preset) {
+static RunPlan rows_plan(const znippy_ctx *ctx, const znippy_rows *r, int preset, bool plain) {
     const auto &sw = ctx->sw;
     RunPlan p{};
-    p.bx = r->bx_slots && ctx->fz_lit_pool && ctx->fz_seq_pool && ctx->bx_fse_pool && ctx->bx_huf_pool && r->bx_hint != 0;
+    const int route = rows_route_hint(r, plain);  // bx_hint, or a decode-only run's own copy of it
+    p.bx = r->bx_slots && ctx->fz_lit_pool && ctx->fz_seq_pool && ctx->bx_fse_pool && ctx->bx_huf_pool && route != 0;
     p.small_off = p.bx && r->small_off && !r->n_bad && !r->force_full && !sw.dbg;
     // (a repository of small files the reference stores as they are — png, jpg, gz —, or one big jar.  The fused small-row kernel
     // copies a stored row with each lane's own 64-byte stores: 100k x 10 KiB stored rows 0.85 ms there, 0.63 through the store path kernel)
     p.stored_only = r->n_compressed == 0 && !preset && !sw.dbg && !sw.no_stored_only && !r->force_full;
-    const bool may_skip = !preset && !r->force_full;  // a run may leave out what the table's last finished run had no use for
+    // (a decode-only run is never a lean run: nothing it queues could flag it, so it leaves nothing out that a row might need — and it has
+    //  no use for the role-split kernel, whose loaders feed hashers)
+    const bool may_skip = !preset && !r->force_full && !plain;  // a run may leave out what the table's last finished run had no use for
     if (!p.small_off && !p.stored_only) {
         // Tables with enough small tiles go to the role-split persistent kernel first (loader + hasher waves: tiles whose rows are all whole-leaf rows of
         // the recognised periodic shape); what it leaves on its list — and small tables, where a persistent grid only adds start-up latency — is k_fused_small's.
-        p.roles = !sw.no_roles && sw.roles_min != 0 && r->n_small_tiles >= sw.roles_min && r->n_small_tiles > 0 && !(sw.dbg & (1 | 2 | 4 | 8 | 128)) && !r->roles_off;
+        p.roles = !sw.no_roles && sw.roles_min != 0 && r->n_small_tiles >= sw.roles_min && r->n_small_tiles > 0 && !(sw.dbg & (1 | 2 | 4 | 8 | 128)) && !r->roles_off && !plain;
         // A table of small rows AND big stored / hashed units (BASELINE configs[4]: 3,500 small files beside 6 GB of jars) whose
         // last run handed nothing over: nothing of the small rows' kernel and the second hash pass depends on the other (C5:
         // 0.28 ms of a 3.45 ms step ran in front of the pass).
@@ -1542,13 +1558,13 @@ static RunPlan rows_plan(const znippy_ctx *ctx, const znippy_rows *r, int preset
     if (!p.decode) return p;
     // a table of big rows only whose last run handed nothing over: the main stream has nothing for the block items to run beside, and
     // the fork and the join between two streams were ~0.1 ms of C3's 1.09 ms step
-    p.one_stream = r->n_cand && r->bx_hint == 0 && r->n_small_tiles == 0;
+    p.one_stream = r->n_cand && route == 0 && r->n_small_tiles == 0;
     // ... and when its last run needed neither the serial block decoder nor the serial decoder behind it (every block item was written and hashed by the
     // fused block kernel), those three launches are left out, the way a lean run of a table of small rows leaves out what stands behind the roles kernel.
     p.lean_blocks = p.one_stream && r->lean_blocks_ok && r->lean_hint2 == 1 && may_skip && r->n_bt && !sw.ddbg && !r->fz_total;
     if (!r->n_compressed) return p;
     // (the serial decoder's launch then returns at once instead of waiting for CUs next to the block kernels: C3's 0.25 ms that only waited)
-    p.behind = !p.bx && r->n_cand && r->bx_hint == 0;
+    p.behind = !p.bx && r->n_cand && route == 0;
     p.rx = p.bx && r->rx_base && ctx->rx_pool && r->rx_words;
     // (only where the chip is not full of blocks anyway: 100k blocks, both kernels chip-wide: 2.98 ms together against 1.85 + 0.96 in a row)
     p.third = p.bx && r->bx_nblk <= 32768;
@@ -1622,6 +1638,10 @@ static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
     f.blob_size = r->blob_size; f.out_cap = run.out_cap; f.status = r->status;
     f.preset = run.preset;
     f.pending = r->pending; f.pending_count = r->hand(H_FUSED);
+    if (run.plain) {  // store-only: one kernel over the plan's small tiles, no diagnostics
+        if (r->n_small_tiles) timed(ctx, "decode_small", s, [&] { launch_decode_small(f, s); });
+        return ZNIPPY_OK;
+    }
     f.dbg = ctx->sw.dbg;
     if (f.dbg & 8) {  // diagnostic: print the previous launch's phase stamps, then reset them
         f.dbg_buf = diag_cycle<8>(ctx, znippy_ctx::DIAG_FUSED, s, nullptr, [](const unsigned long long *h4) {
@@ -1699,7 +1719,8 @@ static int run_block_items(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, co
         fb.item_src = r->item_src; fb.row_flag = r->row_flag;
         fb.tile_done = r->tile_done; fb.item_done = r->item_done;
         fb.dbg = ctx->sw.dbg;
-        timed(ctx, run.verify ? "verify_blocks" : "decode_verify_fused_blocks", ba, [&] { launch_fused_blocks(fb, ba, run.verify); });
+        if (run.plain) timed(ctx, "decode_blocks", ba, [&] { launch_decode_blocks(fb, ba); });
+        else timed(ctx, run.verify ? "verify_blocks" : "decode_verify_fused_blocks", ba, [&] { launch_fused_blocks(fb, ba, run.verify); });
         launch_compact_items(r->item_done, r->n_items, r->todo, r->hand(H_ITEMS), ba);
     }
     DecodeArgs a{};
@@ -1879,13 +1900,22 @@ static void run_second_hash(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, c
         });
 }
 
+// 3') decode-only runs: no hash pass — what is left of it is the copy of the stored rows no kernel in front has written (stored rows
+//     above a tile; stored_only: every row)
+static void run_copy_stored(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
+    if (!p.stored_only && !r->plan.n_big) return;
+    const HashArgs h = rows_hash_args(ctx, r, run);
+    timed(ctx, "copy_stored", ctx->stream, [&] { launch_copy_stored(h, p.stored_only, ctx->stream); });
+}
+
 // 4) verify (a run that left stages out: its lists must be empty, or the counters come back flagged), mirror copy, event
 static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     hipStream_t s = ctx->stream;
     if (p.lean_mixed) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
     const bool skipped = p.lean || p.lean_blocks || p.lean_mixed;
-    timed(ctx, "verify", s, [&] {
-        launch_verify(r->digests, r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt, r->corrupt_cap, s,
+    // (decode-only: the counters pass alone — no checksum column, no digest read, every decoded row counts as verified)
+    timed(ctx, run.plain ? "count_rows" : "verify", s, [&] {
+        launch_verify(r->digests, run.plain ? nullptr : r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt, r->corrupt_cap, s,
                       skipped ? r->ctl_at<uint32_t>(CTL_HAND) : nullptr, (p.lean || p.lean_mixed) ? LEAN_SMALL : LEAN_BLOCKS);
     });
     HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * run.slot, r->counters, CTL_MIRROR, hipMemcpyDeviceToHost, s));
@@ -1901,7 +1931,7 @@ static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const R
 // verify: a verify-only run (d_out / out_cap are not looked at: the run's output region is the context's scratch as it is NOW — a repeat
 // inside rows_settle finds the region wherever a later run of another table has moved it).
 static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap,
-                       unsigned slot, bool verify, bool *queued = nullptr) {
+                       unsigned slot, bool verify, bool plain, bool *queued = nullptr) {
     ctx->n_ktimes = 0;
     int rc = ensure_decoder(ctx);
     if (!rc && verify) {
@@ -1914,28 +1944,32 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
     if (!rc && r->bx_slots) {
         rc = ensure_fz_pools(ctx, r->bx_bytes, r->bx_item_cap);
         if (!rc) rc = ensure_bx_pools(ctx, r->bx_bytes, r->bx_item_cap);
-        if (!rc && r->rx_base && r->bx_hint != 0) rc = ensure_rx_pool(ctx, r->rx_words);
+        if (!rc && r->rx_base && rows_route_hint(r, plain) != 0) rc = ensure_rx_pool(ctx, r->rx_words);
     }
     if (rc) return rc;
     if (r->n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
-    if (r->run_seq && r->bx_hint < 0 && r->n) {  // a run of this table has finished meanwhile?
+    if (r->run_seq && rows_route_hint(r, plain) < 0 && r->n) {  // a run of this table has finished meanwhile?
         const unsigned last = (unsigned)((r->run_seq - 1) & 1);
-        if (hipEventQuery(r->ev_done[last]) == hipSuccess) rows_note_hint(r, last);
-        else (void)hipGetLastError();
+        const bool last_plain = r->run_args[last].plain;  // (a decode-only run teaches the table's own hints nothing)
+        if (last_plain && !plain) (void)0;
+        else if (hipEventQuery(r->ev_done[last]) != hipSuccess) (void)hipGetLastError();
+        else if (last_plain) rows_note_plain(r, last);
+        else rows_note_hint(r, last);
     }
-    const RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot, verify};
-    const RunPlan p = rows_plan(ctx, r, run.preset);
+    const RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot, verify, plain};
+    const RunPlan p = rows_plan(ctx, r, run.preset, plain);
     if (p.small_off && !r->all_rows) {
         if (tmalloc(ctx, &r->all_rows, 4 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
         hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, ctx->stream, r->all_rows, r->n);
     }
-    { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = verify ? nullptr : d_out; ra.cap = verify ? 0 : out_cap; ra.blob_cap = r->blob_cap; ra.verify = verify; }
+    { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = verify ? nullptr : d_out; ra.cap = verify ? 0 : out_cap; ra.blob_cap = r->blob_cap; ra.verify = verify; ra.plain = plain; }
     if (queued) *queued = true;
     if ((rc = run_clear(ctx, r, p, run)) || !r->n) return rc;
     if (!p.small_off && !p.stored_only && (rc = run_small_rows(ctx, r, p, run))) return rc;
     if (p.decode && r->n_cand && (rc = run_block_items(ctx, r, p, run))) return rc;
     if (p.decode && r->n_compressed && (rc = p.bx ? run_batch_path(ctx, r, p, run) : run_serial_flow(ctx, r, p, run))) return rc;
-    if (!p.lean) run_second_hash(ctx, r, p, run);
+    if (plain) run_copy_stored(ctx, r, p, run);
+    else if (!p.lean) run_second_hash(ctx, r, p, run);
     return run_verify(ctx, r, p, run);
 }
 
@@ -1943,10 +1977,10 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
 // main one and waited for, and the table forgets its runs (the control block, the status column and one mirror slot may hold
 // a part of the failed run): results calls see no run until the next one is queued, and that one runs in full.
 static void rows_abandon(znippy_ctx *ctx, znippy_rows *r);
-static int rows_queue(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap, bool verify) {
+static int rows_queue(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap, bool verify, bool plain = false) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     bool queued = false;
-    const int rc = rows_launch(ctx, r, d_blobs, blob_base, d_out, out_cap, (unsigned)(r->run_seq & 1), verify, &queued);
+    const int rc = rows_launch(ctx, r, d_blobs, blob_base, d_out, out_cap, (unsigned)(r->run_seq & 1), verify, plain, &queued);
     if (rc && queued) rows_abandon(ctx, r);
     if (rc) return rc;
     r->run_seq++;
@@ -1968,6 +2002,15 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
     if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
     if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
     return rows_queue(ctx, r, d_blobs, blob_base, d_out, out_cap, false);
+}
+
+// The same run without a hash (znippy_hip.h): every row is written where a decode run writes it and no digest is computed or compared.
+int znippy_decode_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
+    if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
+    return rows_queue(ctx, r, d_blobs, blob_base, d_out, out_cap, false, true);
 }
 
 // The same run without an output: every row is decoded as far as hashing it needs, hashed and compared, and nothing is written
@@ -2022,7 +2065,7 @@ static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
         const znippy_rows::RunArgs ra = r->run_args[order[i]];
         r->blob_cap = ra.blob_cap;
         bool queued = false;
-        const int rc = rows_launch(ctx, r, ra.blobs, ra.base, ra.out, ra.cap, order[i], ra.verify, &queued);
+        const int rc = rows_launch(ctx, r, ra.blobs, ra.base, ra.out, ra.cap, order[i], ra.verify, ra.plain, &queued);
         if (rc) {
             if (queued) rows_abandon(ctx, r);
             return rc;
@@ -2044,7 +2087,8 @@ int znippy_rows_results_lagged(znippy_ctx *ctx, znippy_rows *r, unsigned lag, zn
         HIPCHK(ctx, hipEventSynchronize(r->ev_done[slot]));
         { const int rc = rows_settle(ctx, r, slot); if (rc) return rc; }
         memcpy(c, r->h_counters + 16 * slot, 64);
-        rows_note_hint(r, slot);
+        if (r->run_args[slot].plain) rows_note_plain(r, slot);
+        else rows_note_hint(r, slot);
     }
     counters->total_chunks = c[0]; counters->total_written_bytes = c[1]; counters->verified_bytes = c[2];
     counters->corrupt_bytes = c[3]; counters->corrupt_rows = c[4]; counters->decode_errors = c[5];
@@ -2061,7 +2105,8 @@ int znippy_rows_results(znippy_ctx *ctx, znippy_rows *r, znippy_verify_counters 
     if (r->n && r->run_seq) {
         { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
         memcpy(c, r->h_counters + 16 * ((r->run_seq - 1) & 1), 64);  // copied by the run itself (pinned)
-        rows_note_hint(r, (unsigned)((r->run_seq - 1) & 1));
+        if (r->run_args[(r->run_seq - 1) & 1].plain) rows_note_plain(r, (unsigned)((r->run_seq - 1) & 1));
+        else rows_note_hint(r, (unsigned)((r->run_seq - 1) & 1));
     }
     if (counters) {
         counters->total_chunks = c[0]; counters->total_written_bytes = c[1]; counters->verified_bytes = c[2];
@@ -2092,6 +2137,14 @@ int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_
     return znippy_rows_results(ctx, rows, counters, corrupt_rows, corrupt_cap, row_status);
 }
 
+int znippy_decode_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap,
+                       znippy_verify_counters *counters, int32_t *row_status) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    int rc = znippy_decode_rows_async(ctx, rows, d_blobs, blob_base, d_out, out_cap);
+    if (rc) return rc;
+    return znippy_rows_results(ctx, rows, counters, nullptr, 0, row_status);
+}
+
 int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base,
                        znippy_verify_counters *counters, uint64_t *corrupt_rows, uint64_t corrupt_cap, int32_t *row_status) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
@@ -2106,6 +2159,7 @@ int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (r->n && r->run_seq) { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
+    if (r->run_seq && r->run_args[(r->run_seq - 1) & 1].plain) return ZNIPPY_E_INVAL;  // a decode-only run computes no digest
     if (r->n) HIPCHK(ctx, hipMemcpy(digests, r->digests, 32 * (size_t)r->n, hipMemcpyDeviceToHost));
     return ZNIPPY_OK;
 }

@@ -131,6 +131,11 @@ void launch_hash_tiles(const HashArgs &a, hipStream_t s);
 void launch_fused_small(const FusedArgs &a, hipStream_t s, int grid_cap = 0, bool verify = false);
 void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify = false);
 void init_fused_tables();
+// decode-only runs (znippy_decode_rows): the store-only forms of the three kernels above — small rows, block items of the common
+// shape, stored rows above a tile (all = every tile: stored-only tables) — nothing is hashed
+void launch_decode_small(const FusedArgs &a, hipStream_t s);
+void launch_decode_blocks(const FusedBlocksArgs &a, hipStream_t s);
+void launch_copy_stored(const HashArgs &a, bool all, hipStream_t s);
 void launch_merge_big(const BigUnit *big, uint32_t n_big, uint32_t *tile_cv, uint32_t *digests, const uint32_t *grp_big,
                       const uint32_t *grp_k, uint32_t n_grp, uint32_t max_cvs, hipStream_t s);
 void launch_verify(const uint32_t *digests, const uint8_t *checksum, const uint64_t *usize,

@@ -835,7 +835,9 @@ constexpr uint32_t FOLD_UNITS = 16;  // tiles with more units fold on the spot
 // stored rows are hashed where they lie in the blob region; rows that go through decode_simple or the pre-pass of tiles
 // with more than WROWS rows are hashed from memory and land in their scratch slots (a.h.srcB / offB are then the
 // scratch columns).
-template <bool STORE>
+// HASH = false (decode-only runs, k_decode_small): the same tile with nothing hashed — every recognised row is written from its window by
+// the whole wave, stored rows are copied by the wave in the row loop, and the leaf phase and the fold are left out.
+template <bool STORE, bool HASH = true>
 __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wave, const BlockFold &bf) {
     __shared__ __attribute__((aligned(16))) uint8_t s_W[4][WROWS * WSTRIDE];
     const uint32_t lane = threadIdx.x & 63;
@@ -999,7 +1001,7 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
     const bool early = __ballot(lane < t.n_units && (c_len == 0 || ((uint32_t)c_len & 1023) != 0)) != 0ull || (a.dbg & (1 | 4));
     // (verify-only: such a tile's recognised rows are hashed from their windows by the generic leaf path as well — nothing to write;
     //  under the diagnostic that hashes recognised rows from memory they go to their scratch slots like any decoded row)
-    if (early && fmask && (STORE || (a.dbg & 4))) { em.drain(); need_reread = 1; }
+    if ((early || !HASH) && fmask && (STORE || (a.dbg & 4))) { em.drain(); need_reread = 1; }
     // otherwise every leaf of the tile is full and the recognised rows are written by the lanes that hash them
     if (stamp) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); t1 = __builtin_amdgcn_s_memtime(); }
     // decode = short bursts of scalar parsing + store issue: let it issue ahead of SIMD-mates that are in
@@ -1007,12 +1009,18 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
     if (!(a.dbg & 64)) __builtin_amdgcn_s_setprio(3);
     for (uint32_t u = 0; u < t.n_units && !(a.dbg & 2); u++) {
         const uint32_t row = t.first_unit + u;
-        if (!uni(__shfl(c_sel, u))) continue;  // stored row: copied while it is hashed below
+        if (HASH && !uni(__shfl(c_sel, u))) continue;  // stored row: copied while it is hashed below
         if ((int32_t)uni((uint32_t)__shfl(c_st, u)) < 0) continue;  // host verdict stands
         const uint64_t usize = ((uint64_t)uni((uint32_t)(__shfl(c_len, u) >> 32)) << 32) | uni((uint32_t)__shfl(c_len, u));
         const uint64_t ooff = ((uint64_t)uni((uint32_t)(__shfl(c_oo, u) >> 32)) << 32) | uni((uint32_t)__shfl(c_oo, u));
         const uint64_t soff = ((uint64_t)uni((uint32_t)(__shfl(c_src, u) >> 32)) << 32) | uni((uint32_t)__shfl(c_src, u));
         const uint32_t bsz = uni(__shfl(c_bs, u));
+        if constexpr (!HASH) {
+            if (!uni(__shfl(c_sel, u))) {  // stored row: the blob is the row
+                fwave_copy(a.h.srcB + ooff, a.h.srcA + soff, (uint32_t)usize, lane);
+                continue;
+            }
+        }
         if ((u < 32 && (fmask >> u & 1)) || (done64 >> u & 1)) continue;  // recognised row: written from its window
         int rc;
         Periodic per;
@@ -1042,7 +1050,7 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
     __builtin_amdgcn_s_setprio(0);
     if (need_reread) fwave_mem_sync();
     if (stamp) t2 = __builtin_amdgcn_s_memtime();
-    if (!(a.dbg & 1)) {
+    if (HASH && !(a.dbg & 1)) {
         LdsSrc ls{WL, d_y, d_B, d_off, WROWS, l_st, c_len, c_src, c_oo, c_sel, (!STORE || early || (g_abl & 16)) ? 0u : fmask};
         LeafOut lo;
         hash_tile_leaves<STORE, true>(a.h, t, &ls, lo);
@@ -1741,6 +1749,174 @@ void launch_fused_blocks(const FusedBlocksArgs &a, hipStream_t s, bool verify) {
     if (!a.n_bt) return;
     if (verify) hipLaunchKernelGGL(k_fused_blocks<false>, dim3((a.n_bt + 3) / 4), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(k_fused_blocks<true>, dim3((a.n_bt + 3) / 4), dim3(256), 0, s, a);
+}
+
+// ---- decode-only runs (znippy_decode_rows): the three places where store and hash are one kernel, without the hash ------------
+// Nothing below reads a checksum or computes a digest: a row costs one read of its frame and one write of its bytes.  Every kernel
+// takes its work by a static index (wave = tile, no cursor, no barrier), so there is no control flow a partial wave could hang in.
+
+// Small rows: fused_tile with the leaf phase and the fold left out.  Recognised periodic rows go out from their LDS windows (Emitter:
+// 16 bytes per lane, whole lines wherever the row's place in the output is 16-byte aligned, lane-parallel head and tail bytes where it
+// is not), stored rows are copied by the wave, the other simple shapes are decoded by decode_simple, and whatever is left is handed
+// over on `pending` exactly as k_fused_small hands it over.
+__global__ __launch_bounds__(256, 5) void k_decode_small(FusedArgs a) {
+    __shared__ __attribute__((aligned(16))) uint32_t s_pat[4 * 64 * 8];  // per wave: decode_simple's pattern buffer (EBUF bytes)
+    const BlockFold bf{s_pat, nullptr, nullptr, nullptr};
+    const uint32_t idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx < a.h.n_tiles) fused_tile<true, false>(a, idx, bf);
+}
+
+// Bytes [rel, rel + n) of a recognised periodic block (or row) written by the whole wave from its window, which already carries the 64
+// period bytes behind its literals: any 16 output bytes are 16 contiguous window bytes, at their own position or at B + phase.
+__device__ __forceinline__ void emit_periodic_range(const uint8_t *Y, uint32_t L0, uint32_t off, uint8_t *dst, uint32_t rel, uint32_t n,
+                                                    uint32_t lane) {
+    const uint32_t B = L0 - off, lim = L0 + 64, rb = smod(B, off);
+    const float inv = 1.0f / (float)off;
+    auto at = [&](uint32_t pos, uint32_t len) -> const uint8_t * {  // window address of block bytes [pos, pos + len), len <= 16
+        if (pos + len <= lim) return Y + pos;
+        uint32_t r = lmod(pos, off, inv) + off - rb;  // (pos - B) mod off
+        if (r >= off) r -= off;
+        return Y + B + r;
+    };
+    const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
+    if (n < head + 16) {  // too short for an aligned piece
+        for (uint32_t i = lane; i < n; i += 64) dst[i] = *at(rel + i, 1);
+        return;
+    }
+    if (lane < head) dst[lane] = *at(rel + lane, 1);
+    const uint32_t body16 = (n - head) >> 4;
+    for (uint32_t i0 = 0; i0 < body16; i0 += 256) {  // 4 KiB per trip: four LDS reads in flight before the stores
+        const uint32_t i = i0 + lane, x = head + 16 * i;
+        uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0, v2 = v0, v3 = v0;
+        const bool p0 = i < body16, p1 = i + 64 < body16, p2 = i + 128 < body16, p3 = i + 192 < body16;
+        if (p0) v0 = lds16(at(rel + x, 16));
+        if (p1) v1 = lds16(at(rel + x + 1024, 16));
+        if (p2) v2 = lds16(at(rel + x + 2048, 16));
+        if (p3) v3 = lds16(at(rel + x + 3072, 16));
+        uint8_t *d = dst + x;
+        if (p0) *reinterpret_cast<uint4 *>(d) = v0;
+        if (p1) *reinterpret_cast<uint4 *>(d + 1024) = v1;
+        if (p2) *reinterpret_cast<uint4 *>(d + 2048) = v2;
+        if (p3) *reinterpret_cast<uint4 *>(d + 3072) = v3;
+    }
+    const uint32_t tail = (n - head) & 15, p = head + 16 * body16 + lane;
+    if (lane < tail) dst[p] = *at(rel + p, 1);
+}
+
+// A wave's copy of n bytes, any alignment on either side: lane-parallel bytes up to the destination's first 16-byte boundary, then 16
+// bytes per lane — 1 KiB of whole lines per instruction, four in flight — and the last bytes lane-parallel.
+__device__ __forceinline__ void fwave_copy_lines(uint8_t *dst, const uint8_t *src, uint64_t n, uint32_t lane) {
+    if (n < 128) {
+        for (uint32_t i = lane; i < (uint32_t)n; i += 64) dst[i] = src[i];
+        return;
+    }
+    const uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
+    if (lane < head) dst[lane] = src[lane];
+    const uint64_t body = (n - head) >> 4;
+    const uint8_t *s = src + head;
+    uint8_t *d = dst + head;
+    uint64_t i = lane;
+    for (; i + 192 < body; i += 256) {
+        const uint4 v0 = ld16(s + i * 16), v1 = ld16(s + (i + 64) * 16), v2 = ld16(s + (i + 128) * 16), v3 = ld16(s + (i + 192) * 16);
+        st16(d + i * 16, v0); st16(d + (i + 64) * 16, v1); st16(d + (i + 128) * 16, v2); st16(d + (i + 192) * 16, v3);
+    }
+    for (; i < body; i += 64) st16(d + i * 16, ld16(s + i * 16));
+    const uint64_t done = head + body * 16;
+    if (done + lane < n) dst[done + lane] = src[done + lane];
+}
+
+// Big rows of periodic / raw blocks: k_fused_blocks with its two leaf loops replaced by plain stores — the same tile / item lists, the
+// same tests, the same item_done / tile_done verdicts, so k_compact_items and the block decoder behind it see what they always see.
+__global__ __launch_bounds__(256) void k_decode_blocks(FusedBlocksArgs a) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_Wb[4][WSTRIDE];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint32_t idx = blockIdx.x * 4 + w;
+    if (idx >= a.n_bt) return;
+    const uint32_t ti = a.bt_tile[idx], item = a.bt_item[idx];
+    const Tile t = a.h.tiles[ti];
+    const uint32_t row = t.first_unit;
+    const uint32_t src_pos = a.item_src[item];
+    const uint64_t usize = a.h.len[row];
+    const uint64_t origin = (uint64_t)(t.first_leaf >> 7) << 17;
+    if (src_pos == 0xFFFFFFFFu || a.row_flag[row] != 0 || t.n_leaves != 64 || usize - origin < 128 * 1024) return;
+    uint8_t *const WL = s_Wb[w];
+    const uint64_t n = a.blob_size[row];
+    const uint8_t *const src = a.h.srcA + (a.h.offA[row] - a.h.baseA) + src_pos;
+    const uint32_t avail = n - src_pos < WIN ? (uint32_t)(n - src_pos) : WIN;
+    {
+        const uint32_t o = 8 * lane;
+        uint64_t v = 0;
+        if (o + 8 <= avail) __builtin_memcpy(&v, src + o, 8);
+        else
+            for (uint32_t k = 0; k < 8; k++)
+                if (o + k < avail) v |= (uint64_t)src[o + k] << (8 * k);
+        *reinterpret_cast<uint64_t *>(WL + o) = v;
+        if (lane < (WSTRIDE - WIN) / 4) *reinterpret_cast<uint32_t *>(WL + WIN + 4 * lane) = 0;
+    }
+    FastTabs T;
+    {
+        const DTab eL = c_dll[lane], eM = c_dml[lane], eO = c_dof[lane & 31];
+        T.ll = eL.base | (uint32_t)eL.addbits << 24;
+        T.ml = eM.base | (uint32_t)eM.addbits << 24;
+        T.of = eO.addbits;
+        T.lls = lane < 36 ? c_llb[lane] | (uint32_t)c_lla[lane] << 24 : 0u;
+        T.mls = lane < 53 ? c_mlb[lane] | (uint32_t)c_mla[lane] << 24 : 0u;
+    }
+    const uint64_t tile_at = (uint64_t)t.first_leaf << 10;            // the tile's first byte inside the row
+    const uint32_t rel = (uint32_t)(tile_at - origin);                // ... inside its block: 0 or 64 KiB
+    uint8_t *const dst = a.h.srcB + a.h.offB[row] + tile_at;
+    const uint32_t bh = uni(*reinterpret_cast<const uint32_t *>(WL)) & 0xFFFFFF;
+    if (avail >= 3 && ((bh >> 1) & 3) == 0 && (bh >> 3) == 128 * 1024 && src_pos + 3 + 128 * 1024ull <= n) {
+        fwave_copy_lines(dst, src + 3 + rel, 64 * 1024, lane);  // raw block: its bytes sit in the frame
+        if (lane == 0) { a.tile_done[ti] = 1; a.item_done[item] = 1; }
+    }
+    const FastRow fr = parse_fast_block<false>(WL, 0, avail, 128 * 1024, avail >= 12, T);  // every lane: the same block
+    if (uni(fr.ok)) {
+        const uint32_t lit_at = uni(fr.lit_at), L0 = uni(fr.L0), off = uni(fr.off);
+        uint8_t *y = WL + lit_at;
+        y[L0 + lane] = y[L0 - off + lmod(lane, off, 1.0f / (float)off)];
+        emit_periodic_range(y, L0, off, dst, rel, 64 * 1024, lane);
+        if (lane == 0) { a.tile_done[ti] = 1; a.item_done[item] = 1; }  // the block's other tile comes to the same verdict (same block, same test)
+    }
+}
+
+// Stored rows above a tile (ALL = false: the slice tiles of stored big rows; everything else was written by the kernels in front) and
+// stored-only tables (ALL = true: one pass over every tile): a plain whole-line copy, blob -> output.
+template <bool ALL>
+__global__ __launch_bounds__(256) void k_copy_stored(HashArgs a) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t idx = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (idx >= a.n_tiles) return;
+    const Tile t = a.tiles[idx];
+    if (t.n_units == 0) {
+        const uint32_t row = t.first_unit;
+        if ((a.sel && a.sel[row]) || a.status[row] < 0) return;
+        const uint64_t len = a.len[row], lo = (uint64_t)t.first_leaf << 10;
+        if (len <= lo) return;
+        const uint64_t n = len - lo < ((uint64_t)t.n_leaves << 10) ? len - lo : (uint64_t)t.n_leaves << 10;
+        fwave_copy_lines(a.srcB + a.offB[row] + lo, a.srcA + (a.offA[row] - a.baseA) + lo, n, lane);
+        return;
+    }
+    if (!ALL) return;
+    for (uint32_t u = 0; u < t.n_units; u++) {  // (wave-uniform)
+        const uint32_t row = t.first_unit + u;
+        if ((a.sel && a.sel[row]) || a.status[row] < 0) continue;
+        fwave_copy_lines(a.srcB + a.offB[row], a.srcA + (a.offA[row] - a.baseA), a.len[row], lane);
+    }
+}
+
+void launch_decode_small(const FusedArgs &a, hipStream_t s) {
+    if (!a.h.n_tiles) return;
+    hipLaunchKernelGGL(k_decode_small, dim3((a.h.n_tiles + 3) / 4), dim3(256), 0, s, a);
+}
+void launch_decode_blocks(const FusedBlocksArgs &a, hipStream_t s) {
+    if (!a.n_bt) return;
+    hipLaunchKernelGGL(k_decode_blocks, dim3((a.n_bt + 3) / 4), dim3(256), 0, s, a);
+}
+void launch_copy_stored(const HashArgs &a, bool all, hipStream_t s) {
+    if (!a.n_tiles) return;
+    if (all) hipLaunchKernelGGL(k_copy_stored<true>, dim3((a.n_tiles + 3) / 4), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(k_copy_stored<false>, dim3((a.n_tiles + 3) / 4), dim3(256), 0, s, a);
 }
 
 void set_fused_dbg(unsigned long long *) {}

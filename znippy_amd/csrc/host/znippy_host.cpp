@@ -926,8 +926,9 @@ struct ReadBufs {
 // Blob bytes -> HBM -> decode+verify kernels; the decoded rows stay in bufs.d_out (the caller decides whether
 // they cross PCIe at all).  Stands for the worker loop body, decompress.rs:L135-190.  keep_out = false (save_data=false,
 // L186-189): no output region at all — the rows are checked by a verify-only run (znippy_verify_rows) and bufs.d_out is not touched.
+// decode_only (with keep_out and without verify: the extract path, archive.rs:L144-168): a decode-only run (znippy_decode_rows) — nothing is hashed.
 int decode_range(znippy_ctx *ctx, int arc_fd, const znippy_index &ix, const uint64_t *row_ids, size_t n, bool verify, ReadBufs &bufs,
-                 DecodedRange *dr, bool keep_out = true) {
+                 DecodedRange *dr, bool keep_out = true, bool decode_only = false) {
     std::vector<uint64_t> bo(n), bs(n), us(n);
     std::vector<uint8_t> bitmap((n + 7) / 8, 0), ck(verify ? 32 * n : 0);
     dr->out_off.assign(n, 0);
@@ -977,7 +978,8 @@ int decode_range(znippy_ctx *ctx, int arc_fd, const znippy_index &ix, const uint
     if (rc) return fail(rc, "znippy_rows_create failed");
     znippy_rows_set_blob_cap(rt, nblob);  // a row pointing outside what was read is an error code, not a device fault
     std::vector<uint64_t> cr(n);
-    if (keep_out) rc = znippy_decode_verify_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, cr.data(), n, dr->status.data());
+    if (keep_out && decode_only && !verify) rc = znippy_decode_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, dr->status.data());
+    else if (keep_out) rc = znippy_decode_verify_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, cr.data(), n, dr->status.data());
     else rc = znippy_verify_rows(ctx, rt, bufs.d_blobs.p, base, &dr->cnt, cr.data(), n, dr->status.data());
     znippy_rows_destroy(rt);
     if (rc) return fail(rc, std::string("decode failed: ") + znippy_last_error(ctx));
@@ -1243,7 +1245,10 @@ static int znippy_archive_extract_file_impl(znippy_archive *a, const char *rel, 
         if (rc) return fail(rc, "no usable GPU: the codec/hash path has no CPU fallback");
     }
     DecodedRange dr;
-    int rc = decode_range(a->ctx, a->fd, a->ix, it->second.data(), it->second.size(), verify != 0, a->bufs, &dr);
+    // the unverified extract hashes nothing (ZNIPPY_NO_DECODE_ONLY=1 in the environment: the decode + verify run without a checksum
+    // column, as before — for A/B runs)
+    const bool decode_only = !verify && !env_on("ZNIPPY_NO_DECODE_ONLY");
+    int rc = decode_range(a->ctx, a->fd, a->ix, it->second.data(), it->second.size(), verify != 0, a->bufs, &dr, true, decode_only);
     if (rc) return rc;
     for (int32_t st : dr.status)
         if (st < 0) return fail(st, "OpenZL-equivalent decompress failed");  // propagates (archive.rs:L160)

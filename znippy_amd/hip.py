@@ -194,6 +194,26 @@ class RowTable:
         self._seq += 1
         self._runs.pop(self._seq - 3, None)  # the library keeps two runs
 
+    def decode_async(self, d_blobs, d_out, blob_base=0, out_cap=None, blob_cap=None):
+        """Queue a decode-only run (the extract path, archive.rs:L144-168): every row is written where a decode run writes
+        it and nothing is hashed — the checksum column is not read and digests() is refused while this is the latest run."""
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        if blob_cap is None and not isinstance(d_blobs, int):
+            blob_cap = d_blobs.numel()
+        if blob_cap is not None:
+            self.ctx._chk(self.ctx.L.znippy_rows_set_blob_cap(self.h, int(blob_cap)), "znippy_rows_set_blob_cap")
+        self.ctx._chk(self.ctx.L.znippy_decode_rows_async(self.ctx.h, self.h, _dptr(d_blobs), blob_base, _dptr(d_out), out_cap),
+                      "znippy_decode_rows_async")
+        self._runs[self._seq] = [d_blobs, d_out, False]  # (repeated with these pointers when a flagged run in front of it is)
+        self._seq += 1
+        self._runs.pop(self._seq - 3, None)
+
+    def decode(self, d_blobs, d_out, blob_base=0, out_cap=None, blob_cap=None):
+        """Decode-only run, synchronous: (counters, status)."""
+        self.decode_async(d_blobs, d_out, blob_base, out_cap, blob_cap)
+        counters, _, status = self.results()
+        return counters, status
+
     def verify_async(self, d_blobs, blob_base=0, blob_cap=None):
         """Queue a verify-only run (the read loop with save_data=false, decompress.rs:L186-189): same results calls, same
         counters, corrupt list, status and digests as a decode run over these blobs, and no output."""
