@@ -117,7 +117,13 @@ typedef struct {
  *                                               NULL = a table that can only be verified
  *                                               (znippy_verify_rows; a decode call on it
  *                                               returns ZNIPPY_E_INVAL)
- * Also builds the work plan (tiles of <=64 BLAKE3 leaves) that drives the kernels' cursor. */
+ * Also builds the work plan (tiles of <=64 BLAKE3 leaves) that drives the kernels' cursor.
+ * What may exceed 4 GiB: every byte position and region size of this interface is a 64-bit value; a blob, a frame, a
+ * source round and the output of a stored row may lie across a multiple of 4 GiB.  What may not: a table holds fewer than 2^32 - 16 rows or rounds
+ * (ZNIPPY_E_INVAL), and the fast paths take single rows and rounds below 4 GiB only — a compressed row of 4 GiB or more
+ * is not split into block items and is left to the serial decoder, the batch path refuses frames whose content size
+ * does not fit 32 bits, a table with such a size is uploaded as four 64-bit columns instead of two packed size
+ * columns, and the cross-block match window is not used for a round of 4 GiB or more. */
 int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint64_t *blob_size,
                        const uint8_t *compressed_bitmap, const uint64_t *uncompressed_size,
                        const uint64_t *out_offset, const uint8_t *checksum, uint64_t row_begin,
@@ -212,7 +218,8 @@ int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *rows, uint8_t *digests);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,
- * stream_packer.rs:L98-106).  HOST arrays, n entries. */
+ * stream_packer.rs:L98-106).  HOST arrays, n entries.  src_offset is a full 64-bit value and rounds may share or overlap
+ * source bytes; for sizes see "What may exceed 4 GiB" at znippy_rows_create. */
 int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint64_t *len,
                          const uint8_t *skip, uint64_t n, znippy_rounds **out);
 void znippy_rounds_destroy(znippy_rounds *rounds);

@@ -57,11 +57,12 @@ def run_gpu(gpu_ctx, arch, pad_blobs=0, rt=None):
     return counters, corrupt, status, d_out.cpu().numpy()[:total], rt
 
 
-def oracle_rows(oracle, arch):
-    """The oracle's read loop over the whole archive: (counters, corrupt list, output bytes)."""
+def oracle_rows(oracle, arch, extent=None, fill=0):
+    """The oracle's read loop over the whole archive: (counters, corrupt list, output bytes).  extent / fill: size and
+    initial value of the output image, for archives whose rows do not lie back to back from 0."""
     n = len(arch["usize"])
     bitmap = np.packbits(arch["compressed"].astype(bool), bitorder="little")
-    want_out = np.zeros(int(arch["usize"].sum()), dtype=np.uint8)
+    want_out = np.full(int(arch["usize"].sum()) if extent is None else int(extent), fill, dtype=np.uint8)
     want, want_corrupt = oracle.decompress_rows(arch["blobs"], arch["blob_offset"], arch["blob_size"], arch["usize"],
                                                 arch["out_off"], bitmap, arch["checksum"], 0, n, out=want_out)
     return want, want_corrupt, want_out
@@ -331,3 +332,122 @@ def fuzz_run(gpu_ctx, oracle, bases, per_base, seed, min_ok, min_rej, mutants=No
     assert counters["total_chunks"] == n and counters["decode_errors"] == int((status < 0).sum())
     assert n_ok >= min_ok and n_rej >= min_rej, (n_ok, n_rej)
     print(f"mutants: {n} rows, oracle-accepted {n_ok}, rejected by both {n_rej}, gpu-decoded-but-flagged {n_flagged}")
+
+
+# ---- the small cases several modules run (oracle side: build once per module) -----------------------------------------
+
+def random_case(oracle):
+    arch = random_archive(oracle, seed=4, n_rows=900)
+    return arch, oracle_rows(oracle, arch)
+
+
+def mixed_case(oracle):
+    entries, skip = mixed_archive_entries()
+    arch = build_archive(oracle, entries, level=3, skip=skip)
+    return arch, oracle_rows(oracle, arch)
+
+
+def foreign_case(oracle):
+    """libzstd -19 frames of real text: 10 KiB ones (batch path), 64-256 KiB ones and one above 256 KiB (resolve path),
+    three of them damaged."""
+    data = py_corpus(3 << 20)
+    entries = [data[i * 10240:(i + 1) * 10240] for i in range(160)]
+    entries += [data[2_000_000:2_000_000 + n] for n in (65_537, 100_000, 180_000, 262_143)] + [data[1_700_000:1_700_000 + 300_001]]
+    frames = [workloads.libzstd_compress(e, 19) for e in entries]
+    A = frame_table(oracle, entries, frames)
+    blobs = A["blobs"].copy()
+    rng = np.random.default_rng(8)
+    for i in (17, 161, 164):
+        blobs[int(A["bo"][i]) + int(rng.integers(8, int(A["bs"][i]) - 4))] ^= 0x5A
+    A["blobs"] = blobs
+    arch = dict(blobs=blobs, blob_offset=A["bo"], blob_size=A["bs"], usize=A["us"], out_off=A["oo"], checksum=A["ck"],
+                compressed=np.ones(len(entries), np.uint8))
+    return arch, oracle_rows(oracle, arch)
+
+
+def store_case(oracle):
+    """No compressed row: ragged rows, 64-leaf rows, a 64-leaf row queued beside a big row's first slice (both 64-leaf
+    units of different kinds), odd output offsets, one damaged row."""
+    rng = np.random.default_rng(31)
+    sizes = [65536, 200_000, 65536, 65536, 65537, 3 * 65536, 65536, (1 << 20) + 1] + [int(x) for x in rng.integers(0, 30000, 120)]
+    sizes += [10240] * 40 + [0, 1, 15, 16, 17, 1023, 1024, 1025]
+    rows = [gen.incompressible(900 + i, n) for i, n in enumerate(sizes)]
+    out_off, pos = [], 5
+    for n in sizes:
+        out_off.append(pos)
+        pos += n + 3                                  # odd offsets, 3 guard bytes between rows
+    blobs = np.frombuffer(b"".join(rows) + bytes(64), dtype=np.uint8).copy()
+    bs = np.array(sizes, dtype=np.uint64)
+    bo = (np.cumsum(bs) - bs).astype(np.uint64)
+    ck = np.stack([np.frombuffer(oracle.blake3(d), dtype=np.uint8) for d in rows])
+    bad_row = 9
+    blobs[int(bo[bad_row]) + 7] ^= 0x10
+    total = pos + 64
+    want = np.full(total, 0xA5, np.uint8)
+    for i, o in enumerate(out_off):
+        want[o:o + sizes[i]] = blobs[int(bo[i]):int(bo[i]) + sizes[i]]
+    return dict(blobs=blobs, bo=bo, bs=bs, oo=np.array(out_off, np.uint64), ck=ck, total=total, want=want, bad_row=bad_row,
+                sizes=sizes)
+
+
+def write_case(oracle):
+    entries, skip = random_round_entries(seed=3, n_rounds=160)
+    return entries, skip, [oracle.blake3(e) for e in entries]
+
+
+def periodic(period, n, seed):
+    rng = np.random.default_rng(seed)
+    p = rng.integers(32, 127, size=period, dtype=np.uint8).tobytes()
+    return (p * (n // period + 1))[:n]
+
+
+BLK = 128 * 1024
+
+
+def big_rows_entries():
+    """Big rows for this library's own encoder: blocks that are 'literals + one periodic match' or raw (the fused block
+    kernel), short last blocks, a mixed frame, entropy-coded blocks (block items), two small rows."""
+    return [
+        periodic(45, 8 * BLK, 1),                      # whole blocks, all recognised
+        periodic(7, 3 * BLK + 12345, 2),               # short last block
+        periodic(600, 2 * BLK + 1, 3),
+        gen.incompressible(4, 4 * BLK),                # raw blocks
+        gen.incompressible(5, 2 * BLK + 999),
+        periodic(13, BLK, 6) + gen.incompressible(7, BLK) + gen.pseudo_text(BLK, seed=8) + periodic(200, BLK + 77, 9),  # mixed frame
+        gen.pseudo_text(3 * BLK + 5, seed=10),         # entropy-coded blocks: not for the fused kernel
+        periodic(1, 5 * BLK, 11),
+        gen.text(10240), gen.text(70000),
+    ]
+
+
+def periodic_rows_entries():
+    """A cut of test_periodic_rows_every_period_and_alignment's rows: every period class the recognised-row path of the
+    fused kernel tells apart, whole-leaf and ragged sizes, back to back (so every output alignment), text rows behind."""
+    rng = np.random.default_rng(5)
+    entries = []
+    for i, period in enumerate(list(range(1, 33)) + [45, 63, 64, 65, 100, 127, 128, 129, 255, 256, 257, 400, 511, 600]):
+        n = int(rng.integers(1, 40)) * 1024 if i % 3 else int(rng.integers(70, 40000))
+        entries.append(periodic(period, n, i))
+    return entries + [gen.text(10240)] * 16 + [gen.text(10239), gen.text(10241), gen.text(65536), gen.text(65), gen.text(64)]
+
+
+# ---- far placement: the same rows with offsets beyond 4 GiB ------------------------------------------------------------
+
+FAR_LINE = 1 << 32
+
+
+def place(offsets, sizes, mode, k=None):
+    """The shift to add to an offset column so that its rows lie around the 4 GiB line: "above" — every row above it
+    (line + 64 KiB); "straddle" — the line falls inside row k, near its middle (rows in front of k below it, rows behind k
+    above); "start_at_line" — row k begins at the line when its offset is a multiple of 128, else within 127 bytes
+    behind it.  One shift for the whole column, a multiple of 128: rows keep their distances and their alignment class."""
+    if mode == "above":
+        return FAR_LINE + (64 << 10)
+    off, n = int(offsets[k]), int(sizes[k])
+    assert off + n < FAR_LINE
+    if mode == "straddle":
+        assert n >= 256, "the row is too short to hold the line after rounding"
+        return (FAR_LINE - off - n // 2) // 128 * 128
+    if mode == "start_at_line":
+        return -((off - FAR_LINE) // 128) * 128
+    raise ValueError(mode)

@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 
 import gen
-from gpu_cases import (build_archive, check_random_archive_run, mixed_archive_entries, oracle_rows, random_archive,
-                       run_gpu)
+from gpu_cases import (big_rows_entries, build_archive, check_random_archive_run, mixed_archive_entries, oracle_rows,
+                       periodic, random_archive, run_gpu)
 
 pytestmark = pytest.mark.gpu
 
@@ -203,12 +203,6 @@ def test_block_items_and_their_fallbacks(gpu_ctx, oracle):
     assert "zstd_decode_blocks" in names and "zstd_block_scan" in names
 
 
-def _periodic(period, n, seed):
-    rng = np.random.default_rng(seed)
-    p = rng.integers(32, 127, size=period, dtype=np.uint8).tobytes()
-    return (p * (n // period + 1))[:n]
-
-
 @pytest.mark.parametrize("level", [1, 19])
 def test_periodic_rows_every_period_and_alignment(gpu_ctx, oracle, level):
     """The lane-parallel recognised-row path of the fused kernel (literal prefix + one overlapping match):
@@ -218,7 +212,7 @@ def test_periodic_rows_every_period_and_alignment(gpu_ctx, oracle, level):
     entries = []
     for i, period in enumerate(list(range(1, 70)) + [100, 127, 128, 129, 255, 256, 257, 400, 511, 600]):
         n = int(rng.integers(1, 40)) * 1024 if i % 3 else int(rng.integers(70, 40000))
-        entries.append(_periodic(period, n, i))
+        entries.append(periodic(period, n, i))
     entries += [gen.text(10240)] * 40 + [gen.text(10239), gen.text(10241), gen.text(65536), gen.text(65), gen.text(64)]
     arch = build_archive(oracle, entries, level=level)
     counters, corrupt, status, out, rt = run_gpu(gpu_ctx, arch, pad_blobs=3)
@@ -236,7 +230,7 @@ def test_periodic_rows_from_this_encoder(gpu_ctx, oracle):
     entries = []
     for i, period in enumerate(list(range(1, 70)) + [100, 128, 257, 600, 1000, 1024, 1025, 2000]):
         n = int(rng.integers(1, 40)) * 1024 if i % 3 else int(rng.integers(70, 40000))
-        entries.append(_periodic(period, n, 100 + i))
+        entries.append(periodic(period, n, 100 + i))
     entries += [gen.text(10240)] * 30
     src = np.frombuffer(b"".join(entries), dtype=np.uint8)
     lens = np.array([len(e) for e in entries], dtype=np.uint64)
@@ -262,18 +256,7 @@ def test_big_rows_block_items_fused(gpu_ctx, oracle):
     import torch
     from znippy_amd import hip
     rng = np.random.default_rng(9)
-    BLK = 128 * 1024
-    entries = [
-        _periodic(45, 8 * BLK, 1),                     # whole blocks, all recognised
-        _periodic(7, 3 * BLK + 12345, 2),              # short last block
-        _periodic(600, 2 * BLK + 1, 3),
-        gen.incompressible(4, 4 * BLK),                # raw blocks
-        gen.incompressible(5, 2 * BLK + 999),
-        _periodic(13, BLK, 6) + gen.incompressible(7, BLK) + gen.pseudo_text(BLK, seed=8) + _periodic(200, BLK + 77, 9),  # mixed frame
-        gen.pseudo_text(3 * BLK + 5, seed=10),         # entropy-coded blocks: not for the fused kernel
-        _periodic(1, 5 * BLK, 11),
-        gen.text(10240), gen.text(70000),
-    ]
+    entries = big_rows_entries()
     src = np.frombuffer(b"".join(entries), dtype=np.uint8)
     lens = np.array([len(e) for e in entries], dtype=np.uint64)
     offs = np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64)

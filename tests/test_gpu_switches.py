@@ -12,9 +12,8 @@ import numpy as np
 import pytest
 
 import gen
-import workloads
-from gpu_cases import (build_archive, check_random_archive_run, frame_table, make_ctx, mixed_archive_entries, oracle_rows,
-                       py_corpus, random_archive, random_round_entries, run_gpu)
+import gpu_cases
+from gpu_cases import build_archive, check_random_archive_run, make_ctx, oracle_rows, run_gpu
 
 pytestmark = pytest.mark.gpu
 
@@ -63,66 +62,27 @@ def _names(ctx):
 
 @pytest.fixture(scope="module")
 def random_case(oracle):
-    arch = random_archive(oracle, seed=4, n_rows=900)
-    return arch, oracle_rows(oracle, arch)
+    return gpu_cases.random_case(oracle)
 
 
 @pytest.fixture(scope="module")
 def mixed_case(oracle):
-    entries, skip = mixed_archive_entries()
-    arch = build_archive(oracle, entries, level=3, skip=skip)
-    return arch, oracle_rows(oracle, arch)
+    return gpu_cases.mixed_case(oracle)
 
 
 @pytest.fixture(scope="module")
 def foreign_case(oracle):
-    """libzstd -19 frames of real text: 10 KiB ones (batch path), 64-256 KiB ones and one above 256 KiB (resolve path),
-    three of them damaged."""
-    data = py_corpus(3 << 20)
-    entries = [data[i * 10240:(i + 1) * 10240] for i in range(160)]
-    entries += [data[2_000_000:2_000_000 + n] for n in (65_537, 100_000, 180_000, 262_143)] + [data[1_700_000:1_700_000 + 300_001]]
-    frames = [workloads.libzstd_compress(e, 19) for e in entries]
-    A = frame_table(oracle, entries, frames)
-    blobs = A["blobs"].copy()
-    rng = np.random.default_rng(8)
-    for i in (17, 161, 164):
-        blobs[int(A["bo"][i]) + int(rng.integers(8, int(A["bs"][i]) - 4))] ^= 0x5A
-    A["blobs"] = blobs
-    arch = dict(blobs=blobs, blob_offset=A["bo"], blob_size=A["bs"], usize=A["us"], out_off=A["oo"], checksum=A["ck"],
-                compressed=np.ones(len(entries), np.uint8))
-    return arch, oracle_rows(oracle, arch)
+    return gpu_cases.foreign_case(oracle)
 
 
 @pytest.fixture(scope="module")
 def store_case(oracle):
-    """No compressed row: ragged rows, 64-leaf rows, a 64-leaf row queued beside a big row's first slice (both 64-leaf
-    units of different kinds), odd output offsets, one damaged row."""
-    rng = np.random.default_rng(31)
-    sizes = [65536, 200_000, 65536, 65536, 65537, 3 * 65536, 65536, (1 << 20) + 1] + [int(x) for x in rng.integers(0, 30000, 120)]
-    sizes += [10240] * 40 + [0, 1, 15, 16, 17, 1023, 1024, 1025]
-    rows = [gen.incompressible(900 + i, n) for i, n in enumerate(sizes)]
-    out_off, pos = [], 5
-    for n in sizes:
-        out_off.append(pos)
-        pos += n + 3                                  # odd offsets, 3 guard bytes between rows
-    blobs = np.frombuffer(b"".join(rows) + bytes(64), dtype=np.uint8).copy()
-    bs = np.array(sizes, dtype=np.uint64)
-    bo = (np.cumsum(bs) - bs).astype(np.uint64)
-    ck = np.stack([np.frombuffer(oracle.blake3(d), dtype=np.uint8) for d in rows])
-    bad_row = 9
-    blobs[int(bo[bad_row]) + 7] ^= 0x10
-    total = pos + 64
-    want = np.full(total, 0xA5, np.uint8)
-    for i, o in enumerate(out_off):
-        want[o:o + sizes[i]] = blobs[int(bo[i]):int(bo[i]) + sizes[i]]
-    return dict(blobs=blobs, bo=bo, bs=bs, oo=np.array(out_off, np.uint64), ck=ck, total=total, want=want, bad_row=bad_row,
-                sizes=sizes)
+    return gpu_cases.store_case(oracle)
 
 
 @pytest.fixture(scope="module")
 def write_case(oracle):
-    entries, skip = random_round_entries(seed=3, n_rounds=160)
-    return entries, skip, [oracle.blake3(e) for e in entries]
+    return gpu_cases.write_case(oracle)
 
 
 @pytest.fixture(scope="module")
