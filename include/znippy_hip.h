@@ -228,6 +228,23 @@ void znippy_rounds_destroy(znippy_rounds *rounds);
  * OFF by default — the reference decides by file extension only (index.rs:L470-488), so turning this
  * on changes the `compressed` column for incompressible rounds. */
 int znippy_rounds_set_store_incompressible(znippy_rounds *rounds, int on);
+/* Opt-in aligned blob offsets (what zipalign does for zip): every payload of later znippy_encode_hash_rounds[_async]
+ * calls on this table starts at a multiple of `align` — a power of two in 1 .. 4096; 1, the default, packs back to back.
+ * Anything else, a NULL table or a closed context gives ZNIPPY_E_INVAL and changes nothing.  Runs already queued keep
+ * the value they were queued with, also while two runs are in flight.  With align = a:
+ *   blob_offset[0] = 0, blob_offset[i+1] = round_up(blob_offset[i] + blob_size[i], a);
+ *   blob_size[i] is the payload alone, and the payload's bytes are those of the packed run (frames do not depend on a);
+ *   *blob_bytes = blob_offset[n-1] + blob_size[n-1]: no padding behind the last round;
+ *   the gap bytes between payloads are written as zero; no byte at or beyond *blob_bytes is written;
+ *   an empty payload sits at an aligned offset of its own, and the next round starts there too.
+ * znippy_rounds_blob_bound follows the setter (the packed bound + (n - 1) * (a - 1)); a region smaller than the run
+ * needs gives ZNIPPY_E_DST_SMALL as on the packed path, with nothing written outside [0, blob_cap).  Offsets are relative
+ * to d_blob_out: for absolute alignment, give an aligned base.  With a >= 16 and a 16-byte aligned d_blob_out a
+ * store-heavy table's hash + copy pass always runs its aligned form (which gains where the destinations are whole 128-byte
+ * lines: 128 is the value for that; 4096 is for direct I/O and mapping).  The row table of such an archive is not "front to
+ * back": readers get its offsets from the blob_offset column, as for any index. */
+int znippy_rounds_set_blob_align(znippy_rounds *rounds, uint32_t align);
+uint32_t znippy_rounds_blob_align(const znippy_rounds *rounds); /* 1 for a NULL table */
 /* Upper bound of the blob bytes znippy_encode_hash_rounds can produce for this batch. */
 uint64_t znippy_rounds_blob_bound(const znippy_rounds *rounds);
 

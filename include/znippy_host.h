@@ -52,6 +52,10 @@ typedef struct znippy_index znippy_index;
 const char *znippy_host_last_error(void);
 
 /* ---- write side ---- */
+/* ZNIPPY_HOST_BLOB_ALIGN=<1|2|...|4096> in the environment (read when a pipeline starts, beside ZNIPPY_HOST_SLOT_MB; an
+ * invalid value is 1): every blob_offset of the archive znippy_compress_stream / znippy_compress_dir write is a multiple of
+ * it — znippy_rounds_set_blob_align on every slot's rounds table, and every slot written at an aligned offset.  The gaps
+ * read as zeros, nothing is added behind the last blob, and the read side needs nothing. */
 int znippy_compress_stream(const char *output, int no_skip, int device, znippy_stream **out);
 /* pkg_type < 0 = None, repo NULL = None (ArchiveEntry, stream_packer.rs:L34-44). Data is copied (once, into
  * page-locked staging); full staging slots are encoded while the caller keeps sending. */

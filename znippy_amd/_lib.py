@@ -47,6 +47,7 @@ EXPORTS = [
     "znippy_ctx_set_window_log", "znippy_ctx_window_log",
     "znippy_verify_rows", "znippy_verify_rows_async", "znippy_rows_verify_scratch",
     "znippy_decode_rows", "znippy_decode_rows_async",
+    "znippy_rounds_set_blob_align", "znippy_rounds_blob_align",
 ]
 
 
@@ -121,6 +122,10 @@ def lib():
     if hasattr(L, "znippy_decode_rows"):  # (likewise)
         L.znippy_decode_rows.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(VerifyCounters), vp]
         L.znippy_decode_rows_async.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_uint64]
+    if hasattr(L, "znippy_rounds_set_blob_align"):  # (likewise)
+        L.znippy_rounds_set_blob_align.argtypes = [vp, C.c_uint32]
+        L.znippy_rounds_blob_align.argtypes = [vp]
+        L.znippy_rounds_blob_align.restype = C.c_uint32
     _lib = L
     return L
 

@@ -14,6 +14,7 @@ class HipBackend:
         self.hip = hip
         self.device = torch.cuda.current_device() if device is None else device
         self.ctx = ctx or hip.Context(self.device)
+        self.blob_align = 1
 
     def set_level(self, level):
         """CompressCtx::new(compression_level), codec.rs:L16-28."""
@@ -22,6 +23,11 @@ class HipBackend:
     def set_window_log(self, window_log):
         """Cross-block match window of later encode calls (0 = off, 17..27; znippy_ctx_set_window_log)."""
         self.ctx.set_window_log(window_log)
+
+    def set_blob_align(self, align):
+        """Blob offsets of later encode_hash calls are multiples of `align` inside their region (a power of two, 1 .. 4096;
+        znippy_rounds_set_blob_align on every table built from here on)."""
+        self.blob_align = check_blob_align(align)
 
     def _to_dev(self, a):
         t = self.torch.from_numpy(np.ascontiguousarray(a))
@@ -35,6 +41,8 @@ class HipBackend:
                         checksum=np.zeros((0, 32), np.uint8), compressed=np.zeros(0, np.uint8)), np.zeros(0, np.uint8)
         d_src = self._to_dev(np.concatenate([staging, np.zeros(64, np.uint8)]))
         rt = self.hip.RoundTable(self.ctx, off, length, skip)
+        if self.blob_align > 1:
+            rt.set_blob_align(self.blob_align)
         d_blob = self.torch.empty(rt.blob_bound() + 64, dtype=self.torch.uint8, device=f"cuda:{self.device}")
         res = rt.encode_hash(d_src, d_blob)
         res = {k: (v.copy() if hasattr(v, "copy") else v) for k, v in res.items()}  # views die with the table
@@ -97,6 +105,27 @@ def apply_window_log(backend, window_log):
         backend.set_window_log(window_log)
     elif window_log:
         raise ValueError(f"backend {type(backend).__name__} has no cross-block window")
+
+
+def check_blob_align(align):
+    align = int(align)
+    if not 1 <= align <= 4096 or align & (align - 1):
+        raise ValueError(f"blob_align must be a power of two in 1..4096, not {align}")
+    return align
+
+
+def apply_blob_align(backend, blob_align):
+    """The pipelines' blob_align keyword: set on every backend that has the setting; one that has not takes only 1."""
+    blob_align = check_blob_align(blob_align)
+    if hasattr(backend, "set_blob_align"):
+        backend.set_blob_align(blob_align)
+    elif blob_align > 1:
+        raise ValueError(f"backend {type(backend).__name__} cannot align blob offsets")
+    return blob_align
+
+
+def round_up(v, align):
+    return (int(v) + align - 1) // align * align
 
 
 _default = None

@@ -537,6 +537,8 @@ struct znippy_rounds {
     bool store_incompressible = false;  // opt-in (znippy_rounds_set_store_incompressible)
     int fuse_tiles = 0;  // > 0: every round is a small encoded round (one block, no store path): the encoder hashes its tiles itself, this many per dequeue
     uint32_t *first_item = nullptr;     // first piece of every round
+    uint32_t blob_align = 1;            // opt-in (znippy_rounds_set_blob_align): every blob offset is a multiple of it
+    uint32_t *piece_pad = nullptr;      // zero bytes behind every piece (made by the first alignment above 1; only the rounds' last pieces are ever written)
     uint8_t *stored = nullptr, *h_stored = nullptr;  // per round: turned into a raw payload by the opt-in pass
     uint64_t *blob_offset = nullptr, *blob_size = nullptr, *total = nullptr;
     uint32_t *overflow = nullptr;
@@ -2186,7 +2188,7 @@ void znippy_rounds_destroy(znippy_rounds *r) {
         event_give(r->ctx, r->ev_res[k]);
     }
     void *ptrs[] = {r->src_off, r->len, r->skip, r->res_m[0], r->res_m[1], r->items, r->piece_len, r->piece_len_init,
-                    r->piece_start, r->local_excl, r->block_tot, r->first_item, r->stored, r->order_small, r->order_wide, r->retry_list, r->retry_count,
+                    r->piece_start, r->local_excl, r->block_tot, r->first_item, r->piece_pad, r->stored, r->order_small, r->order_wide, r->retry_list, r->retry_count,
                     r->plan_scratch[0], r->plan_scratch[1], r->plan_scratch[2], r->d_ldm, r->d_ldm_desc};
     pinned_give(r->ctx, r->h_stored, r->h_stored_cap);
     for (void *p : ptrs)
@@ -2285,12 +2287,17 @@ int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint
     return ZNIPPY_OK;
 }
 
-uint64_t znippy_rounds_blob_bound(const znippy_rounds *r) { return r ? r->blob_bound : 0; }
+// (aligned blob offsets: in front of every round but the first, at most align - 1 bytes of gap)
+uint64_t znippy_rounds_blob_bound(const znippy_rounds *r) {
+    if (!r) return 0;
+    return r->blob_bound + (r->n ? (uint64_t)(r->n - 1) * (r->blob_align - 1) : 0);
+}
 
 // d_copy_out != nullptr: the stored (skip) rounds are copied to d_copy_out + blob_offset[round] while they are hashed
 // (store-heavy tables; blob_offset must have been computed on the stream before)
+// copy_align: the alignment of the run's blob offsets (16 and more: every destination is as aligned as d_copy_out is)
 static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, hipStream_t on = nullptr,
-                             void *d_copy_out = nullptr, uint64_t copy_cap = 0) {
+                             void *d_copy_out = nullptr, uint64_t copy_cap = 0, uint32_t copy_align = 1) {
     hipStream_t s = on ? on : ctx->stream;
     HashArgs h{};
     h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
@@ -2301,7 +2308,7 @@ static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_sr
         h.srcB = (uint8_t *)d_copy_out; h.offB = r->blob_offset; h.copy_to_B = 1;
         h.store_tiles = ctx->sw.store_g;
         h.copy_mask = r->skip; h.copy_cap = copy_cap;
-        h.misaligned_dst = !(r->all_stored_aligned && ((uintptr_t)d_copy_out & 15) == 0);
+        h.misaligned_dst = !((r->all_stored_aligned || copy_align >= 16) && ((uintptr_t)d_copy_out & 15) == 0);
     }
     // next to a busy encoder (auxiliary stream) the hash keeps out of LDS: the encoder's residency depends on it
     if (on && r->enc_bytes * 4 >= r->in_bytes) h.fold_tiles_max = 1;
@@ -2453,6 +2460,8 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     const bool high = ctx->level >= HIGH_TIER_LEVEL;
     const int window_log = high ? ctx->window_log : 0;  // (the fast tier keeps its frames)
     const bool far = window_log && ensure_ldm(ctx, r);  // allocations before the first stream operation of the call
+    const uint32_t align = r->blob_align;  // this run's value: a later znippy_rounds_set_blob_align does not reach it
+    const uint32_t *const pad = align > 1 ? r->piece_pad : nullptr;
     if (r->prov_bytes + 64 > ctx->enc_prov_cap) {
         HIPCHK(ctx, hipStreamSynchronize(s));
         if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
@@ -2526,9 +2535,10 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     // Store-heavy table (most bytes are skip rounds): hashing and copying the stored bytes are one pass over them once
     // their blob offsets are known — scan and gather run first (the gather leaves the stored pieces alone), then the
     // hash kernel copies what it hashes.  Otherwise the hash runs beside the encoder on the auxiliary stream.
-    // (Blobs are packed without gaps, so behind a compressed round the offsets are odd: unless every round is stored
-    // and every length a multiple of 16, the launch uses the kernel variant that re-cuts the bytes to 16-byte
-    // boundaries on their way out — plain 16-byte stores at odd addresses cost more than the pass they save.)
+    // (Blobs are packed without gaps by default, so behind a compressed round the offsets are odd: unless every round is
+    // stored and every length a multiple of 16 — or the table asks for blob offsets aligned to 16 bytes or more — the
+    // launch uses the kernel variant that re-cuts the bytes to 16-byte boundaries on their way out: plain 16-byte stores
+    // at odd addresses cost more than the pass they save.)
     const bool heavy = r->in_bytes && (r->in_bytes - r->enc_bytes) * 2 >= r->in_bytes;
     const bool fuse_store = heavy && !r->store_incompressible &&
                             !ctx->sw.no_fused_store && !ctx->sw.nohash;
@@ -2544,8 +2554,14 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
         launch_store_decide(r->first_item, r->items, r->len, r->skip, r->n, r->piece_len, r->stored, s);
         ktime_end(ctx);
     }
+    if (pad) {
+        ktime_begin(ctx, "round_pad");
+        launch_round_pad(r->first_item, r->items, r->len, r->skip, r->store_incompressible ? r->stored : nullptr, r->n, r->piece_len, align,
+                         r->piece_pad, s);
+        ktime_end(ctx);
+    }
     ktime_begin(ctx, "piece_scan");
-    launch_piece_scan(r->piece_len, r->n_items, r->local_excl, r->block_tot, s);
+    launch_piece_scan(r->piece_len, pad, r->n_items, r->local_excl, r->block_tot, s);
     ktime_end(ctx);
     GatherArgs g{};
     g.items = r->items; g.n_pieces = r->n_items; g.piece_len = r->piece_len; g.piece_start = r->piece_start;
@@ -2555,6 +2571,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     g.blob_offset = r->blob_offset; g.blob_size = r->blob_size; g.total = r->total; g.overflow = r->overflow;
     g.stored = r->store_incompressible ? r->stored : nullptr;
     g.skip_stored_copy = fuse_store ? 1 : 0;
+    g.pad = pad;
     // lane-per-piece gather (64 consecutive pieces per wave): only for tables without blocks above 16 KiB — the consecutive
     // blocks of one big round land in one wave, which then copies them one after the other (a table of 4,900 text files, a
     // few of them above 1 MiB: 0.29 ms against 0.03 for a wave per piece).  Store-heavy table: the stored rounds' 64 KiB
@@ -2564,7 +2581,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     launch_gather(g, s);
     ktime_end(ctx);
     if (fuse_store) {
-        rc = hash_rounds_async(ctx, r, d_src, nullptr, d_blob_out, blob_cap);
+        rc = hash_rounds_async(ctx, r, d_src, nullptr, d_blob_out, blob_cap, align);
         if (rc) return rc;
     } else if (!fuse_hash) {
         HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));  // digests are complete once the main stream drains
@@ -2688,6 +2705,23 @@ extern "C" size_t znippy_compress_bound(size_t n) {
     // the higher effort tier puts behind frames of several blocks
     return n + 3 * (n / BLOCK_BYTES + 1) + 19;
 }
+
+extern "C" int znippy_rounds_set_blob_align(znippy_rounds *r, uint32_t align) {
+    if (!r || !r->ctx || r->ctx->closing || align < 1 || align > 4096 || (align & (align - 1))) return ZNIPPY_E_INVAL;
+    znippy_ctx *const ctx = r->ctx;
+    if (align > 1 && !r->piece_pad) {  // cleared once, on the stream the runs are queued on
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = 4 * std::max<size_t>(r->n_items, 4);
+        uint32_t *p = nullptr;
+        if (tmalloc(ctx, &p, bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
+        if (hipMemsetAsync(p, 0, bytes, ctx->stream) != hipSuccess) { (void)hipGetLastError(); tfree(ctx, p); return ZNIPPY_E_HIP; }
+        r->piece_pad = p;
+    }
+    r->blob_align = align;
+    return ZNIPPY_OK;
+}
+
+extern "C" uint32_t znippy_rounds_blob_align(const znippy_rounds *r) { return r ? r->blob_align : 1; }
 
 extern "C" int znippy_rounds_set_store_incompressible(znippy_rounds *r, int on) {
     if (!r) return ZNIPPY_E_INVAL;

@@ -103,13 +103,19 @@ struct GatherArgs {
     const uint8_t *stored;  // optional: rounds the store-if-incompressible pass turned into raw payloads
     int skip_stored_copy;   // store-heavy tables: the hash kernel copies the stored rounds while it hashes them
     int small_pieces;       // the table's rounds average <= 16 KiB: lane = piece (k_gather); else wave = piece (k_gather_wide)
+    const uint32_t *pad;    // aligned blob offsets (opt-in): zero bytes behind every piece (launch_round_pad); NULL = packed
 };
 
 void launch_encode(const EncodeArgs &a, int grid, bool small_blocks, bool high, hipStream_t s);
 constexpr int HIGH_TIER_LEVEL = 4;  // compression levels from here up use the higher effort tier of the wide encoder
 void launch_ldm_index(const LdmRound *rl, uint32_t n_rl, uint32_t n_chunks, const uint8_t *src, const uint64_t *src_off,
                       const uint64_t *len, uint32_t *ldm, hipStream_t s);
-void launch_piece_scan(const uint32_t *piece_len, uint32_t n, uint64_t *local_excl, uint64_t *block_tot, hipStream_t s);
+// pad: optional (aligned blob offsets), added to the scan length of each piece
+void launch_piece_scan(const uint32_t *piece_len, const uint32_t *pad, uint32_t n, uint64_t *local_excl, uint64_t *block_tot, hipStream_t s);
+// aligned blob offsets: pad[last piece of round r] = round_up(payload of r, align) - payload of r, 0 for the table's last round
+// (the other entries of pad[] are never written: zero since the array was made)
+void launch_round_pad(const uint32_t *first_item, const EncItem *items, const uint64_t *len, const uint8_t *skip, const uint8_t *stored,
+                      uint32_t n_rounds, const uint32_t *piece_len, uint32_t align, uint32_t *pad, hipStream_t s);
 void launch_gather(const GatherArgs &g, hipStream_t s);
 void launch_store_decide(const uint32_t *first_item, const EncItem *items, const uint64_t *len, const uint8_t *skip,
                          uint32_t n_rounds, uint32_t *piece_len, uint8_t *stored, hipStream_t s);

@@ -51,6 +51,12 @@ uint64_t env_mb(const char *name, uint64_t dflt_mb) {
 // Bytes per GPU hand-off: one pinned staging slot on the write side, one decoded range on the read side.
 uint64_t stage_bytes() { return env_mb("ZNIPPY_HOST_SLOT_MB", 128); }
 uint64_t range_bytes(bool save) { return env_mb("ZNIPPY_HOST_RANGE_MB", save ? 256 : 1024); }
+// Write side, opt-in: every blob_offset of the archive is a multiple of this power of two (1 .. 4096; anything else: 1).
+uint32_t blob_align() {
+    const char *v = getenv("ZNIPPY_HOST_BLOB_ALIGN");
+    const unsigned long a = v && *v ? strtoul(v, nullptr, 10) : 1;
+    return a >= 1 && a <= 4096 && !(a & (a - 1)) ? (uint32_t)a : 1u;
+}
 // File I/O helper threads.  Readers (compress_dir: open/pread/close, lstat) scale to ~16 threads; writers that
 // CREATE files in one directory contend on its lock and are fastest at ~4 (tmpfs, 100k files: 1 writer 0.50 s,
 // 2: 0.41 s, 4: 0.38 s, 8: 0.52 s, 16: 0.78 s, 32: 1.2 s).  ZNIPPY_HOST_READERS / ZNIPPY_HOST_WRITERS override.
@@ -374,7 +380,7 @@ struct StageSlot {
 
 class Packer {
 public:
-    Packer(int fd, int device, uint64_t max_round) : fd_(fd), device_(device), slot_cap_(std::max(stage_bytes(), max_round)) {}
+    Packer(int fd, int device, uint64_t max_round) : fd_(fd), device_(device), slot_cap_(std::max(stage_bytes(), max_round)), align_(blob_align()) {}
     ~Packer() {
         if (thread_.joinable()) { push_full(nullptr); thread_.join(); }
         if (ctx_) znippy_ctx_destroy(ctx_);
@@ -481,7 +487,8 @@ private:
         znippy_rounds *rt = nullptr;
         uint64_t blob_bytes = 0;
         int rc = znippy_rounds_create(ctx_, off.data(), len.data(), skip.data(), nb, &rt);
-        if (!rc && !d_blob_.reserve(znippy_rounds_blob_bound(rt) + 64)) rc = ZNIPPY_E_NOMEM;
+        if (!rc && align_ > 1) rc = znippy_rounds_set_blob_align(rt, align_);
+        if (!rc && !d_blob_.reserve(znippy_rounds_blob_bound(rt) + 64)) rc = ZNIPPY_E_NOMEM;  // (the bound follows the alignment)
         if (!rc) rc = znippy_encode_hash_rounds(ctx_, rt, d_src_.p, d_blob_.p, d_blob_.cap, boff.data(), bsz.data(), ck.data(), comp.data(), &blob_bytes);
         if (rt) znippy_rounds_destroy(rt);
         if (rc) { *msg = znippy_last_error(ctx_); return rc; }
@@ -489,6 +496,7 @@ private:
         if (!blob_pin_.reserve(blob_bytes)) { *msg = "page-locked blob allocation failed"; return ZNIPPY_E_NOMEM; }
         if (blob_bytes && hipMemcpy(blob_pin_.p, d_blob_.p, blob_bytes, hipMemcpyDeviceToHost) != hipSuccess) { *msg = "D2H failed"; return ZNIPPY_E_HIP; }
         t_d2h_ += now_s() - t; t = now_s();
+        out_cursor = (out_cursor + align_ - 1) & ~(uint64_t)(align_ - 1);  // aligned blob offsets: the hole in front of the slot reads as zeros
         if (!pwrite_all(fd_, blob_pin_.p, blob_bytes, out_cursor)) { *msg = "archive write failed"; return ZNIPPY_E_INVAL; }  // the writer, L255-284
         t_write_ += now_s() - t;
         for (size_t k = 0; k < nb; k++) {
@@ -503,6 +511,7 @@ private:
 
     int fd_, device_;
     uint64_t slot_cap_;
+    uint32_t align_;
     znippy_ctx *ctx_ = nullptr;
     StageSlot slots_[N_STAGE];
     StageSlot *cur_ = nullptr;

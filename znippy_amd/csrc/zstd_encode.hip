@@ -1770,11 +1770,15 @@ __global__ __launch_bounds__(64) void k_zstd_encode(EncodeArgs a) {
 // local exclusive scan of piece lengths inside blocks of 256 pieces + block totals (small workgroups: the
 // scan and the gather run next to the hash kernel of the auxiliary stream and must fit into the wave slots
 // it frees one workgroup at a time)
-__global__ __launch_bounds__(256) void k_piece_scan(const uint32_t *piece_len, uint32_t n, uint64_t *local_excl,
+// PAD (aligned blob offsets): a piece's scan length is its length plus the zero bytes behind it
+template <bool PAD>
+__global__ __launch_bounds__(256) void k_piece_scan(const uint32_t *piece_len, const uint32_t *pad, uint32_t n, uint64_t *local_excl,
                                                     uint64_t *block_tot) {
     __shared__ uint64_t wsum[4];
     const uint32_t i = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint64_t v = i < n ? piece_len[i] : 0, inc = v;
+    uint64_t v = i < n ? piece_len[i] : 0;
+    if (PAD && i < n) v += pad[i];
+    uint64_t inc = v;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         uint64_t y = __shfl_up(inc, d);
@@ -1788,8 +1792,21 @@ __global__ __launch_bounds__(256) void k_piece_scan(const uint32_t *piece_len, u
     if (threadIdx.x == 255) block_tot[blockIdx.x] = wbase + inc;
 }
 
+// n zero bytes at dst by one wave (aligned blob offsets: the gap behind a round, n < 4096)
+__device__ __forceinline__ void wave_zero(uint8_t *dst, uint32_t n, uint32_t lane) {
+    uint32_t head = (uint32_t)((16 - ((uintptr_t)dst & 15)) & 15);
+    if (head > n) head = n;
+    if (lane < head) dst[lane] = 0;
+    const uint32_t body = (n - head) >> 4;
+    for (uint32_t i = lane; i < body; i += 64) *reinterpret_cast<uint4 *>(dst + head + (size_t)i * 16) = make_uint4(0, 0, 0, 0);
+    const uint32_t done = head + body * 16;
+    if (done + lane < n) dst[done + lane] = 0;
+}
+
 // one wave per piece (tables of big pieces: 128 KiB blocks, 64 KiB slices of stored rounds): copy it to its packed position;
-// fill the per-round outputs
+// fill the per-round outputs.  PAD (aligned blob offsets): the gap behind a round's last piece is zero-filled by that
+// piece's wave and counts in its overflow test (a gap is followed by a round, so a run that fits has every gap inside).
+template <bool PAD>
 __global__ __launch_bounds__(256) void k_gather_wide(GatherArgs g) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t piece = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1806,8 +1823,10 @@ __global__ __launch_bounds__(256) void k_gather_wide(GatherArgs g) {
     const uint8_t *s = (it.flags & ITEM_SKIP) ? g.src + g.src_off[it.round] + it.prov : g.prov + g.piece_start[piece];
     if (g.stored && g.stored[it.round]) s = g.src + g.src_off[it.round] + (uint64_t)it.block * BLOCK_BYTES;  // raw bytes of this block
     uint8_t *d = g.blob_out + off;
-    if (off + len <= g.blob_cap) {
+    const uint32_t pad = PAD ? g.pad[piece] : 0u;
+    if (off + len + pad <= g.blob_cap) {
         if (!(g.skip_stored_copy && (it.flags & ITEM_SKIP))) wave_copy(d, s, len, lane);
+        if (PAD && pad) wave_zero(d + len, pad, lane);
     } else if (lane == 0) atomicOr(g.overflow, 1u);
     if (lane == 0) {
         if (it.flags & ITEM_FIRST) g.blob_offset[it.round] = off;
@@ -1820,7 +1839,10 @@ __global__ __launch_bounds__(256) void k_gather_wide(GatherArgs g) {
 // bookkeeping, pieces of <= GATHER_SMALL bytes are copied by their own lanes 16 bytes at a time, the others by the whole
 // wave one after the other.  (First form: one wave per piece — 100,000 waves of five dependent round trips each for C2's
 // 85-byte pieces: 0.055 ms of a 0.87 ms step.)
-constexpr uint32_t GATHER_SMALL = 512;
+// PAD (aligned blob offsets): as in k_gather_wide; gaps of up to GATHER_PAD_LANE bytes are written by the piece's own lane,
+// longer ones (alignments above 16) by the whole wave, one after the other.
+constexpr uint32_t GATHER_SMALL = 512, GATHER_PAD_LANE = 15;
+template <bool PAD>
 __global__ __launch_bounds__(256) void k_gather(GatherArgs g) {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t piece = blockIdx.x * 256 + threadIdx.x;
@@ -1831,22 +1853,34 @@ __global__ __launch_bounds__(256) void k_gather(GatherArgs g) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
     uint64_t off = 0;
-    uint32_t len = 0;
+    uint32_t len = 0, pad = 0;
     const uint8_t *s = g.src;
     bool copy = false;
     if (on) {
         off = part + g.local_excl[piece];
         len = g.piece_len[piece];
+        if (PAD) pad = g.pad[piece];
         const EncItem it = g.items[piece];
         s = (it.flags & ITEM_SKIP) ? g.src + g.src_off[it.round] + it.prov : g.prov + g.piece_start[piece];
         if (g.stored && g.stored[it.round]) s = g.src + g.src_off[it.round] + (uint64_t)it.block * BLOCK_BYTES;  // raw bytes of this block
-        if (off + len <= g.blob_cap) copy = !(g.skip_stored_copy && (it.flags & ITEM_SKIP));
-        else atomicOr(g.overflow, 1u);
+        if (off + len + pad <= g.blob_cap) copy = !(g.skip_stored_copy && (it.flags & ITEM_SKIP));
+        else { atomicOr(g.overflow, 1u); pad = 0; }
         if (it.flags & ITEM_FIRST) g.blob_offset[it.round] = off;
         atomicAdd(reinterpret_cast<unsigned long long *>(&g.blob_size[it.round]), (unsigned long long)len);
         if (piece == g.n_pieces - 1) *g.total = off + len;
     }
     uint8_t *const d = g.blob_out + off;
+    if (PAD) {
+        if (pad <= GATHER_PAD_LANE)
+            for (uint32_t o = 0; o < pad; o++) d[len + o] = 0;
+        uint64_t padm = __ballot(pad > GATHER_PAD_LANE);
+        while (padm) {  // (wave-uniform)
+            const uint32_t j = (uint32_t)__ffsll((long long)padm) - 1;
+            padm &= padm - 1;
+            const uint64_t dz = (((uint64_t)rdlane((uint32_t)((uint64_t)(uintptr_t)d >> 32), j) << 32) | rdlane((uint32_t)(uintptr_t)d, j)) + rdlane(len, j);
+            wave_zero(reinterpret_cast<uint8_t *>((uintptr_t)dz), rdlane(pad, j), lane);
+        }
+    }
     if (copy && len <= GATHER_SMALL) {  // lane = piece
         uint32_t o = 0;
         for (; o + 16 <= len; o += 16) {
@@ -1930,9 +1964,52 @@ void launch_ldm_index(const LdmRound *rl, uint32_t n_rl, uint32_t n_chunks, cons
     hipLaunchKernelGGL(k_ldm_index, dim3(n_chunks), dim3(256), 0, s, rl, n_rl, src, src_off, len, ldm);
 }
 
-void launch_piece_scan(const uint32_t *piece_len, uint32_t n, uint64_t *local_excl, uint64_t *block_tot, hipStream_t s) {
+void launch_piece_scan(const uint32_t *piece_len, const uint32_t *pad, uint32_t n, uint64_t *local_excl, uint64_t *block_tot, hipStream_t s) {
     if (!n) return;
-    hipLaunchKernelGGL(k_piece_scan, dim3((n + 255) / 256), dim3(256), 0, s, piece_len, n, local_excl, block_tot);
+    if (pad) hipLaunchKernelGGL(k_piece_scan<true>, dim3((n + 255) / 256), dim3(256), 0, s, piece_len, pad, n, local_excl, block_tot);
+    else hipLaunchKernelGGL(k_piece_scan<false>, dim3((n + 255) / 256), dim3(256), 0, s, piece_len, pad, n, local_excl, block_tot);
+}
+
+// Aligned blob offsets (opt-in): the zero bytes behind every round.  Lane = round, behind store_decide (the lengths are
+// final) and in front of the scan.  A stored round's payload is its input, whatever its piece count (a 200 MiB stored
+// round: 3,200 pieces); an encoded round of up to ROUND_PAD_LANE pieces is summed by its own lane (100k one-piece rounds:
+// one load each), a longer one by the whole wave, 64 pieces per step — no lane walks a big round alone.
+constexpr uint32_t ROUND_PAD_LANE = 4;
+__global__ __launch_bounds__(256) void k_round_pad(const uint32_t *first_item, const EncItem *items, const uint64_t *len, const uint8_t *skip,
+                                                   const uint8_t *stored, uint32_t n_rounds, const uint32_t *piece_len, uint32_t align,
+                                                   uint32_t *pad) {
+    const uint32_t r = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+    const bool on = r < n_rounds;
+    uint32_t f = 0, nb = 0;
+    uint64_t sum = 0;
+    bool wide = false;
+    if (on) {
+        f = first_item[r];
+        nb = items[f].n_blocks;
+        if (skip[r] || (stored && stored[r])) sum = len[r];
+        else if (nb <= ROUND_PAD_LANE)
+            for (uint32_t k = 0; k < nb; k++) sum += piece_len[f + k];
+        else wide = true;
+    }
+    uint64_t widem = __ballot(wide);
+    while (widem) {  // (wave-uniform)
+        const uint32_t j = (uint32_t)__ffsll((long long)widem) - 1;
+        widem &= widem - 1;
+        const uint32_t fj = rdlane(f, j), nj = rdlane(nb, j);
+        uint64_t part = 0;
+        for (uint32_t k = lane; k < nj; k += 64) part += piece_len[fj + k];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) part += __shfl_xor(part, d);
+        if (lane == j) sum = part;
+    }
+    if (on) pad[f + nb - 1] = r == n_rounds - 1 ? 0u : (uint32_t)(((sum + align - 1) & ~(uint64_t)(align - 1)) - sum);
+}
+
+void launch_round_pad(const uint32_t *first_item, const EncItem *items, const uint64_t *len, const uint8_t *skip, const uint8_t *stored,
+                      uint32_t n_rounds, const uint32_t *piece_len, uint32_t align, uint32_t *pad, hipStream_t s) {
+    if (!n_rounds) return;
+    hipLaunchKernelGGL(k_round_pad, dim3((n_rounds + 255) / 256), dim3(256), 0, s, first_item, items, len, skip, stored, n_rounds,
+                       piece_len, align, pad);
 }
 
 // Opt-in store-if-incompressible (reference wish list, TODO_NOW.md:L37-38): a round whose frame is not
@@ -1969,8 +2046,12 @@ void launch_store_decide(const uint32_t *first_item, const EncItem *items, const
 
 void launch_gather(const GatherArgs &g, hipStream_t s) {
     if (!g.n_pieces) return;
-    if (g.small_pieces) hipLaunchKernelGGL(k_gather, dim3((g.n_pieces + 255) / 256), dim3(256), 0, s, g);
-    else hipLaunchKernelGGL(k_gather_wide, dim3((g.n_pieces + 3) / 4), dim3(256), 0, s, g);
+    const dim3 grid_small((g.n_pieces + 255) / 256), grid_wide((g.n_pieces + 3) / 4);
+    if (g.pad) {
+        if (g.small_pieces) hipLaunchKernelGGL(k_gather<true>, grid_small, dim3(256), 0, s, g);
+        else hipLaunchKernelGGL(k_gather_wide<true>, grid_wide, dim3(256), 0, s, g);
+    } else if (g.small_pieces) hipLaunchKernelGGL(k_gather<false>, grid_small, dim3(256), 0, s, g);
+    else hipLaunchKernelGGL(k_gather_wide<false>, grid_wide, dim3(256), 0, s, g);
 }
 
 // ---- host: FSE encoding tables for the predefined distributions (RFC 8878 §3.1.1.3.2.2) ------

@@ -314,6 +314,14 @@ class RoundTable:
         self.ctx._chk(self.ctx.L.znippy_rounds_set_store_incompressible(self.h, int(on)), "set_store_incompressible")
         self._store_inc = bool(on)
 
+    def set_blob_align(self, align):
+        """Opt-in: every payload of later encode calls starts at a multiple of `align` (a power of two, 1 .. 4096; 1 = packed),
+        gaps zero-filled; blob_bound() follows.  See znippy_rounds_set_blob_align in znippy_hip.h."""
+        self.ctx._chk(self.ctx.L.znippy_rounds_set_blob_align(self.h, int(align)), "znippy_rounds_set_blob_align")
+
+    def blob_align(self):
+        return int(self.ctx.L.znippy_rounds_blob_align(self.h))
+
     def blob_bound(self):
         return int(self.ctx.L.znippy_rounds_blob_bound(self.h))
 

@@ -21,15 +21,18 @@ NUM_SLOTS = 8                  # slot_packer.rs:L31
 
 
 def compress_dir(input_dir, output, no_skip: bool = False, plugin=None, repo: Optional[str] = None, backend=None,
-                 config=None, window_log: int = 0) -> ix.CompressionReport:
-    """window_log: 0 (default) or 17..27, the encoder's opt-in cross-block match window (znippy_ctx_set_window_log)."""
+                 config=None, window_log: int = 0, blob_align: int = 1) -> ix.CompressionReport:
+    """window_log: 0 (default) or 17..27, the encoder's opt-in cross-block match window (znippy_ctx_set_window_log).
+    blob_align: 1 (default) or a power of two up to 4096: every blob_offset of the archive is a multiple of it, the gaps
+    are zero (znippy_rounds_set_blob_align) and the file is longer by them."""
     if plugin is not None:
         raise NotImplementedError("metadata plugins are outside the hot path (SURVEY §2 #12)")
-    from .backend import apply_window_log, default_backend
+    from .backend import apply_blob_align, apply_window_log, default_backend, round_up
     backend = backend or default_backend()
     config = config or ix.CONFIG
     backend.set_level(config.compression_level)  # CompressCtx::new(CONFIG.compression_level), stream_packer.rs:L217 / slot_packer.rs:L551
     apply_window_log(backend, window_log)
+    blob_align = apply_blob_align(backend, blob_align)
     input_dir = str(input_dir)
     total_dirs = 0
     all_files = []
@@ -51,11 +54,11 @@ def compress_dir(input_dir, output, no_skip: bool = False, plugin=None, repo: Op
 
     output_path = with_extension(str(output), "znippy")
     uf = ub = cf = cb = 0
-    out_cursor = 0
+    out_cursor = payload_bytes = 0
     batches = []
     with open(output_path, "wb+") as f:
         def run_pass(indices, is_big):
-            nonlocal uf, ub, cf, cb, out_cursor
+            nonlocal uf, ub, cf, cb, out_cursor, payload_bytes
             rounds = []  # (file_index, file_offset, len, skip, fdata_offset, chunk_seq)
             for i in indices:
                 skip = (not no_skip) and ix.should_skip_compression(all_files[i])
@@ -92,7 +95,9 @@ def compress_dir(input_dir, output, no_skip: bool = False, plugin=None, repo: Op
                     off[q], ln[q], sk[q] = pos, l, 1 if skip else 0
                     pos += l
                 res, blob = backend.encode_hash(staging, off, ln, sk)
+                out_cursor = round_up(out_cursor, blob_align)  # (the hole in front reads as zeros)
                 os.pwrite(f.fileno(), blob.tobytes(), out_cursor)
+                payload_bytes += int(np.asarray(res["blob_size"], np.uint64).sum())
                 for q, (fi, fo, l, skip, fdo, seq) in enumerate(rounds[k:j]):
                     bsz = int(res["blob_size"][q])
                     blobs.append(ix.BlobMeta(
@@ -119,4 +124,4 @@ def compress_dir(input_dir, output, no_skip: bool = False, plugin=None, repo: Op
     return ix.CompressionReport(
         total_files=len(all_files), compressed_files=cf, uncompressed_files=uf, chunks=total_chunks,
         total_dirs=total_dirs, total_bytes_in=cb + ub, total_bytes_out=total_bytes_out, compressed_bytes=cb,
-        uncompressed_bytes=ub, compression_ratio=(cb / max(blob_bytes, 1) * 100.0) if ub > 0 else 0.0)
+        uncompressed_bytes=ub, compression_ratio=(cb / max(payload_bytes, 1) * 100.0) if ub > 0 else 0.0)

@@ -37,12 +37,13 @@ class _Sender:
 
 
 class StreamCompressor:  # stream_packer.rs:L58-76
-    def __init__(self, output: str, no_skip: bool, backend=None, config=None, window_log: int = 0):
+    def __init__(self, output: str, no_skip: bool, backend=None, config=None, window_log: int = 0, blob_align: int = 1):
         self._output = output
         self._no_skip = no_skip
         self._backend = backend
         self._config = config or ix.CONFIG
         self._window_log = window_log
+        self._blob_align = blob_align
         self._entries: List[ArchiveEntry] = []
         self._finished = False
 
@@ -54,12 +55,15 @@ class StreamCompressor:  # stream_packer.rs:L58-76
             raise RuntimeError("already finished")
         self._finished = True
         return run_pipeline(self._entries, self._output, self._no_skip, self._backend, self._config,
-                            window_log=self._window_log)
+                            window_log=self._window_log, blob_align=self._blob_align)
 
 
-def compress_stream(output: str, no_skip: bool = False, backend=None, config=None, window_log: int = 0) -> StreamCompressor:
-    """window_log: 0 (default) or 17..27, the encoder's opt-in cross-block match window (znippy_ctx_set_window_log)."""
-    return StreamCompressor(str(output), no_skip, backend, config, window_log)
+def compress_stream(output: str, no_skip: bool = False, backend=None, config=None, window_log: int = 0,
+                    blob_align: int = 1) -> StreamCompressor:
+    """window_log: 0 (default) or 17..27, the encoder's opt-in cross-block match window (znippy_ctx_set_window_log).
+    blob_align: 1 (default, payloads back to back) or a power of two up to 4096: every blob_offset of the archive is a
+    multiple of it and the gaps are zero (znippy_rounds_set_blob_align); the file is longer by the gaps."""
+    return StreamCompressor(str(output), no_skip, backend, config, window_log, blob_align)
 
 
 def with_extension(path: str, ext: str) -> str:
@@ -94,9 +98,11 @@ def plan_rounds(entries: List[ArchiveEntry], no_skip: bool):
     return rounds, (uf, ub, cf, cb)
 
 
-def encode_round_range(rounds, entries, backend, lo, hi):
+def encode_round_range(rounds, entries, backend, lo, hi, blob_align: int = 1):
     """The barrels' work for rounds [lo, hi): staging batches through the backend.  Returns the per-round columns
-    (blob_offset relative to this range's payload region) and the region's bytes."""
+    (blob_offset relative to this range's payload region) and the region's bytes.  blob_align: what the backend was
+    told (apply_blob_align) — every batch's payloads start at a multiple of it, the gap in front zero-filled."""
+    from .backend import round_up
     n = hi - lo
     cols = dict(blob_offset=np.zeros(n, np.uint64), blob_size=np.zeros(n, np.uint64),
                 checksum=np.zeros((n, 32), np.uint8), compressed=np.zeros(n, np.uint8))
@@ -117,6 +123,9 @@ def encode_round_range(rounds, entries, backend, lo, hi):
             off[k], ln[k], sk[k] = pos, l, 1 if skip else 0
             pos += l
         res, blob = backend.encode_hash(staging, off, ln, sk)
+        if round_up(cursor, blob_align) != cursor:
+            parts.append(bytes(round_up(cursor, blob_align) - cursor))
+            cursor += len(parts[-1])
         cols["blob_offset"][i - lo:j - lo] = np.asarray(res["blob_offset"], np.uint64) + np.uint64(cursor)
         cols["blob_size"][i - lo:j - lo] = res["blob_size"]
         cols["checksum"][i - lo:j - lo] = res["checksum"]
@@ -127,17 +136,36 @@ def encode_round_range(rounds, entries, backend, lo, hi):
     return cols, b"".join(parts)
 
 
-def run_pipeline(entries, output, no_skip, backend=None, config=None, window_log: int = 0) -> ix.CompressionReport:
+def merge_rank_regions(gathered, blob_align: int = 1):
+    """Rank 0's merge of the ranks' (columns, region) pairs, in rank order: every region's offsets are rebased by where
+    the region lands — the running sum of the regions before it, rounded up to blob_align with the gap zero-filled.
+    Returns the concatenated columns and the whole payload region."""
+    from .backend import round_up
+    base, col_parts, regions = 0, [], []
+    for cols, region in gathered:
+        if round_up(base, blob_align) != base:
+            regions.append(bytes(round_up(base, blob_align) - base))
+            base += len(regions[-1])
+        cols = dict(cols)
+        cols["blob_offset"] = cols["blob_offset"] + np.uint64(base)
+        base += len(region)
+        col_parts.append(cols)
+        regions.append(region)
+    return {k: np.concatenate([c[k] for c in col_parts]) for k in col_parts[0]}, b"".join(regions)
+
+
+def run_pipeline(entries, output, no_skip, backend=None, config=None, window_log: int = 0, blob_align: int = 1) -> ix.CompressionReport:
     """Single process: all rounds.  Inside an initialised torch.distributed group every rank encodes a contiguous
     range of the rounds balanced by bytes (its GPU's share), rank 0 concatenates the payload regions in rank order —
     blob offsets are a running sum, so rebasing a region is one addition — and writes the archive; the
     report is the same on every rank.  Every rank is handed the same entries."""
-    from .backend import apply_window_log, default_backend
+    from .backend import apply_blob_align, apply_window_log, default_backend
     from .sharding import split_rows
     backend = backend or default_backend()
     config = config or ix.CONFIG
     backend.set_level(config.compression_level)  # CompressCtx::new(CONFIG.compression_level), stream_packer.rs:L217 / slot_packer.rs:L551
     apply_window_log(backend, window_log)
+    blob_align = apply_blob_align(backend, blob_align)
     output_path = with_extension(output, "znippy")  # L132
     rounds, (uf, ub, cf, cb) = plan_rounds(entries, no_skip)
     rank, world = 0, 1
@@ -149,23 +177,16 @@ def run_pipeline(entries, output, no_skip, backend=None, config=None, window_log
         dist = None
     if world > 1:
         lo, hi = split_rows([r[2] for r in rounds], world)[rank]
-        mine = encode_round_range(rounds, entries, backend, lo, hi)
+        mine = encode_round_range(rounds, entries, backend, lo, hi, blob_align)
         gathered = [None] * world
         dist.all_gather_object(gathered, mine)
         report = [None]
         if rank == 0:
-            base, col_parts, regions = 0, [], []
-            for cols, region in gathered:
-                cols = dict(cols)
-                cols["blob_offset"] = cols["blob_offset"] + np.uint64(base)
-                base += len(region)
-                col_parts.append(cols)
-                regions.append(region)
-            cols = {k: np.concatenate([c[k] for c in col_parts]) for k in col_parts[0]}
-            report[0] = _write_archive(output_path, entries, rounds, cols, b"".join(regions), (uf, ub, cf, cb), config)
+            cols, region = merge_rank_regions(gathered, blob_align)
+            report[0] = _write_archive(output_path, entries, rounds, cols, region, (uf, ub, cf, cb), config)
         dist.broadcast_object_list(report, src=0)
         return report[0]
-    cols, region = encode_round_range(rounds, entries, backend, 0, len(rounds))
+    cols, region = encode_round_range(rounds, entries, backend, 0, len(rounds), blob_align)
     return _write_archive(output_path, entries, rounds, cols, region, (uf, ub, cf, cb), config)
 
 
