@@ -216,6 +216,46 @@ int znippy_rows_results_lagged(znippy_ctx *ctx, znippy_rows *rows, unsigned lag,
 /* Computed digests of the last run (HOST, 32 bytes per row of the table). */
 int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *rows, uint8_t *digests);
 
+/* Byte ranges of rows: what an artifact server answering a range request, or a reader that wants the ZIP central directory of an
+ * archived file first and one entry afterwards (TODO_NOW.md:L200-213), asks for — without paying for the whole chunk (a row is up to
+ * 10 MiB, common_config.rs:L39).  All range arrays are HOST arrays of n_ranges entries:
+ *   range_row    absolute row number of the table
+ *   range_begin, range_len   bytes of the row's decoded content (its length is uncompressed_size, blob_size for a stored row)
+ *   range_out    where the range lands in d_out; NULL = the ranges are packed back to back in array order (range i at the sum of the
+ *                lengths in front of it, whatever their status)
+ *   range_status HOST, optional: 0 or ZNIPPY_E_* per range
+ *   decoded_bytes HOST, optional: the content bytes the decoders produced in this call — the content size of every block decoded on
+ *                its own, plus uncompressed_size of every row decoded whole; nothing for stored rows.  The call's measure of work.
+ * Bytes: for every range with status 0 the bytes at its destination are bytes [begin, begin + len) of what a whole-row decode of that
+ * row writes, whenever that decode succeeds.  Writes: no byte of d_out outside the destinations of status-0 ranges is written;
+ * destinations must not overlap (not checked); len == 0 with begin <= the row's length is status 0 and writes nothing.
+ * Partial decode: a compressed row of >= 2 blocks (and below 4 GiB) whose frame passes the block scan — this library's frames with the
+ * window off: self-contained 128 KiB blocks — has only the blocks decoded that overlap at least one requested range of the row, each
+ * once per call however many ranges touch it and in whatever order, provided each decodes from a clean state.  Such a range reports 0
+ * even if a block it never looked at is damaged: the call vouches for what it decoded and for nothing else, as extract_file does
+ * without a checksum.  Fallback: anything else — a one-block row, another writer's frame, a window frame, a row of 4 GiB or more, a
+ * frame the scan does not accept, a needed block that turns out to need history — is decoded whole into scratch and the range copied
+ * out; a row whose whole decode fails gives every range on it the ZNIPPY_E_* that znippy_decode_rows reports for that row.  A range of
+ * a stored row is a copy out of the blob region.
+ * Host validation, per range, before any kernel runs: row outside the table, or begin + len overflowing or past the row's length:
+ * ZNIPPY_E_INVAL; destination not inside out_cap: ZNIPPY_E_DST_SMALL; the row's blob outside the declared blob region
+ * (znippy_rows_set_blob_cap): ZNIPPY_E_CORRUPT.  No kernel touches such a range and the call still returns ZNIPPY_OK, as a run does
+ * with bad rows.  ZNIPPY_E_INVAL is returned only for NULL arguments, a closed context or a table of another context; n_ranges == 0
+ * is ZNIPPY_OK.
+ * Not a run: the call is synchronous, ordered on the context's stream behind whatever is queued, takes no slot of the two-run ring and
+ * neither reads nor updates what the table remembers of its last run; status column, corrupt list, digests and foreign stats stay as
+ * they are.  It works on tables created without out_offset or without checksum, and may be called between an async run and the read
+ * of its results without changing what either reports (znippy_last_kernel_times then describes this call: range_scan,
+ * range_decode_blocks, range_decode_rows, range_decode_rows_late — the rows a block pass gave up on —, range_copy).
+ * Scratch: decoded blocks and fallback rows land in a region the CONTEXT owns — grow-only, kept until the context goes, capped at
+ * 16 GiB like the verify scratch.  A call that needs more returns ZNIPPY_E_NOMEM: the blocks and the rows known up front to need a
+ * whole decode are sized before anything is queued; rows the block pass gives up on are sized after it, with the stream idle, and
+ * a refusal there still comes before the first byte of d_out is written.  Every offset is a 64-bit value. */
+int znippy_rows_read_ranges(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base,
+                            const uint64_t *range_row, const uint64_t *range_begin, const uint64_t *range_len,
+                            const uint64_t *range_out, uint64_t n_ranges,
+                            void *d_out, uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes);
+
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,
  * stream_packer.rs:L98-106).  HOST arrays, n entries.  src_offset is a full 64-bit value and rounds may share or overlap

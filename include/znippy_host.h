@@ -96,6 +96,13 @@ int znippy_archive_extract_file(znippy_archive *a, const char *relative_path, vo
  * no verification, archive.rs:L144-168; SURVEY §8f rank 1 asks for it): ZNIPPY_E_CHECKSUM on a mismatch. */
 int znippy_archive_extract_file_verified(znippy_archive *a, const char *relative_path, void *dst, size_t cap,
                                          size_t *written);
+/* pread on an archived file: bytes [offset, offset + len) of it land in dst, clamped at the end of the file — *written is
+ * what was copied, 0 for an offset at or past the end.  The range is mapped to the chunks it touches by fdata_offset; only
+ * their blobs are read from the archive, and of a chunk this library wrote only the 128 KiB blocks the range overlaps are
+ * decoded (znippy_rows_read_ranges on the archive's context).  No checksum is looked at, as for extract_file; a chunk
+ * that fails to decode gives its ZNIPPY_E_*, an unknown path ZNIPPY_E_INVAL. */
+int znippy_archive_read_range(znippy_archive *a, const char *relative_path, uint64_t offset, void *dst, size_t len,
+                              size_t *written);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

@@ -48,6 +48,7 @@ EXPORTS = [
     "znippy_verify_rows", "znippy_verify_rows_async", "znippy_rows_verify_scratch",
     "znippy_decode_rows", "znippy_decode_rows_async",
     "znippy_rounds_set_blob_align", "znippy_rounds_blob_align",
+    "znippy_rows_read_ranges",
 ]
 
 
@@ -126,6 +127,9 @@ def lib():
         L.znippy_rounds_set_blob_align.argtypes = [vp, C.c_uint32]
         L.znippy_rounds_blob_align.argtypes = [vp]
         L.znippy_rounds_blob_align.restype = C.c_uint32
+    if hasattr(L, "znippy_rows_read_ranges"):  # (likewise)
+        L.znippy_rows_read_ranges.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                              C.POINTER(C.c_uint64)]
     _lib = L
     return L
 

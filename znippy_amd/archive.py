@@ -92,3 +92,71 @@ class ZnippyArchive:
             end = int(out_off[b - 1] + usz[b - 1])
             results.append(out[start:end].tobytes())
         return results
+
+    def read_range(self, relative_path, offset, length) -> bytes:
+        """pread on an archived file: bytes [offset, offset + length) of it, clamped at its end (an offset at or past the
+        end gives b"").  Only the chunks the range touches are read from disk, and of a chunk this library wrote only the
+        128 KiB blocks it overlaps are decoded.  No checksum is looked at, as for extract_file."""
+        out = self.read_ranges([(relative_path, offset, length)])[0]
+        if isinstance(out, Exception):
+            raise out
+        return out
+
+    def read_ranges(self, requests):
+        """Batch of (relative_path, offset, length): every request's chunk pieces go to the backend as one call.  An
+        unknown path gives a KeyError in its place, a chunk that fails to decode a ValueError."""
+        from .backend import default_backend
+        c = self._c
+        chunk_rows, chunk_at = [], {}  # archive rows the requests touch, in first-touch order; archive row -> its place there
+        rr, rb, rl, spans = [], [], [], []
+        for p, offset, length in requests:
+            rows = self.file_index.get(p)
+            if rows is None:
+                spans.append(None)
+                continue
+            offset, length = int(offset), int(length)
+            if offset < 0 or length < 0:
+                raise ValueError(f"negative offset or length for {p}")
+            first = len(rr)
+            for row in rows:  # (sorted by fdata_offset)
+                lo, n = int(c["fdata_offset"][row]), int(self._rlen[row])
+                a, b = max(offset, lo), min(offset + length, lo + n)
+                if a >= b:
+                    continue
+                if row not in chunk_at:
+                    chunk_at[row] = len(chunk_rows)
+                    chunk_rows.append(row)
+                rr.append(chunk_at[row]); rb.append(a - lo); rl.append(b - a)
+            spans.append((first, len(rr)))
+        status = np.zeros(0, np.int32)
+        pieces = []
+        if rr:
+            rows_np = np.asarray(chunk_rows)
+            bs, usz, comp = c["blob_size"][rows_np], self._rlen[rows_np], c["compressed"][rows_np]
+            with open(self.path, "rb") as f:
+                blobs, bo = read_spans(f, os.path.getsize(self.path), c["blob_offset"][rows_np], bs)
+            rr, rb, rl = np.asarray(rr, np.uint64), np.asarray(rb, np.uint64), np.asarray(rl, np.uint64)
+            backend = self._backend or default_backend()
+            if hasattr(backend, "read_ranges"):
+                status, out, _ = backend.read_ranges(blobs, 0, bo, bs, usz, comp, rr, rb, rl)
+                at = np.concatenate([[0], np.cumsum(rl)]).astype(np.uint64)
+                pieces = [out[int(at[i]):int(at[i + 1])] for i in range(len(rr))]
+            else:  # a backend without range reads: the touched chunks decoded whole, then sliced
+                out_off = np.concatenate([[0], np.cumsum(usz)[:-1]]).astype(np.uint64)
+                if hasattr(backend, "decode"):
+                    _, _, st, out = backend.decode(blobs, 0, bo, bs, usz, out_off, comp, int(usz.sum()))
+                else:
+                    _, _, st, out = backend.decode_verify(blobs, 0, bo, bs, usz, out_off, comp, None, int(usz.sum()))
+                status = np.asarray(st)[rr.astype(np.int64)]
+                pieces = [out[int(out_off[int(k)] + b):int(out_off[int(k)] + b + n)] for k, b, n in zip(rr, rb, rl)]
+        results = []
+        for (p, _, _), sp in zip(requests, spans):
+            if sp is None:
+                results.append(KeyError(f"file not found in archive: {p}"))
+                continue
+            a, b = sp
+            if b > a and (status[a:b] < 0).any():
+                results.append(ValueError(f"range read failed for {p}: status {int(status[a:b].min())}"))
+                continue
+            results.append(b"".join(x.tobytes() for x in pieces[a:b]))
+        return results

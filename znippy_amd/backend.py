@@ -82,6 +82,23 @@ class HipBackend:
         rt.close()
         return counters, np.zeros(0, np.uint64), status, out
 
+    # read side, byte ranges of rows (znippy_rows_read_ranges): range i is bytes [range_begin[i], + range_len[i]) of row range_row[i] of the
+    # given columns.  -> (status per range, the ranges' bytes packed back to back in array order, content bytes the decoders produced)
+    def read_ranges(self, blobs, blob_base, blob_offset, blob_size, usize, compressed, range_row, range_begin, range_len):
+        n = len(range_row)
+        if n == 0:
+            return np.zeros(0, np.int32), np.zeros(0, np.uint8), 0
+        total = sum(int(x) for x in range_len)  # (a table without rows included: the call rules on every range)
+        d_blobs = self._to_dev(np.concatenate([blobs, np.zeros(64, np.uint8)]))
+        d_out = self.torch.empty(total + 64, dtype=self.torch.uint8, device=f"cuda:{self.device}")
+        bitmap = np.packbits(np.asarray(compressed, dtype=bool), bitorder="little")
+        rt = self.hip.RowTable(self.ctx, blob_offset, blob_size, usize, None, bitmap, None)
+        status, decoded = rt.read_ranges(d_blobs, range_row, range_begin, range_len, d_out, blob_base=blob_base, out_cap=total,
+                                         blob_cap=len(blobs))
+        out = d_out[:total].cpu().numpy()
+        rt.close()
+        return status, out, decoded
+
     # read side, verify only (decompress.rs save_data=false): counters, corrupt rows and status, no bytes — nothing is
     # allocated for an output and nothing comes back over the bus
     def verify(self, blobs, blob_base, blob_offset, blob_size, usize, compressed, checksum):

@@ -12,6 +12,8 @@
 #include <cstring>
 #include <chrono>
 #include <memory>
+#include <new>
+#include <stdexcept>
 #include <string>
 #include <vector>
 #include <unordered_map>
@@ -105,6 +107,10 @@ struct znippy_ctx {
     // output (grow-only, ensure_verify_scratch); shared by every table and run of the context — runs are ordered on its stream
     uint8_t *vs_pool = nullptr;
     uint64_t vs_cap = 0;
+    // range reads (znippy_rows_read_ranges): where the blocks and rows a call decodes land before their ranges are gathered (grow-only,
+    // ensure_range_scratch).  [0] the blocks and the rows known up front to need a whole decode, [1] the rows a block pass gave up on
+    uint8_t *rr_pool[2] = {nullptr, nullptr};
+    uint64_t rr_cap[2] = {0, 0};
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_join2 = nullptr;
     // kernel timing
     std::vector<KTime> ktimes;
@@ -455,6 +461,7 @@ struct znippy_rows {
     uint64_t ext_min_bo = 0, ext_max_bend = 0, ext_max_oend = 0;
     bool ext_wrap = false;
     std::vector<uint64_t> h_blob_off, h_blob_size, h_len, h_out_off;
+    std::vector<uint8_t> h_comp;  // range reads: the byte-per-row flags beside the three columns above (rows_host_columns)
     uint64_t blob_cap = ~0ull;  // size of the caller's blob region (znippy_rows_set_blob_cap); ~0 = not declared
     uint64_t val_base = 0, val_bcap = 0, val_ocap = 0;
     bool val_done = false, val_verify = false;
@@ -716,6 +723,20 @@ static int ensure_verify_scratch(znippy_ctx *ctx, uint64_t bytes) {
     ctx->vs_pool = nullptr; ctx->vs_cap = 0;
     if (hipMalloc(&ctx->vs_pool, bytes) != hipSuccess) { (void)hipGetLastError(); ctx->vs_pool = nullptr; return ZNIPPY_E_NOMEM; }
     ctx->vs_cap = bytes;
+    return ZNIPPY_OK;
+}
+// Scratch of the range reads, capped the same way (both regions together): a call that needs more is refused.
+static int ensure_range_scratch(znippy_ctx *ctx, int which, uint64_t bytes) {
+    constexpr uint64_t CAP = 16ull << 30;
+    if (!bytes) return ZNIPPY_OK;
+    if (bytes > CAP || bytes + ctx->rr_cap[which ^ 1] > CAP + 8192) return ZNIPPY_E_NOMEM;
+    bytes += 4096;
+    if (bytes <= ctx->rr_cap[which]) return ZNIPPY_OK;
+    (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->rr_pool[which]) (void)hipFree(ctx->rr_pool[which]);
+    ctx->rr_pool[which] = nullptr; ctx->rr_cap[which] = 0;
+    if (hipMalloc(&ctx->rr_pool[which], bytes) != hipSuccess) { (void)hipGetLastError(); ctx->rr_pool[which] = nullptr; return ZNIPPY_E_NOMEM; }
+    ctx->rr_cap[which] = bytes;
     return ZNIPPY_OK;
 }
 static int ensure_encoder(znippy_ctx *ctx) {
@@ -993,7 +1014,7 @@ static void ctx_teardown(znippy_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
     for (auto &k : ctx->ktimes) { (void)hipEventDestroy(k.t0); (void)hipEventDestroy(k.t1); }
-    void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor, ctx->vs_pool,
+    void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor, ctx->vs_pool, ctx->rr_pool[0], ctx->rr_pool[1],
                    ctx->clk_buf, ctx->shim_in, ctx->shim_out, ctx->enc_prov, ctx->enc_seq, ctx->enc_tabs, ctx->ldm};
     for (void *p : dev) if (p) (void)hipFree(p);
     for (unsigned long long *d : ctx->diag) if (d) (void)hipFree(d);
@@ -2153,6 +2174,298 @@ int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, 
     int rc = znippy_verify_rows_async(ctx, rows, d_blobs, blob_base);
     if (rc) return rc;
     return znippy_rows_results(ctx, rows, counters, corrupt_rows, corrupt_cap, row_status);
+}
+
+// ---- range reads (znippy_rows_read_ranges) --------------------------------------------------------
+// The columns a call validates and plans against, on the host: fetched once per table from the device copies, which hold the
+// effective lengths (a stored row's length is its blob).  The same three vectors rows_validate fills for its per-row pass.
+static int rows_host_columns(znippy_ctx *ctx, znippy_rows *r) {
+    if (!r->n || (!r->h_blob_off.empty() && !r->h_comp.empty())) return ZNIPPY_OK;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    // (into temporaries: a copy that fails leaves the table without a half-filled cache)
+    std::vector<uint64_t> bo(r->n), bs(r->n), len(r->n);
+    std::vector<uint8_t> comp(r->n);
+    HIPCHK(ctx, hipMemcpy(bo.data(), r->blob_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(bs.data(), r->blob_size, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(len.data(), r->usize, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(comp.data(), r->compressed, r->n, hipMemcpyDeviceToHost));
+    if (r->h_blob_off.empty()) { r->h_blob_off.swap(bo); r->h_blob_size.swap(bs); r->h_len.swap(len); }
+    r->h_comp.swap(comp);
+    return ZNIPPY_OK;
+}
+
+namespace {
+constexpr uint64_t RR_BLK = 128 * 1024;
+constexpr uint64_t RR_GUARD = 8192;  // in front of a slot: the block decoder reads up to WIN_HIST bytes of history back from in front of a block
+struct RrRow {                       // a distinct row the ranges of a call touch
+    uint32_t row = 0;                // index in the table
+    bool comp = false, partial = false, late = false;
+    int32_t status = 0;              // 0, or the ZNIPPY_E_* of its whole decode
+    int pool = 0;                    // which scratch region its bytes are in
+    uint64_t slot = 0, first = 0;    // byte b of the row is at pool + slot + (b - first)
+    uint32_t kmin = 0xFFFFFFFFu, kmax = 0;
+    std::vector<uint8_t> need;       // partial: per block, a range overlaps it
+};
+uint8_t *rr_carve_bytes(uint8_t *base, size_t &at, size_t bytes) {  // the next 16-byte aligned piece of a slab
+    at = (at + 15) & ~(size_t)15;
+    uint8_t *p = base + at;
+    at += bytes;
+    return p;
+}
+#define rr_carve(T, base, at, n) reinterpret_cast<T *>(rr_carve_bytes(base, at, sizeof(T) * (size_t)(n)))
+}  // namespace
+
+// Whole rows into the range scratch: a private table over the compact columns of `sel`, one decode-only run of it, the rows' verdicts.
+// The run's kernels are bracketed as one entry of the kernel times (range_decode_rows).
+static int rr_decode_whole(znippy_ctx *ctx, const znippy_rows *r, std::vector<RrRow> &rows, const std::vector<uint32_t> &sel, const void *d_blobs, uint64_t blob_base, int pool) {
+    // (two names: a call may run both passes, and consumers key the kernel times by name)
+    const size_t m = sel.size();
+    if (!m) return ZNIPPY_OK;
+    std::vector<uint64_t> bo(m), bs(m), us(m), oo(m);
+    std::vector<int32_t> st(m, 0);
+    for (size_t i = 0; i < m; i++) {
+        const RrRow &w = rows[sel[i]];
+        bo[i] = r->h_blob_off[w.row]; bs[i] = r->h_blob_size[w.row]; us[i] = r->h_len[w.row]; oo[i] = w.slot;
+    }
+    znippy_rows *t = nullptr;
+    int rc = znippy_rows_create(ctx, bo.data(), bs.data(), nullptr, us.data(), oo.data(), nullptr, 0, m, &t);
+    if (rc) return rc;
+    const int keep = ctx->n_ktimes, level = ctx->sw.ktime;
+    ktime_begin(ctx, pool ? "range_decode_rows_late" : "range_decode_rows");
+    const bool open = ctx->ktime_open;
+    ctx->sw.ktime = 0;  // (the run's own brackets would start the list anew)
+    rc = rows_queue(ctx, t, d_blobs, blob_base, ctx->rr_pool[pool], ctx->rr_cap[pool], false, true);
+    ctx->sw.ktime = level; ctx->n_ktimes = keep; ctx->ktime_open = open;
+    ktime_end(ctx);
+    if (!rc) rc = znippy_rows_results(ctx, t, nullptr, nullptr, 0, st.data());
+    znippy_rows_destroy(t);
+    if (rc) return rc;
+    for (size_t i = 0; i < m; i++) rows[sel[i]].status = st[i];
+    return ZNIPPY_OK;
+}
+
+static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
+                            const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
+                            uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (decoded_bytes) *decoded_bytes = 0;
+    if (!n_ranges) return ZNIPPY_OK;
+    if (!range_row || !range_begin || !range_len || !d_blobs || !d_out) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rows_host_columns(ctx, r);
+    if (rc) return rc;
+    hipStream_t s = ctx->stream;
+    ctx->n_ktimes = 0;
+
+    // 1) every range against the table, the output region and the blob region; the distinct rows the good ones touch
+    std::vector<int32_t> st(n_ranges, 0);
+    std::vector<uint64_t> dst(n_ranges, 0);
+    std::vector<uint32_t> of_row(n_ranges, 0xFFFFFFFFu);  // range -> entry of `rows` (none: nothing to move)
+    std::vector<RrRow> rows;
+    std::unordered_map<uint32_t, uint32_t> row_at;
+    const uint64_t bcap = r->blob_cap;
+    uint64_t packed = 0;
+    bool packed_wrap = false;
+    for (uint64_t i = 0; i < n_ranges; i++) {
+        const uint64_t len = range_len[i], begin = range_begin[i];
+        const bool dst_known = range_out || !packed_wrap;
+        dst[i] = range_out ? range_out[i] : packed;
+        if (!range_out) { packed_wrap |= packed + len < packed; packed += len; }
+        if (range_row[i] < r->row_begin || range_row[i] - r->row_begin >= r->n) { st[i] = ZNIPPY_E_INVAL; continue; }
+        const uint32_t ri = (uint32_t)(range_row[i] - r->row_begin);
+        const uint64_t row_len = r->h_len[ri], bo = r->h_blob_off[ri], bs = r->h_blob_size[ri];
+        if (begin > row_len || len > row_len - begin) { st[i] = ZNIPPY_E_INVAL; continue; }
+        if (!dst_known || len > out_cap || dst[i] > out_cap - len) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (bo < blob_base || (bcap != ~0ull && (bs > bcap || bo - blob_base > bcap - bs))) { st[i] = ZNIPPY_E_CORRUPT; continue; }
+        if (!len) continue;
+        auto it = row_at.find(ri);
+        if (it == row_at.end()) {
+            it = row_at.emplace(ri, (uint32_t)rows.size()).first;
+            RrRow w;
+            w.row = ri;
+            w.comp = r->h_comp[ri] != 0;
+            w.partial = w.comp && row_len > RR_BLK && row_len < 0xFFFFFFFFull;  // >= 2 blocks, below 4 GiB: tried block by block
+            if (w.partial) w.need.assign((size_t)((row_len + RR_BLK - 1) / RR_BLK), 0);
+            rows.push_back(std::move(w));
+        }
+        of_row[i] = it->second;
+        RrRow &w = rows[it->second];
+        if (w.partial) {
+            const uint32_t k0 = (uint32_t)(begin / RR_BLK), k1 = (uint32_t)((begin + len - 1) / RR_BLK);
+            for (uint32_t k = k0; k <= k1; k++) w.need[k] = 1;
+            w.kmin = std::min(w.kmin, k0); w.kmax = std::max(w.kmax, k1);
+        }
+    }
+
+    // 2) the plan: slots in the scratch, the private columns and lists of the block pass, the rows decoded whole from the start
+    std::vector<uint32_t> part, whole;
+    uint64_t n_items = 0, n_todo = 0, need0 = 0;
+    for (uint32_t i = 0; i < rows.size(); i++) {
+        RrRow &w = rows[i];
+        if (!w.comp) continue;
+        if (w.partial && n_items + w.need.size() >= 0x7FFFFFF0ull) w.partial = false;
+        const uint64_t row_len = r->h_len[w.row];
+        need0 = (need0 + 255) & ~255ull;
+        if (w.partial) {
+            part.push_back(i);
+            n_items += w.need.size();
+            for (uint32_t k = w.kmin; k <= w.kmax; k++) n_todo += w.need[k];
+            w.first = (uint64_t)w.kmin * RR_BLK;
+            w.slot = need0 + RR_GUARD;
+            need0 = w.slot + (std::min<uint64_t>(row_len, ((uint64_t)w.kmax + 1) * RR_BLK) - w.first) + 256;
+        } else {
+            whole.push_back(i);
+            w.slot = need0;
+            need0 += row_len + 256;
+        }
+        if (need0 > (32ull << 30)) return ZNIPPY_E_NOMEM;
+    }
+    if ((rc = ensure_range_scratch(ctx, 0, need0))) return rc;
+    const uint32_t m = (uint32_t)part.size();
+    uint8_t *slab = nullptr, *h_slab = nullptr;
+    size_t slab_bytes = 0, h_slab_cap = 0, up_bytes = 0;
+    struct Slab { uint64_t *blob_off, *blob_size, *usize, *out_off, *block_bytes; uint32_t *cand_row, *cand_base, *cand_nb, *item_row, *item_k, *todo, *ctl; int32_t *status; uint8_t *comp; uint32_t *row_flag, *item_src; unsigned long long *decoded; uint8_t *late; } h{}, d{};
+    auto carve = [&](uint8_t *base, Slab &o) {
+        size_t at = 0;
+        o.blob_off = rr_carve(uint64_t, base, at, m); o.blob_size = rr_carve(uint64_t, base, at, m); o.usize = rr_carve(uint64_t, base, at, m);
+        o.out_off = rr_carve(uint64_t, base, at, m); o.block_bytes = rr_carve(uint64_t, base, at, m);
+        o.cand_row = rr_carve(uint32_t, base, at, m); o.cand_base = rr_carve(uint32_t, base, at, m); o.cand_nb = rr_carve(uint32_t, base, at, m);
+        o.item_row = rr_carve(uint32_t, base, at, n_items); o.item_k = rr_carve(uint32_t, base, at, n_items); o.todo = rr_carve(uint32_t, base, at, n_todo);
+        o.ctl = rr_carve(uint32_t, base, at, 4); o.status = rr_carve(int32_t, base, at, m); o.comp = rr_carve(uint8_t, base, at, m);
+        o.decoded = rr_carve(unsigned long long, base, at, 1);
+        up_bytes = at;  // everything up to here is uploaded; what follows is written on the device first
+        o.row_flag = rr_carve(uint32_t, base, at, m); o.item_src = rr_carve(uint32_t, base, at, n_items); o.late = rr_carve(uint8_t, base, at, m);
+        return at;
+    };
+    struct Guard {  // every return below gives the call's buffers back
+        znippy_ctx *ctx; uint8_t *&slab, *&h_slab; size_t &cap; RangePiece *pieces = nullptr;
+        ~Guard() { tfree(ctx, slab); tfree(ctx, pieces); if (h_slab) { (void)hipStreamSynchronize(ctx->stream); pinned_give(ctx, h_slab, cap); } }
+    } guard{ctx, slab, h_slab, h_slab_cap};
+    if (m) {
+        slab_bytes = carve(nullptr, h);
+        if (!(h_slab = (uint8_t *)pinned_take(ctx, slab_bytes + 64, &h_slab_cap)) || tmalloc(ctx, &slab, slab_bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
+        if (!ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) { (void)hipGetLastError(); ctx->lit_scratch_b = nullptr; return ZNIPPY_E_NOMEM; }
+        carve(h_slab, h);
+        carve(slab, d);
+        memset(h_slab, 0, up_bytes);
+        uint32_t item = 0, todo = 0;
+        for (uint32_t c = 0; c < m; c++) {
+            const RrRow &w = rows[part[c]];
+            const uint64_t row_len = r->h_len[w.row];
+            h.blob_off[c] = r->h_blob_off[w.row]; h.blob_size[c] = r->h_blob_size[w.row]; h.usize[c] = row_len;
+            // the block decoder puts block k at out + out_off + k * 128 KiB: the column is biased (modulo 2^64, as the kernels add) so that
+            // the row's first needed block lands at the head of its slot
+            h.out_off[c] = w.slot - w.first;
+            h.cand_row[c] = c; h.cand_base[c] = item; h.cand_nb[c] = (uint32_t)w.need.size();
+            h.comp[c] = 1;
+            for (uint32_t k = 0; k < w.need.size(); k++) {
+                h.item_row[item + k] = c; h.item_k[item + k] = k;
+                if (!w.need[k]) continue;
+                h.todo[todo++] = item + k;
+                h.block_bytes[c] += std::min<uint64_t>(RR_BLK, row_len - (uint64_t)k * RR_BLK);
+            }
+            item += (uint32_t)w.need.size();
+        }
+        h.ctl[0] = todo;  // [0] length of the to-do list, [1] the decoder's work cursor, [2] a hand-over count that stays zero
+    }
+
+    // 3) the block pass: header scan of the candidate frames, the needed blocks, the rows' verdicts
+    unsigned long long dec_blocks = 0;
+    if (m) {
+        HIPCHK(ctx, hipMemcpyAsync(slab, h_slab, up_bytes, hipMemcpyHostToDevice, s));
+        BlockScanArgs b{};
+        b.cand_row = d.cand_row; b.cand_base = d.cand_base; b.cand_nblocks = d.cand_nb; b.n_cand = m;
+        b.blobs = (const uint8_t *)d_blobs; b.blob_base = blob_base;
+        b.blob_off = d.blob_off; b.blob_size = d.blob_size; b.usize = d.usize; b.out_off = d.out_off;
+        b.out_cap = ~0ull;  // (the slots fit the scratch by construction)
+        b.item_src = d.item_src; b.row_flag = d.row_flag; b.status = d.status;
+        timed(ctx, "range_scan", s, [&] { launch_scan_blocks(b, s); });
+        DecodeArgs a{};
+        a.blobs = b.blobs; a.blob_base = blob_base;
+        a.blob_off = d.blob_off; a.blob_size = d.blob_size; a.usize = d.usize; a.out_off = d.out_off;
+        a.out = ctx->rr_pool[0]; a.out_cap = ~0ull; a.status = d.status;
+        a.block_mode = 1;
+        a.item_row = d.item_row; a.item_k = d.item_k; a.item_src = d.item_src; a.n_items = (uint32_t)n_items; a.row_flag = d.row_flag;
+        a.todo = d.todo; a.n_todo = d.ctl;
+        a.pending_count = d.ctl + 2;
+        a.compressed = d.comp;
+        a.n_rows = m; a.cursor = d.ctl + 1;
+        a.lit_scratch = ctx->lit_scratch_b;
+        timed(ctx, "range_decode_blocks", s, [&] { launch_decode(a, (int)std::min<uint64_t>((uint64_t)ctx->decode_grid, n_todo), false, s); });
+        launch_range_status(d.row_flag, d.block_bytes, m, d.late, d.decoded, s);
+        HIPCHK(ctx, hipMemcpyAsync(h.late, d.late, m, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h.decoded, d.decoded, 8, hipMemcpyDeviceToHost, s));
+    }
+    // ... behind it, the rows known from the start to need a whole decode (its results call waits for both)
+    if ((rc = rr_decode_whole(ctx, r, rows, whole, d_blobs, blob_base, 0))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipGetLastError());
+
+    // 4) what the block pass gave up on — a frame the scan does not vouch for, a block that needs history — is decoded whole
+    if (m) {
+        dec_blocks = *h.decoded;
+        std::vector<uint32_t> late;
+        uint64_t need1 = 0;
+        for (uint32_t c = 0; c < m; c++) {
+            if (!h.late[c]) continue;
+            RrRow &w = rows[part[c]];
+            w.late = true; w.pool = 1; w.first = 0;
+            need1 = (need1 + 255) & ~255ull;
+            w.slot = need1;
+            need1 += r->h_len[w.row] + 256;
+            if (need1 > (32ull << 30)) return ZNIPPY_E_NOMEM;
+            late.push_back(part[c]);
+        }
+        if ((rc = ensure_range_scratch(ctx, 1, need1))) return rc;  // (nothing is queued at this point, and d_out is untouched)
+        if ((rc = rr_decode_whole(ctx, r, rows, late, d_blobs, blob_base, 1))) return rc;
+    }
+
+    // 5) the gather: every good range from where its bytes are to its place in d_out
+    uint64_t dec = dec_blocks;
+    for (const RrRow &w : rows)
+        if (w.comp && (!w.partial || w.late) && w.status == 0) dec += r->h_len[w.row];
+    std::vector<RangePiece> pieces;
+    for (uint64_t i = 0; i < n_ranges; i++) {
+        if (of_row[i] == 0xFFFFFFFFu) continue;
+        const RrRow &w = rows[of_row[i]];
+        if (w.status) { st[i] = w.status; continue; }
+        const uint8_t *src = w.comp ? ctx->rr_pool[w.pool] + w.slot + (range_begin[i] - w.first)
+                                    : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base) + range_begin[i];
+        uint8_t *to = (uint8_t *)d_out + dst[i];
+        uint64_t left = range_len[i];
+        uint64_t step = std::min<uint64_t>(left, RANGE_PIECE - ((uintptr_t)to & 127));  // every later piece starts on a 128-byte line of the output
+        while (left) {
+            pieces.push_back(RangePiece{src, to, (uint32_t)step, 0});
+            src += step; to += step; left -= step;
+            step = std::min<uint64_t>(left, RANGE_PIECE);
+        }
+    }
+    if (!pieces.empty()) {
+        if (tmalloc(ctx, &guard.pieces, sizeof(RangePiece) * pieces.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, hipMemcpy(guard.pieces, pieces.data(), sizeof(RangePiece) * pieces.size(), hipMemcpyHostToDevice));
+        timed(ctx, "range_copy", s, [&] {
+            for (size_t at = 0; at < pieces.size(); at += (1u << 30)) launch_range_gather(guard.pieces + at, (uint32_t)std::min<size_t>(pieces.size() - at, 1u << 30), s);
+        });
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        HIPCHK(ctx, hipGetLastError());
+    }
+    if (range_status) memcpy(range_status, st.data(), 4 * (size_t)n_ranges);
+    if (decoded_bytes) *decoded_bytes = dec;
+    return ZNIPPY_OK;
+}
+
+// (the plan is host vectors sized by n_ranges: an allocation failure is an error code at the C boundary, not an exception through it)
+int znippy_rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
+                            const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
+                            uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes) {
+    try {
+        return rows_read_ranges(ctx, r, d_blobs, blob_base, range_row, range_begin, range_len, range_out, n_ranges, d_out, out_cap, range_status, decoded_bytes);
+    } catch (const std::bad_alloc &) {
+        return ZNIPPY_E_NOMEM;
+    } catch (const std::length_error &) {
+        return ZNIPPY_E_NOMEM;
+    }
 }
 
 int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {

@@ -277,4 +277,17 @@ enum BxStage : int { BX_SCAN = 0, BX_PREP = 1, BX_HUF = 2, BX_FSE = 3, BX_EXEC =
 void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s);  // stage: a BxStage
 void bx_predefined_tables(uint16_t cells[160]);  // host: the three predefined tables as pool cells
 
+// Range reads (range_gather.hip): one piece of a requested range — at most RANGE_PIECE bytes, moved by one workgroup from
+// wherever the bytes are (blob region, range scratch) to their place in the caller's output
+struct RangePiece {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint32_t len;
+    uint32_t pad;
+};
+constexpr uint32_t RANGE_PIECE = 32u << 10;
+void launch_range_gather(const RangePiece *pieces, uint32_t n_pieces, hipStream_t s);
+// per private row of the partial route: late[i] = the row goes to the whole-row pass; *decoded += block_bytes[i] of the others
+void launch_range_status(const uint32_t *row_flag, const uint64_t *block_bytes, uint32_t n_rows, uint8_t *late, unsigned long long *decoded, hipStream_t s);
+
 }  // namespace zn

@@ -1270,6 +1270,65 @@ static int znippy_archive_extract_file_impl(znippy_archive *a, const char *rel, 
     return ZNIPPY_OK;
 }
 
+// pread on an archived file (ZnippyArchive.read_range in archive.py): the range is mapped to the chunks it touches by fdata_offset, only
+// their blobs are read from the archive, and znippy_rows_read_ranges decodes no more of them than the range needs.
+static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, uint64_t offset, void *dst, size_t len, size_t *written) {
+    if (!a || !rel || !written || (len && !dst)) return fail(ZNIPPY_E_INVAL, "null argument");
+    *written = 0;
+    auto it = a->files.find(rel);
+    if (it == a->files.end()) return fail(ZNIPPY_E_INVAL, std::string("file not found in archive: ") + rel);
+    const auto &c = a->ix.rows.cols;
+    const uint64_t end = offset + len < offset ? UINT64_MAX : offset + len;
+    std::vector<uint64_t> bo, bs, us, rr, rb, rl;
+    std::vector<uint8_t> bitmap;
+    uint64_t sum = 0, total = 0;
+    for (uint64_t r : it->second) {  // (sorted by fdata_offset)
+        const uint64_t lo = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];  // a stored row is its blob
+        const uint64_t x = std::max(offset, lo), y = std::min(end, lo + n);
+        if (x >= y) continue;
+        const size_t k = bo.size();
+        if (c[5].u64[r] > a->ix.file_size || c[6].u64[r] > a->ix.file_size - c[5].u64[r]) return fail(ZNIPPY_E_CORRUPT, "blob range outside the archive");
+        bo.push_back(sum); bs.push_back(c[6].u64[r]); us.push_back(n);
+        if ((k & 7) == 0) bitmap.push_back(0);
+        if (c[3].u8[r]) bitmap[k >> 3] |= (uint8_t)(1u << (k & 7));
+        rr.push_back(k); rb.push_back(x - lo); rl.push_back(y - x);
+        sum += c[6].u64[r];
+        total += y - x;
+    }
+    if (bo.empty()) return ZNIPPY_OK;  // at or past the end of the file, or an empty range
+    if (!a->ctx) {
+        if (hipSetDevice(a->device) != hipSuccess) return fail(ZNIPPY_E_HIP, "hipSetDevice failed");
+        int rc = znippy_ctx_create(a->device, nullptr, &a->ctx);
+        if (rc) return fail(rc, "no usable GPU: the codec/hash path has no CPU fallback");
+    }
+    ReadBufs &bufs = a->bufs;
+    if (!bufs.blob_pin.reserve(std::max<uint64_t>(sum, total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+    {
+        size_t k = 0;
+        for (uint64_t r : it->second) {  // the same walk: the touched chunks' blobs, packed
+            const uint64_t lo = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];
+            if (std::max(offset, lo) >= std::min(end, lo + n)) continue;
+            if (bs[k] && !pread_all(a->fd, bufs.blob_pin.p + bo[k], bs[k], c[5].u64[r])) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
+            k++;
+        }
+    }
+    if (!bufs.d_blobs.reserve(sum + 64) || !bufs.d_out.reserve(total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+    if (sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+    znippy_rows *rt = nullptr;
+    int rc = znippy_rows_create(a->ctx, bo.data(), bs.data(), bitmap.data(), us.data(), nullptr, nullptr, 0, bo.size(), &rt);
+    if (rc) return fail(rc, "znippy_rows_create failed");
+    znippy_rows_set_blob_cap(rt, sum);
+    std::vector<int32_t> st(rr.size(), 0);
+    rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, st.data(), nullptr);
+    znippy_rows_destroy(rt);
+    if (rc) return fail(rc, std::string("range read failed: ") + znippy_last_error(a->ctx));
+    for (int32_t v : st)
+        if (v < 0) return fail(v, "OpenZL-equivalent decompress failed");
+    if (hipMemcpy(dst, bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+    *written = total;
+    return ZNIPPY_OK;
+}
+
 void znippy_archive_close(znippy_archive *a) {
     if (!a) return;
     if (a->ctx) znippy_ctx_destroy(a->ctx);
@@ -1356,6 +1415,10 @@ int znippy_archive_open(const char *path, int device, znippy_archive **out) {
 
 int znippy_archive_extract_file(znippy_archive *a, const char *rel, void *dst, size_t cap, size_t *written) {
     return guarded([&] { return znippy_archive_extract_file_impl(a, rel, dst, cap, written, 0); });
+}
+
+int znippy_archive_read_range(znippy_archive *a, const char *rel, uint64_t offset, void *dst, size_t len, size_t *written) {
+    return guarded([&] { return znippy_archive_read_range_impl(a, rel, offset, dst, len, written); });
 }
 
 int znippy_index_open(const char *path, znippy_index **out) {

@@ -214,6 +214,27 @@ class RowTable:
         counters, _, status = self.results()
         return counters, status
 
+    def read_ranges(self, d_blobs, rows, begins, lens, d_out, out_offsets=None, blob_base=0, out_cap=None, blob_cap=None):
+        """Byte ranges of rows (znippy_rows_read_ranges): range i is bytes [begins[i], begins[i] + lens[i]) of absolute row
+        rows[i] and lands at d_out + out_offsets[i] (None: packed back to back in array order).  Of a row this library
+        wrote only the 128 KiB blocks a range overlaps are decoded.  Synchronous and not a run: the table's results stay as
+        they are.  Returns (status per range: 0 or ZNIPPY_E_*, content bytes the decoders produced)."""
+        rr, rb, rl = as_np(rows, np.uint64), as_np(begins, np.uint64), as_np(lens, np.uint64)
+        ro = as_np(out_offsets, np.uint64) if out_offsets is not None else None
+        n = len(rr)
+        assert len(rb) == n and len(rl) == n and (ro is None or len(ro) == n), "range arrays differ in length"
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        if blob_cap is None and not isinstance(d_blobs, int):
+            blob_cap = d_blobs.numel()
+        if blob_cap is not None:
+            self.ctx._chk(self.ctx.L.znippy_rows_set_blob_cap(self.h, int(blob_cap)), "znippy_rows_set_blob_cap")
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        decoded = C.c_uint64()
+        self.ctx._chk(self.ctx.L.znippy_rows_read_ranges(self.ctx.h, self.h, _dptr(d_blobs), blob_base, np_ptr(rr), np_ptr(rb), np_ptr(rl),
+                                                         np_ptr(ro) if ro is not None else None, n, _dptr(d_out), out_cap,
+                                                         np_ptr(status), C.byref(decoded)), "znippy_rows_read_ranges")
+        return status[:n], int(decoded.value)
+
     def verify_async(self, d_blobs, blob_base=0, blob_cap=None):
         """Queue a verify-only run (the read loop with save_data=false, decompress.rs:L186-189): same results calls, same
         counters, corrupt list, status and digests as a decode run over these blobs, and no output."""
