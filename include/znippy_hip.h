@@ -42,6 +42,7 @@ extern "C" {
 #define ZNIPPY_E_CORRUPT (-5)     /* malformed frame */
 #define ZNIPPY_E_UNSUPPORTED (-6) /* dictionary frames, unknown content size */
 #define ZNIPPY_E_CHECKSUM (-7)    /* frame content checksum (XXH64) mismatch */
+#define ZNIPPY_E_DIGEST (-8)      /* BLAKE3 of the bytes does not match the index checksum or block tree */
 
 typedef struct znippy_ctx znippy_ctx;
 typedef struct znippy_rows znippy_rows;     /* read side: a range of index rows, device-resident */
@@ -255,6 +256,69 @@ int znippy_rows_read_ranges(znippy_ctx *ctx, znippy_rows *rows, const void *d_bl
                             const uint64_t *range_row, const uint64_t *range_begin, const uint64_t *range_len,
                             const uint64_t *range_out, uint64_t n_ranges,
                             void *d_out, uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes);
+
+/* ---- block tree: range reads verified block by block against the row checksum ----------------------------------------
+ * BLAKE3 is a tree hash and 128 KiB is 128 chunks, a power of two: every aligned 128 KiB block of a row is a complete subtree of the
+ * row's hash tree.  With the chaining values of these subtrees a block can be checked on its own, and the chaining values authenticate
+ * themselves — folded together they must give the row's `checksum` (the construction BLAKE3 was designed for: Bao).
+ * Definitions.  len = a row's content length (uncompressed_size; blob_size for a stored row), BLK = 131072.
+ *   A row has nb = (len > BLK && len < 4 GiB) ? ceil(len / BLK) : 0 entries: rows of at most one block, and rows of 4 GiB or more, are
+ *   verified whole against `checksum` and need none.
+ *   Entry k is the NON-root chaining value of the BLAKE3 subtree over chunks [128k, min(128k + 128, ceil(len / 1024))) of the row's
+ *   content: the chunk counters are the row's own (128k + i), the last chunk may be short, the subtree has the usual left-heavy shape
+ *   (pairwise folding with the odd node promoted gives it), a last block of one chunk is that chunk's chaining value (CHUNK_START |
+ *   CHUNK_END, no parent) and ROOT is never set.  An entry is serialised as eight little-endian 32-bit words (32 bytes).
+ *   The row's digest is the same pairwise fold over its nb >= 2 entries with ROOT on the last parent.
+ *   The block tree of a table is the entries of its rows, concatenated in row order: 32 bytes per 128 KiB, 0.024 % of the content.
+ * Trust.  The tree may come from anywhere — znippy_rows_block_tree_build, a file beside the archive, another machine.  The index
+ * checksum alone is the root of trust: znippy_rows_set_block_tree accepts a row's entries only if they fold to the row's checksum, and
+ * a block is accepted only if its bytes hash to an accepted entry.  Forging either means a BLAKE3 collision.
+ * All four calls are synchronous, ordered on the context's stream, and NOT runs, under the rules of znippy_rows_read_ranges: no slot of
+ * the two-run ring; the table's remembered last run, status column, corrupt list and digests are untouched; they may be called
+ * between an async run and the read of its results (znippy_last_kernel_times then describes the call).  NULL arguments (other than
+ * the optional ones), a closed context or a table of another context give ZNIPPY_E_INVAL.
+ *
+ * znippy_rows_block_tree_layout: *n_entries = entries of the whole table; row_first (HOST, n + 1 values, optional): row i's entries
+ * are [row_first[i], row_first[i + 1]).
+ *
+ * znippy_rows_block_tree_build computes the tree from the blobs (tree: HOST, 32 * n_entries bytes; may be NULL when n_entries is 0).
+ * Rows without entries are not looked at (status 0).  Every other compressed row is decoded whole into context scratch by a private
+ * decode-only run — the range scratch, sized before anything is queued; more than its cap gives ZNIPPY_E_NOMEM with nothing queued —
+ * stored rows are hashed where they lie in the blob region, one launch produces all entries, and on a table with a checksum column
+ * each row's entries are folded and compared with its checksum (a table without one compares nothing).  row_status (HOST, optional,
+ * one per row): 0; the decode run's ZNIPPY_E_* for a row that failed to decode; ZNIPPY_E_CORRUPT for a blob outside the declared blob
+ * region (host validation, as in a run); ZNIPPY_E_DIGEST for a digest mismatch.  The entries of a row whose status is not 0 are written
+ * as zeros.  The call does not install the tree.
+ *
+ * znippy_rows_set_block_tree installs a tree (HOST, 32 * n_entries bytes; NULL removes the installed one).  Needs a table created
+ * with a checksum column (ZNIPPY_E_INVAL otherwise).  The entries are uploaded and every row with entries is authenticated: row_status
+ * (optional) is 0 — accepted, or a row without entries — or ZNIPPY_E_DIGEST — rejected.  The call returns ZNIPPY_OK either way: a
+ * rejected row is simply a row without entries from then on.  The table keeps a device copy and the per-row verdicts until
+ * znippy_rows_destroy; a second call replaces them.
+ *
+ * znippy_rows_read_ranges_verified: znippy_rows_read_ranges — host validation, destinations, packing, decoded_bytes, scratch rules
+ * and fallbacks are exactly that call's — on a table created with a checksum column (ZNIPPY_E_INVAL otherwise), where a range reports
+ * 0 only if EVERY BYTE IT RETURNS WAS COVERED BY A HASH THAT CHAINS TO THE ROW'S CHECKSUM.  Routes:
+ *   by blocks  a compressed row on the partial route whose entries are accepted: after the block pass each decoded block is hashed
+ *              from the scratch and compared with its entry (kernel time: range_verify_blocks);
+ *   stored     a stored row whose entries are accepted: the blocks its ranges overlap are hashed in place in the blob region;
+ *   whole      a row of at most one block; a row without accepted entries (no tree installed, or the row was rejected — such a
+ *              row is not tried block by block); every row the unverified call decodes whole (a foreign or window frame, a frame
+ *              the scan refuses, a "late" row, a row of 4 GiB or more): the private table of the whole-row pass gets the rows'
+ *              checksums and runs decode + verify instead of decode-only.  A stored row on this route is hashed whole where it
+ *              lies by a private verify-only run (kernel time: range_verify_rows).
+ * A block or row that fails gives ZNIPPY_E_DIGEST to every range that overlaps it; decode errors keep their codes.  Verification
+ * happens before the gather: no byte of a range whose status is not 0 is written.  len == 0 ranges are status 0 and verify nothing.
+ * hashed_bytes (HOST, optional): the content bytes hashed in this call, the hash-side twin of decoded_bytes — the content size of
+ * every distinct block hashed on its own, each once per call however many ranges touch it, plus the length of every row hashed whole. */
+int znippy_rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *rows, uint64_t *n_entries, uint64_t *row_first);
+int znippy_rows_block_tree_build(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base, uint8_t *tree,
+                                 int32_t *row_status);
+int znippy_rows_set_block_tree(znippy_ctx *ctx, znippy_rows *rows, const uint8_t *tree, int32_t *row_status);
+int znippy_rows_read_ranges_verified(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base,
+                                     const uint64_t *range_row, const uint64_t *range_begin, const uint64_t *range_len,
+                                     const uint64_t *range_out, uint64_t n_ranges, void *d_out, uint64_t out_cap,
+                                     int32_t *range_status, uint64_t *decoded_bytes, uint64_t *hashed_bytes);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,

@@ -103,6 +103,16 @@ int znippy_archive_extract_file_verified(znippy_archive *a, const char *relative
  * that fails to decode gives its ZNIPPY_E_*, an unknown path ZNIPPY_E_INVAL. */
 int znippy_archive_read_range(znippy_archive *a, const char *relative_path, uint64_t offset, void *dst, size_t len,
                               size_t *written);
+/* The same pread where every byte returned was covered by a BLAKE3 hash that chains to the index's checksum column
+ * (znippy_rows_read_ranges_verified): ZNIPPY_E_CHECKSUM when it was not, and then nothing is copied.  The handle keeps a cache,
+ * archive row -> block tree (32 bytes per 128 KiB block of a chunk of more than one block).  The first verified read that touches
+ * such a chunk builds its entries once — a whole decode of the chunk whose digest must be the index checksum, ZNIPPY_E_CHECKSUM
+ * otherwise; every verified read then installs the cached entries of the chunks it touches (authenticated against the checksum
+ * again, znippy_rows_set_block_tree) and hashes only the blocks the range overlaps.  Chunks of at most one block are hashed whole.
+ * Blobs are read from the archive file on every call, as for znippy_archive_read_range: damage that appears between two reads is
+ * caught for the blocks a read touches. */
+int znippy_archive_read_range_verified(znippy_archive *a, const char *relative_path, uint64_t offset, void *dst, size_t len,
+                                       size_t *written);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

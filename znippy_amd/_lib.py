@@ -13,10 +13,11 @@ from . import _build
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 OK = 0
-E_INVAL, E_HIP, E_NOMEM, E_DST_SMALL, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM = -1, -2, -3, -4, -5, -6, -7
+E_INVAL, E_HIP, E_NOMEM, E_DST_SMALL, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM, E_DIGEST = -1, -2, -3, -4, -5, -6, -7, -8
 _ERRNAMES = {E_INVAL: "invalid argument", E_HIP: "HIP runtime error", E_NOMEM: "out of device memory",
              E_DST_SMALL: "destination too small", E_CORRUPT: "corrupt frame",
-             E_UNSUPPORTED: "unsupported frame", E_CHECKSUM: "content checksum mismatch"}
+             E_UNSUPPORTED: "unsupported frame", E_CHECKSUM: "content checksum mismatch",
+             E_DIGEST: "BLAKE3 digest mismatch"}
 
 
 class ZnippyError(RuntimeError):
@@ -49,6 +50,8 @@ EXPORTS = [
     "znippy_decode_rows", "znippy_decode_rows_async",
     "znippy_rounds_set_blob_align", "znippy_rounds_blob_align",
     "znippy_rows_read_ranges",
+    "znippy_rows_block_tree_layout", "znippy_rows_block_tree_build", "znippy_rows_set_block_tree",
+    "znippy_rows_read_ranges_verified",
 ]
 
 
@@ -130,6 +133,12 @@ def lib():
     if hasattr(L, "znippy_rows_read_ranges"):  # (likewise)
         L.znippy_rows_read_ranges.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp,
                                               C.POINTER(C.c_uint64)]
+    if hasattr(L, "znippy_rows_read_ranges_verified"):  # (likewise)
+        L.znippy_rows_block_tree_layout.argtypes = [vp, vp, C.POINTER(C.c_uint64), vp]
+        L.znippy_rows_block_tree_build.argtypes = [vp, vp, vp, C.c_uint64, vp, vp]
+        L.znippy_rows_set_block_tree.argtypes = [vp, vp, vp, vp]
+        L.znippy_rows_read_ranges_verified.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     _lib = L
     return L
 

@@ -463,6 +463,12 @@ struct znippy_rows {
     std::vector<uint64_t> h_blob_off, h_blob_size, h_len, h_out_off;
     std::vector<uint8_t> h_comp;  // range reads: the byte-per-row flags beside the three columns above (rows_host_columns)
     uint64_t blob_cap = ~0ull;  // size of the caller's blob region (znippy_rows_set_blob_cap); ~0 = not declared
+    // block tree (znippy_rows_set_block_tree): the layout (n + 1 first-entry numbers, filled at first use), a device copy of the
+    // installed entries, which rows' entries fold to their checksum (accepted), and a host copy of the checksum column
+    std::vector<uint64_t> tree_first;
+    uint32_t *tree_dev = nullptr;
+    std::vector<uint8_t> tree_accept;
+    std::vector<uint8_t> h_checksum;
     uint64_t val_base = 0, val_bcap = 0, val_ocap = 0;
     bool val_done = false, val_verify = false;
     uint32_t n_bad = 0;
@@ -1162,7 +1168,7 @@ void znippy_rows_destroy(znippy_rows *r) {
                     r->cand_row, r->cand_base, r->cand_nblocks, r->fz_base, r->fz_cap, r->fz_it_cand, r->fz_nb, r->fz_work, r->fz_items, r->item_row, r->item_k, r->item_src, r->row_flag, r->pending2,
                     r->bt_tile, r->bt_item, r->tile_done, r->todo, r->status_init, r->slow_list,
                     r->bx_cand_row, r->bx_cand_base, r->bx_cand_nb, r->bx_huf_list, r->bx_seq_list, r->bx_items, r->bx_prep, r->d_bitmap, r->bx_sort_tmp,
-                    r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off};
+                    r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off, r->tree_dev};
     for (void *p : ptrs)
         tfree(r->ctx, p);
     if (r->h_counters) {
@@ -2205,6 +2211,9 @@ struct RrRow {                       // a distinct row the ranges of a call touc
     uint64_t slot = 0, first = 0;    // byte b of the row is at pool + slot + (b - first)
     uint32_t kmin = 0xFFFFFFFFu, kmax = 0;
     std::vector<uint8_t> need;       // partial: per block, a range overlaps it
+    bool sblocks = false;            // verified read, stored row with accepted entries: `need` blocks are hashed where they lie
+    bool hashed = false;             // verified read: the row was hashed whole
+    std::vector<uint8_t> bad;        // verified read: per block, its chaining value does not equal its entry
 };
 uint8_t *rr_carve_bytes(uint8_t *base, size_t &at, size_t bytes) {  // the next 16-byte aligned piece of a slab
     at = (at + 15) & ~(size_t)15;
@@ -2215,46 +2224,131 @@ uint8_t *rr_carve_bytes(uint8_t *base, size_t &at, size_t bytes) {  // the next 
 #define rr_carve(T, base, at, n) reinterpret_cast<T *>(rr_carve_bytes(base, at, sizeof(T) * (size_t)(n)))
 }  // namespace
 
+// The checksum column on the host (verified range reads give the private tables of their whole-row passes the rows' checksums).
+static int rows_host_checksum(znippy_ctx *ctx, znippy_rows *r) {
+    if (!r->n || !r->checksum || !r->h_checksum.empty()) return ZNIPPY_OK;
+    std::vector<uint8_t> ck((size_t)32 * r->n);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(ck.data(), r->checksum, ck.size(), hipMemcpyDeviceToHost));
+    r->h_checksum.swap(ck);
+    return ZNIPPY_OK;
+}
+
 // Whole rows into the range scratch: a private table over the compact columns of `sel`, one decode-only run of it, the rows' verdicts.
 // The run's kernels are bracketed as one entry of the kernel times (range_decode_rows).
-static int rr_decode_whole(znippy_ctx *ctx, const znippy_rows *r, std::vector<RrRow> &rows, const std::vector<uint32_t> &sel, const void *d_blobs, uint64_t blob_base, int pool) {
+// `verify` (verified range reads): the private table gets the rows' checksums and the run is a decode + verify run; a row whose digest
+// is not its checksum gets ZNIPPY_E_DIGEST.  `stored`: the rows are stored rows and the run is a verify-only run, which hashes them
+// where they lie in the blob region (nothing lands in the scratch).
+static int rr_decode_whole(znippy_ctx *ctx, const znippy_rows *r, std::vector<RrRow> &rows, const std::vector<uint32_t> &sel, const void *d_blobs, uint64_t blob_base, int pool,
+                           bool verify = false, bool stored = false) {
     // (two names: a call may run both passes, and consumers key the kernel times by name)
     const size_t m = sel.size();
     if (!m) return ZNIPPY_OK;
     std::vector<uint64_t> bo(m), bs(m), us(m), oo(m);
     std::vector<int32_t> st(m, 0);
+    std::vector<uint8_t> ck(verify ? 32 * m : 0), dig(verify ? 32 * m : 0), bitmap(stored ? (m + 7) / 8 : 0, 0);
     for (size_t i = 0; i < m; i++) {
         const RrRow &w = rows[sel[i]];
         bo[i] = r->h_blob_off[w.row]; bs[i] = r->h_blob_size[w.row]; us[i] = r->h_len[w.row]; oo[i] = w.slot;
+        if (verify) memcpy(&ck[32 * i], &r->h_checksum[(size_t)32 * w.row], 32);
     }
     znippy_rows *t = nullptr;
-    int rc = znippy_rows_create(ctx, bo.data(), bs.data(), nullptr, us.data(), oo.data(), nullptr, 0, m, &t);
+    int rc = znippy_rows_create(ctx, bo.data(), bs.data(), stored ? bitmap.data() : nullptr, us.data(), stored ? nullptr : oo.data(), verify ? ck.data() : nullptr, 0, m, &t);
     if (rc) return rc;
     const int keep = ctx->n_ktimes, level = ctx->sw.ktime;
-    ktime_begin(ctx, pool ? "range_decode_rows_late" : "range_decode_rows");
+    ktime_begin(ctx, stored ? "range_verify_rows" : pool ? "range_decode_rows_late" : "range_decode_rows");
     const bool open = ctx->ktime_open;
     ctx->sw.ktime = 0;  // (the run's own brackets would start the list anew)
-    rc = rows_queue(ctx, t, d_blobs, blob_base, ctx->rr_pool[pool], ctx->rr_cap[pool], false, true);
+    rc = stored ? rows_queue(ctx, t, d_blobs, blob_base, nullptr, 0, true)
+                : rows_queue(ctx, t, d_blobs, blob_base, ctx->rr_pool[pool], ctx->rr_cap[pool], false, !verify);
     ctx->sw.ktime = level; ctx->n_ktimes = keep; ctx->ktime_open = open;
     ktime_end(ctx);
     if (!rc) rc = znippy_rows_results(ctx, t, nullptr, nullptr, 0, st.data());
+    if (!rc && verify) rc = znippy_rows_digests(ctx, t, dig.data());
     znippy_rows_destroy(t);
     if (rc) return rc;
-    for (size_t i = 0; i < m; i++) rows[sel[i]].status = st[i];
+    for (size_t i = 0; i < m; i++) {
+        RrRow &w = rows[sel[i]];
+        w.status = st[i];
+        if (verify && !st[i]) {
+            w.hashed = true;
+            if (memcmp(&dig[32 * i], &ck[32 * i], 32)) w.status = ZNIPPY_E_DIGEST;
+        }
+    }
+    return ZNIPPY_OK;
+}
+
+// ---- block tree (znippy_rows_block_tree_*, znippy_rows_set_block_tree) ---------------------------------
+// Entries of a row: one per 128 KiB block of a row of more than one block and below 4 GiB; none otherwise (znippy_hip.h).
+static inline uint64_t tree_entries_of(uint64_t len) { return len > RR_BLK && len < (1ull << 32) ? (len + RR_BLK - 1) / RR_BLK : 0; }
+static int rows_tree_layout(znippy_ctx *ctx, znippy_rows *r) {
+    const int rc = rows_host_columns(ctx, r);
+    if (rc || !r->tree_first.empty()) return rc;
+    std::vector<uint64_t> first((size_t)r->n + 1, 0);
+    for (uint32_t i = 0; i < r->n; i++) first[i + 1] = first[i] + tree_entries_of(r->h_len[i]);
+    r->tree_first.swap(first);
+    return ZNIPPY_OK;
+}
+
+// One k_block_cvs launch over host-built items, synchronous: write mode (d_out) or compare mode (d_expect, *ok = per item verdict).
+static int block_cvs_run(znippy_ctx *ctx, const std::vector<BlockCvItem> &items, uint32_t *d_out, const uint32_t *d_expect, std::vector<uint32_t> *ok, const char *name) {
+    if (items.empty()) return ZNIPPY_OK;
+    if (items.size() > 0x7FFFFFF0ull) return ZNIPPY_E_NOMEM;
+    hipStream_t s = ctx->stream;
+    struct Guard {  // (the buffers go back to the context's pool only once nothing queued can touch them)
+        znippy_ctx *ctx; BlockCvItem *items = nullptr; uint32_t *ok = nullptr;
+        ~Guard() { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, items); tfree(ctx, ok); }
+    } g{ctx};
+    const uint32_t n = (uint32_t)items.size();
+    if (tmalloc(ctx, &g.items, sizeof(BlockCvItem) * (size_t)n) != hipSuccess || (d_expect && tmalloc(ctx, &g.ok, 4 * (size_t)n) != hipSuccess)) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemcpyAsync(g.items, items.data(), sizeof(BlockCvItem) * (size_t)n, hipMemcpyHostToDevice, s));
+    timed(ctx, name, s, [&] { launch_block_cvs(g.items, n, d_out, d_expect, g.ok, s); });
+    if (ok) {
+        ok->assign(n, 0);
+        if (d_expect) HIPCHK(ctx, hipMemcpyAsync(ok->data(), g.ok, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipGetLastError());
+    return ZNIPPY_OK;
+}
+
+// The entries of the table rows `sel` (in d_tree, laid out by tree_first) folded and compared with the rows' checksums, synchronous:
+// ok[i] = the entries of sel[i] are authentic.
+static int tree_fold_check(znippy_ctx *ctx, znippy_rows *r, const uint32_t *d_tree, const std::vector<uint32_t> &sel, std::vector<uint32_t> &ok) {
+    ok.assign(sel.size(), 0);
+    if (sel.empty()) return ZNIPPY_OK;
+    hipStream_t s = ctx->stream;
+    std::vector<BlockTreeRow> h(sel.size());
+    for (size_t i = 0; i < sel.size(); i++) h[i] = BlockTreeRow{r->tree_first[sel[i]], (uint32_t)(r->tree_first[sel[i] + 1] - r->tree_first[sel[i]]), sel[i]};
+    struct Guard {
+        znippy_ctx *ctx; BlockTreeRow *rows = nullptr; uint32_t *ok = nullptr;
+        ~Guard() { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, rows); tfree(ctx, ok); }
+    } g{ctx};
+    if (tmalloc(ctx, &g.rows, sizeof(BlockTreeRow) * h.size()) != hipSuccess || tmalloc(ctx, &g.ok, 4 * h.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemcpyAsync(g.rows, h.data(), sizeof(BlockTreeRow) * h.size(), hipMemcpyHostToDevice, s));
+    timed(ctx, "block_tree_fold", s, [&] { launch_block_tree_fold(g.rows, (uint32_t)h.size(), d_tree, r->checksum, g.ok, s); });
+    HIPCHK(ctx, hipMemcpyAsync(ok.data(), g.ok, 4 * h.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipGetLastError());
     return ZNIPPY_OK;
 }
 
 static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
                             const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
-                            uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes) {
+                            uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes, bool verified = false, uint64_t *hashed_bytes = nullptr) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (verified && !r->checksum && r->n) return ZNIPPY_E_INVAL;  // nothing to verify against
     if (decoded_bytes) *decoded_bytes = 0;
+    if (hashed_bytes) *hashed_bytes = 0;
     if (!n_ranges) return ZNIPPY_OK;
     if (!range_row || !range_begin || !range_len || !d_blobs || !d_out) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = rows_host_columns(ctx, r);
+    if (!rc && verified) rc = rows_host_checksum(ctx, r);
     if (rc) return rc;
+    // verified: a row is looked at block by block only if its entries are installed and fold to its checksum
+    auto by_blocks = [&](uint32_t ri) { return !verified || (ri < r->tree_accept.size() && r->tree_accept[ri]); };
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
 
@@ -2285,13 +2379,14 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
             RrRow w;
             w.row = ri;
             w.comp = r->h_comp[ri] != 0;
-            w.partial = w.comp && row_len > RR_BLK && row_len < 0xFFFFFFFFull;  // >= 2 blocks, below 4 GiB: tried block by block
-            if (w.partial) w.need.assign((size_t)((row_len + RR_BLK - 1) / RR_BLK), 0);
+            w.partial = w.comp && row_len > RR_BLK && row_len < 0xFFFFFFFFull && by_blocks(ri);  // >= 2 blocks, below 4 GiB: tried block by block
+            w.sblocks = verified && !w.comp && row_len > RR_BLK && row_len < 0xFFFFFFFFull && by_blocks(ri);
+            if (w.partial || w.sblocks) w.need.assign((size_t)((row_len + RR_BLK - 1) / RR_BLK), 0);
             rows.push_back(std::move(w));
         }
         of_row[i] = it->second;
         RrRow &w = rows[it->second];
-        if (w.partial) {
+        if (w.partial || w.sblocks) {
             const uint32_t k0 = (uint32_t)(begin / RR_BLK), k1 = (uint32_t)((begin + len - 1) / RR_BLK);
             for (uint32_t k = k0; k <= k1; k++) w.need[k] = 1;
             w.kmin = std::min(w.kmin, k0); w.kmax = std::max(w.kmax, k1);
@@ -2299,11 +2394,14 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
     }
 
     // 2) the plan: slots in the scratch, the private columns and lists of the block pass, the rows decoded whole from the start
-    std::vector<uint32_t> part, whole;
+    std::vector<uint32_t> part, whole, stored_whole;
     uint64_t n_items = 0, n_todo = 0, need0 = 0;
     for (uint32_t i = 0; i < rows.size(); i++) {
         RrRow &w = rows[i];
-        if (!w.comp) continue;
+        if (!w.comp) {
+            if (verified && !w.sblocks) stored_whole.push_back(i);  // hashed whole, where it lies, by a private verify-only run
+            continue;
+        }
         if (w.partial && n_items + w.need.size() >= 0x7FFFFFF0ull) w.partial = false;
         const uint64_t row_len = r->h_len[w.row];
         need0 = (need0 + 255) & ~255ull;
@@ -2398,7 +2496,8 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
         HIPCHK(ctx, hipMemcpyAsync(h.decoded, d.decoded, 8, hipMemcpyDeviceToHost, s));
     }
     // ... behind it, the rows known from the start to need a whole decode (its results call waits for both)
-    if ((rc = rr_decode_whole(ctx, r, rows, whole, d_blobs, blob_base, 0))) return rc;
+    if ((rc = rr_decode_whole(ctx, r, rows, whole, d_blobs, blob_base, 0, verified))) return rc;
+    if ((rc = rr_decode_whole(ctx, r, rows, stored_whole, d_blobs, blob_base, 0, true, true))) return rc;
     HIPCHK(ctx, hipStreamSynchronize(s));
     HIPCHK(ctx, hipGetLastError());
 
@@ -2418,18 +2517,53 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
             late.push_back(part[c]);
         }
         if ((rc = ensure_range_scratch(ctx, 1, need1))) return rc;  // (nothing is queued at this point, and d_out is untouched)
-        if ((rc = rr_decode_whole(ctx, r, rows, late, d_blobs, blob_base, 1))) return rc;
+        if ((rc = rr_decode_whole(ctx, r, rows, late, d_blobs, blob_base, 1, verified))) return rc;
+    }
+
+    // 4b) verified: every block that will serve a range — decoded into the scratch, or a stored row's where it lies — is hashed on its
+    // own and compared with its (accepted) entry, before a byte of it moves
+    uint64_t hashed = 0;
+    if (verified) {
+        std::vector<BlockCvItem> items;
+        std::vector<std::pair<uint32_t, uint32_t>> item_of;  // -> (entry of `rows`, block)
+        for (uint32_t i = 0; i < rows.size(); i++) {
+            RrRow &w = rows[i];
+            if (w.hashed) hashed += r->h_len[w.row];
+            if (!((w.partial && !w.late) || w.sblocks) || w.status) continue;
+            const uint64_t row_len = r->h_len[w.row];
+            w.bad.assign(w.need.size(), 0);
+            for (uint32_t k = w.kmin; k <= w.kmax; k++) {
+                if (!w.need[k]) continue;
+                const uint64_t at = (uint64_t)k * RR_BLK;
+                const uint8_t *src = w.comp ? ctx->rr_pool[0] + w.slot + (at - w.first) : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base) + at;
+                const uint32_t bytes = (uint32_t)std::min<uint64_t>(RR_BLK, row_len - at);
+                items.push_back(BlockCvItem{src, r->tree_first[w.row] + k, bytes, 128u * k});
+                item_of.emplace_back(i, k);
+                hashed += bytes;
+            }
+        }
+        if (!items.empty()) {
+            std::vector<uint32_t> ok;
+            if ((rc = block_cvs_run(ctx, items, nullptr, r->tree_dev, &ok, "range_verify_blocks"))) return rc;
+            for (size_t j = 0; j < items.size(); j++)
+                if (!ok[j]) rows[item_of[j].first].bad[item_of[j].second] = 1;
+        }
     }
 
     // 5) the gather: every good range from where its bytes are to its place in d_out
     uint64_t dec = dec_blocks;
     for (const RrRow &w : rows)
-        if (w.comp && (!w.partial || w.late) && w.status == 0) dec += r->h_len[w.row];
+        if (w.comp && (!w.partial || w.late) && (w.status == 0 || w.status == ZNIPPY_E_DIGEST)) dec += r->h_len[w.row];
     std::vector<RangePiece> pieces;
     for (uint64_t i = 0; i < n_ranges; i++) {
         if (of_row[i] == 0xFFFFFFFFu) continue;
         const RrRow &w = rows[of_row[i]];
         if (w.status) { st[i] = w.status; continue; }
+        if (!w.bad.empty()) {  // a block whose hash does not chain to the checksum fails every range that overlaps it
+            bool bad = false;
+            for (uint64_t k = range_begin[i] / RR_BLK; k <= (range_begin[i] + range_len[i] - 1) / RR_BLK; k++) bad |= w.bad[k] != 0;
+            if (bad) { st[i] = ZNIPPY_E_DIGEST; continue; }
+        }
         const uint8_t *src = w.comp ? ctx->rr_pool[w.pool] + w.slot + (range_begin[i] - w.first)
                                     : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base) + range_begin[i];
         uint8_t *to = (uint8_t *)d_out + dst[i];
@@ -2452,6 +2586,7 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
     }
     if (range_status) memcpy(range_status, st.data(), 4 * (size_t)n_ranges);
     if (decoded_bytes) *decoded_bytes = dec;
+    if (hashed_bytes) *hashed_bytes = hashed;
     return ZNIPPY_OK;
 }
 
@@ -2467,6 +2602,161 @@ int znippy_rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
         return ZNIPPY_E_NOMEM;
     }
 }
+
+int znippy_rows_read_ranges_verified(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
+                                     const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
+                                     uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes, uint64_t *hashed_bytes) {
+    try {
+        return rows_read_ranges(ctx, r, d_blobs, blob_base, range_row, range_begin, range_len, range_out, n_ranges, d_out, out_cap, range_status, decoded_bytes,
+                                true, hashed_bytes);
+    } catch (const std::bad_alloc &) {
+        return ZNIPPY_E_NOMEM;
+    } catch (const std::length_error &) {
+        return ZNIPPY_E_NOMEM;
+    }
+}
+
+static int rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_entries, uint64_t *row_first) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx || !n_entries) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = rows_tree_layout(ctx, r);
+    if (rc) return rc;
+    *n_entries = r->tree_first[r->n];
+    if (row_first) memcpy(row_first, r->tree_first.data(), 8 * ((size_t)r->n + 1));
+    return ZNIPPY_OK;
+}
+
+// The producer: every row with entries decoded whole into the range scratch (stored rows: hashed where they lie), one k_block_cvs
+// launch in write mode for all of them, then the fold against the checksums.  Not a run, and nothing is installed.
+static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, uint8_t *tree, int32_t *row_status) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rows_tree_layout(ctx, r);
+    if (rc) return rc;
+    const uint64_t n_entries = r->tree_first[r->n];
+    if (n_entries && (!d_blobs || !tree)) return ZNIPPY_E_INVAL;
+    std::vector<int32_t> st(r->n, 0);
+    if (row_status && r->n) memset(row_status, 0, 4 * (size_t)r->n);
+    if (!n_entries) return ZNIPPY_OK;
+    hipStream_t s = ctx->stream;
+    ctx->n_ktimes = 0;
+
+    // 1) the rows with entries against the blob region; a slot in the scratch for every compressed one — sized before anything is queued
+    std::vector<RrRow> rows;
+    std::vector<uint32_t> sel;
+    const uint64_t bcap = r->blob_cap;
+    uint64_t need0 = 0;
+    for (uint32_t ri = 0; ri < r->n; ri++) {
+        if (r->tree_first[ri + 1] == r->tree_first[ri]) continue;
+        const uint64_t bo = r->h_blob_off[ri], bs = r->h_blob_size[ri];
+        if (bo < blob_base || (bcap != ~0ull && (bs > bcap || bo - blob_base > bcap - bs))) { st[ri] = ZNIPPY_E_CORRUPT; continue; }
+        RrRow w;
+        w.row = ri;
+        w.comp = r->h_comp[ri] != 0;
+        if (w.comp) {
+            need0 = (need0 + 255) & ~255ull;
+            w.slot = need0;
+            need0 += r->h_len[ri] + 256;
+            if (need0 > (32ull << 30)) return ZNIPPY_E_NOMEM;
+            sel.push_back((uint32_t)rows.size());
+        }
+        rows.push_back(std::move(w));
+    }
+    if ((rc = ensure_range_scratch(ctx, 0, need0))) return rc;
+
+    // 2) a private decode-only run of the compressed rows
+    if ((rc = rr_decode_whole(ctx, r, rows, sel, d_blobs, blob_base, 0))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipGetLastError());
+
+    // 3) every block of every good row: one launch
+    std::vector<BlockCvItem> items;
+    std::vector<uint32_t> good;
+    for (const RrRow &w : rows) {
+        if (w.status) { st[w.row] = w.status; continue; }
+        good.push_back(w.row);
+        const uint64_t row_len = r->h_len[w.row];
+        const uint8_t *base = w.comp ? ctx->rr_pool[0] + w.slot : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base);
+        const uint32_t nb = (uint32_t)(r->tree_first[w.row + 1] - r->tree_first[w.row]);
+        for (uint32_t k = 0; k < nb; k++)
+            items.push_back(BlockCvItem{base + (uint64_t)k * RR_BLK, r->tree_first[w.row] + k, (uint32_t)std::min<uint64_t>(RR_BLK, row_len - (uint64_t)k * RR_BLK), 128u * k});
+    }
+    struct Guard {
+        znippy_ctx *ctx; uint32_t *tree = nullptr;
+        ~Guard() { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, tree); }
+    } g{ctx};
+    if (tmalloc(ctx, &g.tree, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemsetAsync(g.tree, 0, 32 * (size_t)n_entries, s));
+    if ((rc = block_cvs_run(ctx, items, g.tree, nullptr, nullptr, "block_tree_cvs"))) return rc;
+
+    // 4) the entries against the checksums (a table without the column compares nothing)
+    if (r->checksum) {
+        std::vector<uint32_t> ok;
+        if ((rc = tree_fold_check(ctx, r, g.tree, good, ok))) return rc;
+        for (size_t i = 0; i < good.size(); i++)
+            if (!ok[i]) st[good[i]] = ZNIPPY_E_DIGEST;
+    }
+    HIPCHK(ctx, hipMemcpyAsync(tree, g.tree, 32 * (size_t)n_entries, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    for (uint32_t ri = 0; ri < r->n; ri++)  // a row that failed has no entries to offer
+        if (st[ri]) memset(tree + 32 * r->tree_first[ri], 0, 32 * (size_t)(r->tree_first[ri + 1] - r->tree_first[ri]));
+    if (row_status) memcpy(row_status, st.data(), 4 * (size_t)r->n);
+    return ZNIPPY_OK;
+}
+
+// The installer: the caller's entries go to the device, every row's are folded against its checksum, and only those that match count
+// from then on (tree_accept).  The checksum column alone is trusted.
+static int rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *tree, int32_t *row_status) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
+    if (!r->checksum) return ZNIPPY_E_INVAL;  // nothing could authenticate the entries
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    if (row_status && r->n) memset(row_status, 0, 4 * (size_t)r->n);
+    if (!tree) {
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        tfree(ctx, r->tree_dev);
+        r->tree_dev = nullptr;
+        r->tree_accept.clear();
+        return ZNIPPY_OK;
+    }
+    int rc = rows_tree_layout(ctx, r);
+    if (rc) return rc;
+    const uint64_t n_entries = r->tree_first[r->n];
+    ctx->n_ktimes = 0;
+    struct Guard {
+        znippy_ctx *ctx; uint32_t *tree = nullptr;
+        ~Guard() { if (tree) { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, tree); } }
+    } g{ctx};
+    std::vector<uint8_t> accept(r->n, 0);
+    if (n_entries) {
+        if (tmalloc(ctx, &g.tree, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, hipMemcpyAsync(g.tree, tree, 32 * (size_t)n_entries, hipMemcpyHostToDevice, s));
+        std::vector<uint32_t> sel, ok;
+        for (uint32_t ri = 0; ri < r->n; ri++)
+            if (r->tree_first[ri + 1] != r->tree_first[ri]) sel.push_back(ri);
+        if ((rc = tree_fold_check(ctx, r, g.tree, sel, ok))) return rc;
+        for (size_t i = 0; i < sel.size(); i++) {
+            accept[sel[i]] = ok[i] ? 1 : 0;
+            if (!ok[i] && row_status) row_status[sel[i]] = ZNIPPY_E_DIGEST;
+        }
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    std::swap(r->tree_dev, g.tree);  // (the guard frees the tree this one replaces)
+    r->tree_accept.swap(accept);
+    return ZNIPPY_OK;
+}
+
+#define ZN_NO_THROW(call) \
+    try { return call; } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; } catch (const std::length_error &) { return ZNIPPY_E_NOMEM; }
+int znippy_rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_entries, uint64_t *row_first) { ZN_NO_THROW(rows_block_tree_layout(ctx, r, n_entries, row_first)) }
+int znippy_rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, uint8_t *tree, int32_t *row_status) {
+    ZN_NO_THROW(rows_block_tree_build(ctx, r, d_blobs, blob_base, tree, row_status))
+}
+int znippy_rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *tree, int32_t *row_status) { ZN_NO_THROW(rows_set_block_tree(ctx, r, tree, row_status)) }
+#undef ZN_NO_THROW
 
 int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables

@@ -1211,6 +1211,9 @@ struct znippy_archive {
     znippy_ctx *ctx = nullptr;
     int fd = -1;
     ReadBufs bufs;
+    // verified range reads: archive row -> the entries of its block tree (32 bytes per 128 KiB block), built once per chunk by a whole
+    // decode with a root check and authenticated again, against the index checksum, by every read that installs them
+    std::unordered_map<uint64_t, std::vector<uint8_t>> block_trees;
 };
 
 extern "C" {
@@ -1272,15 +1275,19 @@ static int znippy_archive_extract_file_impl(znippy_archive *a, const char *rel, 
 
 // pread on an archived file (ZnippyArchive.read_range in archive.py): the range is mapped to the chunks it touches by fdata_offset, only
 // their blobs are read from the archive, and znippy_rows_read_ranges decodes no more of them than the range needs.
-static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, uint64_t offset, void *dst, size_t len, size_t *written) {
+// verify: znippy_archive_read_range_verified — the small table gets the chunks' checksums and their cached block trees, and the read is
+// znippy_rows_read_ranges_verified.  A chunk with entries that is touched for the first time is built once (a whole decode whose digest
+// must be the index checksum); afterwards a read hashes only the 128 KiB blocks it returns bytes of.  The blobs come from the file on
+// every call, so damage that appears between two reads is caught for the blocks a read touches.
+static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, uint64_t offset, void *dst, size_t len, size_t *written, int verify = 0) {
     if (!a || !rel || !written || (len && !dst)) return fail(ZNIPPY_E_INVAL, "null argument");
     *written = 0;
     auto it = a->files.find(rel);
     if (it == a->files.end()) return fail(ZNIPPY_E_INVAL, std::string("file not found in archive: ") + rel);
     const auto &c = a->ix.rows.cols;
     const uint64_t end = offset + len < offset ? UINT64_MAX : offset + len;
-    std::vector<uint64_t> bo, bs, us, rr, rb, rl;
-    std::vector<uint8_t> bitmap;
+    std::vector<uint64_t> bo, bs, us, rr, rb, rl, arow;
+    std::vector<uint8_t> bitmap, ck;
     uint64_t sum = 0, total = 0;
     for (uint64_t r : it->second) {  // (sorted by fdata_offset)
         const uint64_t lo = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];  // a stored row is its blob
@@ -1292,6 +1299,7 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
         if ((k & 7) == 0) bitmap.push_back(0);
         if (c[3].u8[r]) bitmap[k >> 3] |= (uint8_t)(1u << (k & 7));
         rr.push_back(k); rb.push_back(x - lo); rl.push_back(y - x);
+        if (verify) { arow.push_back(r); ck.insert(ck.end(), &c[7].u8[32 * r], &c[7].u8[32 * r] + 32); }
         sum += c[6].u64[r];
         total += y - x;
     }
@@ -1314,16 +1322,66 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
     }
     if (!bufs.d_blobs.reserve(sum + 64) || !bufs.d_out.reserve(total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
     if (sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+    int rc = ZNIPPY_OK;
+    if (verify) {  // chunks with entries that this handle has not built yet: one private table, one build
+        auto entries_of = [](uint64_t n) -> uint64_t { return n > (128u << 10) && n < (1ull << 32) ? (n + (128u << 10) - 1) / (128u << 10) : 0; };
+        std::vector<size_t> fresh;
+        for (size_t k = 0; k < bo.size(); k++)
+            if (entries_of(us[k]) && !a->block_trees.count(arow[k])) fresh.push_back(k);
+        if (!fresh.empty()) {
+            std::vector<uint64_t> fbo, fbs, fus;
+            std::vector<uint8_t> fbm((fresh.size() + 7) / 8, 0), fck;
+            uint64_t n_entries = 0;
+            for (size_t i = 0; i < fresh.size(); i++) {
+                const size_t k = fresh[i];
+                fbo.push_back(bo[k]); fbs.push_back(bs[k]); fus.push_back(us[k]);
+                if ((bitmap[k >> 3] >> (k & 7)) & 1) fbm[i >> 3] |= (uint8_t)(1u << (i & 7));
+                fck.insert(fck.end(), &ck[32 * k], &ck[32 * k] + 32);
+                n_entries += entries_of(us[k]);
+            }
+            znippy_rows *bt = nullptr;
+            rc = znippy_rows_create(a->ctx, fbo.data(), fbs.data(), fbm.data(), fus.data(), nullptr, fck.data(), 0, fresh.size(), &bt);
+            if (rc) return fail(rc, "znippy_rows_create failed");
+            znippy_rows_set_blob_cap(bt, sum);
+            std::vector<uint8_t> tree(32 * (size_t)n_entries);
+            std::vector<int32_t> bst(fresh.size(), 0);
+            rc = znippy_rows_block_tree_build(a->ctx, bt, bufs.d_blobs.p, 0, tree.data(), bst.data());
+            znippy_rows_destroy(bt);
+            if (rc) return fail(rc, std::string("block tree build failed: ") + znippy_last_error(a->ctx));
+            for (int32_t v : bst) {
+                if (v == ZNIPPY_E_DIGEST) return fail(ZNIPPY_E_CHECKSUM, std::string("checksum mismatch in ") + rel);
+                if (v < 0) return fail(v, "OpenZL-equivalent decompress failed");
+            }
+            size_t at = 0;
+            for (size_t i = 0; i < fresh.size(); i++) {
+                const size_t nb = 32 * (size_t)entries_of(fus[i]);
+                a->block_trees[arow[fresh[i]]].assign(tree.begin() + at, tree.begin() + at + nb);
+                at += nb;
+            }
+        }
+    }
     znippy_rows *rt = nullptr;
-    int rc = znippy_rows_create(a->ctx, bo.data(), bs.data(), bitmap.data(), us.data(), nullptr, nullptr, 0, bo.size(), &rt);
+    rc = znippy_rows_create(a->ctx, bo.data(), bs.data(), bitmap.data(), us.data(), nullptr, verify ? ck.data() : nullptr, 0, bo.size(), &rt);
     if (rc) return fail(rc, "znippy_rows_create failed");
     znippy_rows_set_blob_cap(rt, sum);
     std::vector<int32_t> st(rr.size(), 0);
-    rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, st.data(), nullptr);
+    if (verify) {
+        std::vector<uint8_t> tree;
+        for (size_t k = 0; k < bo.size(); k++) {
+            auto bt = a->block_trees.find(arow[k]);
+            if (bt != a->block_trees.end()) tree.insert(tree.end(), bt->second.begin(), bt->second.end());
+        }
+        tree.push_back(0);  // (never NULL: that would remove the tree)
+        rc = znippy_rows_set_block_tree(a->ctx, rt, tree.data(), nullptr);
+        if (!rc) rc = znippy_rows_read_ranges_verified(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, st.data(), nullptr, nullptr);
+    } else
+        rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, st.data(), nullptr);
     znippy_rows_destroy(rt);
     if (rc) return fail(rc, std::string("range read failed: ") + znippy_last_error(a->ctx));
-    for (int32_t v : st)
+    for (int32_t v : st) {
+        if (v == ZNIPPY_E_DIGEST) return fail(ZNIPPY_E_CHECKSUM, std::string("checksum mismatch in ") + rel);
         if (v < 0) return fail(v, "OpenZL-equivalent decompress failed");
+    }
     if (hipMemcpy(dst, bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
     *written = total;
     return ZNIPPY_OK;
@@ -1419,6 +1477,10 @@ int znippy_archive_extract_file(znippy_archive *a, const char *rel, void *dst, s
 
 int znippy_archive_read_range(znippy_archive *a, const char *rel, uint64_t offset, void *dst, size_t len, size_t *written) {
     return guarded([&] { return znippy_archive_read_range_impl(a, rel, offset, dst, len, written); });
+}
+
+int znippy_archive_read_range_verified(znippy_archive *a, const char *rel, uint64_t offset, void *dst, size_t len, size_t *written) {
+    return guarded([&] { return znippy_archive_read_range_impl(a, rel, offset, dst, len, written, 1); });
 }
 
 int znippy_index_open(const char *path, znippy_index **out) {

@@ -235,6 +235,68 @@ class RowTable:
                                                          np_ptr(status), C.byref(decoded)), "znippy_rows_read_ranges")
         return status[:n], int(decoded.value)
 
+    def read_ranges_verified(self, d_blobs, rows, begins, lens, d_out, out_offsets=None, blob_base=0, out_cap=None, blob_cap=None):
+        """read_ranges on a table with a checksum column, where a range reports 0 only if every byte it returns was covered
+        by a hash that chains to the row's checksum (znippy_rows_read_ranges_verified): block by block for rows whose
+        entries are installed and accepted (set_block_tree), whole rows otherwise.  A block or row that fails gives
+        ZNIPPY_E_DIGEST to every range that overlaps it, and nothing of such a range is written.  Returns (status per range,
+        content bytes decoded, content bytes hashed)."""
+        rr, rb, rl = as_np(rows, np.uint64), as_np(begins, np.uint64), as_np(lens, np.uint64)
+        ro = as_np(out_offsets, np.uint64) if out_offsets is not None else None
+        n = len(rr)
+        assert len(rb) == n and len(rl) == n and (ro is None or len(ro) == n), "range arrays differ in length"
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        if blob_cap is None and not isinstance(d_blobs, int):
+            blob_cap = d_blobs.numel()
+        if blob_cap is not None:
+            self.ctx._chk(self.ctx.L.znippy_rows_set_blob_cap(self.h, int(blob_cap)), "znippy_rows_set_blob_cap")
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        decoded, hashed = C.c_uint64(), C.c_uint64()
+        self.ctx._chk(self.ctx.L.znippy_rows_read_ranges_verified(self.ctx.h, self.h, _dptr(d_blobs), blob_base, np_ptr(rr), np_ptr(rb),
+                                                                  np_ptr(rl), np_ptr(ro) if ro is not None else None, n, _dptr(d_out),
+                                                                  out_cap, np_ptr(status), C.byref(decoded), C.byref(hashed)),
+                      "znippy_rows_read_ranges_verified")
+        return status[:n], int(decoded.value), int(hashed.value)
+
+    def block_tree_layout(self):
+        """(n_entries, row_first): the table's block tree has one 32-byte entry per 128 KiB block of every row of more than
+        one block (and below 4 GiB); row i's entries are [row_first[i], row_first[i + 1])."""
+        n = C.c_uint64()
+        first = np.zeros(self.n + 1, dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.znippy_rows_block_tree_layout(self.ctx.h, self.h, C.byref(n), np_ptr(first)), "znippy_rows_block_tree_layout")
+        return int(n.value), first
+
+    def build_block_tree(self, d_blobs, blob_base=0, blob_cap=None):
+        """Compute the block tree from the blobs (znippy_rows_block_tree_build): (tree uint8[n_entries, 32], status per row —
+        0, a decode error, ZNIPPY_E_CORRUPT for a blob outside the region, ZNIPPY_E_DIGEST when the entries do not fold to the
+        row's checksum; such a row's entries are zeros).  Does not install the tree."""
+        if blob_cap is None and not isinstance(d_blobs, int):
+            blob_cap = d_blobs.numel()
+        if blob_cap is not None:
+            self.ctx._chk(self.ctx.L.znippy_rows_set_blob_cap(self.h, int(blob_cap)), "znippy_rows_set_blob_cap")
+        n, _ = self.block_tree_layout()
+        tree = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        status = np.zeros(max(self.n, 1), dtype=np.int32)
+        self.ctx._chk(self.ctx.L.znippy_rows_block_tree_build(self.ctx.h, self.h, _dptr(d_blobs), blob_base, np_ptr(tree), np_ptr(status)),
+                      "znippy_rows_block_tree_build")
+        return tree[:n], status[:self.n]
+
+    def set_block_tree(self, tree):
+        """Install a block tree (uint8, 32 bytes per entry, from anywhere) or remove it (None).  Every row's entries are
+        authenticated against its checksum: status per row is 0 (accepted, or a row without entries) or ZNIPPY_E_DIGEST
+        (rejected: the row is verified whole from then on)."""
+        status = np.zeros(max(self.n, 1), dtype=np.int32)
+        t = None
+        if tree is not None:
+            t = as_np(tree, np.uint8).reshape(-1)
+            n, _ = self.block_tree_layout()
+            assert t.size == 32 * n, "the tree has 32 bytes per entry of block_tree_layout()"
+            if not t.size:
+                t = np.zeros(1, dtype=np.uint8)  # (a table without entries: NULL would mean "remove")
+        self.ctx._chk(self.ctx.L.znippy_rows_set_block_tree(self.ctx.h, self.h, np_ptr(t) if t is not None else None, np_ptr(status)),
+                      "znippy_rows_set_block_tree")
+        return status[:self.n]
+
     def verify_async(self, d_blobs, blob_base=0, blob_cap=None):
         """Queue a verify-only run (the read loop with save_data=false, decompress.rs:L186-189): same results calls, same
         counters, corrupt list, status and digests as a decode run over these blobs, and no output."""
