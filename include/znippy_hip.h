@@ -80,7 +80,8 @@ int znippy_ctx_level(const znippy_ctx *ctx);
 int znippy_ctx_set_window_log(znippy_ctx *ctx, int window_log);
 int znippy_ctx_window_log(const znippy_ctx *ctx);
 const char *znippy_last_error(const znippy_ctx *ctx);
-/* Block until everything queued on the context's stream has finished. */
+/* Block until everything the context has queued has finished: its stream, and the streams of its own that carry a part of a
+ * run beside it (a read run's verify and counters, the write side's hash and result copy). */
 int znippy_ctx_sync(znippy_ctx *ctx);
 
 /* ---- (1) bounds ---------------------------------------------------------------------- */
@@ -163,7 +164,13 @@ int znippy_rows_set_blob_cap(znippy_rows *rows, uint64_t blob_cap);
  * and digests (znippy_rows_results, znippy_rows_digests) again describe the latest run.  d_blobs / d_out of a queued run
  * must therefore stay valid until its results have been read, and those of the latest run until the run before it has
  * been read as well (ZNIPPY_NO_LEAN=1 in the environment of znippy_ctx_create: every run is a full one).  A failed
- * queueing call that had already queued work leaves the table with no readable run. */
+ * queueing call that had already queued work leaves the table with no readable run.
+ * Ordering: a run's kernels that write d_out are queued on the context's stream, so work queued there behind the call sees
+ * the bytes of every row the run decoded.  The run's verify, its counters and the event the results calls wait for may be
+ * queued on a stream of the context's own beside the NEXT run's kernels (a table keeps two sets of control block, status
+ * column, digests and corrupt list — 44 bytes per row more — and run k uses set k & 1): the context's stream alone does
+ * not order them.  Every results call, znippy_ctx_sync and the destroy calls wait for them (ZNIPPY_NO_FORK_VERIFY=1 in the
+ * environment of znippy_ctx_create: every run's verify on the context's stream, as before). */
 int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs,
                               uint64_t blob_base, void *d_out, uint64_t out_cap,
                               znippy_verify_counters *counters, uint64_t *corrupt_rows,

@@ -131,7 +131,7 @@ struct znippy_ctx {
         unsigned lds_pad = 0;    // ZNIPPY_LDS_PAD
         int store_g = 0;         // ZNIPPY_STORE_G: tiles per wave of the store path kernel (0 = from the tile count)
         bool no_block_items = false, no_fused_blocks = false, ddbg = false, edbg = false, no_fused_store = false,
-             nohash = false, no_roles = false, no_fz = false, fz_only = false, no_bx = false, tdbg = false, no_fuse_hash = false, trace = false, no_rx = false, no_pack = false, no_lean = false, no_stored_only = false;
+             no_fork_verify = false, nohash = false, no_roles = false, no_fz = false, fz_only = false, no_bx = false, tdbg = false, no_fuse_hash = false, trace = false, no_rx = false, no_pack = false, no_lean = false, no_stored_only = false;
         // ZNIPPY_ROLES_MIN: small tiles from which the role-split persistent kernel takes the table (0 = never; below
         // a few CU-fillings a persistent grid only adds start-up latency)
         unsigned roles_min = 2048;
@@ -140,6 +140,10 @@ struct znippy_ctx {
         int ktime = 2;  // per-kernel HIP events: 2 = every kernel, 1 = the dominant read kernels only, 0 = none
     } sw;
     int cus = 256;
+    // A lean run's verify is queued on the auxiliary stream, beside the next run's role-split kernel (run_verify): decided at
+    // creation from what the two kernels take of a CU — a verify that cannot be resident beside that persistent kernel would
+    // wait a whole step and stall the caller's lagged read
+    bool fork_verify = false;
     // Lifetime (znippy_hip.h): tables hold a reference to their context.  znippy_ctx_destroy with tables still alive only
     // closes the context (every call on it fails with ZNIPPY_E_INVAL from then on); its memory and device resources go
     // when the last table is destroyed.
@@ -167,6 +171,7 @@ static void read_switches(znippy_ctx *ctx) {
     ctx->sw.tdbg = on("ZNIPPY_TDBG");
     ctx->sw.trace = on("ZNIPPY_TRACE");
     ctx->sw.no_lean = on("ZNIPPY_NO_LEAN");  // A/B: every run launches the kernels behind the role-split one
+    ctx->sw.no_fork_verify = on("ZNIPPY_NO_FORK_VERIFY");  // A/B, tests: every run's verify on the main stream, in front of the next run
     ctx->sw.no_pack = on("ZNIPPY_NO_PACK");  // A/B: the index columns always as four 64-bit copies
     if (const char *e = getenv("ZNIPPY_STORE_G")) ctx->sw.store_g = atoi(e) == 1 ? 1 : (atoi(e) == 2 ? 2 : 0);  // A/B, tests: tiles per wave of the store path kernel
     ctx->sw.no_stored_only = on("ZNIPPY_NO_STORED_ONLY");  // A/B: tables without a compressed row through the fused small-row kernels (until round 3's last day)
@@ -416,6 +421,20 @@ struct znippy_rows {
     int32_t *status = nullptr;
     uint32_t *digests = nullptr;
     uint64_t *counters = nullptr;
+    // Two slots of the per-run device state, like the mirror below: run k owns control block, digest column and corrupt list
+    // k & 1, so the verify of run k need not stand between the main kernels of run k and run k + 1 (run_verify).  ctl,
+    // status, counters, digests and corrupt above are the slot of the run queued LAST (select: rows_launch, behind the run's
+    // allocations), which is what the "latest run" outputs read and what a run's stages are given.
+    uint8_t *ctl_m[2] = {nullptr, nullptr};
+    uint32_t *digests_m[2] = {nullptr, nullptr};
+    uint64_t *corrupt_m[2] = {nullptr, nullptr};
+    void select(unsigned slot) {
+        ctl = ctl_m[slot]; digests = digests_m[slot]; corrupt = corrupt_m[slot];
+        counters = ctl_at<uint64_t>(CTL_COUNTERS);
+        status = reinterpret_cast<int32_t *>(ctl + CTL_HEAD);
+    }
+    hipEvent_t ev_main[2] = {nullptr, nullptr};  // forked verify: the end of the run's kernels on the main stream
+    bool aux_used = false;  // a verify of this table was ever queued on the auxiliary stream (whoever reuses a slot or frees the table joins it)
     // pinned mirror of the counters, filled by the run's own D2H copy.  Two slots + one event each: run k uses slot
     // k & 1, so the counters of run k can be read while run k + 1 is already executing (znippy_rows_results_lagged)
     uint64_t *h_counters = nullptr;  // per slot CTL_MIRROR bytes (16 x u64): the counters, then the 16 hand-over counts (u32)
@@ -998,6 +1017,12 @@ int znippy_ctx_create(int device, void *hip_stream, znippy_ctx **out) {
         ctx->encode_grid = cus * 8;         // 16 KiB hash table per wave
         ctx->encode_grid_small = cus * 16;  // 4 KiB hash table per wave
     }
+    if (!ctx->sw.no_fork_verify) {
+        // gfx950: 512 registers per SIMD lane handed out in blocks of 8, 160 KiB of LDS per CU; a workgroup of k_verify is one wave per SIMD
+        int rr = 0, rw = 0, rl = 0, vr = 0, vl = 0;
+        if (roles_footprint(&rr, &rw, &rl) == 0 && verify_footprint(&vr, &vl) == 0)
+            ctx->fork_verify = rw * ((rr + 7) / 8 * 8) + (vr + 7) / 8 * 8 <= 512 && rl + vl <= 160 * 1024 && rw + 1 <= 8;
+    }
     *out = ctx;
     return ZNIPPY_OK;
 }
@@ -1008,6 +1033,7 @@ void znippy_ctx_destroy(znippy_ctx *ctx) {
     if (ctx->live_tables) {  // tables outlive the call: they keep the context's memory until the last of them is destroyed
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
+        if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
         ctx->closing = true;
         return;
     }
@@ -1019,6 +1045,7 @@ static void table_released(znippy_ctx *ctx) {
 static void ctx_teardown(znippy_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
     for (auto &k : ctx->ktimes) { (void)hipEventDestroy(k.t0); (void)hipEventDestroy(k.t1); }
     void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor, ctx->vs_pool, ctx->rr_pool[0], ctx->rr_pool[1],
                    ctx->clk_buf, ctx->shim_in, ctx->shim_out, ctx->enc_prov, ctx->enc_seq, ctx->enc_tabs, ctx->ldm};
@@ -1042,6 +1069,7 @@ int znippy_ctx_sync(znippy_ctx *ctx) {
     if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
     if (!ctx) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (ctx->aux) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // a run's verify and result copy may be queued there (run_verify)
     if (ctx->copy) HIPCHK(ctx, hipStreamSynchronize(ctx->copy));
     return ZNIPPY_OK;
 }
@@ -1164,15 +1192,18 @@ void znippy_rows_destroy(znippy_rows *r) {
     if (!r) return;
     (void)hipSetDevice(r->ctx->device);
     void *ptrs[] = {r->blob_off, r->blob_size, r->usize, r->out_off, r->compressed, r->checksum,
-                    r->ctl, r->digests, r->corrupt, r->list_a, r->pending,
+                    r->ctl_m[0], r->ctl_m[1], r->digests_m[0], r->digests_m[1], r->corrupt_m[0], r->corrupt_m[1], r->list_a, r->pending,
                     r->cand_row, r->cand_base, r->cand_nblocks, r->fz_base, r->fz_cap, r->fz_it_cand, r->fz_nb, r->fz_work, r->fz_items, r->item_row, r->item_k, r->item_src, r->row_flag, r->pending2,
                     r->bt_tile, r->bt_item, r->tile_done, r->todo, r->status_init, r->slow_list,
                     r->bx_cand_row, r->bx_cand_base, r->bx_cand_nb, r->bx_huf_list, r->bx_seq_list, r->bx_items, r->bx_prep, r->d_bitmap, r->bx_sort_tmp,
                     r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off, r->tree_dev};
+    // (the pool hands these buffers to the next table, whose work is ordered on the main stream: what this table still has on
+    // the auxiliary stream — a forked verify — is joined into it first)
+    if (r->aux_used && hipEventRecord(r->ctx->ev_join, r->ctx->aux) == hipSuccess) (void)hipStreamWaitEvent(r->ctx->stream, r->ctx->ev_join, 0);
     for (void *p : ptrs)
         tfree(r->ctx, p);
     if (r->h_counters) {
-        (void)hipStreamSynchronize(r->ctx->stream);  // a queued run may still copy into the slot
+        (void)hipStreamSynchronize(r->ctx->stream);  // a queued run may still write into the slot
         pinned_give(r->ctx, r->h_counters, r->h_counters_cap);
     }
     if (r->h_pack) {
@@ -1180,6 +1211,7 @@ void znippy_rows_destroy(znippy_rows *r) {
         pinned_give(r->ctx, r->h_pack, r->h_pack_cap);
     }
     for (hipEvent_t e : r->ev_done) event_give(r->ctx, e);
+    for (hipEvent_t e : r->ev_main) event_give(r->ctx, e);
     free_plan(r->ctx, r->plan);
     znippy_ctx *const c = r->ctx;
     delete r;
@@ -1398,14 +1430,14 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
     if (rc) return rc;
     r->corrupt_cap = std::max<uint32_t>(n, 1);
     r->ctl_bytes = CTL_HEAD + std::max<size_t>(4 * (size_t)n, 16);
-    if (tmalloc(ctx, &r->ctl, r->ctl_bytes) != hipSuccess ||
-        tmalloc(ctx, &r->digests, std::max<size_t>(32 * (size_t)n, 32)) != hipSuccess ||
-        !(r->h_counters = (uint64_t *)pinned_take(ctx, 256, &r->h_counters_cap)) ||
-        !(r->ev_done[0] = event_take(ctx)) || !(r->ev_done[1] = event_take(ctx)) ||
-        tmalloc(ctx, &r->corrupt, 8 * (size_t)r->corrupt_cap) != hipSuccess)
-        return ZNIPPY_E_NOMEM;
-    r->counters = r->ctl_at<uint64_t>(CTL_COUNTERS);
-    r->status = reinterpret_cast<int32_t *>(r->ctl + CTL_HEAD);
+    for (int s = 0; s < 2; s++)
+        if (tmalloc(ctx, &r->ctl_m[s], r->ctl_bytes) != hipSuccess ||
+            tmalloc(ctx, &r->digests_m[s], std::max<size_t>(32 * (size_t)n, 32)) != hipSuccess ||
+            tmalloc(ctx, &r->corrupt_m[s], 8 * (size_t)r->corrupt_cap) != hipSuccess ||
+            !(r->ev_done[s] = event_take(ctx)) || !(r->ev_main[s] = event_take(ctx)))
+            return ZNIPPY_E_NOMEM;
+    if (!(r->h_counters = (uint64_t *)pinned_take(ctx, 256, &r->h_counters_cap))) return ZNIPPY_E_NOMEM;
+    r->select(0);
     td.mark("allocs");
     PlanBuf p;
     // a stored row IS its blob (see k_rows_fixup): its effective length is blob_size.  (allc and the column pointers by value: the pass over
@@ -1651,6 +1683,8 @@ static void decode_rest(znippy_ctx *ctx, const znippy_rows *r, DecodeArgs a, uin
 // counters, hand-over counts, work cursors and the status column: one stream operation
 static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     hipStream_t s = ctx->stream;
+    // (the slot's last user — the run before last — may have had its verify on the auxiliary stream: long done in a steady pipeline)
+    if (r->aux_used) HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_done[run.slot], 0));
     if (run.preset) HIPCHK(ctx, hipMemcpyAsync(r->ctl, r->status_init, r->ctl_bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(r->ctl, 0, r->ctl_bytes, s));
     // (the second hash pass looks at small tiles only when rows were handed over)
@@ -1942,6 +1976,15 @@ static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const R
     hipStream_t s = ctx->stream;
     if (p.lean_mixed) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
     const bool skipped = p.lean || p.lean_blocks || p.lean_mixed;
+    // A lean run has nothing between its one kernel and the verify, and nothing of the NEXT run's kernels reads what the verify
+    // writes (the other slot is theirs): verify, result copy and the run's event go to the auxiliary stream behind an event, and
+    // the next run's kernel follows this run's directly.  The slot's next run is ordered behind ev_done (run_clear).
+    if (ctx->fork_verify && p.lean) {
+        HIPCHK(ctx, hipEventRecord(r->ev_main[run.slot], s));
+        s = ctx->aux;
+        HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_main[run.slot], 0));
+        r->aux_used = true;
+    }
     // (decode-only: the counters pass alone — no checksum column, no digest read, every decoded row counts as verified)
     timed(ctx, run.plain ? "count_rows" : "verify", s, [&] {
         launch_verify(r->digests, run.plain ? nullptr : r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt, r->corrupt_cap, s,
@@ -1992,6 +2035,7 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, ctx->stream, r->all_rows, r->n);
     }
     { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = verify ? nullptr : d_out; ra.cap = verify ? 0 : out_cap; ra.blob_cap = r->blob_cap; ra.verify = verify; ra.plain = plain; }
+    r->select(slot);
     if (queued) *queued = true;
     if ((rc = run_clear(ctx, r, p, run)) || !r->n) return rc;
     if (!p.small_off && !p.stored_only && (rc = run_small_rows(ctx, r, p, run))) return rc;
@@ -2086,6 +2130,7 @@ static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
     if (!r->n || !r->run_seq || !(r->h_counters[16 * slot + 7])) return ZNIPPY_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     r->force_full = true;
     r->lean_hint = 0; r->lean_hint2 = 0;
     const unsigned latest = (unsigned)((r->run_seq - 1) & 1);
@@ -2130,6 +2175,7 @@ int znippy_rows_results(znippy_ctx *ctx, znippy_rows *r, znippy_verify_counters 
     if (!ctx || !r) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (r->aux_used) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     uint64_t c[8] = {0};
     if (r->n && r->run_seq) {
         { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
@@ -2763,6 +2809,7 @@ int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
     if (!ctx || !r || !digests) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (r->aux_used) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     if (r->n && r->run_seq) { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
     if (r->run_seq && r->run_args[(r->run_seq - 1) & 1].plain) return ZNIPPY_E_INVAL;  // a decode-only run computes no digest
     if (r->n) HIPCHK(ctx, hipMemcpy(digests, r->digests, 32 * (size_t)r->n, hipMemcpyDeviceToHost));

@@ -141,6 +141,9 @@ void launch_merge_big(const BigUnit *big, uint32_t n_big, uint32_t *tile_cv, uin
 void launch_verify(const uint32_t *digests, const uint8_t *checksum, const uint64_t *usize,
                    const int32_t *status, uint32_t n_rows, uint64_t row_begin, uint64_t *counters,
                    uint64_t *corrupt_rows, uint32_t corrupt_cap, hipStream_t s, const uint32_t *lean_lists = nullptr, uint32_t lean_mask = 0);
+// what the two kernels take of a CU, from hipFuncGetAttributes (-1: not known)
+int verify_footprint(int *regs, int *lds);
+int roles_footprint(int *regs, int *waves_per_simd, int *lds);
 int decode_grid_size(int device);
 void launch_decode(const DecodeArgs &a, int grid, bool wide, hipStream_t s);
 // block-item path: header scan of the candidate frames, then (after the block-mode decode) the per-row verdict

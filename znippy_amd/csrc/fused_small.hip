@@ -1638,6 +1638,16 @@ void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify)
     else hipLaunchKernelGGL(k_fused_roles<true>, dim3(grid), dim3(R_WAVES * 64), sizeof(RolesShared), s, a);
 }
 
+// what the decode + verify instantiation holds of a CU while it runs (registers per lane, waves per SIMD, LDS bytes), as
+// launch_fused_roles sizes its grid
+int roles_footprint(int *regs, int *waves_per_simd, int *lds) {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_fused_roles<true>)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    const int per_cu = sizeof(RolesShared) > 80 * 1024 ? 1 : 2;
+    *regs = fa.numRegs; *waves_per_simd = (int)(R_WAVES * per_cu + 3) / 4; *lds = per_cu * (int)(sizeof(RolesShared) + fa.sharedSizeBytes);
+    return 0;
+}
+
 // ---- big rows: block items of the common shape --------------------------------------------------------
 // A frame written block by block from periodic data (a 2 GiB text file in 8 MiB or 200 MiB rounds) is thousands of
 // 128 KiB blocks, each "literals + one sequence repeating a period inside them" — the shape parse_fast_block

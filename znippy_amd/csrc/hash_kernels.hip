@@ -343,33 +343,39 @@ __global__ __launch_bounds__(256) void k_verify(const uint32_t *digests, const u
         for (uint32_t i = 0; i < 8; i++) if ((lean_mask >> i) & 1u) any |= lean_lists[i];
         if (any) counters[7] = 1;
     }
-    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
+    // (five accumulators, not six 64-bit ones — rows are counted in 32 bits and the written bytes are the sum of the verified and the
+    // corrupt ones — and the digest compared half by half: the kernel stays within 32 registers, so that a workgroup of it fits on
+    // a CU beside the role-split kernel's sixteen waves when the run's verify is queued beside the next run, api.hip: run_verify)
+    uint32_t n_all = 0, n_bad = 0, n_err = 0;
+    unsigned long long ok_bytes = 0, bad_bytes = 0;
     // grid-stride: a few dozen workgroups, so that the counters' cache line takes a few hundred atomics per run
     // (one workgroup per 256 rows put 1,200 on it for 100k rows: ~13 us of the step)
     for (uint32_t r = blockIdx.x * 256 + threadIdx.x; r < n_rows; r += gridDim.x * 256) {
-        v[0] += 1;
+        n_all += 1;
         if (status && status[r] < 0) {
-            v[5] += 1;
+            n_err += 1;
         } else {
             const unsigned long long len = usize[r];
-            v[1] += len;
             bool ok = true;
             if (checksum) {
                 const uint4 *want = reinterpret_cast<const uint4 *>(checksum) + (size_t)r * 2;
                 const uint4 *got = reinterpret_cast<const uint4 *>(digests) + (size_t)r * 2;
-                const uint4 w0 = want[0], w1 = want[1], g0 = got[0], g1 = got[1];
-                ok = w0.x == g0.x && w0.y == g0.y && w0.z == g0.z && w0.w == g0.w &&
-                     w1.x == g1.x && w1.y == g1.y && w1.z == g1.z && w1.w == g1.w;
+                uint4 w = want[0], g = got[0];
+                uint32_t d = (w.x ^ g.x) | (w.y ^ g.y) | (w.z ^ g.z) | (w.w ^ g.w);
+                w = want[1]; g = got[1];
+                d |= (w.x ^ g.x) | (w.y ^ g.y) | (w.z ^ g.z) | (w.w ^ g.w);
+                ok = d == 0;
             }
-            if (ok) v[2] += len;
+            if (ok) ok_bytes += len;
             else {
-                v[3] += len;
-                v[4] += 1;
+                bad_bytes += len;
+                n_bad += 1;
                 unsigned long long slot = atomicAdd(&counters[6], 1ull);
                 if (corrupt_rows && slot < corrupt_cap) corrupt_rows[slot] = row_begin + r;
             }
         }
     }
+    const unsigned long long v[6] = {n_all, ok_bytes + bad_bytes, ok_bytes, bad_bytes, n_bad, n_err};
     __shared__ unsigned long long red[6][4];
 #pragma unroll
     for (int c = 0; c < 6; c++) {
@@ -391,6 +397,15 @@ void launch_verify(const uint32_t *digests, const uint8_t *checksum, const uint6
     if (!n_rows) return;
     hipLaunchKernelGGL(k_verify, dim3(std::min<uint32_t>((n_rows + 255) / 256, 128)), dim3(256), 0, s, digests, checksum, usize, status,
                        n_rows, row_begin, reinterpret_cast<unsigned long long *>(counters), corrupt_rows, corrupt_cap, lean_lists, lean_mask);
+}
+
+// what a workgroup of k_verify takes of a CU (registers per lane, static LDS bytes): api.hip decides with it whether the kernel
+// can be resident beside the role-split kernel
+int verify_footprint(int *regs, int *lds) {
+    hipFuncAttributes fa;
+    if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_verify)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+    *regs = fa.numRegs; *lds = (int)fa.sharedSizeBytes;
+    return 0;
 }
 
 // ---- measurement hook: the VALU floor of the hash ------------------------------------------------------------
