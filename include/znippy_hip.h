@@ -356,6 +356,25 @@ int znippy_rounds_set_store_incompressible(znippy_rounds *rounds, int on);
  * back": readers get its offsets from the blob_offset column, as for any index. */
 int znippy_rounds_set_blob_align(znippy_rounds *rounds, uint32_t align);
 uint32_t znippy_rounds_blob_align(const znippy_rounds *rounds); /* 1 for a NULL table */
+/* Opt-in block tree from the write side ("block tree" above): the hash of a round above 64 KiB already computes the non-root
+ * chaining value of every 64 KiB tile, a 128 KiB block is two tiles, so one small kernel behind the hash (kernel time:
+ * block_tree_entries) turns them into the entries of the archive rows these rounds become — no input byte is read a second time,
+ * where znippy_rows_block_tree_build decodes and hashes every multi-block row whole.
+ * znippy_rounds_emit_block_tree: OFF by default; applies to later znippy_encode_hash_rounds[_async] calls on this table; runs
+ * already queued keep the setting they were queued with, also while two runs are in flight.  The first switch-on makes every
+ * allocation the feature needs (no queueing call allocates for it): the list of rounds with entries and, per slot of the two-run
+ * ring, a device tree buffer and a pinned host mirror.  With emission off no launch, allocation or result differs from a table that
+ * was never asked.  A NULL table or a closed context gives ZNIPPY_E_INVAL.
+ * znippy_rounds_block_tree_layout: znippy_rows_block_tree_layout with len = the round's source length; round_first (HOST, n + 1
+ * values) is optional; works whether emission is on or off.
+ * znippy_rounds_block_tree: the tree of the run `lag` (0 or 1) runs before the latest queued one, into `tree` (HOST, 32 * n_entries
+ * bytes; may be NULL when n_entries is 0).  The tree leaves on the copy stream with that run's results and the call waits for that
+ * copy only.  ZNIPPY_E_INVAL if there is no such run or it was queued with emission off.
+ * The entries are byte for byte what znippy_rows_block_tree_build returns for those rows: they depend on the source bytes alone —
+ * not on level, window, store_incompressible, blob alignment or the hash route.  znippy_hash_rounds emits nothing. */
+int znippy_rounds_emit_block_tree(znippy_rounds *rounds, int on);
+int znippy_rounds_block_tree_layout(znippy_ctx *ctx, znippy_rounds *rounds, uint64_t *n_entries, uint64_t *round_first);
+int znippy_rounds_block_tree(znippy_ctx *ctx, znippy_rounds *rounds, unsigned lag, uint8_t *tree);
 /* Upper bound of the blob bytes znippy_encode_hash_rounds can produce for this batch. */
 uint64_t znippy_rounds_blob_bound(const znippy_rounds *rounds);
 

@@ -55,7 +55,15 @@ const char *znippy_host_last_error(void);
 /* ZNIPPY_HOST_BLOB_ALIGN=<1|2|...|4096> in the environment (read when a pipeline starts, beside ZNIPPY_HOST_SLOT_MB; an
  * invalid value is 1): every blob_offset of the archive znippy_compress_stream / znippy_compress_dir write is a multiple of
  * it — znippy_rounds_set_blob_align on every slot's rounds table, and every slot written at an aligned offset.  The gaps
- * read as zeros, nothing is added behind the last blob, and the read side needs nothing. */
+ * read as zeros, nothing is added behind the last blob, and the read side needs nothing.
+ * ZNIPPY_HOST_BLOCK_TREE=1 in the environment (read at the same moment): both pipelines switch znippy_rounds_emit_block_tree on for
+ * every slot's rounds table, fetch each slot's block tree after its encode, keep it by row and, when the metadata layer is written,
+ * write the sidecar `<output>.znippy.b3t` beside the archive.  The archive's bytes do not depend on it.  Unset or 0: nothing is
+ * emitted and no .b3t file is created, touched or removed.
+ * The sidecar, little-endian: 8 bytes "ZNPYB3T1"; u32 block log = 17; u32 zero; u64 n_rows — all rows of the archive, in the order
+ * znippy_index_* numbers them; u64 n_entries; then the entries, 32 bytes each, concatenated in row order, in the layout
+ * znippy_rows_block_tree_layout gives for a table made from the index columns.  The file is exactly 32 + 32 * n_entries bytes.  It
+ * has no checksum of its own: the index's checksum column authenticates every row's entries. */
 int znippy_compress_stream(const char *output, int no_skip, int device, znippy_stream **out);
 /* pkg_type < 0 = None, repo NULL = None (ArchiveEntry, stream_packer.rs:L34-44). Data is copied (once, into
  * page-locked staging); full staging slots are encoded while the caller keeps sending. */
@@ -110,9 +118,18 @@ int znippy_archive_read_range(znippy_archive *a, const char *relative_path, uint
  * otherwise; every verified read then installs the cached entries of the chunks it touches (authenticated against the checksum
  * again, znippy_rows_set_block_tree) and hashes only the blocks the range overlaps.  Chunks of at most one block are hashed whole.
  * Blobs are read from the archive file on every call, as for znippy_archive_read_range: damage that appears between two reads is
- * caught for the blocks a read touches. */
+ * caught for the blocks a read touches.
+ * With a sidecar (znippy_archive_open reads `<path>.b3t` if it exists; one that is missing, malformed, or whose n_rows or n_entries
+ * disagree with the index is ignored and the open succeeds as without it): the first verified touch of such a chunk offers the
+ * sidecar's entries to znippy_rows_set_block_tree instead.  Accepted entries go into the cache without any decode; a rejected chunk
+ * falls back to the whole-decode build.  A damaged or forged sidecar therefore costs time, never correctness.  One behaviour comes
+ * with it: a fresh handle that reads an undamaged block of a chunk damaged elsewhere succeeds, because only the touched blocks are
+ * hashed; without a sidecar that first touch decodes the whole chunk and gives ZNIPPY_E_CHECKSUM. */
 int znippy_archive_read_range_verified(znippy_archive *a, const char *relative_path, uint64_t offset, void *dst, size_t len,
                                        size_t *written);
+/* stats[0] entries loaded from the sidecar at open (0: none in use); [1] chunks whose sidecar entries were accepted; [2] chunks
+ * whose sidecar entries were rejected; [3] chunks whose entries were built by a whole decode. */
+int znippy_archive_block_tree_stats(const znippy_archive *a, uint64_t stats[4]);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

@@ -52,6 +52,7 @@ EXPORTS = [
     "znippy_rows_read_ranges",
     "znippy_rows_block_tree_layout", "znippy_rows_block_tree_build", "znippy_rows_set_block_tree",
     "znippy_rows_read_ranges_verified",
+    "znippy_rounds_emit_block_tree", "znippy_rounds_block_tree_layout", "znippy_rounds_block_tree",
 ]
 
 
@@ -139,6 +140,10 @@ def lib():
         L.znippy_rows_set_block_tree.argtypes = [vp, vp, vp, vp]
         L.znippy_rows_read_ranges_verified.argtypes = [vp, vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, C.c_uint64, vp,
                                                        C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    if hasattr(L, "znippy_rounds_emit_block_tree"):  # (likewise)
+        L.znippy_rounds_emit_block_tree.argtypes = [vp, C.c_int]
+        L.znippy_rounds_block_tree_layout.argtypes = [vp, vp, C.POINTER(C.c_uint64), vp]
+        L.znippy_rounds_block_tree.argtypes = [vp, vp, C.c_uint, vp]
     _lib = L
     return L
 

@@ -581,6 +581,16 @@ struct znippy_rounds {
     uint32_t ldm_chunks = 0;
     LdmRound *d_ldm = nullptr;
     uint64_t *d_ldm_desc = nullptr;  // per round: its region (LDM_NONE: not indexed)
+    // block tree (opt-in, znippy_rounds_emit_block_tree): the runs queued while it is on leave their entries in the slot's buffer
+    bool emit_tree = false;
+    bool tree_run[2] = {false, false};  // the run in this slot was queued with emission on
+    std::vector<uint64_t> tree_first;   // round i's entries are [tree_first[i], tree_first[i + 1]) (made by the first call that asks)
+    TreeUnit *tree_units = nullptr;     // the big units with entries + a sentinel (made by the first switch-on, as everything below)
+    uint32_t n_tree_units = 0, n_tree_entries = 0;
+    bool tree_ready = false;
+    uint32_t *tree_m[2] = {nullptr, nullptr};
+    uint8_t *h_tree_m[2] = {nullptr, nullptr};
+    size_t h_tree_cap_m[2] = {0, 0};
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -2836,7 +2846,10 @@ void znippy_rounds_destroy(znippy_rounds *r) {
         pinned_give(r->ctx, r->h_res_m[k], r->h_res_cap_m[k]);
         event_give(r->ctx, r->ev_enc[k]);
         event_give(r->ctx, r->ev_res[k]);
+        pinned_give(r->ctx, r->h_tree_m[k], r->h_tree_cap_m[k]);
+        tfree(r->ctx, r->tree_m[k]);
     }
+    tfree(r->ctx, r->tree_units);
     void *ptrs[] = {r->src_off, r->len, r->skip, r->res_m[0], r->res_m[1], r->items, r->piece_len, r->piece_len_init,
                     r->piece_start, r->local_excl, r->block_tot, r->first_item, r->piece_pad, r->stored, r->order_small, r->order_wide, r->retry_list, r->retry_count,
                     r->plan_scratch[0], r->plan_scratch[1], r->plan_scratch[2], r->d_ldm, r->d_ldm_desc};
@@ -2946,8 +2959,9 @@ uint64_t znippy_rounds_blob_bound(const znippy_rounds *r) {
 // d_copy_out != nullptr: the stored (skip) rounds are copied to d_copy_out + blob_offset[round] while they are hashed
 // (store-heavy tables; blob_offset must have been computed on the stream before)
 // copy_align: the alignment of the run's blob offsets (16 and more: every destination is as aligned as d_copy_out is)
+// tree_out != nullptr: the run's block tree entries (znippy_rounds_emit_block_tree), made from the tile CVs behind the merge
 static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, hipStream_t on = nullptr,
-                             void *d_copy_out = nullptr, uint64_t copy_cap = 0, uint32_t copy_align = 1) {
+                             void *d_copy_out = nullptr, uint64_t copy_cap = 0, uint32_t copy_align = 1, uint32_t *tree_out = nullptr) {
     hipStream_t s = on ? on : ctx->stream;
     HashArgs h{};
     h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
@@ -2971,6 +2985,13 @@ static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_sr
         // four free wave slots on one CU, which the encoder's waves leave only when they retire (seen: 53 ms behind a 65 ms encode)
         launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, r->digests, r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, on ? 0xFFFFFFFFu : r->plan.max_cvs, s);
         ktime_end(ctx, s);
+        // same stream, directly behind the merge: whatever orders the merge (ev_join, the main stream) orders this too, and the
+        // next run's hash, which overwrites tile_cv, is behind it as it is behind the merge
+        if (tree_out) {
+            ktime_begin(ctx, "block_tree_entries", s);
+            launch_round_block_entries(r->tree_units, r->n_tree_units, r->n_tree_entries, r->plan.tile_cv, tree_out, s);
+            ktime_end(ctx, s);
+        }
     }
     HIPCHK(ctx, hipGetLastError());
     return ZNIPPY_OK;
@@ -3112,6 +3133,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     const bool far = window_log && ensure_ldm(ctx, r);  // allocations before the first stream operation of the call
     const uint32_t align = r->blob_align;  // this run's value: a later znippy_rounds_set_blob_align does not reach it
     const uint32_t *const pad = align > 1 ? r->piece_pad : nullptr;
+    const bool emit_tree = r->emit_tree && !ctx->sw.nohash;  // this run's setting, as for the alignment (the diagnostic no-hash switch leaves nothing to make entries from)
     if (r->prov_bytes + 64 > ctx->enc_prov_cap) {
         HIPCHK(ctx, hipStreamSynchronize(s));
         if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
@@ -3121,6 +3143,8 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     }
     const unsigned slot = (unsigned)(r->run_seq & 1);
     rounds_select(r, slot);
+    r->tree_run[slot] = emit_tree;
+    uint32_t *const tree_out = emit_tree && r->n_tree_entries ? r->tree_m[slot] : nullptr;
     if (r->run_seq >= 2) HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_res[slot], 0));  // the slab's previous results have left
     HIPCHK(ctx, hipMemsetAsync(r->res, 0, 16 + 16 * (size_t)r->n, s));  // total, overflow, blob_offset, blob_size
     HIPCHK(ctx, hipMemsetAsync(ctx->cursor, 0, 64, s));  // work cursors + (last word) the count of blocks handed to the wide variant
@@ -3149,6 +3173,9 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
                               (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0]);
         });
     // Tables of small encoded rounds only: the encoder's waves hash the rounds they are about to encode (EncodeArgs::fuse_tiles)
+    // (Block tree: fuse_tiles is only set for tables whose every round is one piece, at most one 128 KiB block — n_items == n,
+    // znippy_rounds_create — and a round of at most one block has no entries: such a table's tree is empty, and the entry kernel,
+    // which hash_rounds_async queues behind the merge of big units, has nothing to do on this route.)
     const bool fuse_hash = r->fuse_tiles && !r->store_incompressible && !ctx->sw.nohash && !ctx->sw.no_fuse_hash;
     ktime_begin(ctx, fuse_hash ? "zstd_encode_hash" : "zstd_encode");
     for (int wide = 1; wide >= 0; wide--) {  // the wide share first: its blocks are the long ones
@@ -3195,7 +3222,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     int rc = ZNIPPY_OK;
     if (!fuse_store && !fuse_hash) {
         HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-        rc = ctx->sw.nohash ? ZNIPPY_OK : hash_rounds_async(ctx, r, d_src, ctx->aux);  // diagnostic switch
+        rc = ctx->sw.nohash ? ZNIPPY_OK : hash_rounds_async(ctx, r, d_src, ctx->aux, nullptr, 0, 1, tree_out);  // diagnostic switch
         if (rc) return rc;
         HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
     }
@@ -3231,7 +3258,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
     launch_gather(g, s);
     ktime_end(ctx);
     if (fuse_store) {
-        rc = hash_rounds_async(ctx, r, d_src, nullptr, d_blob_out, blob_cap, align);
+        rc = hash_rounds_async(ctx, r, d_src, nullptr, d_blob_out, blob_cap, align, tree_out);
         if (rc) return rc;
     } else if (!fuse_hash) {
         HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));  // digests are complete once the main stream drains
@@ -3246,6 +3273,11 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
         // the next run's kernels (4-16 workgroups: 0.84 ms per C2 write step, 64: 0.88, 1,024: 0.90)
         hipLaunchKernelGGL(k_results_out, dim3(std::min<uint32_t>((n16 + 255) / 256, 8)), dim3(256), 0, ctx->copy,
                            reinterpret_cast<uint4 *>(r->h_res), reinterpret_cast<const uint4 *>(r->res), n16);
+        if (tree_out) {  // the tree leaves with the results, in front of ev_res: the slab-reuse wait covers its buffer too
+            const uint32_t t16 = 2 * r->n_tree_entries;
+            hipLaunchKernelGGL(k_results_out, dim3(std::min<uint32_t>((t16 + 255) / 256, 8)), dim3(256), 0, ctx->copy,
+                               reinterpret_cast<uint4 *>(r->h_tree_m[slot]), reinterpret_cast<const uint4 *>(tree_out), t16);
+        }
     }
     HIPCHK(ctx, hipEventRecord(r->ev_res[slot], ctx->copy));
     r->run_seq++;
@@ -3372,6 +3404,93 @@ extern "C" int znippy_rounds_set_blob_align(znippy_rounds *r, uint32_t align) {
 }
 
 extern "C" uint32_t znippy_rounds_blob_align(const znippy_rounds *r) { return r ? r->blob_align : 1; }
+
+// ---- block tree of a rounds table -------------------------------------------------------------------
+// The layout needs the lengths on the host; the table keeps them on the device only, so the first call that asks fetches them.
+static int rounds_tree_layout(znippy_ctx *ctx, znippy_rounds *r) {
+    if (!r->tree_first.empty()) return ZNIPPY_OK;
+    std::vector<uint64_t> len(r->n), first((size_t)r->n + 1, 0);
+    if (r->n) HIPCHK(ctx, hipMemcpy(len.data(), r->len, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+    for (uint32_t i = 0; i < r->n; i++) first[i + 1] = first[i] + tree_entries_of(len[i]);
+    r->tree_first.swap(first);
+    return ZNIPPY_OK;
+}
+
+static int rounds_block_tree_layout(znippy_ctx *ctx, znippy_rounds *r, uint64_t *n_entries, uint64_t *round_first) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx || !n_entries) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const int rc = rounds_tree_layout(ctx, r);
+    if (rc) return rc;
+    *n_entries = r->tree_first[r->n];
+    if (round_first) memcpy(round_first, r->tree_first.data(), 8 * ((size_t)r->n + 1));
+    return ZNIPPY_OK;
+}
+
+// Everything the feature needs, once per table: the list of units with entries and, per slot of the two-run ring, a device tree
+// buffer and its pinned mirror.  A failure leaves the table as it was (emission off, nothing kept).
+static int rounds_emit_block_tree(znippy_rounds *r, int on) {
+    if (!r || !r->ctx || r->ctx->closing) return ZNIPPY_E_INVAL;
+    znippy_ctx *const ctx = r->ctx;
+    if (!on || r->tree_ready) { r->emit_tree = on != 0; return ZNIPPY_OK; }
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc = rounds_tree_layout(ctx, r);
+    if (rc) return rc;
+    const uint64_t n_entries = r->tree_first[r->n];
+    if (n_entries) {
+        if (n_entries > 0x7FFFFFF0ull) return ZNIPPY_E_NOMEM;
+        std::vector<BigUnit> big(r->plan.n_big);
+        HIPCHK(ctx, hipMemcpy(big.data(), r->plan.big, sizeof(BigUnit) * big.size(), hipMemcpyDeviceToHost));
+        std::vector<TreeUnit> units;
+        for (const BigUnit &b : big) {  // (in round order, as the tree is)
+            const uint64_t first = r->tree_first[b.unit], cnt = r->tree_first[(size_t)b.unit + 1] - first;
+            if (!cnt) continue;  // one block (n_cvs <= 2), or 4 GiB and more
+            if (cnt != ((uint64_t)b.n_cvs + 1) / 2) return ZNIPPY_E_INVAL;  // (the plan and the layout are cut from the same lengths)
+            units.push_back(TreeUnit{(uint32_t)first, b.cv_base, b.n_cvs, 0});
+        }
+        units.push_back(TreeUnit{(uint32_t)n_entries, 0, 0, 0});
+        struct Guard {  // (nothing below is kept unless all of it succeeds)
+            znippy_ctx *ctx; TreeUnit *units = nullptr; uint32_t *tree[2] = {nullptr, nullptr}; void *h[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0};
+            ~Guard() { tfree(ctx, units); for (int k = 0; k < 2; k++) { tfree(ctx, tree[k]); pinned_give(ctx, h[k], cap[k]); } }
+        } g{ctx};
+        if (tmalloc(ctx, &g.units, sizeof(TreeUnit) * units.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+        for (int k = 0; k < 2; k++)
+            if (tmalloc(ctx, &g.tree[k], 32 * (size_t)n_entries) != hipSuccess || !(g.h[k] = pinned_take(ctx, 32 * (size_t)n_entries, &g.cap[k]))) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, hipMemcpy(g.units, units.data(), sizeof(TreeUnit) * units.size(), hipMemcpyHostToDevice));
+        r->tree_units = g.units; g.units = nullptr;
+        r->n_tree_units = (uint32_t)units.size() - 1;
+        for (int k = 0; k < 2; k++) {
+            r->tree_m[k] = g.tree[k]; g.tree[k] = nullptr;
+            r->h_tree_m[k] = (uint8_t *)g.h[k]; g.h[k] = nullptr;
+            r->h_tree_cap_m[k] = g.cap[k];
+        }
+        r->n_tree_entries = (uint32_t)n_entries;
+    }
+    r->tree_ready = true;
+    r->emit_tree = true;
+    return ZNIPPY_OK;
+}
+
+static int rounds_block_tree(znippy_ctx *ctx, znippy_rounds *r, unsigned lag, uint8_t *tree) {
+    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx || !r || r->ctx != ctx || lag > 1 || r->run_seq <= lag) return ZNIPPY_E_INVAL;
+    const unsigned slot = (unsigned)((r->run_seq - 1 - lag) & 1);
+    if (!r->tree_run[slot]) return ZNIPPY_E_INVAL;  // that run was queued with emission off
+    if (!r->n_tree_entries) return ZNIPPY_OK;
+    if (!tree) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipEventSynchronize(r->ev_res[slot]));  // that run's result copy, which the tree travels with
+    memcpy(tree, r->h_tree_m[slot], 32 * (size_t)r->n_tree_entries);
+    return ZNIPPY_OK;
+}
+
+#define ZN_NO_THROW(call) try { return (call); } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; }
+extern "C" int znippy_rounds_emit_block_tree(znippy_rounds *r, int on) { ZN_NO_THROW(rounds_emit_block_tree(r, on)) }
+extern "C" int znippy_rounds_block_tree_layout(znippy_ctx *ctx, znippy_rounds *r, uint64_t *n_entries, uint64_t *round_first) {
+    ZN_NO_THROW(rounds_block_tree_layout(ctx, r, n_entries, round_first))
+}
+extern "C" int znippy_rounds_block_tree(znippy_ctx *ctx, znippy_rounds *r, unsigned lag, uint8_t *tree) { ZN_NO_THROW(rounds_block_tree(ctx, r, lag, tree)) }
+#undef ZN_NO_THROW
 
 extern "C" int znippy_rounds_set_store_incompressible(znippy_rounds *r, int on) {
     if (!r) return ZNIPPY_E_INVAL;

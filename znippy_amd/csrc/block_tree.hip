@@ -6,6 +6,9 @@
 //   k_block_cvs        one wave per block: the block's chaining value, written or compared with the entry it should equal
 //   k_block_tree_fold  one wave per row: the row's entries folded to its digest and compared with the index checksum —
 //                      which is what authenticates the entries, wherever they came from
+// The write side has a third (znippy_rounds_emit_block_tree):
+//   k_round_block_entries  lane = entry: the entry made from the one or two 64-leaf tile chaining values the round's hash left
+//                          in tile_cv — no input byte is read a second time
 // Integer/byte work bounded by the VALU and HBM as in hash_kernels.hip; no MFMA, no inline assembly.
 #include "common.h"
 #include "hash_dev.h"
@@ -116,6 +119,50 @@ __global__ __launch_bounds__(64) void k_block_tree_fold(const BlockTreeRow *rows
     }
 }
 
+// Write side: a 128 KiB block is two 64-leaf tiles, and the hash of a round above 64 KiB leaves every tile's non-root chaining value
+// in tile_cv[cv_base + t] (all routes; the merge kernels only read these slots).  Entry k of a unit with entries is therefore
+// parent(tile_cv[cv_base + 2k], tile_cv[cv_base + 2k + 1]) with ROOT clear, or tile_cv[cv_base + 2k] itself where the last block has at
+// most 64 chunks.  Lane = entry of the whole table; the lane finds its unit by a binary search of fixed trip count (`top` = the
+// largest power of two below n_units, 0 for one unit) over units[].first, which rises strictly — every listed unit has at least two
+// entries — and ends with the sentinel units[n_units].first = n_entries.  Every lane runs the one compress (a lane past the end
+// redoes the last entry, a lone tile's lane pairs the tile with itself) and only the store is predicated.
+// Reads: units[0 .. n_units), tile CVs cv_base + [0, n_cvs) of listed units.  Writes: tree[0 .. 8 * n_entries).
+__global__ __launch_bounds__(256) void k_round_block_entries(const TreeUnit *units, uint32_t n_units, uint32_t top, uint32_t n_entries,
+                                                             const uint32_t *tile_cv, uint32_t *tree) {
+    const uint32_t e0 = blockIdx.x * 256 + threadIdx.x;
+    const bool on = e0 < n_entries;
+    const uint32_t e = on ? e0 : n_entries - 1;
+    uint32_t lo = 0;  // the last unit whose first entry is <= e
+    for (uint32_t step = top; step; step >>= 1) {  // (uniform over the grid)
+        const uint32_t cand = lo + step;
+        const uint32_t first = units[cand < n_units ? cand : n_units - 1].first;
+        lo = cand < n_units && first <= e ? cand : lo;
+    }
+    const uint4 uw = *reinterpret_cast<const uint4 *>(units + lo);  // first, cv_base, n_cvs, -
+    const uint32_t k = e - uw.x;
+    const bool lone = 2 * k + 1 >= uw.z;
+    const size_t il = (size_t)uw.y + 2 * k, ir = lone ? il : il + 1;
+    const uint4 *const pl = reinterpret_cast<const uint4 *>(tile_cv + il * 8), *const pr = reinterpret_cast<const uint4 *>(tile_cv + ir * 8);
+    const uint4 l0 = pl[0], l1 = pl[1], r0 = pr[0], r1 = pr[1];
+    const uint32_t L[8] = {l0.x, l0.y, l0.z, l0.w, l1.x, l1.y, l1.z, l1.w};
+    const uint32_t R[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+    uint32_t out[8];
+    b3::parent(out, L, R, false);
+#pragma unroll
+    for (int i = 0; i < 8; i++) out[i] = lone ? L[i] : out[i];
+    if (on) {
+        uint4 *const po = reinterpret_cast<uint4 *>(tree + (size_t)e0 * 8);
+        po[0] = make_uint4(out[0], out[1], out[2], out[3]);
+        po[1] = make_uint4(out[4], out[5], out[6], out[7]);
+    }
+}
+
+void launch_round_block_entries(const TreeUnit *units, uint32_t n_units, uint32_t n_entries, const uint32_t *tile_cv, uint32_t *tree, hipStream_t s) {
+    if (!n_units || !n_entries) return;
+    uint32_t top = 0;
+    for (uint32_t p = 1; p < n_units; p <<= 1) top = p;
+    hipLaunchKernelGGL(k_round_block_entries, dim3((n_entries + 255) / 256), dim3(256), 0, s, units, n_units, top, n_entries, tile_cv, tree);
+}
 void launch_block_cvs(const BlockCvItem *items, uint32_t n_items, uint32_t *out, const uint32_t *expect, uint32_t *verdict, hipStream_t s) {
     if (!n_items) return;
     const uint32_t grid = std::min<uint32_t>((n_items + 3) / 4, 4096);

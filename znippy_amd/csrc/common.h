@@ -310,5 +310,15 @@ struct BlockTreeRow {  // one row with entries
 void launch_block_cvs(const BlockCvItem *items, uint32_t n_items, uint32_t *out, const uint32_t *expect, uint32_t *verdict, hipStream_t s);
 // verdict[i] = 1 if rows[i]'s entries fold to checksum[32 * row ..]
 void launch_block_tree_fold(const BlockTreeRow *rows, uint32_t n_rows, const uint32_t *tree, const uint8_t *checksum, uint32_t *verdict, hipStream_t s);
+// Write side (znippy_rounds_emit_block_tree): one big unit of a rounds table that has entries, in round order; the list ends with a
+// sentinel whose `first` is the table's entry count
+struct TreeUnit {
+    uint32_t first;    // its first entry in the table's tree
+    uint32_t cv_base;  // BigUnit::cv_base
+    uint32_t n_cvs;    // BigUnit::n_cvs (>= 3): the unit has ceil(n_cvs / 2) entries
+    uint32_t pad;
+};
+// tree[e] for every entry e of the table, from the tile CVs the run's hash left in tile_cv (read only)
+void launch_round_block_entries(const TreeUnit *units, uint32_t n_units, uint32_t n_entries, const uint32_t *tile_cv, uint32_t *tree, hipStream_t s);
 
 }  // namespace zn

@@ -369,6 +369,8 @@ struct RowMeta {  // BlobMeta + ChunkMeta, meta.rs:L4-21
     bool compressed;
     uint8_t pass;
     uint8_t checksum[32];
+    uint64_t tree_at;  // ZNIPPY_HOST_BLOCK_TREE: the row's block tree entries in Packer::tree (byte position), tree_n of them
+    uint32_t tree_n;
 };
 
 struct StageSlot {
@@ -380,7 +382,8 @@ struct StageSlot {
 
 class Packer {
 public:
-    Packer(int fd, int device, uint64_t max_round) : fd_(fd), device_(device), slot_cap_(std::max(stage_bytes(), max_round)), align_(blob_align()) {}
+    Packer(int fd, int device, uint64_t max_round)
+        : emit_tree(env_on("ZNIPPY_HOST_BLOCK_TREE")), fd_(fd), device_(device), slot_cap_(std::max(stage_bytes(), max_round)), align_(blob_align()) {}
     ~Packer() {
         if (thread_.joinable()) { push_full(nullptr); thread_.join(); }
         if (ctx_) znippy_ctx_destroy(ctx_);
@@ -433,6 +436,8 @@ public:
     }
     std::vector<RowMeta> rows;
     uint64_t out_cursor = 0;  // blob region starts at 0 (stream_packer.rs:L134)
+    const bool emit_tree;       // ZNIPPY_HOST_BLOCK_TREE, read when the pipeline starts: every slot's rounds table emits its block tree
+    std::vector<uint8_t> tree;  // ... and the slots' trees are kept here, found by row through RowMeta::tree_at
 
 private:
     void push_full(StageSlot *s) {
@@ -488,8 +493,19 @@ private:
         uint64_t blob_bytes = 0;
         int rc = znippy_rounds_create(ctx_, off.data(), len.data(), skip.data(), nb, &rt);
         if (!rc && align_ > 1) rc = znippy_rounds_set_blob_align(rt, align_);
+        if (!rc && emit_tree) rc = znippy_rounds_emit_block_tree(rt, 1);
         if (!rc && !d_blob_.reserve(znippy_rounds_blob_bound(rt) + 64)) rc = ZNIPPY_E_NOMEM;  // (the bound follows the alignment)
         if (!rc) rc = znippy_encode_hash_rounds(ctx_, rt, d_src_.p, d_blob_.p, d_blob_.cap, boff.data(), bsz.data(), ck.data(), comp.data(), &blob_bytes);
+        std::vector<uint64_t> tfirst(nb + 1, 0);
+        const size_t tree_base = tree.size();
+        if (!rc && emit_tree) {  // the slot's tree arrived with its results: kept by row until the metadata layer is written
+            uint64_t ne = 0;
+            rc = znippy_rounds_block_tree_layout(ctx_, rt, &ne, tfirst.data());
+            if (!rc) {
+                tree.resize(tree_base + 32 * (size_t)ne);
+                rc = znippy_rounds_block_tree(ctx_, rt, 0, ne ? tree.data() + tree_base : nullptr);
+            }
+        }
         if (rt) znippy_rounds_destroy(rt);
         if (rc) { *msg = znippy_last_error(ctx_); return rc; }
         t_kern_ += now_s() - t; t = now_s();
@@ -501,7 +517,8 @@ private:
         t_write_ += now_s() - t;
         for (size_t k = 0; k < nb; k++) {
             const RoundRec &r = s.rounds[k];
-            RowMeta m{r.file_index, r.chunk_seq, r.fdata_offset, r.len, out_cursor + boff[k], bsz[k], comp[k] != 0, r.pass, {0}};
+            RowMeta m{r.file_index, r.chunk_seq, r.fdata_offset, r.len, out_cursor + boff[k], bsz[k], comp[k] != 0, r.pass, {0},
+                      tree_base + 32 * (size_t)tfirst[k], (uint32_t)(tfirst[k + 1] - tfirst[k])};
             std::memcpy(m.checksum, &ck[32 * k], 32);
             rows.push_back(m);
         }
@@ -572,6 +589,36 @@ uint64_t write_metadata(int fd, uint64_t blob_end, const std::vector<RowMeta> &r
     pwrite_all(fd, &manifest_offset, 8, cursor + 8);
     fsync(fd);
     return cursor + 16;
+}
+
+// The block tree sidecar `<archive path>.b3t` (znippy_host.h): header + the rows' entries in the order the index numbers the rows —
+// sub-index by sub-index, batch by batch, as write_metadata lays them down.
+constexpr char B3T_MAGIC[9] = "ZNPYB3T1";
+constexpr uint32_t B3T_BLOCK_LOG = 17;
+constexpr size_t B3T_HEADER = 32;
+
+bool write_sidecar(const std::string &archive_path, const std::vector<RowMeta> &rows, const std::vector<uint8_t> &tree, const std::vector<SubIndex> &subs) {
+    std::vector<uint8_t> out(B3T_HEADER, 0);
+    uint64_t n_rows = 0;
+    for (const auto &g : subs)
+        for (const auto &ids : g.batches)
+            for (size_t k : ids) {
+                const RowMeta &m = rows[k];
+                out.insert(out.end(), tree.begin() + m.tree_at, tree.begin() + m.tree_at + 32 * (size_t)m.tree_n);
+                n_rows++;
+            }
+    const uint64_t n_entries = (out.size() - B3T_HEADER) / 32;
+    const uint32_t log = B3T_BLOCK_LOG;
+    std::memcpy(out.data(), B3T_MAGIC, 8);
+    std::memcpy(out.data() + 8, &log, 4);
+    std::memcpy(out.data() + 16, &n_rows, 8);
+    std::memcpy(out.data() + 24, &n_entries, 8);
+    const std::string path = archive_path + ".b3t";
+    const int fd = open(path.c_str(), O_CREAT | O_TRUNC | O_WRONLY, 0644);
+    if (fd < 0) return false;
+    const bool ok = pwrite_all(fd, out.data(), out.size(), 0);
+    close(fd);
+    return ok;
 }
 
 struct FileMeta {
@@ -699,6 +746,7 @@ static int znippy_stream_finish_impl(znippy_stream *sp, znippy_compression_repor
     for (auto &g : groups) subs.push_back({g.first.first, g.first.second, {std::move(g.second)}});
     const uint64_t total_bytes_out =
         write_metadata(s->fd, s->packer->out_cursor, rows, [&](uint32_t fi) -> const std::string & { return s->files[fi].path; }, subs);
+    if (s->packer->emit_tree && !write_sidecar(s->out_path, rows, s->packer->tree, subs)) return fail(ZNIPPY_E_INVAL, "cannot write " + s->out_path + ".b3t");
     if (trace_on())
         fprintf(stderr, "[host] compress_stream: open->finish %.1f ms (send calls %.1f ms)  drain %.1f ms  metadata %.1f ms\n",
                 (t0 - s->t_open) * 1e3, s->t_send * 1e3, (t1 - t0) * 1e3, (now_s() - t1) * 1e3);
@@ -855,6 +903,8 @@ static int znippy_compress_dir_impl(const char *input_dir, const char *output, i
     if (fd < 0) return fail(ZNIPPY_E_INVAL, "cannot create " + out_path);
     uint64_t uf = 0, ub = 0, cf = 0, cb = 0;
     std::vector<RowMeta> rows;
+    std::vector<uint8_t> tree;
+    bool emit_tree = false;
     uint64_t blob_bytes = 0;
     {
         Packer pk(fd, device, std::max<uint64_t>(slice_size, 1));
@@ -887,6 +937,8 @@ static int znippy_compress_dir_impl(const char *input_dir, const char *output, i
         rc = pk.finish();
         if (rc) { close(fd); return rc; }
         rows = std::move(pk.rows);
+        tree = std::move(pk.tree);
+        emit_tree = pk.emit_tree;
         blob_bytes = pk.out_cursor;
     }
     const double t_pack = now_s();
@@ -902,6 +954,7 @@ static int znippy_compress_dir_impl(const char *input_dir, const char *output, i
     for (size_t i = 0; i < files.size(); i++) rel[i] = files[i].compare(0, root.size() + 1, root + "/") == 0 ? files[i].substr(root.size() + 1) : files[i];
     const uint64_t total_bytes_out = write_metadata(fd, blob_bytes, rows, [&](uint32_t fi) -> const std::string & { return rel[fi]; }, {sub});
     close(fd);
+    if (emit_tree && !write_sidecar(out_path, rows, tree, {sub})) return fail(ZNIPPY_E_INVAL, "cannot write " + out_path + ".b3t");
     if (trace_on())
         fprintf(stderr, "[host] compress_dir: walk %.1f ms  pack %.1f ms  metadata %.1f ms\n", (t_walk - t_begin) * 1e3, (t_pack - t_walk) * 1e3,
                 (now_s() - t_pack) * 1e3);
@@ -1214,7 +1267,46 @@ struct znippy_archive {
     // verified range reads: archive row -> the entries of its block tree (32 bytes per 128 KiB block), built once per chunk by a whole
     // decode with a root check and authenticated again, against the index checksum, by every read that installs them
     std::unordered_map<uint64_t, std::vector<uint8_t>> block_trees;
+    // the sidecar `<path>.b3t`, if one was there at open and agrees with the index: the entries of all rows and where each row's start.
+    // Untrusted — a chunk's entries enter block_trees only once znippy_rows_set_block_tree has accepted them against the index checksum
+    std::vector<uint8_t> side_tree;
+    std::vector<uint64_t> side_first;  // n + 1 values; empty: no usable sidecar
+    uint64_t tree_stats[4] = {0, 0, 0, 0};  // znippy_archive_block_tree_stats
 };
+
+namespace {
+uint64_t tree_entries_of(uint64_t n) { return n > (128u << 10) && n < (1ull << 32) ? (n + (128u << 10) - 1) / (128u << 10) : 0; }
+
+// A sidecar that is missing, malformed, or disagrees with the index in n_rows or n_entries is ignored.
+void load_sidecar(znippy_archive *a) {
+    const std::string path = a->path + ".b3t";
+    const int fd = open(path.c_str(), O_RDONLY);
+    if (fd < 0) return;
+    struct stat st;
+    std::vector<uint8_t> raw;
+    const bool ok = fstat(fd, &st) == 0 && (uint64_t)st.st_size >= B3T_HEADER && ((uint64_t)st.st_size - B3T_HEADER) % 32 == 0 &&
+                    (raw.resize((size_t)st.st_size), pread_all(fd, raw.data(), raw.size(), 0));
+    close(fd);
+    if (!ok) return;
+    uint32_t log = 0, zero = 0;
+    uint64_t n_rows = 0, n_entries = 0;
+    std::memcpy(&log, raw.data() + 8, 4);
+    std::memcpy(&zero, raw.data() + 12, 4);
+    std::memcpy(&n_rows, raw.data() + 16, 8);
+    std::memcpy(&n_entries, raw.data() + 24, 8);
+    if (std::memcmp(raw.data(), B3T_MAGIC, 8) != 0 || log != B3T_BLOCK_LOG || zero != 0 || n_rows != a->ix.n() ||
+        n_entries != (raw.size() - B3T_HEADER) / 32)
+        return;
+    const auto &c = a->ix.rows.cols;
+    std::vector<uint64_t> first(a->ix.n() + 1, 0);
+    for (uint64_t r = 0; r < a->ix.n(); r++) first[r + 1] = first[r] + tree_entries_of(c[3].u8[r] ? c[4].u64[r] : c[6].u64[r]);
+    if (first.back() != n_entries) return;
+    a->side_tree.assign(raw.begin() + B3T_HEADER, raw.end());
+    a->side_first.swap(first);
+    a->tree_stats[0] = n_entries;
+}
+}  // namespace
+
 
 extern "C" {
 
@@ -1232,6 +1324,7 @@ static int znippy_archive_open_impl(const char *path, int device, znippy_archive
         });
     a->fd = open(path, O_RDONLY);
     if (a->fd < 0) return fail(ZNIPPY_E_INVAL, "cannot open archive");
+    load_sidecar(a.get());
     *out = a.release();
     return ZNIPPY_OK;
 }
@@ -1324,10 +1417,43 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
     if (sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
     int rc = ZNIPPY_OK;
     if (verify) {  // chunks with entries that this handle has not built yet: one private table, one build
-        auto entries_of = [](uint64_t n) -> uint64_t { return n > (128u << 10) && n < (1ull << 32) ? (n + (128u << 10) - 1) / (128u << 10) : 0; };
+        auto entries_of = [](uint64_t n) -> uint64_t { return tree_entries_of(n); };
         std::vector<size_t> fresh;
         for (size_t k = 0; k < bo.size(); k++)
             if (entries_of(us[k]) && !a->block_trees.count(arow[k])) fresh.push_back(k);
+        if (!fresh.empty() && !a->side_first.empty()) {  // the sidecar's entries for these chunks: offered, and cached without any decode if accepted
+            std::vector<uint64_t> fbo, fbs, fus;
+            std::vector<uint8_t> fbm((fresh.size() + 7) / 8, 0), fck, tree;
+            for (size_t i = 0; i < fresh.size(); i++) {
+                const size_t k = fresh[i];
+                fbo.push_back(bo[k]); fbs.push_back(bs[k]); fus.push_back(us[k]);
+                if ((bitmap[k >> 3] >> (k & 7)) & 1) fbm[i >> 3] |= (uint8_t)(1u << (i & 7));
+                fck.insert(fck.end(), &ck[32 * k], &ck[32 * k] + 32);
+                const uint64_t r = arow[k];  // (the sidecar's layout was checked against the index: this row has entries_of(us[k]) there)
+                tree.insert(tree.end(), a->side_tree.begin() + 32 * a->side_first[r], a->side_tree.begin() + 32 * a->side_first[r + 1]);
+            }
+            znippy_rows *bt = nullptr;
+            rc = znippy_rows_create(a->ctx, fbo.data(), fbs.data(), fbm.data(), fus.data(), nullptr, fck.data(), 0, fresh.size(), &bt);
+            if (rc) return fail(rc, "znippy_rows_create failed");
+            std::vector<int32_t> bst(fresh.size(), 0);
+            rc = znippy_rows_set_block_tree(a->ctx, bt, tree.data(), bst.data());
+            znippy_rows_destroy(bt);
+            if (rc) return fail(rc, std::string("block tree check failed: ") + znippy_last_error(a->ctx));
+            std::vector<size_t> rest;
+            size_t at = 0;
+            for (size_t i = 0; i < fresh.size(); i++) {
+                const size_t nb = 32 * (size_t)entries_of(fus[i]);
+                if (bst[i] == 0) {
+                    a->block_trees[arow[fresh[i]]].assign(tree.begin() + at, tree.begin() + at + nb);
+                    a->tree_stats[1]++;
+                } else {  // rejected: today's whole-decode build
+                    rest.push_back(fresh[i]);
+                    a->tree_stats[2]++;
+                }
+                at += nb;
+            }
+            fresh.swap(rest);
+        }
         if (!fresh.empty()) {
             std::vector<uint64_t> fbo, fbs, fus;
             std::vector<uint8_t> fbm((fresh.size() + 7) / 8, 0), fck;
@@ -1356,6 +1482,7 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
             for (size_t i = 0; i < fresh.size(); i++) {
                 const size_t nb = 32 * (size_t)entries_of(fus[i]);
                 a->block_trees[arow[fresh[i]]].assign(tree.begin() + at, tree.begin() + at + nb);
+                a->tree_stats[3]++;
                 at += nb;
             }
         }
@@ -1384,6 +1511,12 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
     }
     if (hipMemcpy(dst, bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
     *written = total;
+    return ZNIPPY_OK;
+}
+
+int znippy_archive_block_tree_stats(const znippy_archive *a, uint64_t stats[4]) {
+    if (!a || !stats) return ZNIPPY_E_INVAL;
+    std::memcpy(stats, a->tree_stats, sizeof a->tree_stats);
     return ZNIPPY_OK;
 }
 

@@ -408,6 +408,27 @@ class RoundTable:
     def blob_bound(self):
         return int(self.ctx.L.znippy_rounds_blob_bound(self.h))
 
+    def emit_block_tree(self, on=True):
+        """Opt-in: later encode calls also leave the block tree of the rows these rounds become (block_tree()), made from the
+        hash's own tile chaining values.  See znippy_rounds_emit_block_tree in znippy_hip.h."""
+        self.ctx._chk(self.ctx.L.znippy_rounds_emit_block_tree(self.h, int(on)), "znippy_rounds_emit_block_tree")
+
+    def block_tree_layout(self):
+        """(n_entries, round_first): as RowTable.block_tree_layout, with a round's source length as the row's length."""
+        n = C.c_uint64()
+        first = np.zeros(self.n + 1, dtype=np.uint64)
+        self.ctx._chk(self.ctx.L.znippy_rounds_block_tree_layout(self.ctx.h, self.h, C.byref(n), np_ptr(first)),
+                      "znippy_rounds_block_tree_layout")
+        return int(n.value), first
+
+    def block_tree(self, lag=0):
+        """The tree of the run `lag` runs before the latest queued one (uint8 [n_entries, 32]); waits for that run's result
+        copy only.  Raises (ZNIPPY_E_INVAL) when that run was queued with emission off."""
+        n, _ = self.block_tree_layout()
+        tree = np.zeros((max(n, 1), 32), dtype=np.uint8)
+        self.ctx._chk(self.ctx.L.znippy_rounds_block_tree(self.ctx.h, self.h, int(lag), np_ptr(tree)), "znippy_rounds_block_tree")
+        return tree[:n]
+
     def hash(self, d_src):
         out = np.zeros((max(self.n, 1), 32), dtype=np.uint8)
         self.ctx._chk(self.ctx.L.znippy_hash_rounds(self.ctx.h, self.h, _dptr(d_src), np_ptr(out)), "znippy_hash_rounds")

@@ -29,7 +29,7 @@ class _ME(C.Structure):
 HOST_EXPORTS = [
     "znippy_host_last_error", "znippy_compress_stream", "znippy_stream_send", "znippy_stream_send_packed", "znippy_stream_finish",
     "znippy_compress_dir", "znippy_decompress_archive", "znippy_archive_open", "znippy_archive_file_count", "znippy_archive_file_size",
-    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
+    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
     "znippy_index_manifest_len", "znippy_index_manifest_entry", "znippy_index_row", "znippy_index_metadata",
     "znippy_index_close", "znippy_interpret_footer", "znippy_write_manifest_bytes",
 ]
@@ -58,6 +58,7 @@ def lib():
         L.znippy_archive_extract_file_verified.argtypes = [vp, C.c_char_p, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.znippy_archive_read_range.argtypes = [vp, C.c_char_p, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.znippy_archive_read_range_verified.argtypes = [vp, C.c_char_p, C.c_uint64, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.znippy_archive_block_tree_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.znippy_archive_close.argtypes = [vp]
         L.znippy_archive_close.restype = None
         L.znippy_index_open.argtypes = [C.c_char_p, C.POINTER(vp)]
@@ -213,6 +214,13 @@ class ZnippyArchive:
         _chk(lib().znippy_archive_read_range_verified(self.h, rel.encode(), int(offset), buf.ctypes.data_as(vp), int(length), C.byref(w)),
              "read_range_verified")
         return buf[:w.value].tobytes()
+
+    def block_tree_stats(self):
+        """[entries loaded from the sidecar `<path>.b3t` at open, chunks whose sidecar entries were accepted, chunks whose
+        sidecar entries were rejected, chunks whose block tree was built by a whole decode]."""
+        st = (C.c_uint64 * 4)()
+        _chk(lib().znippy_archive_block_tree_stats(self.h, st), "block_tree_stats")
+        return [int(v) for v in st]
 
     def close(self):
         if self.h:
