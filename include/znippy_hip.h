@@ -170,7 +170,21 @@ int znippy_rows_set_blob_cap(znippy_rows *rows, uint64_t blob_cap);
  * queued on a stream of the context's own beside the NEXT run's kernels (a table keeps two sets of control block, status
  * column, digests and corrupt list — 44 bytes per row more — and run k uses set k & 1): the context's stream alone does
  * not order them.  Every results call, znippy_ctx_sync and the destroy calls wait for them (ZNIPPY_NO_FORK_VERIFY=1 in the
- * environment of znippy_ctx_create: every run's verify on the context's stream, as before). */
+ * environment of znippy_ctx_create: every run's verify on the context's stream, as before).
+ * Run lanes: on a context that owns its stream (znippy_ctx_create with hip_stream == NULL) a run without those kernels may
+ * also be queued beside the run queued directly in front of it instead of behind it, on a second stream of the context's own
+ * (run k of a table on lane k & 1; lane 0 is the context's stream): its clear executes while the earlier run's kernel runs and
+ * its workgroups take over each CU as the earlier run's leave.  Two runs are left unordered only when neither can see the other:
+ * both are such runs; they belong to different tables or use the two sets of one table; the bytes they write cannot differ —
+ * either is a verify-only run, or [d_out, d_out + out_cap) of the two are disjoint, or table, d_blobs, blob_base, the declared
+ * blob size (znippy_rows_set_blob_cap), d_out and out_cap are all identical (the blobs of a queued run may not change, so both
+ * write the same bytes); and neither run's blob region overlaps the other's output region (a blob region of undeclared size
+ * qualifies in the identical case only).  Otherwise the run waits for the earlier run's kernel, as it always did.  Everything
+ * else queued through the context — a full run, another kind of call, a call on another table, the write side — stands behind
+ * every such run queued before it, and such a run stands behind everything queued before it on the context's stream.  A context
+ * created on a caller's stream never does this: work queued on that stream behind a call sees the run's bytes, literally.
+ * ZNIPPY_NO_RUN_LANES=1 (or ZNIPPY_NO_FORK_VERIFY=1) in the environment of znippy_ctx_create: every run in queue order on the
+ * context's stream. */
 int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs,
                               uint64_t blob_base, void *d_out, uint64_t out_cap,
                               znippy_verify_counters *counters, uint64_t *corrupt_rows,
@@ -412,8 +426,21 @@ int znippy_rounds_results_lagged(znippy_ctx *ctx, znippy_rounds *rounds, unsigne
 int znippy_hash_rounds(znippy_ctx *ctx, znippy_rounds *rounds, const void *d_src, uint8_t *digests);
 
 /* ---- measurement hooks (bench.py): device time of the last async call's kernels, by HIP
- * events on the context's stream.  names/ms: up to cap entries; returns the count. */
+ * events on the stream each kernel was queued on.  names/ms: up to cap entries; returns the count.
+ * A run queued on a run lane beside another run (see znippy_decode_verify_rows) has its events on that lane: the bracketed
+ * kernel's time then includes its wait for CUs the earlier run still holds.  With nothing else in flight (queue, read the
+ * results, ask) the times are the kernels' own. */
 int znippy_last_kernel_times(znippy_ctx *ctx, const char **names, float *ms, int cap);
+/* Run lanes, host-side counters since the context was created, by what the streams really order: out[0] lean runs queued
+ * on the other stream than their predecessor with no wait for it (the only runs that can execute beside another), out[1]
+ * lane runs behind their predecessor — by a wait for its event, by standing on the same stream, or with no lane run in
+ * front of them —, out[2] lane runs in front of which a mark was recorded on the context's stream because other work had
+ * been queued there, out[3] lean runs kept off the lanes (a caller's stream, ZNIPPY_NO_RUN_LANES, ZNIPPY_NO_FORK_VERIFY).
+ * znippy_ctx_run_lane_older_waits (introspection for the tests only, not part of the stable interface): lane runs that were made to wait for a run OLDER than their predecessor which had not
+ * ended on the other stream (a run only ever starts with nothing but its predecessor still executing).
+ * Both queue nothing and wait for nothing. */
+int znippy_ctx_run_lane_stats(znippy_ctx *ctx, uint64_t out[4]);
+int znippy_ctx_run_lane_older_waits(znippy_ctx *ctx, uint64_t *out);
 /* How many of those event pairs a call records: 2 = around every kernel (default), 1 = around the dominant read
  * kernels only (decode_verify_*), 0 = none (a caller that never asks for kernel times: each pair costs the stream
  * two markers).  ZNIPPY_KTIME in the environment sets the initial level. */

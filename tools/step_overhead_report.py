@@ -2,8 +2,11 @@
 decode_verify_async + results_lagged(1), two runs in flight, kernel timing level 1 — timed in blocks of pipelined steps by the
 wall clock, the sides taking turns (the order rotates every round).  Sides: P1 and P2, two contexts of the other build
 (ZN_LIB_B=path/to/libznippy_hip.so — the parent commit's; without it, this build's) whose spread |P1 / P2 - 1| is the margin of
-the report; this build with the default ordering and with ZNIPPY_NO_FORK_VERIFY (every verify in line).  Per side: ms per step
-(median of the rounds), the longest bracketed kernel's time by its HIP events, and step minus that kernel.  c2 is the headline
+the report; this build with the default ordering and with ZNIPPY_NO_RUN_LANES (every lean run in queue order on the main stream:
+the parent's order of stream operations).  Per side: ms per step (median of the rounds), the longest bracketed kernel's time by
+its HIP events, and step minus that kernel — except on a side whose runs went to the run lanes, where the events stand on the lane
+and the kernel's time includes its wait for CUs the run in front still holds: there the step alone counts, and the line says so
+(with the context's lane counters).  c2 is the headline
 table (100k x 10 KiB, libzstd -19 frames); the other workloads are this build's own archives and are there to show that nothing
 gets slower: each side must stay within the other build's A/A spread.
 
@@ -31,7 +34,7 @@ this_first = len(sys.argv) > 4 and sys.argv[4] == "this_first"
 
 lib_b = os.environ.get("ZN_LIB_B")
 so_a = _build.SO
-SIDES = [("P1", None), ("P2", None), ("default", {}), ("no_fork_verify", {"ZNIPPY_NO_FORK_VERIFY": "1"})]
+SIDES = [("P1", None), ("P2", None), ("default", {}), ("no_run_lanes", {"ZNIPPY_NO_RUN_LANES": "1"})]
 ctx_t = [make_ctx(env) for _, env in SIDES[2:]] if this_first else []
 if lib_b:
     _lib._lib = None
@@ -94,6 +97,9 @@ for name in names:
     level = 1 if name in ("c2", "c2small") else 2  # as bench.py's timed region
     t = [[] for _ in ctxs]
     main = [[] for _ in ctxs]
+    def lane_stats(c):  # (a library without the counters — an older build as the other side — has no lanes)
+        return c.run_lane_stats() if hasattr(c.L, "znippy_ctx_run_lane_stats") else {}
+    lanes0 = [lane_stats(c) for c in ctxs]
     for c in ctxs:
         c.set_kernel_timing(level)
     for i in range(rounds + 2):
@@ -125,8 +131,12 @@ for name in names:
             gain = 1.0 - med[j] / base
             slower = med[j] > max(med[0], med[1]) * (1.0 + spread)
             ok_all &= not slower
-            verdict = f"  vs other build {gain * 100:+.2f} %" + ("  beats it by more than 2 x spread" if gain > 2 * spread else "") + ("  SLOWER than its margin" if slower else "")
-        print(f"  {side:15s} step {med[j]:.4f} ms   main kernel {mk[j]:.4f} ms   step - main kernel {(med[j] - mk[j]) * 1e3:6.1f} us{verdict}")
+            verdict = f"  vs other build {gain * 100:+.2f} %" + ("  beats it by more than 5 x spread" if gain > 5 * spread else "") + ("  SLOWER than its margin" if slower else "")
+        lanes = {k: v - lanes0[j][k] for k, v in lane_stats(ctxs[j]).items()}
+        if lanes.get("unordered"):  # the bracketed kernel waited for CUs inside its events: no "step - kernel"
+            print(f"  {side:15s} step {med[j]:.4f} ms   main kernel {mk[j]:.4f} ms INCLUDING its wait on the lane   lanes {lanes}{verdict}")
+        else:
+            print(f"  {side:15s} step {med[j]:.4f} ms   main kernel {mk[j]:.4f} ms   step - main kernel {(med[j] - mk[j]) * 1e3:6.1f} us{verdict}")
     for j in (0, 2):
         print(f"  kernels of {SIDES[j][0]}: " + "  ".join(f"{k} {v:.4f}" for k, v in kall[j].items()))
     for r in rts:

@@ -44,7 +44,7 @@ EXPORTS = [
     "znippy_decode_verify_rows_async", "znippy_rows_results", "znippy_rows_digests",
     "znippy_rounds_create", "znippy_rounds_destroy", "znippy_rounds_blob_bound",
     "znippy_encode_hash_rounds", "znippy_encode_hash_rounds_async", "znippy_rounds_results",
-    "znippy_rounds_results_view", "znippy_rows_results_lagged", "znippy_rows_set_blob_cap", "znippy_rounds_results_lagged", "znippy_rounds_set_store_incompressible", "znippy_hash_rounds", "znippy_last_kernel_times", "znippy_measure_blake3_pass_ns", "znippy_last_shader_ghz", "znippy_ctx_set_kernel_timing", "znippy_rows_foreign_stats", "znippy_ctx_set_level", "znippy_ctx_level",
+    "znippy_rounds_results_view", "znippy_rows_results_lagged", "znippy_rows_set_blob_cap", "znippy_rounds_results_lagged", "znippy_rounds_set_store_incompressible", "znippy_hash_rounds", "znippy_last_kernel_times", "znippy_measure_blake3_pass_ns", "znippy_last_shader_ghz", "znippy_ctx_set_kernel_timing", "znippy_rows_foreign_stats", "znippy_ctx_run_lane_stats", "znippy_ctx_run_lane_older_waits", "znippy_ctx_set_level", "znippy_ctx_level",
     "znippy_ctx_set_window_log", "znippy_ctx_window_log",
     "znippy_verify_rows", "znippy_verify_rows_async", "znippy_rows_verify_scratch",
     "znippy_decode_rows", "znippy_decode_rows_async",
@@ -144,6 +144,9 @@ def lib():
         L.znippy_rounds_emit_block_tree.argtypes = [vp, C.c_int]
         L.znippy_rounds_block_tree_layout.argtypes = [vp, vp, C.POINTER(C.c_uint64), vp]
         L.znippy_rounds_block_tree.argtypes = [vp, vp, C.c_uint, vp]
+    if hasattr(L, "znippy_ctx_run_lane_stats"):  # (likewise)
+        L.znippy_ctx_run_lane_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.znippy_ctx_run_lane_older_waits.argtypes = [vp, C.POINTER(C.c_uint64)]
     _lib = L
     return L
 

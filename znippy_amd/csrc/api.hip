@@ -5,6 +5,7 @@
 #include "common.h"
 #include "encode.h"
 #include "../../include/znippy_hip.h"
+#include "host/run_overlap.h"
 
 #include <algorithm>
 #include <cstdio>
@@ -131,7 +132,7 @@ struct znippy_ctx {
         unsigned lds_pad = 0;    // ZNIPPY_LDS_PAD
         int store_g = 0;         // ZNIPPY_STORE_G: tiles per wave of the store path kernel (0 = from the tile count)
         bool no_block_items = false, no_fused_blocks = false, ddbg = false, edbg = false, no_fused_store = false,
-             no_fork_verify = false, nohash = false, no_roles = false, no_fz = false, fz_only = false, no_bx = false, tdbg = false, no_fuse_hash = false, trace = false, no_rx = false, no_pack = false, no_lean = false, no_stored_only = false;
+             no_fork_verify = false, no_run_lanes = false, nohash = false, no_roles = false, no_fz = false, fz_only = false, no_bx = false, tdbg = false, no_fuse_hash = false, trace = false, no_rx = false, no_pack = false, no_lean = false, no_stored_only = false;
         // ZNIPPY_ROLES_MIN: small tiles from which the role-split persistent kernel takes the table (0 = never; below
         // a few CU-fillings a persistent grid only adds start-up latency)
         unsigned roles_min = 2048;
@@ -144,6 +145,32 @@ struct znippy_ctx {
     // creation from what the two kernels take of a CU — a verify that cannot be resident beside that persistent kernel would
     // wait a whole step and stall the caller's lagged read
     bool fork_verify = false;
+    // Run lanes: the main chain of a lean run — the wait for its slot, the clear, the role-split kernel, the
+    // ev_main record — is queued on one of two run streams, run k of a table on lane k & 1.  Lane 0 is the context's main
+    // stream, lane 1 a stream of its own (`lane`), so a read step stays within main + auxiliary + one more stream.  Two
+    // consecutive lane runs that cannot see each other (zn_runs_may_overlap) are left unordered: the next run's clear executes
+    // beside the previous run's kernel and its workgroups take each CU the moment the previous run's workgroup leaves it.
+    // Only a context that owns its stream and forks its verify has lanes (lanes_on).
+    //  - lane_join: the ev_main of the last run on `lane` that the main stream has not waited for yet.  Everything else a
+    //    context queues goes to the main stream through ctx_enter (or rows_launch), which waits for it first (lanes_close).
+    //  - main_dirty: work other than lane runs has been queued on the main stream since a lane run last ordered itself behind
+    //    it.  The next lane run records ev_mark there; a run on `lane` waits for it (mark_pending: a run on lane 0 recorded
+    //    it in front of itself and the next run on `lane` still has to wait).  Clear in a steady pipeline: nothing waits.
+    //  - lane_prev: the lane run queued last (the predecessor: the one run the rule is asked about).  lane_hist[s]: the two runs
+    //    queued last on stream s ([0] the later).  A lane run waits for the latest run on the OTHER stream that is older than its
+    //    predecessor (everything older on that stream ended before it; everything older on its own stream ends before the run
+    //    starts), so when a lane run starts nothing but its predecessor can still be executing: every pair of runs that can
+    //    execute at the same time has been through the rule.
+    //  - lane_ev[s]: the context's own events for that, two per stream taken in turn and recorded behind a run's ev_main (a
+    //    table's ev_main is recorded again by the slot's next run: a wait for an older run would become a wait for a newer one).
+    hipStream_t lane = nullptr;
+    hipEvent_t ev_mark = nullptr, lane_join = nullptr;
+    hipEvent_t lane_ev[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
+    unsigned lane_n[2] = {0, 0};  // lane runs queued on each stream so far
+    bool lanes_on = false, main_dirty = true, mark_pending = false;
+    struct LaneRun { zn_run_desc d; hipEvent_t ev; bool on_lane, valid; } lane_prev = {}, lane_hist[2][2] = {};
+    // znippy_ctx_run_lane_stats; [4]: lane runs that waited for a run OLDER than their predecessor that had not ended (znippy_ctx_run_lane_older_waits)
+    uint64_t lane_stats[5] = {0, 0, 0, 0, 0};
     // Lifetime (znippy_hip.h): tables hold a reference to their context.  znippy_ctx_destroy with tables still alive only
     // closes the context (every call on it fails with ZNIPPY_E_INVAL from then on); its memory and device resources go
     // when the last table is destroyed.
@@ -172,6 +199,7 @@ static void read_switches(znippy_ctx *ctx) {
     ctx->sw.trace = on("ZNIPPY_TRACE");
     ctx->sw.no_lean = on("ZNIPPY_NO_LEAN");  // A/B: every run launches the kernels behind the role-split one
     ctx->sw.no_fork_verify = on("ZNIPPY_NO_FORK_VERIFY");  // A/B, tests: every run's verify on the main stream, in front of the next run
+    ctx->sw.no_run_lanes = on("ZNIPPY_NO_RUN_LANES");  // A/B, tests: every lean run's main chain on the main stream, in queue order
     ctx->sw.no_pack = on("ZNIPPY_NO_PACK");  // A/B: the index columns always as four 64-bit copies
     if (const char *e = getenv("ZNIPPY_STORE_G")) ctx->sw.store_g = atoi(e) == 1 ? 1 : (atoi(e) == 2 ? 2 : 0);  // A/B, tests: tiles per wave of the store path kernel
     ctx->sw.no_stored_only = on("ZNIPPY_NO_STORED_ONLY");  // A/B: tables without a compressed row through the fused small-row kernels (until round 3's last day)
@@ -227,6 +255,30 @@ static void event_give(znippy_ctx *ctx, hipEvent_t e) {
     if (!e) return;
     if (ctx->event_pool.size() < 64) ctx->event_pool.push_back(e);
     else (void)hipEventDestroy(e);
+}
+
+// ---- run lanes: what every entry point and every run that is not a lane run does first ----------------------------------
+// The main stream gets behind every lane run queued so far, and the next lane run will get behind the main stream.
+static void lanes_close(znippy_ctx *ctx) {
+    if (!ctx->lanes_on) return;
+    if (ctx->lane_join) { (void)hipStreamWaitEvent(ctx->stream, ctx->lane_join, 0); ctx->lane_join = nullptr; }
+    ctx->main_dirty = true; ctx->mark_pending = false;
+    ctx->lane_prev.valid = false;  // (the main stream, and with it the mark the next lane run stands behind, is behind every lane run)
+    for (auto &h : ctx->lane_hist) h[0].valid = h[1].valid = false;
+}
+static hipError_t lanes_sync(znippy_ctx *ctx) { return ctx->lane ? hipStreamSynchronize(ctx->lane) : hipSuccess; }
+// Opens every public entry point that takes a context: false = the context was destroyed and is only kept alive by its tables
+// (every call fails with ZNIPPY_E_INVAL).  ENTER_WORK: the call may queue work on the main stream, so the lanes are closed
+// first — an entry point written after this pattern is ordered against the lane runs without knowing of them.  ENTER_RUN:
+// the async run calls and the results calls, whose every stream operation goes through rows_launch: that closes the lanes
+// itself unless the run is a lane run, and a results call that repeats nothing queues nothing.  ENTER_HOST: calls that read
+// or set host state only (levels, kernel timing, the last kernel times) and can never queue or wait for device work.
+enum EnterKind { ENTER_WORK, ENTER_RUN, ENTER_HOST };
+static inline bool ctx_enter(znippy_ctx *ctx, EnterKind kind = ENTER_WORK) {
+    if (!ctx) return true;  // (the null check and its return value are the entry point's own)
+    if (ctx->closing) return false;
+    if (kind == ENTER_WORK) lanes_close(ctx);
+    return true;
 }
 
 // Device memory of the tables (index columns, plans, per-run scratch) comes from a per-context pool: a table is
@@ -434,6 +486,7 @@ struct znippy_rows {
         status = reinterpret_cast<int32_t *>(ctl + CTL_HEAD);
     }
     hipEvent_t ev_main[2] = {nullptr, nullptr};  // forked verify: the end of the run's kernels on the main stream
+    bool lane_used = false;  // a run of this table was ever queued on the context's run lane (the same parties wait for that stream)
     bool aux_used = false;  // a verify of this table was ever queued on the auxiliary stream (whoever reuses a slot or frees the table joins it)
     // pinned mirror of the counters, filled by the run's own D2H copy.  Two slots + one event each: run k uses slot
     // k & 1, so the counters of run k can be read while run k + 1 is already executing (znippy_rows_results_lagged)
@@ -647,7 +700,8 @@ static unsigned long long *diag_cycle(znippy_ctx *ctx, znippy_ctx::Diag which, h
 // what the caller gave a run; preset != 0: the status column starts as the host's verdicts (rows_validate found bad rows); slot: its mirror slot and event
 // verify: a verify-only run — d_out / out_cap are the context's scratch and the extent of the table's slots in it, and the output column is vs_off
 // plain: a decode-only run (znippy_decode_rows) — rows are written as in a decode run and nothing is hashed
-struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; bool verify; bool plain; };
+// on: the stream of the run's main chain — the context's main stream, or for a lean run on lane 1 the run lane (lane_begin)
+struct RowsRun { const void *d_blobs; uint64_t blob_base; void *d_out; uint64_t out_cap; int preset; unsigned slot; bool verify; bool plain; hipStream_t on; hipEvent_t lane_ev; };
 // the ten row columns every decode path's argument struct has under the same names (BlockScanArgs: all but `out`)
 static void set_out(BlockScanArgs &, uint8_t *) {}
 template <class A> static void set_out(A &a, uint8_t *out) { a.out = out; }
@@ -1033,6 +1087,19 @@ int znippy_ctx_create(int device, void *hip_stream, znippy_ctx **out) {
         if (roles_footprint(&rr, &rw, &rl) == 0 && verify_footprint(&vr, &vl) == 0)
             ctx->fork_verify = rw * ((rr + 7) / 8 * 8) + (vr + 7) / 8 * 8 <= 512 && rl + vl <= 160 * 1024 && rw + 1 <= 8;
     }
+    // Run lanes: the same gate (the verify then runs beside the SUCCESSOR's workgroups, whose footprint is the same), and only on
+    // a stream of the context's own: work a caller queues on ITS stream behind a call sees the run's bytes, as the header promises
+    if (ctx->fork_verify && ctx->own_stream && !ctx->sw.no_run_lanes) {
+        if (hipStreamCreateWithFlags(&ctx->lane, hipStreamNonBlocking) != hipSuccess ||
+            hipEventCreateWithFlags(&ctx->ev_mark, hipEventDisableTiming) != hipSuccess) {
+            znippy_ctx_destroy(ctx);
+            return ZNIPPY_E_HIP;
+        }
+        for (auto &pair : ctx->lane_ev)
+            for (hipEvent_t &e : pair)
+                if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { znippy_ctx_destroy(ctx); return ZNIPPY_E_HIP; }
+        ctx->lanes_on = true;
+    }
     *out = ctx;
     return ZNIPPY_OK;
 }
@@ -1043,6 +1110,7 @@ void znippy_ctx_destroy(znippy_ctx *ctx) {
     if (ctx->live_tables) {  // tables outlive the call: they keep the context's memory until the last of them is destroyed
         (void)hipSetDevice(ctx->device);
         (void)hipStreamSynchronize(ctx->stream);
+        (void)lanes_sync(ctx);
         if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
         ctx->closing = true;
         return;
@@ -1055,6 +1123,7 @@ static void table_released(znippy_ctx *ctx) {
 static void ctx_teardown(znippy_ctx *ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
+    (void)lanes_sync(ctx);
     if (ctx->aux) (void)hipStreamSynchronize(ctx->aux);
     for (auto &k : ctx->ktimes) { (void)hipEventDestroy(k.t0); (void)hipEventDestroy(k.t1); }
     void *dev[] = {ctx->lit_scratch, ctx->lit_scratch_b, ctx->fz_lit_pool, ctx->fz_seq_pool, ctx->bx_fse_pool, ctx->bx_huf_pool, ctx->rx_pool, ctx->rx_chunk, ctx->rx_cdone, ctx->cursor, ctx->vs_pool, ctx->rr_pool[0], ctx->rr_pool[1],
@@ -1063,6 +1132,10 @@ static void ctx_teardown(znippy_ctx *ctx) {
     for (unsigned long long *d : ctx->diag) if (d) (void)hipFree(d);
     if (ctx->aux) { (void)hipStreamSynchronize(ctx->aux); (void)hipStreamDestroy(ctx->aux); }
     if (ctx->copy) { (void)hipStreamSynchronize(ctx->copy); (void)hipStreamDestroy(ctx->copy); }
+    if (ctx->lane) (void)hipStreamDestroy(ctx->lane);
+    if (ctx->ev_mark) (void)hipEventDestroy(ctx->ev_mark);
+    for (auto &pair : ctx->lane_ev)
+        for (hipEvent_t e : pair) if (e) (void)hipEventDestroy(e);
     for (auto &e : ctx->pinned_pool) (void)hipHostFree(e.second);
     for (auto &e : ctx->dev_pool) (void)hipFree(e.second);
     for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
@@ -1076,16 +1149,17 @@ static void ctx_teardown(znippy_ctx *ctx) {
 const char *znippy_last_error(const znippy_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
 
 int znippy_ctx_sync(znippy_ctx *ctx) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, lanes_sync(ctx));  // a lean run's kernel may be queued there (lane_begin)
     if (ctx->aux) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // a run's verify and result copy may be queued there (run_verify)
     if (ctx->copy) HIPCHK(ctx, hipStreamSynchronize(ctx->copy));
     return ZNIPPY_OK;
 }
 
 int znippy_last_kernel_times(znippy_ctx *ctx, const char **names, float *ms, int cap) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
     if (!ctx) return 0;
     int n = std::min(cap, ctx->n_ktimes);
     for (int i = 0; i < n; i++) {
@@ -1096,8 +1170,19 @@ int znippy_last_kernel_times(znippy_ctx *ctx, const char **names, float *ms, int
     return n;
 }
 
+int znippy_ctx_run_lane_stats(znippy_ctx *ctx, uint64_t out[4]) {
+    if (!ctx || ctx->closing || !out) return ZNIPPY_E_INVAL;  // (queues nothing: the lanes stay as they are)
+    memcpy(out, ctx->lane_stats, 4 * sizeof(uint64_t));
+    return ZNIPPY_OK;
+}
+int znippy_ctx_run_lane_older_waits(znippy_ctx *ctx, uint64_t *out) {
+    if (!ctx || ctx->closing || !out) return ZNIPPY_E_INVAL;
+    *out = ctx->lane_stats[4];
+    return ZNIPPY_OK;
+}
+
 int znippy_rows_foreign_stats(znippy_ctx *ctx, znippy_rows *r, uint64_t stats[8]) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !stats) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1107,7 +1192,7 @@ int znippy_rows_foreign_stats(znippy_ctx *ctx, znippy_rows *r, uint64_t stats[8]
 }
 
 int znippy_ctx_set_level(znippy_ctx *ctx, int level) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
     if (!ctx || level < 1 || level > 22) return ZNIPPY_E_INVAL;
     ctx->level = level;
     return ZNIPPY_OK;
@@ -1116,7 +1201,7 @@ int znippy_ctx_set_level(znippy_ctx *ctx, int level) {
 int znippy_ctx_level(const znippy_ctx *ctx) { return ctx ? ctx->level : ZNIPPY_E_INVAL; }
 
 int znippy_ctx_set_window_log(znippy_ctx *ctx, int window_log) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
     if (!ctx || (window_log != 0 && (window_log < WINDOW_LOG_MIN || window_log > WINDOW_LOG_MAX))) return ZNIPPY_E_INVAL;
     ctx->window_log = window_log;
     return ZNIPPY_OK;
@@ -1125,14 +1210,14 @@ int znippy_ctx_set_window_log(znippy_ctx *ctx, int window_log) {
 int znippy_ctx_window_log(const znippy_ctx *ctx) { return ctx && !ctx->closing ? ctx->window_log : ZNIPPY_E_INVAL; }
 
 int znippy_ctx_set_kernel_timing(znippy_ctx *ctx, int level) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
     if (!ctx || level < 0 || level > 2) return ZNIPPY_E_INVAL;
     ctx->sw.ktime = level;
     return ZNIPPY_OK;
 }
 
 int znippy_measure_blake3_pass_ns(znippy_ctx *ctx, float *ns_per_pass_per_simd, float *shader_ghz) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !ns_per_pass_per_simd) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1142,7 +1227,7 @@ int znippy_measure_blake3_pass_ns(znippy_ctx *ctx, float *ns_per_pass_per_simd, 
 // Shader clock a read-side kernel held during the last run with ZNIPPY_DBG bit 32768 set: one wave's life in shader
 // cycles / in 100 MHz ticks (MI355X_MICROARCH.md, DVFS give-back (6)).  0 if nothing was recorded.
 int znippy_last_shader_ghz(znippy_ctx *ctx, float *ghz) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !ghz) return ZNIPPY_E_INVAL;
     *ghz = 0.f;
     if (!ctx->clk_buf) return ZNIPPY_OK;
@@ -1209,6 +1294,10 @@ void znippy_rows_destroy(znippy_rows *r) {
                     r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off, r->tree_dev};
     // (the pool hands these buffers to the next table, whose work is ordered on the main stream: what this table still has on
     // the auxiliary stream — a forked verify — is joined into it first)
+    // (... and its runs on the run lane: the lanes are closed — no later run is compared with, or waits for an event of, this table —
+    // and waited for)
+    lanes_close(r->ctx);
+    if (r->lane_used) (void)lanes_sync(r->ctx);
     if (r->aux_used && hipEventRecord(r->ctx->ev_join, r->ctx->aux) == hipSuccess) (void)hipStreamWaitEvent(r->ctx->stream, r->ctx->ev_join, 0);
     for (void *p : ptrs)
         tfree(r->ctx, p);
@@ -1406,7 +1495,7 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
                        const uint8_t *compressed_bitmap, const uint64_t *uncompressed_size,
                        const uint64_t *out_offset, const uint8_t *checksum, uint64_t row_begin,
                        uint64_t row_end, znippy_rows **out) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !out || row_end < row_begin || !blob_offset || !blob_size || !uncompressed_size)
         return ZNIPPY_E_INVAL;
     if (row_end - row_begin >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
@@ -1692,7 +1781,7 @@ static void decode_rest(znippy_ctx *ctx, const znippy_rows *r, DecodeArgs a, uin
 
 // counters, hand-over counts, work cursors and the status column: one stream operation
 static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
-    hipStream_t s = ctx->stream;
+    hipStream_t s = run.on;
     // (the slot's last user — the run before last — may have had its verify on the auxiliary stream: long done in a steady pipeline)
     if (r->aux_used) HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_done[run.slot], 0));
     if (run.preset) HIPCHK(ctx, hipMemcpyAsync(r->ctl, r->status_init, r->ctl_bytes, hipMemcpyDeviceToDevice, s));
@@ -1704,7 +1793,7 @@ static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const Ro
 
 // 1) small rows: decode simple frames + hash (+ copy stored rows), one wave per tile; the role-split kernel in front
 static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
-    hipStream_t s = ctx->stream;
+    hipStream_t s = run.on;
     FusedArgs f{};
     f.h = rows_hash_args(ctx, r, run);
     f.h.pass = 1;  // PASS_FUSED
@@ -1983,7 +2072,7 @@ static void run_copy_stored(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, c
 
 // 4) verify (a run that left stages out: its lists must be empty, or the counters come back flagged), mirror copy, event
 static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
-    hipStream_t s = ctx->stream;
+    hipStream_t s = run.on;
     if (p.lean_mixed) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
     const bool skipped = p.lean || p.lean_blocks || p.lean_mixed;
     // A lean run has nothing between its one kernel and the verify, and nothing of the NEXT run's kernels reads what the verify
@@ -1991,6 +2080,7 @@ static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const R
     // the next run's kernel follows this run's directly.  The slot's next run is ordered behind ev_done (run_clear).
     if (ctx->fork_verify && p.lean) {
         HIPCHK(ctx, hipEventRecord(r->ev_main[run.slot], s));
+        if (run.lane_ev) HIPCHK(ctx, hipEventRecord(run.lane_ev, s));  // (what later lane runs and the main stream wait for: lane_begin)
         s = ctx->aux;
         HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_main[run.slot], 0));
         r->aux_used = true;
@@ -2003,6 +2093,71 @@ static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const R
     HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * run.slot, r->counters, CTL_MIRROR, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipEventRecord(r->ev_done[run.slot], s));
     HIPCHK(ctx, hipGetLastError());
+    return ZNIPPY_OK;
+}
+
+// A lean run on a context with run lanes: picks the run's stream (run k of a table: lane k & 1; lane 0 is the main stream) and
+// queues on it whatever the run has to wait for — never more than an event wait, and nothing at all in a steady pipeline.
+//  - Main-stream work queued since the last lane run (main_dirty): a mark is recorded on the main stream in front of this run and
+//    a run on lane 1 waits for it; a run on lane 0 stands behind it anyway and leaves the wait to the next run on lane 1.
+//  - The latest run on the OTHER stream that is older than the predecessor: waited for unless it has ended (one event query).
+//    Runs older than that on the other stream ended before it, older runs on this stream end before this run starts, so only
+//    the predecessor can still be executing when this run starts (the same slot's last run is behind ev_done besides).
+//  - The predecessor: on this stream the run stands behind it whatever the rule says.  On the other stream
+//    zn_runs_may_overlap decides (host/run_overlap.cc): beside it, or behind its event.
+// The main stream does NOT wait for a run on lane 1 here — the next run on lane 0 would stand behind it; lanes_close does, in front
+// of anything else the context queues.
+// What two lean runs side by side share, checked against the kernels:
+//  - slow_list is one per table and both runs' role-split kernels may append to it, each with its own count (H_TILES of its slot,
+//    at most the tile count, so no append leaves the list).  No lean run reads the list: a run that appended comes back flagged,
+//    and rows_settle synchronises every stream and runs it again in full, by itself.
+//  - No pool of the context: the role-split kernel reads blobs and writes rows (k_fused_roles<true>) or hashes the periodic shape
+//    in LDS and writes digests only (<false>, a verify-only run: its d_out, the verify scratch, is never dereferenced — rows of
+//    any other shape go to slow_list, i.e. to a full run).
+static int lane_begin(znippy_ctx *ctx, znippy_rows *r, unsigned slot, hipStream_t *on, hipEvent_t *record) {
+    const auto &ra = r->run_args[slot];
+    const bool on_lane = (slot & 1) != 0;
+    const unsigned si = on_lane ? 1 : 0, oi = si ^ 1;
+    const hipStream_t s = on_lane ? ctx->lane : ctx->stream;
+    const zn_run_desc d{r, slot, 1, (uint8_t)ra.verify, (uint64_t)(uintptr_t)ra.blobs, ra.base, ra.blob_cap, (uint64_t)(uintptr_t)ra.out, ra.cap};
+    auto wait_on = [&](hipEvent_t e) {
+        if (!on_lane && e == ctx->lane_join) ctx->lane_join = nullptr;  // (the main stream is behind that run now)
+        return hipStreamWaitEvent(s, e, 0);
+    };
+    if (ctx->main_dirty) {  // (lanes_close has left no predecessor and no history)
+        HIPCHK(ctx, hipEventRecord(ctx->ev_mark, ctx->stream));
+        ctx->main_dirty = false; ctx->mark_pending = true;
+        ctx->lane_stats[2]++;
+    }
+    if (on_lane && ctx->mark_pending) {
+        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_mark, 0));
+        ctx->mark_pending = false;
+    }
+    const znippy_ctx::LaneRun p0 = ctx->lane_prev;
+    const bool p0_other = p0.valid && p0.on_lane != on_lane;
+    // the latest run on the other stream that is older than the predecessor
+    const znippy_ctx::LaneRun &older = ctx->lane_hist[oi][p0_other ? 1 : 0];
+    if (older.valid) {
+        if (hipEventQuery(older.ev) == hipSuccess) (void)0;  // it has ended, and with it everything in front of it on that stream
+        else {
+            (void)hipGetLastError();  // (hipErrorNotReady)
+            HIPCHK(ctx, wait_on(older.ev));
+            ctx->lane_stats[4]++;
+        }
+    }
+    const bool beside = p0_other && zn_runs_may_overlap(&p0.d, &d);
+    if (p0_other && !beside) HIPCHK(ctx, wait_on(p0.ev));
+    ctx->lane_stats[beside ? 0 : 1]++;  // beside: on another stream than the predecessor and with no wait for it
+    // The run's event enters predecessor, history and lane_join HERE, before run_verify records it: nothing between the two
+    // queues a lane run, and a run that fails in between ends in rows_abandon, which closes the lanes (no entry survives) and
+    // synchronises.  (The event taken is the one just shifted out of this stream's history.)
+    hipEvent_t ev = ctx->lane_ev[si][ctx->lane_n[si]++ & 1];
+    ctx->lane_prev = znippy_ctx::LaneRun{d, ev, on_lane, true};
+    ctx->lane_hist[si][1] = ctx->lane_hist[si][0];
+    ctx->lane_hist[si][0] = ctx->lane_prev;
+    if (on_lane) { ctx->lane_join = ev; r->lane_used = true; }
+    *on = s;
+    *record = ev;
     return ZNIPPY_OK;
 }
 
@@ -2038,7 +2193,7 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         else if (last_plain) rows_note_plain(r, last);
         else rows_note_hint(r, last);
     }
-    const RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot, verify, plain};
+    RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot, verify, plain, ctx->stream, nullptr};
     const RunPlan p = rows_plan(ctx, r, run.preset, plain);
     if (p.small_off && !r->all_rows) {
         if (tmalloc(ctx, &r->all_rows, 4 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
@@ -2047,6 +2202,12 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
     { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = verify ? nullptr : d_out; ra.cap = verify ? 0 : out_cap; ra.blob_cap = r->blob_cap; ra.verify = verify; ra.plain = plain; }
     r->select(slot);
     if (queued) *queued = true;
+    if (p.lean && ctx->lanes_on) {
+        if ((rc = lane_begin(ctx, r, slot, &run.on, &run.lane_ev))) return rc;
+    } else {
+        if (p.lean) ctx->lane_stats[3]++;  // a lean run kept off the lanes: a caller's stream, or a switch
+        lanes_close(ctx);                  // what this run queues on the main stream stands behind every lane run
+    }
     if ((rc = run_clear(ctx, r, p, run)) || !r->n) return rc;
     if (!p.small_off && !p.stored_only && (rc = run_small_rows(ctx, r, p, run))) return rc;
     if (p.decode && r->n_cand && (rc = run_block_items(ctx, r, p, run))) return rc;
@@ -2070,6 +2231,8 @@ static int rows_queue(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint
     return ZNIPPY_OK;
 }
 static void rows_abandon(znippy_ctx *ctx, znippy_rows *r) {
+    lanes_close(ctx);
+    (void)lanes_sync(ctx);
     if (hipEventRecord(ctx->ev_join, ctx->aux) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipGetLastError();
@@ -2080,7 +2243,7 @@ static void rows_abandon(znippy_ctx *ctx, znippy_rows *r) {
 
 int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs,
                                     uint64_t blob_base, void *d_out, uint64_t out_cap) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
     if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
@@ -2089,7 +2252,7 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
 
 // The same run without a hash (znippy_hip.h): every row is written where a decode run writes it and no digest is computed or compared.
 int znippy_decode_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
     if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
@@ -2099,14 +2262,14 @@ int znippy_decode_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blob
 // The same run without an output: every row is decoded as far as hashing it needs, hashed and compared, and nothing is written
 // that no kernel reads back (znippy_hip.h).  A run like any other in the table's sequence.
 int znippy_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (r->n && !d_blobs) return ZNIPPY_E_INVAL;
     return rows_queue(ctx, r, d_blobs, blob_base, nullptr, 0, true);
 }
 
 int znippy_rows_verify_scratch(znippy_ctx *ctx, znippy_rows *r, const void **d_base, uint64_t *bytes, uint64_t *row_offset) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !d_base || !bytes) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = rows_verify_slots(ctx, r);
@@ -2140,6 +2303,7 @@ static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
     if (!r->n || !r->run_seq || !(r->h_counters[16 * slot + 7])) return ZNIPPY_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, lanes_sync(ctx));                 // the latest run's kernel may be queued there
     HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     r->force_full = true;
     r->lean_hint = 0; r->lean_hint2 = 0;
@@ -2163,7 +2327,7 @@ static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
 // keeps two runs in flight reads run k's counters while run k + 1 executes (the read loop reports after the loop,
 // not per row: decompress.rs:L195-221).
 int znippy_rows_results_lagged(znippy_ctx *ctx, znippy_rows *r, unsigned lag, znippy_verify_counters *counters) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !counters || lag > 1 || r->run_seq <= lag) return ZNIPPY_E_INVAL;
     uint64_t c[8] = {0};
     if (r->n) {
@@ -2181,10 +2345,11 @@ int znippy_rows_results_lagged(znippy_ctx *ctx, znippy_rows *r, unsigned lag, zn
 
 int znippy_rows_results(znippy_ctx *ctx, znippy_rows *r, znippy_verify_counters *counters,
                         uint64_t *corrupt_rows, uint64_t corrupt_cap, int32_t *row_status) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (r->lane_used) HIPCHK(ctx, lanes_sync(ctx));
     if (r->aux_used) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     uint64_t c[8] = {0};
     if (r->n && r->run_seq) {
@@ -2216,7 +2381,7 @@ int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_
                               uint64_t blob_base, void *d_out, uint64_t out_cap,
                               znippy_verify_counters *counters, uint64_t *corrupt_rows,
                               uint64_t corrupt_cap, int32_t *row_status) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     int rc = znippy_decode_verify_rows_async(ctx, rows, d_blobs, blob_base, d_out, out_cap);
     if (rc) return rc;
     return znippy_rows_results(ctx, rows, counters, corrupt_rows, corrupt_cap, row_status);
@@ -2224,7 +2389,7 @@ int znippy_decode_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_
 
 int znippy_decode_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap,
                        znippy_verify_counters *counters, int32_t *row_status) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     int rc = znippy_decode_rows_async(ctx, rows, d_blobs, blob_base, d_out, out_cap);
     if (rc) return rc;
     return znippy_rows_results(ctx, rows, counters, nullptr, 0, row_status);
@@ -2232,7 +2397,7 @@ int znippy_decode_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, 
 
 int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, uint64_t blob_base,
                        znippy_verify_counters *counters, uint64_t *corrupt_rows, uint64_t corrupt_cap, int32_t *row_status) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     int rc = znippy_verify_rows_async(ctx, rows, d_blobs, blob_base);
     if (rc) return rc;
     return znippy_rows_results(ctx, rows, counters, corrupt_rows, corrupt_cap, row_status);
@@ -2392,7 +2557,7 @@ static int tree_fold_check(znippy_ctx *ctx, znippy_rows *r, const uint32_t *d_tr
 static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
                             const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
                             uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes, bool verified = false, uint64_t *hashed_bytes = nullptr) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (verified && !r->checksum && r->n) return ZNIPPY_E_INVAL;  // nothing to verify against
     if (decoded_bytes) *decoded_bytes = 0;
@@ -2673,7 +2838,7 @@ int znippy_rows_read_ranges_verified(znippy_ctx *ctx, znippy_rows *r, const void
 }
 
 static int rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_entries, uint64_t *row_first) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !n_entries) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int rc = rows_tree_layout(ctx, r);
@@ -2686,7 +2851,7 @@ static int rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_e
 // The producer: every row with entries decoded whole into the range scratch (stored rows: hashed where they lie), one k_block_cvs
 // launch in write mode for all of them, then the fold against the checksums.  Not a run, and nothing is installed.
 static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, uint8_t *tree, int32_t *row_status) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = rows_tree_layout(ctx, r);
@@ -2765,7 +2930,7 @@ static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_
 // The installer: the caller's entries go to the device, every row's are folded against its checksum, and only those that match count
 // from then on (tree_accept).  The checksum column alone is trusted.
 static int rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *tree, int32_t *row_status) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (!r->checksum) return ZNIPPY_E_INVAL;  // nothing could authenticate the entries
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -2815,10 +2980,11 @@ int znippy_rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *t
 #undef ZN_NO_THROW
 
 int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || !digests) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    if (r->lane_used) HIPCHK(ctx, lanes_sync(ctx));
     if (r->aux_used) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     if (r->n && r->run_seq) { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
     if (r->run_seq && r->run_args[(r->run_seq - 1) & 1].plain) return ZNIPPY_E_INVAL;  // a decode-only run computes no digest
@@ -2864,7 +3030,7 @@ void znippy_rounds_destroy(znippy_rounds *r) {
 
 int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint64_t *len,
                          const uint8_t *skip, uint64_t n, znippy_rounds **out) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !out || (n && (!src_offset || !len)) || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     TDbg td(ctx->sw.tdbg, "rounds_create");
@@ -2998,7 +3164,7 @@ static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_sr
 }
 
 int znippy_hash_rounds(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, uint8_t *digests) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !digests || (r->n && !d_src)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->n_ktimes = 0;
@@ -3029,7 +3195,7 @@ static int shim_reserve(znippy_ctx *ctx, size_t in_need, size_t out_need) {
 }
 
 int znippy_blake3(znippy_ctx *ctx, const void *src, size_t n, uint8_t out[32]) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !out || (n && !src)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = shim_reserve(ctx, n, 0);
@@ -3045,7 +3211,7 @@ int znippy_blake3(znippy_ctx *ctx, const void *src, size_t n, uint8_t out[32]) {
 }
 
 int znippy_decompress(znippy_ctx *ctx, const void *frame, size_t n, void *dst, size_t cap, size_t *written) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !frame || !written || (cap && !dst)) return ZNIPPY_E_INVAL;
     uint64_t usize = 0;
     int rc = znippy_get_decompressed_size(frame, n, &usize);
@@ -3121,7 +3287,7 @@ static bool ensure_ldm(znippy_ctx *ctx, znippy_rounds *r) {
 
 extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out,
                                                uint64_t blob_cap) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || (r->n && (!d_src || !d_blob_out))) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
@@ -3289,7 +3455,7 @@ extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r
 // that run's copy only.  Valid until two more encode calls have been queued on the table.
 extern "C" int znippy_rounds_results_lagged(znippy_ctx *ctx, znippy_rounds *r, unsigned lag, const uint64_t **blob_offset,
                                             const uint64_t **blob_size, const uint8_t **checksum, uint64_t *blob_bytes) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || lag > 1 || r->run_seq <= lag) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const unsigned slot = (unsigned)((r->run_seq - 1 - lag) & 1);
@@ -3310,7 +3476,7 @@ extern "C" int znippy_rounds_results_lagged(znippy_ctx *ctx, znippy_rounds *r, u
 
 extern "C" int znippy_rounds_results(znippy_ctx *ctx, znippy_rounds *r, uint64_t *blob_offset, uint64_t *blob_size,
                                      uint8_t *checksum, uint8_t *compressed, uint64_t *blob_bytes) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     if (blob_bytes) *blob_bytes = 0;
@@ -3341,7 +3507,7 @@ extern "C" int znippy_rounds_results(znippy_ctx *ctx, znippy_rounds *r, uint64_t
 // on this table (compressed[] = !skip is known to the caller already).
 extern "C" int znippy_rounds_results_view(znippy_ctx *ctx, znippy_rounds *r, const uint64_t **blob_offset,
                                           const uint64_t **blob_size, const uint8_t **checksum, uint64_t *blob_bytes) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     int rc = znippy_rounds_results(ctx, r, nullptr, nullptr, nullptr, nullptr, blob_bytes);
     if (rc) return rc;
     const size_t n = r->n;
@@ -3354,14 +3520,14 @@ extern "C" int znippy_rounds_results_view(znippy_ctx *ctx, znippy_rounds *r, con
 extern "C" int znippy_encode_hash_rounds(znippy_ctx *ctx, znippy_rounds *rounds, const void *d_src, void *d_blob_out,
                                          uint64_t blob_cap, uint64_t *blob_offset, uint64_t *blob_size,
                                          uint8_t *checksum, uint8_t *compressed, uint64_t *blob_bytes) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     int rc = znippy_encode_hash_rounds_async(ctx, rounds, d_src, d_blob_out, blob_cap);
     if (rc) return rc;
     return znippy_rounds_results(ctx, rounds, blob_offset, blob_size, checksum, compressed, blob_bytes);
 }
 
 extern "C" int znippy_compress(znippy_ctx *ctx, const void *src, size_t n, void *dst, size_t cap, size_t *written) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !written || !dst || (n && !src)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const size_t bound = znippy_compress_bound(n);
@@ -3389,7 +3555,7 @@ extern "C" size_t znippy_compress_bound(size_t n) {
 }
 
 extern "C" int znippy_rounds_set_blob_align(znippy_rounds *r, uint32_t align) {
-    if (!r || !r->ctx || r->ctx->closing || align < 1 || align > 4096 || (align & (align - 1))) return ZNIPPY_E_INVAL;
+    if (!r || !r->ctx || !ctx_enter(r->ctx) || align < 1 || align > 4096 || (align & (align - 1))) return ZNIPPY_E_INVAL;
     znippy_ctx *const ctx = r->ctx;
     if (align > 1 && !r->piece_pad) {  // cleared once, on the stream the runs are queued on
         HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -3417,7 +3583,7 @@ static int rounds_tree_layout(znippy_ctx *ctx, znippy_rounds *r) {
 }
 
 static int rounds_block_tree_layout(znippy_ctx *ctx, znippy_rounds *r, uint64_t *n_entries, uint64_t *round_first) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !n_entries) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int rc = rounds_tree_layout(ctx, r);
@@ -3430,7 +3596,7 @@ static int rounds_block_tree_layout(znippy_ctx *ctx, znippy_rounds *r, uint64_t 
 // Everything the feature needs, once per table: the list of units with entries and, per slot of the two-run ring, a device tree
 // buffer and its pinned mirror.  A failure leaves the table as it was (emission off, nothing kept).
 static int rounds_emit_block_tree(znippy_rounds *r, int on) {
-    if (!r || !r->ctx || r->ctx->closing) return ZNIPPY_E_INVAL;
+    if (!r || !r->ctx || !ctx_enter(r->ctx)) return ZNIPPY_E_INVAL;
     znippy_ctx *const ctx = r->ctx;
     if (!on || r->tree_ready) { r->emit_tree = on != 0; return ZNIPPY_OK; }
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -3472,7 +3638,7 @@ static int rounds_emit_block_tree(znippy_rounds *r, int on) {
 }
 
 static int rounds_block_tree(znippy_ctx *ctx, znippy_rounds *r, unsigned lag, uint8_t *tree) {
-    if (ctx && ctx->closing) return ZNIPPY_E_INVAL;  // destroyed context kept alive by its tables
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || lag > 1 || r->run_seq <= lag) return ZNIPPY_E_INVAL;
     const unsigned slot = (unsigned)((r->run_seq - 1 - lag) & 1);
     if (!r->tree_run[slot]) return ZNIPPY_E_INVAL;  // that run was queued with emission off

@@ -71,6 +71,19 @@ class Context:
         n = self.L.znippy_last_kernel_times(self.h, names, ms, 48)
         return [(names[i].decode(), float(ms[i])) for i in range(n)]
 
+    def run_lane_stats(self):
+        """Run lanes (znippy_hip.h): lean runs queued beside their predecessor / behind it / in front of which a main-stream
+        mark was recorded / kept off the lanes, since the context was created."""
+        st = (C.c_uint64 * 4)()
+        self._chk(self.L.znippy_ctx_run_lane_stats(self.h, st), "znippy_ctx_run_lane_stats")
+        return dict(zip(("unordered", "ordered", "marks", "off_lanes"), (int(v) for v in st)))
+
+    def run_lane_older_waits(self):
+        """Test introspection: lane runs made to wait for a run older than their predecessor that had not ended (znippy_hip.h)."""
+        v = C.c_uint64()
+        self._chk(self.L.znippy_ctx_run_lane_older_waits(self.h, C.byref(v)), "znippy_ctx_run_lane_older_waits")
+        return int(v.value)
+
     def set_level(self, level):
         """CompressCtx::new(compression_level), codec.rs:L16-28: levels 1-3 fast tier, 4-22 higher effort tier."""
         self._chk(self.L.znippy_ctx_set_level(self.h, int(level)), "znippy_ctx_set_level")
