@@ -21,6 +21,8 @@
  *                                barrel + writer bodies        znippy-compress/src/stream_packer.rs:L217-284,
  *                                                              znippy-compress/src/slot_packer.rs:L551-609
  *   znippy_hash_rounds           blake3-only / store path      slot_packer.rs:L553-560 (skip branch)
+ *   znippy_inflate_batch         ljar::decompress_jar_filter   znippy-plugin-maven/src/native.rs:L28-31,L47 (the inflate of the
+ *                                over a batch of containers     entry the filter chose), znippy-plugin-python/src/native.rs:L85-89
  *
  * Codec wire format: one standard Zstandard frame (RFC 8878) per chunk.  (The reference's
  * OpenZL framing cannot be reproduced or checked offline — see DESIGN.md "Oracle".)
@@ -43,6 +45,7 @@ extern "C" {
 #define ZNIPPY_E_UNSUPPORTED (-6) /* dictionary frames, unknown content size */
 #define ZNIPPY_E_CHECKSUM (-7)    /* frame content checksum (XXH64) mismatch */
 #define ZNIPPY_E_DIGEST (-8)      /* BLAKE3 of the bytes does not match the index checksum or block tree */
+#define ZNIPPY_E_NOENT (-9)       /* no entry of the container matches */
 
 typedef struct znippy_ctx znippy_ctx;
 typedef struct znippy_rows znippy_rows;     /* read side: a range of index rows, device-resident */
@@ -340,6 +343,49 @@ int znippy_rows_read_ranges_verified(znippy_ctx *ctx, znippy_rows *rows, const v
                                      const uint64_t *range_row, const uint64_t *range_begin, const uint64_t *range_len,
                                      const uint64_t *range_out, uint64_t n_ranges, void *d_out, uint64_t out_cap,
                                      int32_t *range_status, uint64_t *decoded_bytes, uint64_t *hashed_bytes);
+
+/* ---- raw DEFLATE of ZIP entries the engine already holds ----------------------------------------------------------------
+ * What the ingest plugins do to every jar, war and wheel (ljar::decompress_jar_filter, znippy-plugin-maven/src/native.rs:L28-31, batched
+ * at L47; znippy-plugin-python/src/native.rs:L85-89): one small entry of a ZIP container is found through the central directory and only
+ * that entry is inflated (TODO_NOW.md:L200-213: the filter comes before any decompression work).  The container bytes are in device
+ * memory already — the staging slot on the write side, the blob region or the output of a range read on the read side; this call turns a
+ * batch of such entries into their content without leaving the device.  Raw DEFLATE (RFC 1951) only: no gzip, zlib or deflate64 framing.
+ * All arrays are HOST arrays of n entries:
+ *   src_off, src_len   item i's compressed bytes are d_src[src_off[i] .. + src_len[i]); src_cap = size of the region at d_src
+ *   method             ZIP's numbers; NULL = every item is 8.  8: DEFLATE.  0: a copy, which needs src_len == out_len (ZNIPPY_E_CORRUPT
+ *                      otherwise).  Anything else: ZNIPPY_E_UNSUPPORTED
+ *   out_off            where item i lands in d_out; NULL = the outputs are packed back to back in array order (item i at the sum of the
+ *                      out_len in front of it, whatever their status)
+ *   out_len            the size the content must have (the central directory has it)
+ *   crc32              optional: the ZIP CRC-32 the content must have; a mismatch on an otherwise clean item is ZNIPPY_E_CHECKSUM
+ *   status             HOST, optional: 0 or ZNIPPY_E_* per item
+ *   crc_out            HOST, optional: the CRC-32 (ZIP polynomial, reflected) of the bytes produced, computed on the device, whenever the
+ *                      stream decoded to out_len bytes — status 0, and ZNIPPY_E_CHECKSUM, where it is the computed value; undefined for
+ *                      every other status
+ * Per item, a stream is valid exactly when zlib's raw inflate accepts it: block type 3, a stored block whose LEN is not the complement of
+ * NLEN, HLIT above 286 or HDIST above 30, a repeat without a previous length or past HLIT + HDIST (the two sets of lengths are one
+ * sequence: a repeat may cross from one into the other), an over-subscribed set, an incomplete code-length set, an incomplete
+ * literal/length or distance set unless its longest code has one bit, a missing symbol 256, decoded symbols 286, 287 or distance symbols
+ * 30, 31, a distance beyond the bytes produced so far and input that ends before the final block's end-of-block are ZNIPPY_E_CORRUPT.
+ * Every check of a symbol comes before its first output byte.  A symbol that would write past out_len is ZNIPPY_E_DST_SMALL; the final
+ * block's end-of-block with fewer than out_len bytes produced is ZNIPPY_E_CORRUPT; bytes of src_len behind the final block are ignored.
+ * A damaged stream is a status, never a fault, a hang or a write outside the item's destination.
+ * Host validation, per item, before any kernel runs: source not inside [0, src_cap), or off + len overflowing: ZNIPPY_E_INVAL;
+ * destination not inside out_cap: ZNIPPY_E_DST_SMALL; src_len or out_len of 4 GiB or more: ZNIPPY_E_UNSUPPORTED; then the method.  No
+ * kernel touches such an item and the call still returns ZNIPPY_OK, whatever the items report.  ZNIPPY_E_INVAL is returned only for NULL
+ * required arguments (src_off, src_len, out_len; d_src and d_out when n > 0), a closed context, or n of 2^32 - 16 or more; n == 0 is
+ * ZNIPPY_OK.
+ * Writes: no byte of d_out outside the destinations of the items is written; inside the destination of an item whose status is not 0 the
+ * bytes are unspecified; destinations must not overlap (not checked).  Every offset is a 64-bit value.
+ * Not a run: the call is synchronous, ordered on the context's stream behind whatever is queued, takes no slot of any table's two-run
+ * ring and leaves every table untouched.  It may be called between an async run and the read of its results without changing what that
+ * run reports (znippy_last_kernel_times then describes this call: inflate, inflate_crc).  Every allocation is made before the first
+ * stream operation.
+ * Kernels: one wave decodes one stream, its decoding tables in LDS (csrc/inflate.hip); the CRC is a launch of its own in which a
+ * workgroup splits an entry across its 256 lanes and folds the lane CRCs by multiplying with x^(8 len) mod P, as zlib's crc32_combine. */
+int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
+                         const uint8_t *method, void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
+                         const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,

@@ -130,6 +130,54 @@ int znippy_archive_read_range_verified(znippy_archive *a, const char *relative_p
 /* stats[0] entries loaded from the sidecar at open (0: none in use); [1] chunks whose sidecar entries were accepted; [2] chunks
  * whose sidecar entries were rejected; [3] chunks whose entries were built by a whole decode. */
 int znippy_archive_block_tree_stats(const znippy_archive *a, uint64_t stats[4]);
+/* ---- ZIP containers inside the archive ---- */
+/* ZIP directory locator (csrc/host/zip_dir.cc): pure functions over caller buffers — no I/O, no allocation, every read bounds-checked,
+ * so a crafted container is an error code.  Sizes and the CRC-32 come from the central directory, so entries written with a data
+ * descriptor (flag bit 3) need nothing more.  Not supported, each ZNIPPY_E_UNSUPPORTED: zip64 (by its locator or by the 0xFFFFFFFF /
+ * 0xFFFF markers), archives of several disks, encrypted entries (flag bit 0).  A malformed record is ZNIPPY_E_CORRUPT.
+ * The filter — the first entry, in directory order, whose name starts with `prefix` and ends with `suffix`, compared byte-wise, either
+ * may be empty — is this library's: ljar, whose decompress_jar_filter the reference calls, is not part of the reference tree and its
+ * rule cannot be read there.  The reference's callers apply exactly this test to what ljar returns
+ * (znippy-plugin-maven/src/native.rs:L31: the name ends with "pom.xml"). */
+typedef struct {
+    uint64_t local_header_offset, compressed_size, uncompressed_size; /* from the central directory */
+    uint32_t crc32;
+    uint16_t method, flags;
+    uint32_t name_len;
+    uint32_t dir_pos; /* where the entry's record starts inside the directory */
+} znippy_zip_entry;
+/* tail: the last tail_len = min(file_size, 65557) bytes of the file (the 22-byte end record behind a comment of up to 65,535 bytes;
+ * fewer are accepted, and then a longer comment is not found).  The record taken is the last one whose comment ends exactly where the
+ * file ends.  Directory offset, size and entry count are checked against the file: the directory lies in front of the record and
+ * holds at least 46 bytes per entry. */
+int znippy_zip_end_of_directory(const uint8_t *tail, size_t tail_len, uint64_t file_size, uint64_t *dir_offset, uint64_t *dir_size,
+                                uint64_t *n_entries);
+/* dir: the dir_len bytes of the central directory.  ZNIPPY_E_NOENT when none of the n_entries entries matches; the zip64, disk and
+ * encryption checks are made on the matching entry alone. */
+int znippy_zip_find_entry(const uint8_t *dir, size_t dir_len, uint64_t n_entries, const char *prefix, size_t prefix_len,
+                          const char *suffix, size_t suffix_len, znippy_zip_entry *out);
+/* header: the fixed 30 bytes of the entry's local header (at local_header_offset).  *data_offset = 30 + name length + extra length,
+ * both from the local header — they may differ from the central copy; the entry's data starts that far behind the header. */
+int znippy_zip_local_data_offset(const uint8_t *header, size_t header_len, uint64_t *data_offset);
+
+/* For every archived file of relative_paths (n_files of them; each a ZIP container: a jar, a war, a wheel): the content of its first
+ * entry whose name starts with name_prefix and ends with name_suffix (either may be NULL or empty) — what the reference's ingest
+ * plugins ask of ljar::decompress_jar_filter per container, on the read side and for all files at once.  No per-file round trip: one
+ * range-read pass (znippy_rows_read_ranges over a table of the chunks touched, so containers stored or compressed, in one chunk or
+ * several, all work) fetches every file's last 65,557 bytes, a second one the central directories, a third one each chosen entry's
+ * local header and compressed bytes; the compressed streams go to the device in one upload, through one znippy_inflate_batch with the
+ * directory's CRC-32s, and come back in one copy.
+ * Cost: every pass reads from the archive file, uploads and copies back on its own — of a stored chunk only the requested bytes, of a
+ * compressed chunk the whole frame in each pass that touches it; the third pass asks for up to 131,100 bytes beyond an entry's data,
+ * because the lengths that place the data are the local header's.
+ * Contents are packed in dst: file i at [entry_off[i], entry_off[i + 1]) (entry_off: n_files + 1 values), of length 0 when its status is
+ * not 0.  status (optional), per file: 0; ZNIPPY_E_INVAL an unknown path; the locator's codes (ZNIPPY_E_NOENT, ZNIPPY_E_CORRUPT,
+ * ZNIPPY_E_UNSUPPORTED); the inflate's codes (ZNIPPY_E_CORRUPT, ZNIPPY_E_CHECKSUM, ZNIPPY_E_UNSUPPORTED for a method other than 0 and 8);
+ * ZNIPPY_E_DST_SMALL when cap does not hold it (the files in front of it are unaffected); a chunk's decode error.  The call returns
+ * ZNIPPY_OK whatever the files report; NULL arguments give ZNIPPY_E_INVAL. */
+int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files,
+                                       const char *name_prefix, const char *name_suffix, void *dst, size_t cap,
+                                       uint64_t *entry_off /* n_files + 1 */, int32_t *status);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

@@ -1,0 +1,581 @@
+"""znippy_inflate_batch: raw DEFLATE streams decoded on the device, against Python's zlib as arbiter.
+Every batch goes through one call; sources start at odd offsets; 0xA5 guard bytes stand around the destinations and are checked
+afterwards.  Hand-built streams come from the small bit writer below, and every one of them is first shown to zlib, which must
+accept or reject it as the case intends.  The expected status of any stream with expected length n is what zlib makes of it:
+  raises / does not reach eof / eof with fewer than n bytes -> ZNIPPY_E_CORRUPT;  an (n+1)-th byte -> ZNIPPY_E_DST_SMALL;
+  eof with exactly n bytes -> 0 and zlib's bytes."""
+import ctypes as C
+import zlib
+
+import numpy as np
+import pytest
+
+import gen
+
+pytestmark = pytest.mark.gpu
+
+OK, E_INVAL, E_DST_SMALL, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM = 0, -1, -4, -5, -6, -7
+GUARD = 0xA5
+
+
+# ---- the arbiter ---------------------------------------------------------------------------------------------------------------
+
+def classify(data, n):
+    """(expected status, expected bytes or None) of stream `data` with expected length n, from zlib's raw inflate"""
+    d = zlib.decompressobj(-15)
+    try:
+        out = d.decompress(bytes(data), n + 1)
+    except zlib.error:
+        return E_CORRUPT, None
+    if len(out) > n:
+        return E_DST_SMALL, None
+    if not d.eof or len(out) < n:
+        return E_CORRUPT, None
+    return OK, out
+
+
+def deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    return c.compress(data) + c.flush()
+
+
+# ---- a bit writer and RFC 1951's codes -----------------------------------------------------------------------------------------
+
+LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+LEXT = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
+DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
+FIXED_LL = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
+FIXED_D = [5] * 32
+PLAIN_CL = [4] * 13 + [5] * 6          # a complete code over all 19 code-length symbols
+
+
+class Bits:
+    def __init__(self):
+        self.b = []
+
+    def put(self, v, n):                # a value, least significant bit first
+        self.b += [(v >> i) & 1 for i in range(n)]
+
+    def code(self, c):                  # a Huffman code (value, length), most significant bit first
+        v, n = c
+        self.b += [(v >> i) & 1 for i in reversed(range(n))]
+
+    def align(self):
+        self.b += [0] * (-len(self.b) % 8)
+
+    def raw(self, data):
+        assert len(self.b) % 8 == 0
+        for x in data:
+            self.put(x, 8)
+
+    def bytes(self):
+        return np.packbits(np.array(self.b, np.uint8), bitorder="little").tobytes()
+
+
+def canon(lens):
+    """symbol -> (code, length) of the canonical code with these lengths (complete or not)"""
+    count = [0] * 17
+    for n in lens:
+        count[n] += 1
+    count[0] = 0
+    nxt, code = [0] * 17, 0
+    for n in range(1, 16):
+        code = (code + count[n - 1]) << 1
+        nxt[n] = code
+    out = {}
+    for s, n in enumerate(lens):
+        if n:
+            out[s] = (nxt[n], n)
+            nxt[n] += 1
+    return out
+
+
+def put_ops(bw, ops, ll, dd, eob=True):
+    """ops: ints (literals), ('m', length, distance), ('ll', symbol) a bare literal/length symbol, ('sym', symbol, extra value,
+    distance symbol, extra value) a match given by its symbols"""
+    for op in ops:
+        if isinstance(op, int):
+            bw.code(ll[op])
+        elif op[0] == "ll":
+            bw.code(ll[op[1]])
+        elif op[0] == "sym":
+            _, ls, lx, ds, dx = op
+            bw.code(ll[ls]); bw.put(lx, LEXT[ls - 257] if ls <= 285 else 0)
+            bw.code(dd[ds]); bw.put(dx, DEXT[ds] if ds < 30 else 0)
+        else:
+            _, length, dist = op
+            i = max(k for k in range(29) if LBASE[k] <= length and (k == 28 or length < 258))
+            bw.code(ll[257 + i]); bw.put(length - LBASE[i], LEXT[i])
+            j = max(k for k in range(30) if DBASE[k] <= dist)
+            bw.code(dd[j]); bw.put(dist - DBASE[j], DEXT[j])
+    if eob:
+        bw.code(ll[256])
+
+
+def fixed_block(bw, ops, final=1, eob=True):
+    bw.put(final, 1); bw.put(1, 2)
+    put_ops(bw, ops, canon(FIXED_LL), canon(FIXED_D), eob)
+
+
+def stored_block(bw, data, final=1, nlen=None):
+    bw.put(final, 1); bw.put(0, 2); bw.align()
+    bw.put(len(data), 16); bw.put((len(data) ^ 0xFFFF) if nlen is None else nlen, 16)
+    bw.raw(data)
+
+
+def dynamic_block(bw, ll_lens, d_lens, ops, final=1, cl_lens=None, cl_syms=None, hlit=None, hdist=None, body=True, eob=True):
+    """cl_syms: the code-length symbols as (symbol, extra value) pairs; None: every length as a symbol of its own"""
+    cl_lens = PLAIN_CL if cl_lens is None else cl_lens
+    if cl_syms is None:
+        cl_syms = [(n, 0) for n in list(ll_lens) + list(d_lens)]
+    bw.put(final, 1); bw.put(2, 2)
+    bw.put((len(ll_lens) if hlit is None else hlit) - 257, 5)
+    bw.put((len(d_lens) if hdist is None else hdist) - 1, 5)
+    bw.put(19 - 4, 4)
+    for s in CL_ORDER:
+        bw.put(cl_lens[s], 3)
+    cc = canon(cl_lens)
+    for s, x in cl_syms:
+        bw.code(cc[s])
+        bw.put(x, {16: 2, 17: 3, 18: 7}.get(s, 0))
+    if body:
+        put_ops(bw, ops, canon(ll_lens), canon(d_lens), eob)
+
+
+def ll_lens_for(pairs, n=257):
+    lens = [0] * n
+    for s, k in pairs:
+        lens[s] = k
+    return lens
+
+
+TEXT = gen.pseudo_text(300_000, seed=7)
+
+
+# ---- cases ---------------------------------------------------------------------------------------------------------------------
+
+def block_kind_cases():
+    rnd = np.random.default_rng(11).integers(0, 256, 32768, dtype=np.uint8).tobytes()
+    cases = [("empty", bytes([3, 0]), 0), ("one byte", deflate(b"Z"), 1),
+             ("stored 70000", deflate((rnd * 3)[:70000], 0), 70000),
+             ("fixed text", deflate(TEXT[:5000], 6, zlib.Z_FIXED), 5000),
+             ("level 9 text", deflate(TEXT, 9), len(TEXT)),
+             ("rle zeros", deflate(bytes(300_000), 6, zlib.Z_RLE), 300_000),
+             ("huffman only", deflate(TEXT[:20000], 6, zlib.Z_HUFFMAN_ONLY), 20000)]
+    bw = Bits()
+    stored_block(bw, b"", final=0)
+    fixed_block(bw, list(b"behind an empty stored block"))
+    cases.append(("empty stored block first", bw.bytes(), 28))
+    for dist in (1, 2, 3, 63, 64, 65, 257, 258, 259, 32768):
+        bw = Bits()
+        head = rnd if dist == 32768 else rnd[:dist]
+        if dist == 32768:
+            stored_block(bw, head, final=0)
+            fixed_block(bw, [("m", 258, dist)])
+        else:
+            fixed_block(bw, list(head) + [("m", 258, dist)])
+        cases.append((f"match 258 at distance {dist}", bw.bytes(), len(head) + 258))
+    return cases
+
+
+def table_corner_cases():
+    cases = []
+    # literal/length codes of 15 bits, and a lone distance code of length 1
+    ll = ll_lens_for([(97 + k, k + 1) for k in range(13)] + [(257, 14), (110, 15), (256, 15)], 258)
+    bw = Bits()
+    dynamic_block(bw, ll, [1], list(b"abcdefghijklmnnmlkjihgfedcba") + [("m", 3, 1)] * 3 + [110])
+    cases.append(("15-bit codes, lone distance code", bw.bytes(), 28 + 9 + 1))
+    # HLIT 286 with HDIST 30
+    bw = Bits()
+    dynamic_block(bw, [8] * 226 + [9] * 60, [4] * 2 + [5] * 28, list(b"all 286 and all 30") + [("m", 258, 18), ("m", 100, 3), 255, 0])
+    cases.append(("HLIT 286, HDIST 30", bw.bytes(), 18 + 258 + 100 + 2))
+    # a code-16 repeat that crosses from the literal/length lengths into the distance lengths: 120 zeros, 1, 2, 134 zeros, a 4 for
+    # symbol 256, then "repeat it" 6 times — symbols 257, 258, 259 and the first three distance codes — and 13 more distance codes
+    ll = ll_lens_for([(120, 1), (121, 2), (256, 4), (257, 4), (258, 4), (259, 4)], 260)
+    syms = [(18, 120 - 11), (1, 0), (2, 0), (18, 134 - 11), (4, 0), (16, 6 - 3), (16, 6 - 3), (16, 6 - 3), (4, 0)]
+    bw = Bits()
+    dynamic_block(bw, ll, [4] * 16, [120, 121, 120, 120, ("m", 5, 4), ("m", 3, 7)], cl_syms=syms)
+    cases.append(("repeat across the two sets", bw.bytes(), 4 + 5 + 3))
+    # a dynamic block holding only end-of-block (its one code has one bit, and there is no distance code), then a fixed block
+    bw = Bits()
+    dynamic_block(bw, ll_lens_for([(256, 1)]), [0], [], final=0, cl_syms=[(18, 127), (18, 118 - 11), (1, 0), (0, 0)])
+    fixed_block(bw, list(b"after nothing"))
+    cases.append(("dynamic block of end-of-block only", bw.bytes(), 13))
+    # a stored block begun at bit 3 of a byte
+    bw = Bits()
+    fixed_block(bw, [200], final=0)
+    assert len(bw.b) % 8 == 3
+    stored_block(bw, b"stored from bit 3")
+    cases.append(("stored block at bit 3", bw.bytes(), 1 + 17))
+    return cases
+
+
+def rejection_cases():
+    """(what, stream, n): every one must classify as ZNIPPY_E_CORRUPT"""
+    out = []
+
+    def add(what, bw, n=10):
+        out.append((what, bw.bytes() + bytes(8), n))   # (zeros behind it: the error is the stream's, not a short input's)
+    bw = Bits(); bw.put(1, 1); bw.put(3, 2); add("block type 3", bw)
+    bw = Bits(); stored_block(bw, b"0123456789", nlen=10); add("LEN is not the complement of NLEN", bw)
+    ok_ll = ll_lens_for([(65, 1), (256, 1)])
+    for hlit in (287, 288):
+        bw = Bits(); dynamic_block(bw, [8] * 224 + [9] * 64, [1, 1], [], hlit=hlit, body=False); add(f"HLIT {hlit}", bw)
+    for hdist in (31, 32):
+        bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], hdist=hdist, body=False); add(f"HDIST {hdist}", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_syms=[(16, 0)], body=False); add("code 16 with no previous length", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_syms=[(18, 127), (18, 127)], body=False); add("repeat past HLIT + HDIST", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_syms=[(18, 127), (18, 107), (1, 0), (1, 0), (17, 0)], body=False); add("zeros past HLIT + HDIST", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_lens=[1, 1, 1] + [0] * 16, cl_syms=[], body=False); add("over-subscribed code-length set", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_lens=[2, 2, 2] + [0] * 16, cl_syms=[], body=False); add("incomplete code-length set", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_lens=[0] * 18 + [1], cl_syms=[], body=False); add("code-length set of one 1-bit code", bw)
+    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 1), (66, 1), (256, 1)]), [1, 1], [], body=False); add("over-subscribed literal/length set", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1, 1], [], body=False); add("over-subscribed distance set", bw)
+    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 2), (66, 2), (256, 2)]), [1, 1], [], body=False); add("incomplete literal/length set", bw)
+    bw = Bits(); dynamic_block(bw, ok_ll, [2, 2, 2], [], body=False); add("incomplete distance set", bw)
+    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 1), (66, 1)]), [1, 1], [], body=False); add("no end-of-block code", bw)
+    # a lone 1-bit literal/length code is allowed; the bit pattern it leaves unused is not
+    bw = Bits(); dynamic_block(bw, ll_lens_for([(256, 1)]), [0], [], body=False); bw.put(1, 1); add("unused code of an incomplete set", bw, 0)
+    # ... nor is any distance code where the block has none, or the unused one of a lone distance code
+    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 2), (256, 2), (257, 1)], 258), [0], [65, 65, 65, ("ll", 257)], eob=False); bw.put(0, 4); add("a match in a block without distance codes", bw)
+    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 2), (256, 2), (257, 1)], 258), [1], [65, 65, 65, ("ll", 257)], eob=False); bw.put(1, 4); add("unused code of a lone distance code", bw)
+    for s in (286, 287):
+        bw = Bits(); fixed_block(bw, [65, 66, ("ll", s)]); add(f"literal/length symbol {s}", bw)
+    for s in (30, 31):
+        bw = Bits(); fixed_block(bw, [65, 66, 67, ("sym", 257, 0, s, 0)]); add(f"distance symbol {s}", bw)
+    bw = Bits(); fixed_block(bw, [65, 66, 67, ("m", 3, 4)]); add("distance beyond the bytes produced", bw)
+    bw = Bits(); fixed_block(bw, [("m", 3, 1)]); add("a match as the first symbol", bw)
+    bw = Bits(); fixed_block(bw, list(b"0123456789"), final=0); out.append(("no final block", bw.bytes(), 10))
+    bw = Bits(); fixed_block(bw, list(b"01234")); add("end-of-block short of the expected length", bw)
+    return out
+
+
+def truncation_cases():
+    fixed = deflate(TEXT[:150], 6, zlib.Z_FIXED)
+    i = 150
+    while len(fixed) != 91:        # grow or shrink the input until the stream has the length the case names
+        i += 1 if len(fixed) < 91 else -1
+        fixed = deflate(TEXT[:i], 6, zlib.Z_FIXED)
+        assert 20 < i < 1000
+    nf = i
+    j = 400
+    dyn = deflate(TEXT[1000:1000 + j], 9)
+    seen = set()
+    while len(dyn) != 260:
+        assert j not in seen, "no input of this text deflates to 260 bytes"
+        seen.add(j)
+        j += 1 if len(dyn) < 260 else -1
+        dyn = deflate(TEXT[1000:1000 + j], 9)
+    assert dyn[0] & 6 == 4 and fixed[0] & 6 == 2
+    return [(f"fixed[:{k}]", fixed[:k], nf) for k in range(len(fixed))] + [(f"dynamic[:{k}]", dyn[:k], j) for k in range(len(dyn))], (fixed, nf), (dyn, j)
+
+
+def mutant_streams():
+    return [(deflate(TEXT[:200], 6, zlib.Z_FIXED), 200), (deflate(TEXT[:3000], 9), 3000), (deflate(TEXT[5000:5100], 0), 100),
+            (deflate(TEXT[:600], 6, zlib.Z_HUFFMAN_ONLY), 600)]
+
+
+def all_mutants():
+    out = []
+    for s, n in mutant_streams():
+        for bit in range(8 * len(s)):
+            m = bytearray(s)
+            m[bit >> 3] ^= 1 << (bit & 7)
+            out.append((bytes(m), n))
+    return out
+
+
+# ---- one call ------------------------------------------------------------------------------------------------------------------
+
+def run_batch(ctx, items, layout="packed", crc32=None, method=None, gap=37):
+    """items: (stream, expected length).  layout: "packed" (out_off NULL), "reversed" (explicit offsets, the last item first, a guard
+    gap in front of every destination).  Returns (status, crc_out, list of produced bytes); asserts that every byte outside the
+    destinations still holds the guard value."""
+    import torch
+    n = len(items)
+    src_off, pos = [], 1
+    for s, _ in items:
+        src_off.append(pos)
+        pos = (pos + len(s)) | 1                  # every source starts at an odd offset
+    src = np.full(pos + 64, 0x5A, np.uint8)
+    for (s, _), o in zip(items, src_off):
+        src[o:o + len(s)] = np.frombuffer(s, np.uint8)
+    lens = [k for _, k in items]
+    if layout == "packed":
+        out_off, total = None, sum(lens) + gap
+        offs = np.cumsum([0] + lens[:-1]) if n else np.zeros(0)
+    else:
+        offs, at = [0] * n, 0
+        for i in reversed(range(n)):
+            at += gap
+            offs[i] = at
+            at += lens[i]
+        total = at + gap
+        out_off = offs
+    d_src = torch.from_numpy(src).cuda()
+    d_out = torch.full((total,), GUARD, dtype=torch.uint8, device="cuda")
+    status, crc = ctx.inflate_batch(d_src, src_off, [len(s) for s, _ in items], d_out, lens, out_off=out_off, crc32=crc32, method=method)
+    img = d_out.cpu().numpy()
+    outside = np.ones(total, bool)
+    got = []
+    for o, k in zip(offs, lens):
+        outside[int(o):int(o) + k] = False
+        got.append(img[int(o):int(o) + k].tobytes())
+    assert (img[outside] == GUARD).all(), "a byte outside the destinations was written"
+    return status, crc, got
+
+
+def check(ctx, cases, layout="packed", accept_only=False):
+    """cases: (what, stream, n).  Every status is zlib's verdict; every clean item has zlib's bytes and CRC."""
+    want = [classify(s, n) for _, s, n in cases]
+    if accept_only:
+        for (what, _, _), (st, _) in zip(cases, want):
+            assert st == OK, f"zlib itself does not accept the fixture: {what}"
+    status, crc, got = run_batch(ctx, [(s, n) for _, s, n in cases], layout)
+    for i, ((what, _, n), (st, ref)) in enumerate(zip(cases, want)):
+        assert status[i] == st, (what, int(status[i]), st)
+        if st == OK:
+            assert got[i] == ref, what
+            assert int(crc[i]) == zlib.crc32(ref), what
+    return status
+
+
+# ---- 1. every block kind -------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("layout", ["packed", "reversed"])
+def test_every_block_kind(gpu_ctx, layout):
+    cases = block_kind_cases()
+    assert deflate(bytes(70000), 0)[:5] == bytes([0, 0xFF, 0xFF, 0, 0])          # level 0: a first stored block of the maximum 65,535
+    check(gpu_ctx, cases, layout, accept_only=True)
+
+
+# ---- 2. table corners ----------------------------------------------------------------------------------------------------------
+
+def test_table_corners(gpu_ctx):
+    check(gpu_ctx, table_corner_cases(), "reversed", accept_only=True)
+
+
+# ---- 3. rejections -------------------------------------------------------------------------------------------------------------
+
+def test_rejections_between_clean_items(gpu_ctx):
+    bad = rejection_cases()
+    for what, s, n in bad:
+        assert classify(s, n)[0] == E_CORRUPT, f"zlib does not reject the fixture: {what}"
+    trunc, (fixed, nf), (dyn, nd) = truncation_cases()
+    for what, s, n in trunc:
+        assert classify(s, n)[0] == E_CORRUPT, what
+    clean = [("clean fixed", fixed, nf), ("clean dynamic", dyn, nd), ("clean stored", deflate(TEXT[:300], 0), 300)]
+    cases = []
+    for k, c in enumerate(bad + trunc):
+        cases += [c, clean[k % 3]]
+    status = check(gpu_ctx, cases, "reversed")
+    assert (status[0::2] == E_CORRUPT).all() and (status[1::2] == OK).all()
+
+
+# ---- 4. every single-bit mutant ------------------------------------------------------------------------------------------------
+
+def test_every_single_bit_mutant(gpu_ctx):
+    muts = all_mutants()
+    want = [classify(s, n) for s, n in muts]
+    counts = {k: sum(1 for st, _ in want if st == k) for k in (E_CORRUPT, E_DST_SMALL, OK)}
+    print("mutants", len(muts), counts)
+    assert len(muts) == sum(8 * len(s) for s, _ in mutant_streams()) and sum(counts.values()) == len(muts)
+    status, crc, got = run_batch(gpu_ctx, muts, "reversed", gap=5)
+    wrong = [(i, int(status[i]), st) for i, (st, _) in enumerate(want) if status[i] != st]
+    assert not wrong, (len(wrong), wrong[:10])
+    for i, (st, ref) in enumerate(want):
+        if st == OK:
+            assert got[i] == ref and int(crc[i]) == zlib.crc32(ref), i
+
+
+# ---- 5. methods and CRC --------------------------------------------------------------------------------------------------------
+
+def test_methods_and_crc(gpu_ctx):
+    a, b = TEXT[:4000], TEXT[4000:4777]
+    items = [(deflate(a), len(a)), (deflate(b), len(b)), (a, len(a)), (b, len(b) + 1), (deflate(a), len(a)), (b, len(b))]
+    method = [8, 8, 0, 0, 12, 0]
+    crcs = [zlib.crc32(a), zlib.crc32(b) ^ 0x8000, zlib.crc32(a), 0, 0, zlib.crc32(b) ^ 1]
+    status, crc, got = run_batch(gpu_ctx, items, "reversed", crc32=crcs, method=method)
+    assert list(status) == [OK, E_CHECKSUM, OK, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM]
+    assert got[0] == a and got[2] == a
+    assert [int(crc[i]) for i in (0, 1, 2, 5)] == [zlib.crc32(a), zlib.crc32(b), zlib.crc32(a), zlib.crc32(b)]   # a mismatch returns the computed value
+    status, crc, got = run_batch(gpu_ctx, items[:3], "packed", crc32=None, method=None)                       # method NULL: every item is DEFLATE
+    assert list(status) == [OK, OK, classify(a, len(a))[0]] and status[2] != OK and int(crc[1]) == zlib.crc32(b)
+
+
+# ---- 6. host validation and the call's rules -----------------------------------------------------------------------------------
+
+def test_host_validation_and_call_rules(gpu_ctx):
+    import torch
+    from znippy_amd import _lib
+    L = _lib.lib()
+    s = deflate(TEXT[:1000])
+    d_src = torch.from_numpy(np.frombuffer(bytes(7) + s, np.uint8).copy()).cuda()
+    d_out = torch.full((4096,), GUARD, dtype=torch.uint8, device="cuda")
+    big = (1 << 64) - 4
+    src_off = [7, 7, big, 7, 7, 7, 7]
+    src_len = [len(s), len(s) + 1, 8, len(s), len(s), 1 << 32, len(s)]
+    out_off = [0, 1000, 1000, 4096 - 999, big, 1000, 2000]
+    out_len = [1000, 1000, 1000, 1000, 1000, 1000, 1000]
+    status, _ = gpu_ctx.inflate_batch(d_src, src_off, src_len, d_out, out_len, out_off=out_off)
+    assert list(status) == [OK, E_INVAL, E_INVAL, E_DST_SMALL, E_DST_SMALL, E_INVAL, OK]    # past src_cap, overflowing, past out_cap
+    img = d_out.cpu().numpy()
+    assert img[:1000].tobytes() == TEXT[:1000] and img[2000:3000].tobytes() == TEXT[:1000] and (img[1000:2000] == GUARD).all() and (img[3000:] == GUARD).all()
+    # sizes of 4 GiB and more are refused before any kernel (the regions only have to be declared that big)
+    status, _ = gpu_ctx.inflate_batch(d_src, [0, 0], [1 << 32, 8], d_out, [8, 1 << 32], out_off=[0, 0], src_cap=1 << 33, out_cap=1 << 33)
+    assert list(status) == [E_UNSUPPORTED, E_UNSUPPORTED]
+    # n == 0, NULL arguments, n too large, a closed context
+    u64 = lambda *v: (C.c_uint64 * len(v))(*v)   # noqa: E731
+    st = (C.c_int32 * 1)(99)
+    sp, op = C.c_void_p(d_src.data_ptr()), C.c_void_p(d_out.data_ptr())
+
+    def call(h, dsrc, so, sl, dout, ol, n):
+        return L.znippy_inflate_batch(h, dsrc, d_src.numel(), so, sl, None, dout, d_out.numel(), None, ol, None, n, st, None)
+    assert call(gpu_ctx.h, None, None, None, None, None, 0) == OK
+    assert call(gpu_ctx.h, sp, u64(7), u64(len(s)), op, u64(1000), 1) == OK and st[0] == OK
+    for args in [(None, u64(7), u64(len(s)), op, u64(1000)), (sp, None, u64(len(s)), op, u64(1000)), (sp, u64(7), None, op, u64(1000)),
+                 (sp, u64(7), u64(len(s)), None, u64(1000)), (sp, u64(7), u64(len(s)), op, None)]:
+        assert call(gpu_ctx.h, *args, 1) == E_INVAL
+    assert call(None, sp, u64(7), u64(len(s)), op, u64(1000), 1) == E_INVAL
+    assert call(gpu_ctx.h, sp, u64(7), u64(len(s)), op, u64(1000), (1 << 32) - 16) == E_INVAL
+    other = C.c_void_p()
+    assert L.znippy_ctx_create(0, None, C.byref(other)) == 0
+    t = C.c_void_p()
+    bitmap = (C.c_uint8 * 1)(0)
+    assert L.znippy_rows_create(other, u64(0), u64(500), bitmap, u64(500), None, None, 0, 1, C.byref(t)) == 0
+    L.znippy_ctx_destroy(other)                                # closed, kept alive by its table
+    assert call(other, sp, u64(7), u64(len(s)), op, u64(1000), 1) == E_INVAL
+    L.znippy_rows_destroy(t)
+    torch.cuda.synchronize()
+
+
+def test_not_a_run_and_kernel_times(gpu_ctx, oracle):
+    from test_gpu_ranges import own_frames, sentinel, table_of
+    rows = [gen.pseudo_text(300_001, seed=51), gen.incompressible(9, 70_000), gen.text(10_240)]
+    comp = [1, 0, 1]
+    frames = [f if c else r for f, r, c in zip(own_frames(19, rows), rows, comp)]
+    ck = np.stack([np.frombuffer(oracle.blake3(r), np.uint8) for r in rows])
+    ck[2] ^= 1                                                  # one mismatch, so that the corrupt list has an entry
+    total = sum(len(r) for r in rows)
+    items = [(deflate(TEXT[:3000]), 3000), (deflate(TEXT[:100]) + b"trailing bytes", 100)]
+
+    def sequence(mixed_in):
+        rt, d_blobs, _ = table_of(gpu_ctx, frames, rows, comp=comp, checksum=ck)
+        out = sentinel(total + 64)
+        rt.decode_verify_async(d_blobs, out)
+        if mixed_in:
+            status, crc, got = run_batch(gpu_ctx, items)
+            assert list(status) == [OK, OK] and got[0] == TEXT[:3000] and got[1] == TEXT[:100]   # (bytes behind the final block are ignored)
+            names = [k for k, _ in gpu_ctx.kernel_times()]
+            assert names == ["inflate", "inflate_crc"], names
+        counters, corrupt, status = rt.results()
+        res = (counters, list(corrupt), status.copy(), rt.digests().copy(), out.cpu().numpy())
+        rt.close()
+        return res
+    plain, mixed = sequence(False), sequence(True)
+    assert plain[0]["corrupt_rows"] == 1 and plain[1] == [2]
+    for k, (x, y) in enumerate(zip(plain, mixed)):
+        assert np.array_equal(x, y) if isinstance(x, np.ndarray) else x == y, k
+
+
+# ---- 7. size and count ---------------------------------------------------------------------------------------------------------
+
+def test_one_big_entry_and_many_small_ones(gpu_ctx):
+    big = gen.pseudo_text(3 << 20, seed=3)
+    check(gpu_ctx, [("3 MiB", deflate(big, 6), len(big))], "reversed", accept_only=True)
+    small = [(f"entry {i}", deflate(TEXT[37 * i:37 * i + 4096], 6), 4096) for i in range(2000)]
+    check(gpu_ctx, small, "packed", accept_only=True)
+
+
+# ---- 8. beyond 4 GiB -----------------------------------------------------------------------------------------------------------
+
+def test_sources_and_destinations_beyond_4_gib(gpu_ctx):
+    import torch
+    T = 1 << 32
+    size = T + (1 << 20)
+    free, _ = torch.cuda.mem_get_info()
+    if free < 3 * size:
+        pytest.skip(f"two regions of 4 GiB + 1 MiB need {3 * size >> 20} MiB of free device memory, {free >> 20} MiB are free")
+    d_src = torch.empty(size, dtype=torch.uint8, device="cuda")
+    d_out = torch.empty(size, dtype=torch.uint8, device="cuda")
+    datas = [TEXT[:40_000], TEXT[40_000:140_000], TEXT[150_000:150_900], TEXT[200_000:260_000]]
+    streams = [deflate(d, 6) for d in datas]
+    assert len(streams[0]) > 2002
+    # source / destination: across the line, above it, below it (destination above), above it (destination across)
+    src_off = [T - 1001, T + 300_001, 12_345, T + 500_001]
+    out_off = [T + 700_000, T + 100_000, T + 600_001, T - 30_000]
+    W = 64
+
+    def windows(o, k):
+        """the guard windows of a destination: around it, and where offsets cut to 32 bits would put its bytes above the line"""
+        return [(o - W, o), (o + k, o + k + W), (max(max(o, T) - T - W, 0), o + k - T + W)]
+    for s, o in zip(streams, src_off):
+        d_src[o:o + len(s)] = torch.from_numpy(np.frombuffer(s, np.uint8).copy()).cuda()
+    for d, o in zip(datas, out_off):
+        for lo, hi in windows(o, len(d)):
+            d_out[lo:hi] = GUARD
+    status, crc = gpu_ctx.inflate_batch(d_src, src_off, [len(s) for s in streams], d_out, [len(d) for d in datas], out_off=out_off,
+                                        crc32=[zlib.crc32(d) for d in datas])
+    assert list(status) == [OK] * 4
+    for d, o, c in zip(datas, out_off, crc):
+        assert d_out[o:o + len(d)].cpu().numpy().tobytes() == d and int(c) == zlib.crc32(d)
+        for lo, hi in windows(o, len(d)):
+            assert (d_out[lo:hi] == GUARD).all().item(), (o, lo)
+    del d_src, d_out
+    torch.cuda.empty_cache()
+
+
+# ---- 9. stored blocks in the middle of a stream: flush points ------------------------------------------------------------------
+
+def flushed_stream(data, piece, kinds, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
+    """`data` deflated with a flush of kinds[k % len] behind every `piece` bytes: each flush writes an empty stored block"""
+    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
+    out = []
+    for k, at in enumerate(range(0, len(data), piece)):
+        out.append(c.compress(data[at:at + piece]))
+        out.append(c.flush(kinds[k % len(kinds)]))
+    return b"".join(out) + c.flush()
+
+
+def test_flush_points_all_over_the_input_window(gpu_ctx):
+    """Z_SYNC_FLUSH and Z_FULL_FLUSH write an empty stored block wherever they are asked to: behind a Huffman block, at any byte
+    of the stream — also where the decoder's 2 KiB input window has just been loaded anew while the bit buffer still held bytes from
+    in front of it, so that the stored block sets the read position back in front of the window.  Streams of several window lengths
+    with flushes every 50 to 3,000 bytes; then one flush behind P literal-only bytes for every P of a range in which the empty
+    block moves byte by byte across the first two places the window is reloaded at (near stream offsets 2,057 and 4,100)."""
+    cases = []
+    for piece, kinds in [(50, [zlib.Z_SYNC_FLUSH]), (97, [zlib.Z_FULL_FLUSH]), (211, [zlib.Z_SYNC_FLUSH, zlib.Z_FULL_FLUSH]), (500, [zlib.Z_SYNC_FLUSH]),
+                         (1301, [zlib.Z_FULL_FLUSH, zlib.Z_SYNC_FLUSH]), (3000, [zlib.Z_SYNC_FLUSH])]:
+        for k in range(4):
+            d = TEXT[10_000 * k:10_000 * k + 40_000 + 13 * k]
+            s = flushed_stream(d, piece + k, kinds, 6 if k % 2 else 9)
+            assert len(s) > 4 * 2048
+            cases.append((f"flush every {piece + k}", s, len(d)))
+    for p in range(2600, 7400, 7):
+        d = TEXT[:p + 300]
+        c = zlib.compressobj(6, zlib.DEFLATED, -15, 9, zlib.Z_HUFFMAN_ONLY)
+        s = c.compress(d[:p]) + c.flush(zlib.Z_SYNC_FLUSH if p % 2 else zlib.Z_FULL_FLUSH) + c.compress(d[p:]) + c.flush()
+        cases.append((f"one flush behind {p} bytes", s, len(d)))
+    check(gpu_ctx, cases, "reversed", accept_only=True)
+
+
+def test_short_stored_blocks_at_every_byte_around_the_window_reloads(gpu_ctx):
+    """Hand-built: a fixed block of P literals (8 bits each), a stored block of 0, 1 or 5 bytes, a final fixed block.  The stored
+    block's header begins at bit 10 + 8 P of the stream: P sweeps it byte by byte over stream offsets 2,036 – 2,076 and 4,091 –
+    4,136, around the first two places at which the decoder loads its input window anew."""
+    text = bytes(b & 0x7F for b in TEXT[:4200])           # literals below 144: 8-bit codes
+    pre = Bits()
+    fixed_block(pre, list(text), final=0, eob=False)
+    tail = list(b"behind the stored block " * 3)
+    cases = []
+    for lo, hi in ((2035, 2076), (4090, 4136)):
+        for p in range(lo, hi):
+            for short in (b"", b"x", b"short"):
+                bw = Bits()
+                bw.b = pre.b[:3 + 8 * p] + [0] * 7        # P literals and the end-of-block code
+                stored_block(bw, short, final=0)
+                fixed_block(bw, tail)
+                cases.append((f"{len(short)} stored bytes behind {p} literals", bw.bytes(), p + len(short) + len(tail)))
+    check(gpu_ctx, cases, "packed", accept_only=True)

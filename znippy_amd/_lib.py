@@ -13,11 +13,11 @@ from . import _build
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 OK = 0
-E_INVAL, E_HIP, E_NOMEM, E_DST_SMALL, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM, E_DIGEST = -1, -2, -3, -4, -5, -6, -7, -8
+E_INVAL, E_HIP, E_NOMEM, E_DST_SMALL, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM, E_DIGEST, E_NOENT = -1, -2, -3, -4, -5, -6, -7, -8, -9
 _ERRNAMES = {E_INVAL: "invalid argument", E_HIP: "HIP runtime error", E_NOMEM: "out of device memory",
              E_DST_SMALL: "destination too small", E_CORRUPT: "corrupt frame",
              E_UNSUPPORTED: "unsupported frame", E_CHECKSUM: "content checksum mismatch",
-             E_DIGEST: "BLAKE3 digest mismatch"}
+             E_DIGEST: "BLAKE3 digest mismatch", E_NOENT: "no entry of the container matches"}
 
 
 class ZnippyError(RuntimeError):
@@ -53,6 +53,7 @@ EXPORTS = [
     "znippy_rows_block_tree_layout", "znippy_rows_block_tree_build", "znippy_rows_set_block_tree",
     "znippy_rows_read_ranges_verified",
     "znippy_rounds_emit_block_tree", "znippy_rounds_block_tree_layout", "znippy_rounds_block_tree",
+    "znippy_inflate_batch",
 ]
 
 
@@ -147,6 +148,8 @@ def lib():
     if hasattr(L, "znippy_ctx_run_lane_stats"):  # (likewise)
         L.znippy_ctx_run_lane_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.znippy_ctx_run_lane_older_waits.argtypes = [vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "znippy_inflate_batch"):  # (likewise)
+        L.znippy_inflate_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, vp, vp, C.c_uint64, vp, vp, vp, C.c_uint64, vp, vp]
     _lib = L
     return L
 

@@ -3663,3 +3663,83 @@ extern "C" int znippy_rounds_set_store_incompressible(znippy_rounds *r, int on) 
     r->store_incompressible = on != 0;
     return ZNIPPY_OK;
 }
+
+// ---- raw DEFLATE of ZIP entries (znippy_inflate_batch) ---------------------------------------------
+// Not a run: no table is involved.  Every item is validated on the host; the items that pass are uploaded as one list, decoded by one
+// launch (wave = stream) and checksummed by a second one; status and CRC come back in one copy each.
+static int inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
+                         const uint8_t *method, void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
+                         const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
+    if (!n) return ZNIPPY_OK;
+    if (!src_off || !src_len || !out_len || !d_src || !d_out) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ctx->n_ktimes = 0;
+
+    // 1) every item against the source region, the output region and the sizes and methods the kernel takes
+    std::vector<int32_t> st(n, 0);
+    std::vector<InflateItem> items;
+    std::vector<uint32_t> item_of;  // list entry -> item
+    uint64_t packed = 0;
+    bool packed_wrap = false;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t so = src_off[i], sl = src_len[i], ol = out_len[i];
+        const bool dst_known = out_off || !packed_wrap;
+        const uint64_t dst = out_off ? out_off[i] : packed;
+        if (!out_off) { packed_wrap |= packed + ol < packed; packed += ol; }
+        const unsigned m = method ? method[i] : 8u;
+        if (so > src_cap || sl > src_cap - so) { st[i] = ZNIPPY_E_INVAL; continue; }
+        if (!dst_known || ol > out_cap || dst > out_cap - ol) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (sl >= (1ull << 32) || ol >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
+        if (m != 0 && m != 8) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
+        if (m == 0 && sl != ol) { st[i] = ZNIPPY_E_CORRUPT; continue; }
+        InflateItem it;
+        it.src = (const uint8_t *)d_src + so;
+        it.dst = (uint8_t *)d_out + dst;
+        it.src_len = (uint32_t)sl; it.out_len = (uint32_t)ol;
+        it.method = m;
+        it.want_crc = crc32 ? crc32[i] : 0; it.has_crc = crc32 ? 1 : 0;
+        it.pad = 0;
+        items.push_back(it);
+        item_of.push_back((uint32_t)i);
+    }
+    const uint32_t n_items = (uint32_t)items.size();
+    std::vector<int32_t> h_st(n_items, 0);
+    std::vector<uint32_t> h_crc(n_items, 0);
+    if (n_items) {
+        // 2) every allocation, then the stream
+        struct Guard {
+            znippy_ctx *ctx;
+            InflateItem *items = nullptr; int32_t *st = nullptr; uint32_t *crc = nullptr;
+            ~Guard() { tfree(ctx, items); tfree(ctx, st); tfree(ctx, crc); }
+        } g{ctx};
+        HIPCHK(ctx, tmalloc(ctx, &g.items, sizeof(InflateItem) * n_items));
+        HIPCHK(ctx, tmalloc(ctx, &g.st, sizeof(int32_t) * n_items));
+        HIPCHK(ctx, tmalloc(ctx, &g.crc, sizeof(uint32_t) * n_items));
+        HIPCHK(ctx, hipMemcpyAsync(g.items, items.data(), sizeof(InflateItem) * n_items, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(g.crc, 0, sizeof(uint32_t) * n_items, s));
+        timed(ctx, "inflate", s, [&] { launch_inflate(g.items, n_items, g.st, s); });
+        timed(ctx, "inflate_crc", s, [&] { launch_inflate_crc(g.items, n_items, g.st, g.crc, s); });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(h_st.data(), g.st, sizeof(int32_t) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(h_crc.data(), g.crc, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    if (crc_out) memset(crc_out, 0, sizeof(uint32_t) * n);
+    for (uint32_t k = 0; k < n_items; k++) {
+        st[item_of[k]] = h_st[k];
+        if (crc_out) crc_out[item_of[k]] = h_crc[k];
+    }
+    if (status) memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
+                                    const uint8_t *method, void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
+                                    const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out) {
+    try {
+        return inflate_batch(ctx, d_src, src_cap, src_off, src_len, method, d_out, out_cap, out_off, out_len, crc32, n, status, crc_out);
+    } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; }
+}

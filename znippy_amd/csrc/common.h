@@ -321,4 +321,19 @@ struct TreeUnit {
 // tree[e] for every entry e of the table, from the tile CVs the run's hash left in tile_cv (read only)
 void launch_round_block_entries(const TreeUnit *units, uint32_t n_units, uint32_t n_entries, const uint32_t *tile_cv, uint32_t *tree, hipStream_t s);
 
+
+// Raw DEFLATE of ZIP entries (inflate.hip, znippy_inflate_batch): one item the host has validated, decoded by one wave
+struct InflateItem {
+    const uint8_t *src;  // the compressed bytes, any alignment
+    uint8_t *dst;
+    uint32_t src_len, out_len;  // both below 4 GiB
+    uint32_t method;            // 8: DEFLATE; 0: a copy (src_len == out_len)
+    uint32_t want_crc, has_crc;
+    uint32_t pad;
+};
+// status[i] = 0 or ZNIPPY_E_* for every item; no byte outside [dst, dst + out_len) of any item is written
+void launch_inflate(const InflateItem *items, uint32_t n_items, int32_t *status, hipStream_t s);
+// for every item with status 0: crc_out[i] = CRC-32 of its out_len bytes; status[i] = ZNIPPY_E_CHECKSUM where has_crc and it is not want_crc
+void launch_inflate_crc(const InflateItem *items, uint32_t n_items, int32_t *status, uint32_t *crc_out, hipStream_t s);
+
 }  // namespace zn

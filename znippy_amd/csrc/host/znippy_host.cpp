@@ -5,6 +5,7 @@
 #include "../../../include/znippy_host.h"
 #include "../../../include/znippy_hip.h"
 #include "arrow_ipc.h"
+#include "zip_dir.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1512,6 +1513,227 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
     if (hipMemcpy(dst, bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
     *written = total;
     return ZNIPPY_OK;
+}
+
+}  // extern "C"
+
+// ---- entries of archived ZIP containers (znippy_archive_extract_zip_entries) ----------------------------
+namespace {
+
+struct FileRange {  // bytes [off, off + len) of one archived file, wholly inside it
+    const std::vector<uint64_t> *rows;  // the file's archive rows, sorted by fdata_offset
+    uint64_t off, len;
+};
+
+// One range-read pass for many files: every request is mapped to the chunks it touches; of a stored chunk the requested bytes, of a
+// compressed chunk the whole frame (once per pass) are read from the archive and uploaded in one copy, ONE znippy_rows_read_ranges
+// over a private table of them gathers all requests packed back to back, and one copy brings them to the host: request i at
+// host[at[i] .. at[i] + len), st[i] = 0 or a chunk's ZNIPPY_E_*.  Nothing is kept between passes: a compressed chunk that two passes
+// touch is read and uploaded twice.
+int read_file_ranges(znippy_archive *a, const std::vector<FileRange> &req, std::vector<uint8_t> *host, std::vector<uint64_t> *at,
+                     std::vector<int32_t> *st) {
+    const auto &c = a->ix.rows.cols;
+    std::vector<uint64_t> bo, bs, us, fpos, rr, rb, rl;  // fpos: where a table row's blob bytes lie in the archive file
+    std::vector<uint8_t> bitmap;
+    std::vector<size_t> of_req;  // range -> request
+    std::unordered_map<uint64_t, uint64_t> row_at;
+    uint64_t sum = 0, total = 0;
+    at->assign(req.size(), 0);
+    st->assign(req.size(), 0);
+    for (size_t i = 0; i < req.size(); i++) {
+        (*at)[i] = total;
+        const uint64_t lo = req[i].off, hi = req[i].off + req[i].len;
+        uint64_t covered = 0;
+        const size_t first_range = rr.size();
+        for (uint64_t r : *req[i].rows) {
+            const uint64_t f0 = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];  // a stored row is its blob
+            const uint64_t x = std::max(lo, f0), y = std::min(hi, f0 + n);
+            if (x >= y) continue;
+            if (c[5].u64[r] > a->ix.file_size || c[6].u64[r] > a->ix.file_size - c[5].u64[r]) { (*st)[i] = ZNIPPY_E_CORRUPT; break; }
+            if (!c[3].u8[r]) {
+                // a stored chunk is its blob: only the bytes asked for are read and uploaded, as a stored row of their own (a jar is
+                // stored by the extension rule, and of a jar of many MB the three passes want the tail, the directory and one entry)
+                const size_t k = bo.size();
+                bo.push_back(sum); bs.push_back(y - x); us.push_back(y - x); fpos.push_back(c[5].u64[r] + (x - f0));
+                if ((k & 7) == 0) bitmap.push_back(0);
+                sum += y - x;
+                rr.push_back(k); rb.push_back(0); rl.push_back(y - x); of_req.push_back(i);
+                covered += y - x;
+                continue;
+            }
+            auto it = row_at.find(r);
+            if (it == row_at.end()) {  // a compressed chunk: its whole frame, once per pass however many requests touch it
+                const size_t k = bo.size();
+                it = row_at.emplace(r, k).first;
+                bo.push_back(sum); bs.push_back(c[6].u64[r]); us.push_back(n); fpos.push_back(c[5].u64[r]);
+                if ((k & 7) == 0) bitmap.push_back(0);
+                bitmap[k >> 3] |= (uint8_t)(1u << (k & 7));
+                sum += c[6].u64[r];
+            }
+            rr.push_back(it->second); rb.push_back(x - f0); rl.push_back(y - x); of_req.push_back(i);
+            covered += y - x;
+        }
+        if ((*st)[i] == 0 && covered != req[i].len) (*st)[i] = ZNIPPY_E_CORRUPT;  // the index does not cover the file
+        if ((*st)[i]) { rr.resize(first_range); rb.resize(first_range); rl.resize(first_range); of_req.resize(first_range); continue; }
+        total += req[i].len;
+    }
+    host->assign((size_t)total, 0);
+    if (rr.empty()) return ZNIPPY_OK;
+    ReadBufs &bufs = a->bufs;
+    if (!bufs.blob_pin.reserve(std::max<uint64_t>(sum, total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+    for (size_t k = 0; k < bo.size(); k++)
+        if (bs[k] && !pread_all(a->fd, bufs.blob_pin.p + bo[k], bs[k], fpos[k])) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
+    if (!bufs.d_blobs.reserve(sum + 64) || !bufs.d_out.reserve(total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+    if (sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+    znippy_rows *rt = nullptr;
+    int rc = znippy_rows_create(a->ctx, bo.data(), bs.data(), bitmap.data(), us.data(), nullptr, nullptr, 0, bo.size(), &rt);
+    if (rc) return fail(rc, "znippy_rows_create failed");
+    znippy_rows_set_blob_cap(rt, sum);
+    std::vector<int32_t> rst(rr.size(), 0);
+    rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, rst.data(), nullptr);
+    znippy_rows_destroy(rt);
+    if (rc) return fail(rc, std::string("range read failed: ") + znippy_last_error(a->ctx));
+    for (size_t k = 0; k < rst.size(); k++)
+        if (rst[k] < 0 && (*st)[of_req[k]] == 0) (*st)[of_req[k]] = rst[k];
+    if (total && hipMemcpy(host->data(), bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+    return ZNIPPY_OK;
+}
+
+}  // namespace
+
+static int znippy_archive_extract_zip_entries_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, const char *name_prefix,
+                                                   const char *name_suffix, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {
+    if (!a || !entry_off || (n_files && !paths) || (cap && !dst)) return fail(ZNIPPY_E_INVAL, "null argument");
+    const char *prefix = name_prefix ? name_prefix : "", *suffix = name_suffix ? name_suffix : "";
+    const size_t n = (size_t)n_files;
+    std::vector<int32_t> st(n, 0);
+    std::vector<const std::vector<uint64_t> *> rows(n, nullptr);
+    std::vector<uint64_t> fsize(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        auto it = paths[i] ? a->files.find(paths[i]) : a->files.end();
+        if (it == a->files.end()) { st[i] = ZNIPPY_E_INVAL; continue; }
+        rows[i] = &it->second;
+        for (uint64_t r : it->second) fsize[i] += a->ix.rows.cols[3].u8[r] ? a->ix.rows.cols[4].u64[r] : a->ix.rows.cols[6].u64[r];
+    }
+    if (!a->ctx) {
+        if (hipSetDevice(a->device) != hipSuccess) return fail(ZNIPPY_E_HIP, "hipSetDevice failed");
+        int rc = znippy_ctx_create(a->device, nullptr, &a->ctx);
+        if (rc) return fail(rc, "no usable GPU: the codec/hash path has no CPU fallback");
+    }
+    std::vector<FileRange> req;
+    std::vector<size_t> who;  // request -> file
+    std::vector<uint8_t> bytes;
+    std::vector<uint64_t> at;
+    std::vector<int32_t> rst;
+    auto pass = [&]() -> int {
+        const int rc = read_file_ranges(a, req, &bytes, &at, &rst);
+        if (!rc)
+            for (size_t k = 0; k < req.size(); k++)
+                if (rst[k] && st[who[k]] == 0) st[who[k]] = rst[k];
+        return rc;
+    };
+    // 1) the tails: where each container's central directory is
+    std::vector<uint64_t> dir_off(n, 0), dir_size(n, 0), dir_n(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        if (st[i] == 0 && fsize[i] < 22) st[i] = ZNIPPY_E_CORRUPT;  // no room for an end record
+        if (st[i]) continue;
+        const uint64_t tl = std::min<uint64_t>(fsize[i], ZN_ZIP_TAIL_MAX);
+        req.push_back(FileRange{rows[i], fsize[i] - tl, tl});
+        who.push_back(i);
+    }
+    int rc = pass();
+    if (rc) return rc;
+    for (size_t k = 0; k < req.size(); k++) {
+        const size_t i = who[k];
+        if (st[i] == 0) st[i] = znippy_zip_end_of_directory(bytes.data() + at[k], (size_t)req[k].len, fsize[i], &dir_off[i], &dir_size[i], &dir_n[i]);
+    }
+    // 2) the central directories: the first entry that matches
+    std::vector<znippy_zip_entry> ent(n);
+    req.clear(); who.clear();
+    for (size_t i = 0; i < n; i++) {
+        if (st[i]) continue;
+        req.push_back(FileRange{rows[i], dir_off[i], dir_size[i]});
+        who.push_back(i);
+    }
+    rc = pass();
+    if (rc) return rc;
+    for (size_t k = 0; k < req.size(); k++) {
+        const size_t i = who[k];
+        if (st[i]) continue;
+        st[i] = znippy_zip_find_entry(bytes.data() + at[k], (size_t)req[k].len, dir_n[i], prefix, strlen(prefix), suffix, strlen(suffix), &ent[i]);
+        if (st[i] == 0 && ent[i].method > 255) st[i] = ZNIPPY_E_UNSUPPORTED;
+        // the entry lies in front of the directory: its fixed header at least, and then its data
+        if (st[i] == 0 && (ent[i].local_header_offset > dir_off[i] || dir_off[i] - ent[i].local_header_offset < 30 + ent[i].compressed_size)) st[i] = ZNIPPY_E_CORRUPT;
+    }
+    // 3) local header + compressed bytes.  The name and extra lengths that place the data are the LOCAL header's, unknown until it is
+    //    read: the request runs to the farthest place they can put the end of the data, or to the directory if that comes first
+    req.clear(); who.clear();
+    for (size_t i = 0; i < n; i++) {
+        if (st[i]) continue;
+        const uint64_t lho = ent[i].local_header_offset, reach = 30 + 2 * 65535ull + ent[i].compressed_size;
+        req.push_back(FileRange{rows[i], lho, std::min(reach, dir_off[i] - lho)});
+        who.push_back(i);
+    }
+    rc = pass();
+    if (rc) return rc;
+    // 4) the compressed streams, packed, in one upload
+    std::vector<uint64_t> s_off, s_len, u_len, u_off;
+    std::vector<uint8_t> method;
+    std::vector<uint32_t> crc;
+    std::vector<size_t> item_file;
+    uint64_t c_total = 0, u_total = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> where;  // item -> (position in `bytes`, length)
+    for (size_t k = 0; k < req.size(); k++) {
+        const size_t i = who[k];
+        if (st[i]) continue;
+        uint64_t data_off = 0;
+        st[i] = znippy_zip_local_data_offset(bytes.data() + at[k], (size_t)std::min<uint64_t>(req[k].len, 30), &data_off);
+        if (st[i] == 0 && (data_off > req[k].len || req[k].len - data_off < ent[i].compressed_size)) st[i] = ZNIPPY_E_CORRUPT;
+        if (st[i]) continue;
+        where.emplace_back(at[k] + data_off, ent[i].compressed_size);
+        s_off.push_back(c_total); s_len.push_back(ent[i].compressed_size); u_off.push_back(u_total); u_len.push_back(ent[i].uncompressed_size);
+        method.push_back((uint8_t)ent[i].method); crc.push_back(ent[i].crc32); item_file.push_back(i);
+        c_total += ent[i].compressed_size;
+        u_total += ent[i].uncompressed_size;
+    }
+    ReadBufs &bufs = a->bufs;
+    if (!item_file.empty()) {
+        if (!bufs.blob_pin.reserve(std::max(c_total, u_total) + 64) || !bufs.d_blobs.reserve(c_total + 64) || !bufs.d_out.reserve(u_total + 64))
+            return fail(ZNIPPY_E_NOMEM, "allocation failed");
+        for (size_t j = 0; j < where.size(); j++)
+            if (where[j].second) std::memcpy(bufs.blob_pin.p + s_off[j], bytes.data() + where[j].first, (size_t)where[j].second);
+        if (c_total && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, c_total, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+        // 5) one inflate over all of them, against the directory's CRCs
+        std::vector<int32_t> ist(item_file.size(), 0);
+        rc = znippy_inflate_batch(a->ctx, bufs.d_blobs.p, c_total, s_off.data(), s_len.data(), method.data(), bufs.d_out.p, u_total, nullptr, u_len.data(),
+                                  crc.data(), item_file.size(), ist.data(), nullptr);
+        if (rc) return fail(rc, std::string("inflate failed: ") + znippy_last_error(a->ctx));
+        for (size_t j = 0; j < item_file.size(); j++) st[item_file[j]] = ist[j];
+        // 6) one copy back
+        if (u_total && hipMemcpy(bufs.blob_pin.p, bufs.d_out.p, u_total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+    }
+    // the contents, packed in file order; a file that does not fit is left out and the ones behind it may still fit
+    std::vector<uint64_t> item_of(n, UINT64_MAX);
+    for (size_t j = 0; j < item_file.size(); j++) item_of[item_file[j]] = j;
+    uint64_t cursor = 0;
+    for (size_t i = 0; i < n; i++) {
+        entry_off[i] = cursor;
+        if (st[i] || item_of[i] == UINT64_MAX) continue;
+        const uint64_t j = item_of[i], len = u_len[j];
+        if (len > cap - cursor) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (len) std::memcpy((uint8_t *)dst + cursor, bufs.blob_pin.p + u_off[j], (size_t)len);
+        cursor += len;
+    }
+    entry_off[n] = cursor;
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" {
+
+int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
+                                       const char *name_suffix, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {
+    return guarded([&] { return znippy_archive_extract_zip_entries_impl(a, relative_paths, n_files, name_prefix, name_suffix, dst, cap, entry_off, status); });
 }
 
 int znippy_archive_block_tree_stats(const znippy_archive *a, uint64_t stats[4]) {

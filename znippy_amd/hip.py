@@ -145,6 +145,27 @@ class Context:
                   "znippy_compress")
         return out[:w.value].tobytes()
 
+    # ---- raw DEFLATE of ZIP entries held in device memory ----
+    def inflate_batch(self, d_src, src_off, src_len, d_out, out_len, out_off=None, method=None, crc32=None, src_cap=None, out_cap=None):
+        """znippy_inflate_batch: item i is the raw DEFLATE stream (method 8; 0 = a copy) d_src[src_off[i] .. + src_len[i]) and must
+        decode to exactly out_len[i] bytes at d_out + out_off[i] (None: packed back to back in array order).  crc32: the CRC-32 each
+        content must have (None: nothing is compared).  Synchronous and not a run.  Returns (status per item: 0 or ZNIPPY_E_*,
+        CRC-32 per item as computed on the device — defined for status 0 and ZNIPPY_E_CHECKSUM)."""
+        so, sl, ol = as_np(src_off, np.uint64), as_np(src_len, np.uint64), as_np(out_len, np.uint64)
+        oo = as_np(out_off, np.uint64) if out_off is not None else None
+        me = as_np(method, np.uint8) if method is not None else None
+        cr = as_np(crc32, np.uint32) if crc32 is not None else None
+        n = len(so)
+        assert len(sl) == n and len(ol) == n and all(a is None or len(a) == n for a in (oo, me, cr)), "item arrays differ in length"
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        crc = np.zeros(max(n, 1), dtype=np.uint32)
+        opt = lambda a: np_ptr(a) if a is not None else None  # noqa: E731
+        self._chk(self.L.znippy_inflate_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), opt(me), _dptr(d_out), int(out_cap),
+                                              opt(oo), np_ptr(ol), opt(cr), n, np_ptr(status), np_ptr(crc)), "znippy_inflate_batch")
+        return status[:n], crc[:n]
+
 
 def get_decompressed_size(frame) -> int:
     a = np.frombuffer(frame, dtype=np.uint8)
