@@ -5,6 +5,7 @@
 #include "common.h"
 #include "encode.h"
 #include "../../include/znippy_hip.h"
+#include "host/range_plan.h"
 #include "host/run_overlap.h"
 
 #include <algorithm>
@@ -39,6 +40,12 @@ extern "C" int zn_rows_pack32(const uint64_t *bo, const uint64_t *bs, const uint
             return ZNIPPY_E_HIP;                                                                  \
         }                                                                                         \
     } while (0)
+// The body of an entry point whose work allocates host vectors sized by caller data: an allocation failure is an error code at the
+// C boundary, not an exception through it.
+#define ZN_NO_THROW(call) \
+    try { return (call); } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; } catch (const std::length_error &) { return ZNIPPY_E_NOMEM; }
+static_assert(RP_OK == ZNIPPY_OK && RP_E_INVAL == ZNIPPY_E_INVAL && RP_E_NOMEM == ZNIPPY_E_NOMEM && RP_E_DST_SMALL == ZNIPPY_E_DST_SMALL &&
+              RP_E_CORRUPT == ZNIPPY_E_CORRUPT && RP_E_DIGEST == ZNIPPY_E_DIGEST, "host/range_plan.h gives out the codes of znippy_hip.h");
 
 // diagnostic (ZNIPPY_TDBG): wall time of the sections of a table constructor
 struct TDbg {
@@ -318,6 +325,19 @@ static void tfree(znippy_ctx *ctx, void *p) {
         ctx->dev_pool_bytes += cap;
     } else (void)hipFree(p);
 }
+// Up to two tmalloc'ed buffers of a call that go back to the pool when the call returns — once the main stream has run whatever is
+// still queued on them.
+template <class A, class B = void>
+struct SyncFree {
+    znippy_ctx *ctx;
+    A *a = nullptr;
+    B *b = nullptr;
+    ~SyncFree() {
+        if (!a && !b) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        tfree(ctx, a); tfree(ctx, b);
+    }
+};
 
 struct PlanBuf {
     std::vector<Tile> tiles;
@@ -2421,29 +2441,11 @@ static int rows_host_columns(znippy_ctx *ctx, znippy_rows *r) {
     return ZNIPPY_OK;
 }
 
-namespace {
-constexpr uint64_t RR_BLK = 128 * 1024;
-constexpr uint64_t RR_GUARD = 8192;  // in front of a slot: the block decoder reads up to WIN_HIST bytes of history back from in front of a block
-struct RrRow {                       // a distinct row the ranges of a call touch
-    uint32_t row = 0;                // index in the table
-    bool comp = false, partial = false, late = false;
-    int32_t status = 0;              // 0, or the ZNIPPY_E_* of its whole decode
-    int pool = 0;                    // which scratch region its bytes are in
-    uint64_t slot = 0, first = 0;    // byte b of the row is at pool + slot + (b - first)
-    uint32_t kmin = 0xFFFFFFFFu, kmax = 0;
-    std::vector<uint8_t> need;       // partial: per block, a range overlaps it
-    bool sblocks = false;            // verified read, stored row with accepted entries: `need` blocks are hashed where they lie
-    bool hashed = false;             // verified read: the row was hashed whole
-    std::vector<uint8_t> bad;        // verified read: per block, its chaining value does not equal its entry
-};
-uint8_t *rr_carve_bytes(uint8_t *base, size_t &at, size_t bytes) {  // the next 16-byte aligned piece of a slab
-    at = (at + 15) & ~(size_t)15;
-    uint8_t *p = base + at;
-    at += bytes;
-    return p;
+// What a call plans against (host/range_plan.h): the host columns above and, where they exist, the tree's layout and verdicts.
+static RrTable rows_table_view(const znippy_rows *r) {
+    return RrTable{r->n, r->row_begin, r->blob_cap, r->h_blob_off.data(), r->h_blob_size.data(), r->h_len.data(), r->h_comp.data(),
+                   r->tree_first.data(), r->tree_first.size(), r->tree_accept.data(), r->tree_accept.size()};
 }
-#define rr_carve(T, base, at, n) reinterpret_cast<T *>(rr_carve_bytes(base, at, sizeof(T) * (size_t)(n)))
-}  // namespace
 
 // The checksum column on the host (verified range reads give the private tables of their whole-row passes the rows' checksums).
 static int rows_host_checksum(znippy_ctx *ctx, znippy_rows *r) {
@@ -2500,8 +2502,7 @@ static int rr_decode_whole(znippy_ctx *ctx, const znippy_rows *r, std::vector<Rr
 }
 
 // ---- block tree (znippy_rows_block_tree_*, znippy_rows_set_block_tree) ---------------------------------
-// Entries of a row: one per 128 KiB block of a row of more than one block and below 4 GiB; none otherwise (znippy_hip.h).
-static inline uint64_t tree_entries_of(uint64_t len) { return len > RR_BLK && len < (1ull << 32) ? (len + RR_BLK - 1) / RR_BLK : 0; }
+// Entries of a row: tree_entries_of (host/range_plan.h).
 static int rows_tree_layout(znippy_ctx *ctx, znippy_rows *r) {
     const int rc = rows_host_columns(ctx, r);
     if (rc || !r->tree_first.empty()) return rc;
@@ -2514,19 +2515,16 @@ static int rows_tree_layout(znippy_ctx *ctx, znippy_rows *r) {
 // One k_block_cvs launch over host-built items, synchronous: write mode (d_out) or compare mode (d_expect, *ok = per item verdict).
 static int block_cvs_run(znippy_ctx *ctx, const std::vector<BlockCvItem> &items, uint32_t *d_out, const uint32_t *d_expect, std::vector<uint32_t> *ok, const char *name) {
     if (items.empty()) return ZNIPPY_OK;
-    if (items.size() > 0x7FFFFFF0ull) return ZNIPPY_E_NOMEM;
+    if (items.size() > RR_ITEMS_MAX) return ZNIPPY_E_NOMEM;
     hipStream_t s = ctx->stream;
-    struct Guard {  // (the buffers go back to the context's pool only once nothing queued can touch them)
-        znippy_ctx *ctx; BlockCvItem *items = nullptr; uint32_t *ok = nullptr;
-        ~Guard() { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, items); tfree(ctx, ok); }
-    } g{ctx};
+    SyncFree<BlockCvItem, uint32_t> g{ctx};  // a = the items, b = the verdicts
     const uint32_t n = (uint32_t)items.size();
-    if (tmalloc(ctx, &g.items, sizeof(BlockCvItem) * (size_t)n) != hipSuccess || (d_expect && tmalloc(ctx, &g.ok, 4 * (size_t)n) != hipSuccess)) return ZNIPPY_E_NOMEM;
-    HIPCHK(ctx, hipMemcpyAsync(g.items, items.data(), sizeof(BlockCvItem) * (size_t)n, hipMemcpyHostToDevice, s));
-    timed(ctx, name, s, [&] { launch_block_cvs(g.items, n, d_out, d_expect, g.ok, s); });
+    if (tmalloc(ctx, &g.a, sizeof(BlockCvItem) * (size_t)n) != hipSuccess || (d_expect && tmalloc(ctx, &g.b, 4 * (size_t)n) != hipSuccess)) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemcpyAsync(g.a, items.data(), sizeof(BlockCvItem) * (size_t)n, hipMemcpyHostToDevice, s));
+    timed(ctx, name, s, [&] { launch_block_cvs(g.a, n, d_out, d_expect, g.b, s); });
     if (ok) {
         ok->assign(n, 0);
-        if (d_expect) HIPCHK(ctx, hipMemcpyAsync(ok->data(), g.ok, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
+        if (d_expect) HIPCHK(ctx, hipMemcpyAsync(ok->data(), g.b, 4 * (size_t)n, hipMemcpyDeviceToHost, s));
     }
     HIPCHK(ctx, hipStreamSynchronize(s));
     HIPCHK(ctx, hipGetLastError());
@@ -2541,14 +2539,92 @@ static int tree_fold_check(znippy_ctx *ctx, znippy_rows *r, const uint32_t *d_tr
     hipStream_t s = ctx->stream;
     std::vector<BlockTreeRow> h(sel.size());
     for (size_t i = 0; i < sel.size(); i++) h[i] = BlockTreeRow{r->tree_first[sel[i]], (uint32_t)(r->tree_first[sel[i] + 1] - r->tree_first[sel[i]]), sel[i]};
-    struct Guard {
-        znippy_ctx *ctx; BlockTreeRow *rows = nullptr; uint32_t *ok = nullptr;
-        ~Guard() { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, rows); tfree(ctx, ok); }
-    } g{ctx};
-    if (tmalloc(ctx, &g.rows, sizeof(BlockTreeRow) * h.size()) != hipSuccess || tmalloc(ctx, &g.ok, 4 * h.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
-    HIPCHK(ctx, hipMemcpyAsync(g.rows, h.data(), sizeof(BlockTreeRow) * h.size(), hipMemcpyHostToDevice, s));
-    timed(ctx, "block_tree_fold", s, [&] { launch_block_tree_fold(g.rows, (uint32_t)h.size(), d_tree, r->checksum, g.ok, s); });
-    HIPCHK(ctx, hipMemcpyAsync(ok.data(), g.ok, 4 * h.size(), hipMemcpyDeviceToHost, s));
+    SyncFree<BlockTreeRow, uint32_t> g{ctx};  // a = the rows, b = the verdicts
+    if (tmalloc(ctx, &g.a, sizeof(BlockTreeRow) * h.size()) != hipSuccess || tmalloc(ctx, &g.b, 4 * h.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemcpyAsync(g.a, h.data(), sizeof(BlockTreeRow) * h.size(), hipMemcpyHostToDevice, s));
+    timed(ctx, "block_tree_fold", s, [&] { launch_block_tree_fold(g.a, (uint32_t)h.size(), d_tree, r->checksum, g.b, s); });
+    HIPCHK(ctx, hipMemcpyAsync(ok.data(), g.b, 4 * h.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    HIPCHK(ctx, hipGetLastError());
+    return ZNIPPY_OK;
+}
+
+// ---- the range-read call: the plan is host/range_plan.cc, the stages below queue what it describes ----
+struct RangeBufs {  // the buffers of one call; every return gives them back
+    znippy_ctx *ctx;
+    uint8_t *slab = nullptr, *h_slab = nullptr;  // the private columns and lists of the block pass, and their pinned image
+    size_t h_cap = 0, up_bytes = 0;
+    RangeSlab h{}, d{};
+    RangePiece *pieces = nullptr;
+    ~RangeBufs() { tfree(ctx, slab); tfree(ctx, pieces); if (h_slab) { (void)hipStreamSynchronize(ctx->stream); pinned_give(ctx, h_slab, h_cap); } }
+};
+
+// The slab of the block pass: allocated on both sides, filled on the host.
+static int range_slab_make(znippy_ctx *ctx, const RrTable &t, const RangePlan &p, RangeBufs &b) {
+    const size_t bytes = range_slab_layout(p, &b.up_bytes);
+    if (!(b.h_slab = (uint8_t *)pinned_take(ctx, bytes + 64, &b.h_cap)) || tmalloc(ctx, &b.slab, bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
+    if (!ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) { (void)hipGetLastError(); ctx->lit_scratch_b = nullptr; return ZNIPPY_E_NOMEM; }
+    range_slab_bind(b.h_slab, p, b.h);
+    range_slab_bind(b.slab, p, b.d);
+    range_slab_fill(t, p, b.h_slab);
+    return ZNIPPY_OK;
+}
+
+// The block pass, queued: header scan of the candidate frames, the needed blocks, the rows' verdicts and the decoded total on their way back.
+static int run_range_blocks(znippy_ctx *ctx, const RangePlan &p, const RangeBufs &bufs, const void *d_blobs, uint64_t blob_base) {
+    hipStream_t s = ctx->stream;
+    const RangeSlab &d = bufs.d;
+    const uint32_t m = (uint32_t)p.part.size();
+    HIPCHK(ctx, hipMemcpyAsync(bufs.slab, bufs.h_slab, bufs.up_bytes, hipMemcpyHostToDevice, s));
+    BlockScanArgs b{};
+    b.cand_row = d.cand_row; b.cand_base = d.cand_base; b.cand_nblocks = d.cand_nb; b.n_cand = m;
+    b.blobs = (const uint8_t *)d_blobs; b.blob_base = blob_base;
+    b.blob_off = d.blob_off; b.blob_size = d.blob_size; b.usize = d.usize; b.out_off = d.out_off;
+    b.out_cap = ~0ull;  // (the slots fit the scratch by construction)
+    b.item_src = d.item_src; b.row_flag = d.row_flag; b.status = d.status;
+    timed(ctx, "range_scan", s, [&] { launch_scan_blocks(b, s); });
+    DecodeArgs a{};
+    a.blobs = b.blobs; a.blob_base = blob_base;
+    a.blob_off = d.blob_off; a.blob_size = d.blob_size; a.usize = d.usize; a.out_off = d.out_off;
+    a.out = ctx->rr_pool[0]; a.out_cap = ~0ull; a.status = d.status;
+    a.block_mode = 1;
+    a.item_row = d.item_row; a.item_k = d.item_k; a.item_src = d.item_src; a.n_items = (uint32_t)p.n_items; a.row_flag = d.row_flag;
+    a.todo = d.todo; a.n_todo = d.ctl;
+    a.pending_count = d.ctl + 2;
+    a.compressed = d.comp;
+    a.n_rows = m; a.cursor = d.ctl + 1;
+    a.lit_scratch = ctx->lit_scratch_b;
+    timed(ctx, "range_decode_blocks", s, [&] { launch_decode(a, (int)std::min<uint64_t>((uint64_t)ctx->decode_grid, p.n_todo), false, s); });
+    launch_range_status(d.row_flag, d.block_bytes, m, d.late, d.decoded, s);
+    HIPCHK(ctx, hipMemcpyAsync(bufs.h.late, d.late, m, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(bufs.h.decoded, d.decoded, 8, hipMemcpyDeviceToHost, s));
+    return ZNIPPY_OK;
+}
+
+// Verified: every block that will serve a range — decoded into the scratch, or a stored row's where it lies — is hashed on its own
+// and compared with its (accepted) entry, before a byte of it moves.
+static int run_range_verify_blocks(znippy_ctx *ctx, const znippy_rows *r, const RrTable &t, RangePlan &p, const void *d_blobs, uint64_t blob_base, uint64_t *hashed) {
+    std::vector<BlockCvItem> items;
+    std::vector<std::pair<uint32_t, uint32_t>> item_of;
+    *hashed = range_plan_block_items(t, p, ctx->rr_pool[0], (const uint8_t *)d_blobs, blob_base, items, item_of);
+    if (items.empty()) return ZNIPPY_OK;
+    std::vector<uint32_t> ok;
+    const int rc = block_cvs_run(ctx, items, nullptr, r->tree_dev, &ok, "range_verify_blocks");
+    if (rc) return rc;
+    for (size_t j = 0; j < items.size(); j++)
+        if (!ok[j]) p.rows[item_of[j].first].bad[item_of[j].second] = 1;
+    return ZNIPPY_OK;
+}
+
+// The gather: every piece from where its bytes are to its place in d_out, synchronous.
+static int run_range_gather(znippy_ctx *ctx, const std::vector<RangePiece> &pieces, RangeBufs &bufs) {
+    if (pieces.empty()) return ZNIPPY_OK;
+    hipStream_t s = ctx->stream;
+    if (tmalloc(ctx, &bufs.pieces, sizeof(RangePiece) * pieces.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemcpy(bufs.pieces, pieces.data(), sizeof(RangePiece) * pieces.size(), hipMemcpyHostToDevice));
+    timed(ctx, "range_copy", s, [&] {
+        for (size_t at = 0; at < pieces.size(); at += (1u << 30)) launch_range_gather(bufs.pieces + at, (uint32_t)std::min<size_t>(pieces.size() - at, 1u << 30), s);
+    });
     HIPCHK(ctx, hipStreamSynchronize(s));
     HIPCHK(ctx, hipGetLastError());
     return ZNIPPY_OK;
@@ -2568,273 +2644,58 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
     int rc = rows_host_columns(ctx, r);
     if (!rc && verified) rc = rows_host_checksum(ctx, r);
     if (rc) return rc;
-    // verified: a row is looked at block by block only if its entries are installed and fold to its checksum
-    auto by_blocks = [&](uint32_t ri) { return !verified || (ri < r->tree_accept.size() && r->tree_accept[ri]); };
-    hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
 
-    // 1) every range against the table, the output region and the blob region; the distinct rows the good ones touch
-    std::vector<int32_t> st(n_ranges, 0);
-    std::vector<uint64_t> dst(n_ranges, 0);
-    std::vector<uint32_t> of_row(n_ranges, 0xFFFFFFFFu);  // range -> entry of `rows` (none: nothing to move)
-    std::vector<RrRow> rows;
-    std::unordered_map<uint32_t, uint32_t> row_at;
-    const uint64_t bcap = r->blob_cap;
-    uint64_t packed = 0;
-    bool packed_wrap = false;
-    for (uint64_t i = 0; i < n_ranges; i++) {
-        const uint64_t len = range_len[i], begin = range_begin[i];
-        const bool dst_known = range_out || !packed_wrap;
-        dst[i] = range_out ? range_out[i] : packed;
-        if (!range_out) { packed_wrap |= packed + len < packed; packed += len; }
-        if (range_row[i] < r->row_begin || range_row[i] - r->row_begin >= r->n) { st[i] = ZNIPPY_E_INVAL; continue; }
-        const uint32_t ri = (uint32_t)(range_row[i] - r->row_begin);
-        const uint64_t row_len = r->h_len[ri], bo = r->h_blob_off[ri], bs = r->h_blob_size[ri];
-        if (begin > row_len || len > row_len - begin) { st[i] = ZNIPPY_E_INVAL; continue; }
-        if (!dst_known || len > out_cap || dst[i] > out_cap - len) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
-        if (bo < blob_base || (bcap != ~0ull && (bs > bcap || bo - blob_base > bcap - bs))) { st[i] = ZNIPPY_E_CORRUPT; continue; }
-        if (!len) continue;
-        auto it = row_at.find(ri);
-        if (it == row_at.end()) {
-            it = row_at.emplace(ri, (uint32_t)rows.size()).first;
-            RrRow w;
-            w.row = ri;
-            w.comp = r->h_comp[ri] != 0;
-            w.partial = w.comp && row_len > RR_BLK && row_len < 0xFFFFFFFFull && by_blocks(ri);  // >= 2 blocks, below 4 GiB: tried block by block
-            w.sblocks = verified && !w.comp && row_len > RR_BLK && row_len < 0xFFFFFFFFull && by_blocks(ri);
-            if (w.partial || w.sblocks) w.need.assign((size_t)((row_len + RR_BLK - 1) / RR_BLK), 0);
-            rows.push_back(std::move(w));
-        }
-        of_row[i] = it->second;
-        RrRow &w = rows[it->second];
-        if (w.partial || w.sblocks) {
-            const uint32_t k0 = (uint32_t)(begin / RR_BLK), k1 = (uint32_t)((begin + len - 1) / RR_BLK);
-            for (uint32_t k = k0; k <= k1; k++) w.need[k] = 1;
-            w.kmin = std::min(w.kmin, k0); w.kmax = std::max(w.kmax, k1);
-        }
-    }
+    // the plan: every range validated, the distinct rows, their routes and slots — then the scratch and the block pass's slab
+    const RrTable t = rows_table_view(r);
+    const RrCall call{range_row, range_begin, range_len, range_out, n_ranges, out_cap, blob_base, verified};
+    RangePlan p;
+    if ((rc = range_plan_build(t, call, p))) return rc;
+    if ((rc = ensure_range_scratch(ctx, 0, p.need0))) return rc;
+    const bool blocks = !p.part.empty();
+    RangeBufs bufs{ctx};
+    if (blocks && (rc = range_slab_make(ctx, t, p, bufs))) return rc;
 
-    // 2) the plan: slots in the scratch, the private columns and lists of the block pass, the rows decoded whole from the start
-    std::vector<uint32_t> part, whole, stored_whole;
-    uint64_t n_items = 0, n_todo = 0, need0 = 0;
-    for (uint32_t i = 0; i < rows.size(); i++) {
-        RrRow &w = rows[i];
-        if (!w.comp) {
-            if (verified && !w.sblocks) stored_whole.push_back(i);  // hashed whole, where it lies, by a private verify-only run
-            continue;
-        }
-        if (w.partial && n_items + w.need.size() >= 0x7FFFFFF0ull) w.partial = false;
-        const uint64_t row_len = r->h_len[w.row];
-        need0 = (need0 + 255) & ~255ull;
-        if (w.partial) {
-            part.push_back(i);
-            n_items += w.need.size();
-            for (uint32_t k = w.kmin; k <= w.kmax; k++) n_todo += w.need[k];
-            w.first = (uint64_t)w.kmin * RR_BLK;
-            w.slot = need0 + RR_GUARD;
-            need0 = w.slot + (std::min<uint64_t>(row_len, ((uint64_t)w.kmax + 1) * RR_BLK) - w.first) + 256;
-        } else {
-            whole.push_back(i);
-            w.slot = need0;
-            need0 += row_len + 256;
-        }
-        if (need0 > (32ull << 30)) return ZNIPPY_E_NOMEM;
-    }
-    if ((rc = ensure_range_scratch(ctx, 0, need0))) return rc;
-    const uint32_t m = (uint32_t)part.size();
-    uint8_t *slab = nullptr, *h_slab = nullptr;
-    size_t slab_bytes = 0, h_slab_cap = 0, up_bytes = 0;
-    struct Slab { uint64_t *blob_off, *blob_size, *usize, *out_off, *block_bytes; uint32_t *cand_row, *cand_base, *cand_nb, *item_row, *item_k, *todo, *ctl; int32_t *status; uint8_t *comp; uint32_t *row_flag, *item_src; unsigned long long *decoded; uint8_t *late; } h{}, d{};
-    auto carve = [&](uint8_t *base, Slab &o) {
-        size_t at = 0;
-        o.blob_off = rr_carve(uint64_t, base, at, m); o.blob_size = rr_carve(uint64_t, base, at, m); o.usize = rr_carve(uint64_t, base, at, m);
-        o.out_off = rr_carve(uint64_t, base, at, m); o.block_bytes = rr_carve(uint64_t, base, at, m);
-        o.cand_row = rr_carve(uint32_t, base, at, m); o.cand_base = rr_carve(uint32_t, base, at, m); o.cand_nb = rr_carve(uint32_t, base, at, m);
-        o.item_row = rr_carve(uint32_t, base, at, n_items); o.item_k = rr_carve(uint32_t, base, at, n_items); o.todo = rr_carve(uint32_t, base, at, n_todo);
-        o.ctl = rr_carve(uint32_t, base, at, 4); o.status = rr_carve(int32_t, base, at, m); o.comp = rr_carve(uint8_t, base, at, m);
-        o.decoded = rr_carve(unsigned long long, base, at, 1);
-        up_bytes = at;  // everything up to here is uploaded; what follows is written on the device first
-        o.row_flag = rr_carve(uint32_t, base, at, m); o.item_src = rr_carve(uint32_t, base, at, n_items); o.late = rr_carve(uint8_t, base, at, m);
-        return at;
-    };
-    struct Guard {  // every return below gives the call's buffers back
-        znippy_ctx *ctx; uint8_t *&slab, *&h_slab; size_t &cap; RangePiece *pieces = nullptr;
-        ~Guard() { tfree(ctx, slab); tfree(ctx, pieces); if (h_slab) { (void)hipStreamSynchronize(ctx->stream); pinned_give(ctx, h_slab, cap); } }
-    } guard{ctx, slab, h_slab, h_slab_cap};
-    if (m) {
-        slab_bytes = carve(nullptr, h);
-        if (!(h_slab = (uint8_t *)pinned_take(ctx, slab_bytes + 64, &h_slab_cap)) || tmalloc(ctx, &slab, slab_bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
-        if (!ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) { (void)hipGetLastError(); ctx->lit_scratch_b = nullptr; return ZNIPPY_E_NOMEM; }
-        carve(h_slab, h);
-        carve(slab, d);
-        memset(h_slab, 0, up_bytes);
-        uint32_t item = 0, todo = 0;
-        for (uint32_t c = 0; c < m; c++) {
-            const RrRow &w = rows[part[c]];
-            const uint64_t row_len = r->h_len[w.row];
-            h.blob_off[c] = r->h_blob_off[w.row]; h.blob_size[c] = r->h_blob_size[w.row]; h.usize[c] = row_len;
-            // the block decoder puts block k at out + out_off + k * 128 KiB: the column is biased (modulo 2^64, as the kernels add) so that
-            // the row's first needed block lands at the head of its slot
-            h.out_off[c] = w.slot - w.first;
-            h.cand_row[c] = c; h.cand_base[c] = item; h.cand_nb[c] = (uint32_t)w.need.size();
-            h.comp[c] = 1;
-            for (uint32_t k = 0; k < w.need.size(); k++) {
-                h.item_row[item + k] = c; h.item_k[item + k] = k;
-                if (!w.need[k]) continue;
-                h.todo[todo++] = item + k;
-                h.block_bytes[c] += std::min<uint64_t>(RR_BLK, row_len - (uint64_t)k * RR_BLK);
-            }
-            item += (uint32_t)w.need.size();
-        }
-        h.ctl[0] = todo;  // [0] length of the to-do list, [1] the decoder's work cursor, [2] a hand-over count that stays zero
-    }
-
-    // 3) the block pass: header scan of the candidate frames, the needed blocks, the rows' verdicts
-    unsigned long long dec_blocks = 0;
-    if (m) {
-        HIPCHK(ctx, hipMemcpyAsync(slab, h_slab, up_bytes, hipMemcpyHostToDevice, s));
-        BlockScanArgs b{};
-        b.cand_row = d.cand_row; b.cand_base = d.cand_base; b.cand_nblocks = d.cand_nb; b.n_cand = m;
-        b.blobs = (const uint8_t *)d_blobs; b.blob_base = blob_base;
-        b.blob_off = d.blob_off; b.blob_size = d.blob_size; b.usize = d.usize; b.out_off = d.out_off;
-        b.out_cap = ~0ull;  // (the slots fit the scratch by construction)
-        b.item_src = d.item_src; b.row_flag = d.row_flag; b.status = d.status;
-        timed(ctx, "range_scan", s, [&] { launch_scan_blocks(b, s); });
-        DecodeArgs a{};
-        a.blobs = b.blobs; a.blob_base = blob_base;
-        a.blob_off = d.blob_off; a.blob_size = d.blob_size; a.usize = d.usize; a.out_off = d.out_off;
-        a.out = ctx->rr_pool[0]; a.out_cap = ~0ull; a.status = d.status;
-        a.block_mode = 1;
-        a.item_row = d.item_row; a.item_k = d.item_k; a.item_src = d.item_src; a.n_items = (uint32_t)n_items; a.row_flag = d.row_flag;
-        a.todo = d.todo; a.n_todo = d.ctl;
-        a.pending_count = d.ctl + 2;
-        a.compressed = d.comp;
-        a.n_rows = m; a.cursor = d.ctl + 1;
-        a.lit_scratch = ctx->lit_scratch_b;
-        timed(ctx, "range_decode_blocks", s, [&] { launch_decode(a, (int)std::min<uint64_t>((uint64_t)ctx->decode_grid, n_todo), false, s); });
-        launch_range_status(d.row_flag, d.block_bytes, m, d.late, d.decoded, s);
-        HIPCHK(ctx, hipMemcpyAsync(h.late, d.late, m, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(h.decoded, d.decoded, 8, hipMemcpyDeviceToHost, s));
-    }
-    // ... behind it, the rows known from the start to need a whole decode (its results call waits for both)
-    if ((rc = rr_decode_whole(ctx, r, rows, whole, d_blobs, blob_base, 0, verified))) return rc;
-    if ((rc = rr_decode_whole(ctx, r, rows, stored_whole, d_blobs, blob_base, 0, true, true))) return rc;
-    HIPCHK(ctx, hipStreamSynchronize(s));
+    // the block pass and, behind it, the rows known from the start to need a whole decode (its results call waits for both)
+    if (blocks && (rc = run_range_blocks(ctx, p, bufs, d_blobs, blob_base))) return rc;
+    if ((rc = rr_decode_whole(ctx, r, p.rows, p.whole, d_blobs, blob_base, 0, verified))) return rc;
+    if ((rc = rr_decode_whole(ctx, r, p.rows, p.stored_whole, d_blobs, blob_base, 0, true, true))) return rc;
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipGetLastError());
 
-    // 4) what the block pass gave up on — a frame the scan does not vouch for, a block that needs history — is decoded whole
-    if (m) {
-        dec_blocks = *h.decoded;
+    // what the block pass gave up on — a frame the scan does not vouch for, a block that needs history — is decoded whole
+    if (blocks) {
         std::vector<uint32_t> late;
         uint64_t need1 = 0;
-        for (uint32_t c = 0; c < m; c++) {
-            if (!h.late[c]) continue;
-            RrRow &w = rows[part[c]];
-            w.late = true; w.pool = 1; w.first = 0;
-            need1 = (need1 + 255) & ~255ull;
-            w.slot = need1;
-            need1 += r->h_len[w.row] + 256;
-            if (need1 > (32ull << 30)) return ZNIPPY_E_NOMEM;
-            late.push_back(part[c]);
-        }
+        if ((rc = range_plan_late(t, p, bufs.h.late, late, need1))) return rc;
         if ((rc = ensure_range_scratch(ctx, 1, need1))) return rc;  // (nothing is queued at this point, and d_out is untouched)
-        if ((rc = rr_decode_whole(ctx, r, rows, late, d_blobs, blob_base, 1, verified))) return rc;
+        if ((rc = rr_decode_whole(ctx, r, p.rows, late, d_blobs, blob_base, 1, verified))) return rc;
     }
-
-    // 4b) verified: every block that will serve a range — decoded into the scratch, or a stored row's where it lies — is hashed on its
-    // own and compared with its (accepted) entry, before a byte of it moves
     uint64_t hashed = 0;
-    if (verified) {
-        std::vector<BlockCvItem> items;
-        std::vector<std::pair<uint32_t, uint32_t>> item_of;  // -> (entry of `rows`, block)
-        for (uint32_t i = 0; i < rows.size(); i++) {
-            RrRow &w = rows[i];
-            if (w.hashed) hashed += r->h_len[w.row];
-            if (!((w.partial && !w.late) || w.sblocks) || w.status) continue;
-            const uint64_t row_len = r->h_len[w.row];
-            w.bad.assign(w.need.size(), 0);
-            for (uint32_t k = w.kmin; k <= w.kmax; k++) {
-                if (!w.need[k]) continue;
-                const uint64_t at = (uint64_t)k * RR_BLK;
-                const uint8_t *src = w.comp ? ctx->rr_pool[0] + w.slot + (at - w.first) : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base) + at;
-                const uint32_t bytes = (uint32_t)std::min<uint64_t>(RR_BLK, row_len - at);
-                items.push_back(BlockCvItem{src, r->tree_first[w.row] + k, bytes, 128u * k});
-                item_of.emplace_back(i, k);
-                hashed += bytes;
-            }
-        }
-        if (!items.empty()) {
-            std::vector<uint32_t> ok;
-            if ((rc = block_cvs_run(ctx, items, nullptr, r->tree_dev, &ok, "range_verify_blocks"))) return rc;
-            for (size_t j = 0; j < items.size(); j++)
-                if (!ok[j]) rows[item_of[j].first].bad[item_of[j].second] = 1;
-        }
-    }
+    if (verified && (rc = run_range_verify_blocks(ctx, r, t, p, d_blobs, blob_base, &hashed))) return rc;
 
-    // 5) the gather: every good range from where its bytes are to its place in d_out
-    uint64_t dec = dec_blocks;
-    for (const RrRow &w : rows)
-        if (w.comp && (!w.partial || w.late) && (w.status == 0 || w.status == ZNIPPY_E_DIGEST)) dec += r->h_len[w.row];
+    // the gather: every good range from where its bytes are to its place in d_out
+    const uint8_t *const pools[2] = {ctx->rr_pool[0], ctx->rr_pool[1]};
     std::vector<RangePiece> pieces;
-    for (uint64_t i = 0; i < n_ranges; i++) {
-        if (of_row[i] == 0xFFFFFFFFu) continue;
-        const RrRow &w = rows[of_row[i]];
-        if (w.status) { st[i] = w.status; continue; }
-        if (!w.bad.empty()) {  // a block whose hash does not chain to the checksum fails every range that overlaps it
-            bool bad = false;
-            for (uint64_t k = range_begin[i] / RR_BLK; k <= (range_begin[i] + range_len[i] - 1) / RR_BLK; k++) bad |= w.bad[k] != 0;
-            if (bad) { st[i] = ZNIPPY_E_DIGEST; continue; }
-        }
-        const uint8_t *src = w.comp ? ctx->rr_pool[w.pool] + w.slot + (range_begin[i] - w.first)
-                                    : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base) + range_begin[i];
-        uint8_t *to = (uint8_t *)d_out + dst[i];
-        uint64_t left = range_len[i];
-        uint64_t step = std::min<uint64_t>(left, RANGE_PIECE - ((uintptr_t)to & 127));  // every later piece starts on a 128-byte line of the output
-        while (left) {
-            pieces.push_back(RangePiece{src, to, (uint32_t)step, 0});
-            src += step; to += step; left -= step;
-            step = std::min<uint64_t>(left, RANGE_PIECE);
-        }
-    }
-    if (!pieces.empty()) {
-        if (tmalloc(ctx, &guard.pieces, sizeof(RangePiece) * pieces.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
-        HIPCHK(ctx, hipMemcpy(guard.pieces, pieces.data(), sizeof(RangePiece) * pieces.size(), hipMemcpyHostToDevice));
-        timed(ctx, "range_copy", s, [&] {
-            for (size_t at = 0; at < pieces.size(); at += (1u << 30)) launch_range_gather(guard.pieces + at, (uint32_t)std::min<size_t>(pieces.size() - at, 1u << 30), s);
-        });
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        HIPCHK(ctx, hipGetLastError());
-    }
-    if (range_status) memcpy(range_status, st.data(), 4 * (size_t)n_ranges);
-    if (decoded_bytes) *decoded_bytes = dec;
+    range_plan_pieces(t, call, p, pools, (const uint8_t *)d_blobs, (uint8_t *)d_out, pieces);
+    if ((rc = run_range_gather(ctx, pieces, bufs))) return rc;
+    if (range_status) memcpy(range_status, p.st.data(), 4 * (size_t)n_ranges);
+    if (decoded_bytes) *decoded_bytes = range_plan_decoded(t, p, blocks ? *bufs.h.decoded : 0);
     if (hashed_bytes) *hashed_bytes = hashed;
     return ZNIPPY_OK;
 }
 
-// (the plan is host vectors sized by n_ranges: an allocation failure is an error code at the C boundary, not an exception through it)
 int znippy_rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
                             const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
                             uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes) {
-    try {
-        return rows_read_ranges(ctx, r, d_blobs, blob_base, range_row, range_begin, range_len, range_out, n_ranges, d_out, out_cap, range_status, decoded_bytes);
-    } catch (const std::bad_alloc &) {
-        return ZNIPPY_E_NOMEM;
-    } catch (const std::length_error &) {
-        return ZNIPPY_E_NOMEM;
-    }
+    ZN_NO_THROW(rows_read_ranges(ctx, r, d_blobs, blob_base, range_row, range_begin, range_len, range_out, n_ranges, d_out, out_cap, range_status, decoded_bytes))
 }
 
 int znippy_rows_read_ranges_verified(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, const uint64_t *range_row,
                                      const uint64_t *range_begin, const uint64_t *range_len, const uint64_t *range_out, uint64_t n_ranges, void *d_out,
                                      uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes, uint64_t *hashed_bytes) {
-    try {
-        return rows_read_ranges(ctx, r, d_blobs, blob_base, range_row, range_begin, range_len, range_out, n_ranges, d_out, out_cap, range_status, decoded_bytes,
-                                true, hashed_bytes);
-    } catch (const std::bad_alloc &) {
-        return ZNIPPY_E_NOMEM;
-    } catch (const std::length_error &) {
-        return ZNIPPY_E_NOMEM;
-    }
+    ZN_NO_THROW(rows_read_ranges(ctx, r, d_blobs, blob_base, range_row, range_begin, range_len, range_out, n_ranges, d_out, out_cap, range_status, decoded_bytes,
+                                 true, hashed_bytes))
 }
 
 static int rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_entries, uint64_t *row_first) {
@@ -2865,26 +2726,11 @@ static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_
     ctx->n_ktimes = 0;
 
     // 1) the rows with entries against the blob region; a slot in the scratch for every compressed one — sized before anything is queued
+    const RrTable t = rows_table_view(r);
     std::vector<RrRow> rows;
     std::vector<uint32_t> sel;
-    const uint64_t bcap = r->blob_cap;
     uint64_t need0 = 0;
-    for (uint32_t ri = 0; ri < r->n; ri++) {
-        if (r->tree_first[ri + 1] == r->tree_first[ri]) continue;
-        const uint64_t bo = r->h_blob_off[ri], bs = r->h_blob_size[ri];
-        if (bo < blob_base || (bcap != ~0ull && (bs > bcap || bo - blob_base > bcap - bs))) { st[ri] = ZNIPPY_E_CORRUPT; continue; }
-        RrRow w;
-        w.row = ri;
-        w.comp = r->h_comp[ri] != 0;
-        if (w.comp) {
-            need0 = (need0 + 255) & ~255ull;
-            w.slot = need0;
-            need0 += r->h_len[ri] + 256;
-            if (need0 > (32ull << 30)) return ZNIPPY_E_NOMEM;
-            sel.push_back((uint32_t)rows.size());
-        }
-        rows.push_back(std::move(w));
-    }
+    if ((rc = tree_plan_rows(t, blob_base, st, rows, sel, need0))) return rc;
     if ((rc = ensure_range_scratch(ctx, 0, need0))) return rc;
 
     // 2) a private decode-only run of the compressed rows
@@ -2895,31 +2741,20 @@ static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_
     // 3) every block of every good row: one launch
     std::vector<BlockCvItem> items;
     std::vector<uint32_t> good;
-    for (const RrRow &w : rows) {
-        if (w.status) { st[w.row] = w.status; continue; }
-        good.push_back(w.row);
-        const uint64_t row_len = r->h_len[w.row];
-        const uint8_t *base = w.comp ? ctx->rr_pool[0] + w.slot : (const uint8_t *)d_blobs + (r->h_blob_off[w.row] - blob_base);
-        const uint32_t nb = (uint32_t)(r->tree_first[w.row + 1] - r->tree_first[w.row]);
-        for (uint32_t k = 0; k < nb; k++)
-            items.push_back(BlockCvItem{base + (uint64_t)k * RR_BLK, r->tree_first[w.row] + k, (uint32_t)std::min<uint64_t>(RR_BLK, row_len - (uint64_t)k * RR_BLK), 128u * k});
-    }
-    struct Guard {
-        znippy_ctx *ctx; uint32_t *tree = nullptr;
-        ~Guard() { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, tree); }
-    } g{ctx};
-    if (tmalloc(ctx, &g.tree, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
-    HIPCHK(ctx, hipMemsetAsync(g.tree, 0, 32 * (size_t)n_entries, s));
-    if ((rc = block_cvs_run(ctx, items, g.tree, nullptr, nullptr, "block_tree_cvs"))) return rc;
+    tree_plan_items(t, rows, ctx->rr_pool[0], (const uint8_t *)d_blobs, blob_base, st, good, items);
+    SyncFree<uint32_t> g{ctx};  // a = the tree on the device
+    if (tmalloc(ctx, &g.a, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
+    HIPCHK(ctx, hipMemsetAsync(g.a, 0, 32 * (size_t)n_entries, s));
+    if ((rc = block_cvs_run(ctx, items, g.a, nullptr, nullptr, "block_tree_cvs"))) return rc;
 
     // 4) the entries against the checksums (a table without the column compares nothing)
     if (r->checksum) {
         std::vector<uint32_t> ok;
-        if ((rc = tree_fold_check(ctx, r, g.tree, good, ok))) return rc;
+        if ((rc = tree_fold_check(ctx, r, g.a, good, ok))) return rc;
         for (size_t i = 0; i < good.size(); i++)
             if (!ok[i]) st[good[i]] = ZNIPPY_E_DIGEST;
     }
-    HIPCHK(ctx, hipMemcpyAsync(tree, g.tree, 32 * (size_t)n_entries, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(tree, g.a, 32 * (size_t)n_entries, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
     for (uint32_t ri = 0; ri < r->n; ri++)  // a row that failed has no entries to offer
         if (st[ri]) memset(tree + 32 * r->tree_first[ri], 0, 32 * (size_t)(r->tree_first[ri + 1] - r->tree_first[ri]));
@@ -2947,37 +2782,31 @@ static int rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *t
     if (rc) return rc;
     const uint64_t n_entries = r->tree_first[r->n];
     ctx->n_ktimes = 0;
-    struct Guard {
-        znippy_ctx *ctx; uint32_t *tree = nullptr;
-        ~Guard() { if (tree) { (void)hipStreamSynchronize(ctx->stream); tfree(ctx, tree); } }
-    } g{ctx};
+    SyncFree<uint32_t> g{ctx};  // a = the tree on the device
     std::vector<uint8_t> accept(r->n, 0);
     if (n_entries) {
-        if (tmalloc(ctx, &g.tree, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
-        HIPCHK(ctx, hipMemcpyAsync(g.tree, tree, 32 * (size_t)n_entries, hipMemcpyHostToDevice, s));
+        if (tmalloc(ctx, &g.a, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, hipMemcpyAsync(g.a, tree, 32 * (size_t)n_entries, hipMemcpyHostToDevice, s));
         std::vector<uint32_t> sel, ok;
         for (uint32_t ri = 0; ri < r->n; ri++)
             if (r->tree_first[ri + 1] != r->tree_first[ri]) sel.push_back(ri);
-        if ((rc = tree_fold_check(ctx, r, g.tree, sel, ok))) return rc;
+        if ((rc = tree_fold_check(ctx, r, g.a, sel, ok))) return rc;
         for (size_t i = 0; i < sel.size(); i++) {
             accept[sel[i]] = ok[i] ? 1 : 0;
             if (!ok[i] && row_status) row_status[sel[i]] = ZNIPPY_E_DIGEST;
         }
     }
     HIPCHK(ctx, hipStreamSynchronize(s));
-    std::swap(r->tree_dev, g.tree);  // (the guard frees the tree this one replaces)
+    std::swap(r->tree_dev, g.a);  // (the guard frees the tree this one replaces)
     r->tree_accept.swap(accept);
     return ZNIPPY_OK;
 }
 
-#define ZN_NO_THROW(call) \
-    try { return call; } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; } catch (const std::length_error &) { return ZNIPPY_E_NOMEM; }
 int znippy_rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_entries, uint64_t *row_first) { ZN_NO_THROW(rows_block_tree_layout(ctx, r, n_entries, row_first)) }
 int znippy_rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, uint8_t *tree, int32_t *row_status) {
     ZN_NO_THROW(rows_block_tree_build(ctx, r, d_blobs, blob_base, tree, row_status))
 }
 int znippy_rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *tree, int32_t *row_status) { ZN_NO_THROW(rows_set_block_tree(ctx, r, tree, row_status)) }
-#undef ZN_NO_THROW
 
 int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
     if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
@@ -3650,13 +3479,11 @@ static int rounds_block_tree(znippy_ctx *ctx, znippy_rounds *r, unsigned lag, ui
     return ZNIPPY_OK;
 }
 
-#define ZN_NO_THROW(call) try { return (call); } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; }
 extern "C" int znippy_rounds_emit_block_tree(znippy_rounds *r, int on) { ZN_NO_THROW(rounds_emit_block_tree(r, on)) }
 extern "C" int znippy_rounds_block_tree_layout(znippy_ctx *ctx, znippy_rounds *r, uint64_t *n_entries, uint64_t *round_first) {
     ZN_NO_THROW(rounds_block_tree_layout(ctx, r, n_entries, round_first))
 }
 extern "C" int znippy_rounds_block_tree(znippy_ctx *ctx, znippy_rounds *r, unsigned lag, uint8_t *tree) { ZN_NO_THROW(rounds_block_tree(ctx, r, lag, tree)) }
-#undef ZN_NO_THROW
 
 extern "C" int znippy_rounds_set_store_incompressible(znippy_rounds *r, int on) {
     if (!r) return ZNIPPY_E_INVAL;
@@ -3739,7 +3566,5 @@ static int inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, c
 extern "C" int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
                                     const uint8_t *method, void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
                                     const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out) {
-    try {
-        return inflate_batch(ctx, d_src, src_cap, src_off, src_len, method, d_out, out_cap, out_off, out_len, crc32, n, status, crc_out);
-    } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; }
+    ZN_NO_THROW(inflate_batch(ctx, d_src, src_cap, src_off, src_len, method, d_out, out_cap, out_off, out_len, crc32, n, status, crc_out))
 }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "host/range_plan.h"
 
 namespace zn {
 
@@ -280,32 +281,15 @@ enum BxStage : int { BX_SCAN = 0, BX_PREP = 1, BX_HUF = 2, BX_FSE = 3, BX_EXEC =
 void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s);  // stage: a BxStage
 void bx_predefined_tables(uint16_t cells[160]);  // host: the three predefined tables as pool cells
 
-// Range reads (range_gather.hip): one piece of a requested range — at most RANGE_PIECE bytes, moved by one workgroup from
-// wherever the bytes are (blob region, range scratch) to their place in the caller's output
-struct RangePiece {
-    const uint8_t *src;
-    uint8_t *dst;
-    uint32_t len;
-    uint32_t pad;
-};
-constexpr uint32_t RANGE_PIECE = 32u << 10;
+// Range reads (range_gather.hip) and the block tree (block_tree.hip): RangePiece, RANGE_PIECE, BlockCvItem and BlockTreeRow are in
+// host/range_plan.h, beside the host code that builds the lists of them (host/range_plan.cc) — plain C++ that a stand-alone program
+// tests, which this header, with its HIP include, is not.
 void launch_range_gather(const RangePiece *pieces, uint32_t n_pieces, hipStream_t s);
 // per private row of the partial route: late[i] = the row goes to the whole-row pass; *decoded += block_bytes[i] of the others
 void launch_range_status(const uint32_t *row_flag, const uint64_t *block_bytes, uint32_t n_rows, uint8_t *late, unsigned long long *decoded, hipStream_t s);
 
 // Block tree (block_tree.hip): one 32-byte entry per 128 KiB block of a row of more than one block (and below 4 GiB).
 constexpr uint32_t BLOCK_TREE_BLK = 128u << 10;
-struct BlockCvItem {       // one block to hash, by one wave
-    const uint8_t *src;    // its first byte, any alignment (an item of fewer than 16 bytes has readable bytes in front of it)
-    uint64_t slot;         // entry index: out[slot] is written, expect[slot] compared
-    uint32_t bytes;        // 1 .. BLOCK_TREE_BLK
-    uint32_t first_chunk;  // chunk counter of its first KiB inside the row (128 * block number)
-};
-struct BlockTreeRow {  // one row with entries
-    uint64_t first;    // its first entry
-    uint32_t n;        // 2 .. 32,768 entries
-    uint32_t row;      // index of its checksum
-};
 // write mode: out != NULL; compare mode: expect != NULL, verdict[item] = 1 if the block's chaining value equals expect[slot]
 void launch_block_cvs(const BlockCvItem *items, uint32_t n_items, uint32_t *out, const uint32_t *expect, uint32_t *verdict, hipStream_t s);
 // verdict[i] = 1 if rows[i]'s entries fold to checksum[32 * row ..]

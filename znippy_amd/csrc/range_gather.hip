@@ -3,8 +3,8 @@
 // has to land at its own place in the caller's output.  Byte-granular on both sides: a source and a destination share
 // no alignment in general.
 //
-// The host cuts every range into pieces of at most RANGE_PIECE bytes whose destinations, from the second piece of a
-// range on, start on a 128-byte line; one workgroup moves one piece:
+// The host (range_plan_pieces in host/range_plan.cc) cuts every range into pieces of at most RANGE_PIECE bytes whose
+// destinations, from the second piece of a range on, start on a 128-byte line; one workgroup moves one piece:
 //   head   the bytes in front of the destination's first whole 128-byte line, a byte per lane
 //   body   whole lines, 16 bytes per lane with aligned 16-byte stores (eight neighbouring lanes write one line).  The
 //          source of a body is read with aligned 16-byte loads as well: where it shares the destination's alignment one
