@@ -497,6 +497,23 @@ int znippy_ctx_set_kernel_timing(znippy_ctx *ctx, int level);
  * for an error the serial decoder will report, stats[5] a Treeless / Repeat_Mode table more than 64 blocks back,
  * stats[6] a pool that ran out, stats[7] a value outside the record format.  Synchronises. */
 int znippy_rows_foreign_stats(znippy_ctx *ctx, znippy_rows *rows, uint64_t stats[8]);
+/* Content checksums on the batch path (opt-in, off by default).  A zstd frame may end with a Content_Checksum: 4 bytes, the
+ * low 32 bits of XXH64 (seed 0) over its content (RFC 8878 3.1.1; `zstd` on the command line writes one by default).  With the
+ * switch off such a frame is decoded and checked by the serial decoder, one workgroup per frame.  With it on, the read runs of
+ * this context (decode + verify, decode-only, verify-only) take these frames through the batch and resolve paths like any other
+ * foreign frame, and a stage behind them (kernel time name zstd_batch_checksum) hashes every frame that was decoded there and
+ * compares it with the trailer.  A frame whose trailer differs is not reported by that stage: it is handed to the serial
+ * decoder, which decodes it again and reports ZNIPPY_E_CHECKSUM for the row, as it does with the switch off — statuses, bytes
+ * and counters of a run are the same either way.  Frames without a trailer, and every frame the batch path declines, go the way
+ * they went.  The value is read at the start of every run: a table may be run with the switch on and off in turn.
+ * on: 0 or 1; anything else, and a closed context, give ZNIPPY_E_INVAL.  ZNIPPY_BX_CHECKSUM=1 in the environment of
+ * znippy_ctx_create sets the initial value.  znippy_ctx_batch_checksums returns the value. */
+int znippy_ctx_set_batch_checksums(znippy_ctx *ctx, int on);
+int znippy_ctx_batch_checksums(const znippy_ctx *ctx);
+/* The checksum stage's counters of the table's last run: stats[0] frames whose trailer it checked and found right, stats[1]
+ * frames it checked and found wrong (handed to the serial decoder), stats[2] content bytes it hashed, stats[3] 0.  All zero
+ * for a run with the switch off.  Synchronises. */
+int znippy_rows_checksum_stats(znippy_ctx *ctx, znippy_rows *rows, uint64_t stats[4]);
 /* The hash's VALU floor, measured: nanoseconds one 64-lane BLAKE3 compress pass costs a SIMD when nothing else runs
  * (a kernel of compressions only, 4 waves per SIMD on every CU), and the shader clock that kernel held (may be NULL).
  * bench.py prices the read step's passes with it. */

@@ -46,6 +46,7 @@ EXPORTS = [
     "znippy_encode_hash_rounds", "znippy_encode_hash_rounds_async", "znippy_rounds_results",
     "znippy_rounds_results_view", "znippy_rows_results_lagged", "znippy_rows_set_blob_cap", "znippy_rounds_results_lagged", "znippy_rounds_set_store_incompressible", "znippy_hash_rounds", "znippy_last_kernel_times", "znippy_measure_blake3_pass_ns", "znippy_last_shader_ghz", "znippy_ctx_set_kernel_timing", "znippy_rows_foreign_stats", "znippy_ctx_run_lane_stats", "znippy_ctx_run_lane_older_waits", "znippy_ctx_set_level", "znippy_ctx_level",
     "znippy_ctx_set_window_log", "znippy_ctx_window_log",
+    "znippy_ctx_set_batch_checksums", "znippy_ctx_batch_checksums", "znippy_rows_checksum_stats",
     "znippy_verify_rows", "znippy_verify_rows_async", "znippy_rows_verify_scratch",
     "znippy_decode_rows", "znippy_decode_rows_async",
     "znippy_rounds_set_blob_align", "znippy_rounds_blob_align",
@@ -121,6 +122,10 @@ def lib():
     L.znippy_ctx_set_window_log.argtypes = [vp, C.c_int]
     L.znippy_ctx_window_log.argtypes = [vp]
     L.znippy_rows_foreign_stats.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
+    if hasattr(L, "znippy_ctx_set_batch_checksums"):  # (likewise)
+        L.znippy_ctx_set_batch_checksums.argtypes = [vp, C.c_int]
+        L.znippy_ctx_batch_checksums.argtypes = [vp]
+        L.znippy_rows_checksum_stats.argtypes = [vp, vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "znippy_verify_rows"):  # (an older build loaded beside this one for an A/B has not got them: calling them raises)
         L.znippy_verify_rows.argtypes = [vp, vp, vp, C.c_uint64, C.POINTER(VerifyCounters), vp, C.c_uint64, vp]
         L.znippy_verify_rows_async.argtypes = [vp, vp, vp, C.c_uint64]

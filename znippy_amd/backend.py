@@ -24,6 +24,10 @@ class HipBackend:
         """Cross-block match window of later encode calls (0 = off, 17..27; znippy_ctx_set_window_log)."""
         self.ctx.set_window_log(window_log)
 
+    def set_batch_checksums(self, on):
+        """Frames with a content checksum through the batch path of later read runs (0 = off; znippy_ctx_set_batch_checksums)."""
+        self.ctx.set_batch_checksums(on)
+
     def set_blob_align(self, align):
         """Blob offsets of later encode_hash calls are multiples of `align` inside their region (a power of two, 1 .. 4096;
         znippy_rounds_set_blob_align on every table built from here on)."""

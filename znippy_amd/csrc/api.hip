@@ -87,6 +87,7 @@ struct znippy_ctx {
     int gen_share = 3;  // workgroups per CU the general decoder takes while block items / foreign frames run beside it (4 = the whole register file)
     int level = 19;  // CompressCtx::new(compression_level), codec.rs:L16-28; CONFIG.compression_level is 19 (common_config.rs:L37)
     int window_log = 0;  // cross-block window of the higher effort tier (znippy_ctx_set_window_log); 0 = self-contained blocks
+    int batch_checksums = 0;  // the batch path takes frames with a content checksum and checks it itself (znippy_ctx_set_batch_checksums); read at the start of every run
     uint32_t *ldm = nullptr;  // far window index (grow-only, entries)
     size_t ldm_cap = 0;
     uint8_t *enc_prov = nullptr;
@@ -216,6 +217,7 @@ static void read_switches(znippy_ctx *ctx) {
     if (const char *e = getenv("ZNIPPY_BX_BIG")) { ctx->sw.bx_big = (unsigned)atoi(e); ctx->sw.bx_big_set = true; }  // A/B: foreign frames through the round-2 paths (serial decoder + wave-per-block two-phase path)
     if (const char *lv = getenv("ZNIPPY_LEVEL")) { const int v = atoi(lv); if (v >= 1 && v <= 22) ctx->level = v; }  // initial level of every context (tests, A/B runs)
     if (const char *wl = getenv("ZNIPPY_WINDOW_LOG")) { const int v = atoi(wl); if (v == 0 || (v >= WINDOW_LOG_MIN && v <= WINDOW_LOG_MAX)) ctx->window_log = v; }  // initial window of every context (host layer, tools)
+    if (const char *bc = getenv("ZNIPPY_BX_CHECKSUM")) { const int v = atoi(bc); if (v == 0 || v == 1) ctx->batch_checksums = v; }  // initial switch of every context (host layer, tools)
     if (const char *gs = getenv("ZNIPPY_GEN_SHARE")) { const int v = atoi(gs); if (v >= 1 && v <= 4) ctx->gen_share = v; }  // A/B
     ctx->sw.fz_only = on("ZNIPPY_FZ_ONLY");  // test hook: no serial fallback behind the two-phase path (what it leaves shows up as corrupt rows)
     if (const char *e = getenv("ZNIPPY_ROLES_MIN")) ctx->sw.roles_min = (unsigned)atoi(e);
@@ -457,7 +459,8 @@ constexpr CtlRegion CTL_FZ_POOL{192, 8 * 8};   // u64: pool counters of the two-
 constexpr CtlRegion CTL_BX_POOL{256, 16 * 8};  // u64: pool counters of the batch path (BxArgs::pool_used)
 constexpr CtlRegion CTL_BX_CTR{384, 16 * 4};   // u32: its work counters (BxArgs::ctr)
 constexpr CtlRegion CTL_RX{448, 16 * 4};       // u32: words left after each resolve round (BxArgs::rx_pending, RX_ROUNDS of them); [RX_ZERO] is never written
-constexpr size_t CTL_HEAD = 512, CTL_MIRROR = 128, CTL_FLAG = 7;
+constexpr CtlRegion CTL_BX_XXH{512, 4 * 8};    // u64: the checksum stage's counters (BxArgs::xxh_stat, znippy_rows_checksum_stats)
+constexpr size_t CTL_HEAD = 768, CTL_MIRROR = 128, CTL_FLAG = 7;  // (the status column keeps the 256-byte alignment it had at 512)
 constexpr uint32_t RX_ZERO = 15;
 enum Hand : uint32_t {  // length of a list one kernel leaves to another; the mirror tells the next run's plan which were empty
     H_FUSED = 0,    // rows handed over by the fused kernels (pending)
@@ -471,7 +474,8 @@ enum Cursor : uint32_t { CUR_GENERAL = 0, CUR_ROLES = 2, CUR_ITEMS = 4, CUR_FALL
 constexpr uint32_t LEAN_ANY = 1u << H_FUSED | 1u << H_SERIAL | 1u << H_FLAGGED, LEAN_SMALL = LEAN_ANY | 1u << H_TILES, LEAN_BLOCKS = LEAN_ANY | 1u << H_ITEMS;
 constexpr bool ctl_before(CtlRegion a, CtlRegion b) { return a.at + a.bytes <= b.at; }
 static_assert(ctl_before(CTL_COUNTERS, CTL_HAND) && ctl_before(CTL_HAND, CTL_CURSORS) && ctl_before(CTL_CURSORS, CTL_FZ_POOL) && ctl_before(CTL_FZ_POOL, CTL_BX_POOL) &&
-              ctl_before(CTL_BX_POOL, CTL_BX_CTR) && ctl_before(CTL_BX_CTR, CTL_RX) && CTL_RX.at + CTL_RX.bytes <= CTL_HEAD, "control block: regions overlap or pass the head");
+              ctl_before(CTL_BX_POOL, CTL_BX_CTR) && ctl_before(CTL_BX_CTR, CTL_RX) && ctl_before(CTL_RX, CTL_BX_XXH) && CTL_BX_XXH.at + CTL_BX_XXH.bytes <= CTL_HEAD && CTL_HEAD % 256 == 0,
+              "control block: regions overlap or pass the head");
 static_assert(CTL_COUNTERS.at == 0 && CTL_HAND.at == CTL_COUNTERS.bytes && CTL_MIRROR == CTL_HAND.at + CTL_HAND.bytes, "the mirror is exactly counters + hand-over counts");
 static_assert(CTL_FLAG < 8 && H_FLAGGED == H_SERIAL + 4 && H_FLAGGED < 8 && CUR_FZ_WORK < 16 && zn::RX_ROUNDS <= RX_ZERO && RX_ZERO < 16, "control block: a word outside its region");
 
@@ -586,6 +590,8 @@ struct znippy_rows {
     uint32_t bx_slots = 0, bx_item_cap = 0;
     uint64_t bx_bytes = 0;  // content bytes of all compressed rows
     uint64_t bx_nblk = 0;   // their 128 KiB blocks, as the index columns have them
+    uint32_t *bx_cand_ck = nullptr;  // checksum stage: which slots hold a frame with a trailer (allocated by the first run with the switch on)
+    int xxh_forms = 0;               // ... and the forms its rows call for (BxArgs::xxh_forms)
     uint32_t *bx_cand_row = nullptr, *bx_cand_base = nullptr, *bx_cand_nb = nullptr, *bx_huf_list = nullptr, *bx_seq_list = nullptr, *bx_sort_tmp = nullptr;
     zn::FzItem *bx_items = nullptr;
     zn::BxPrep *bx_prep = nullptr;
@@ -1211,6 +1217,26 @@ int znippy_rows_foreign_stats(znippy_ctx *ctx, znippy_rows *r, uint64_t stats[8]
     return ZNIPPY_OK;
 }
 
+int znippy_rows_checksum_stats(znippy_ctx *ctx, znippy_rows *r, uint64_t stats[4]) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || !r || r->ctx != ctx || !stats) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    static_assert(CTL_BX_XXH.bytes == 4 * sizeof(uint64_t), "checksum_stats");
+    HIPCHK(ctx, hipMemcpy(stats, r->ctl + CTL_BX_XXH.at, CTL_BX_XXH.bytes, hipMemcpyDeviceToHost));
+    stats[3] = 0;
+    return ZNIPPY_OK;
+}
+
+int znippy_ctx_set_batch_checksums(znippy_ctx *ctx, int on) {
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
+    if (!ctx || (on != 0 && on != 1)) return ZNIPPY_E_INVAL;
+    ctx->batch_checksums = on;
+    return ZNIPPY_OK;
+}
+
+int znippy_ctx_batch_checksums(const znippy_ctx *ctx) { return ctx && !ctx->closing ? ctx->batch_checksums : ZNIPPY_E_INVAL; }
+
 int znippy_ctx_set_level(znippy_ctx *ctx, int level) {
     if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
     if (!ctx || level < 1 || level > 22) return ZNIPPY_E_INVAL;
@@ -1311,7 +1337,7 @@ void znippy_rows_destroy(znippy_rows *r) {
                     r->cand_row, r->cand_base, r->cand_nblocks, r->fz_base, r->fz_cap, r->fz_it_cand, r->fz_nb, r->fz_work, r->fz_items, r->item_row, r->item_k, r->item_src, r->row_flag, r->pending2,
                     r->bt_tile, r->bt_item, r->tile_done, r->todo, r->status_init, r->slow_list,
                     r->bx_cand_row, r->bx_cand_base, r->bx_cand_nb, r->bx_huf_list, r->bx_seq_list, r->bx_items, r->bx_prep, r->d_bitmap, r->bx_sort_tmp,
-                    r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off, r->tree_dev};
+                    r->rx_base, r->rx_fail, r->rx_blk, r->rx_list, r->bx_cand_ck, r->d_pack, r->d_pack_sums, r->all_rows, r->vs_off, r->tree_dev};
     // (the pool hands these buffers to the next table, whose work is ordered on the main stream: what this table still has on
     // the auxiliary stream — a forked verify — is joined into it first)
     // (... and its runs on the run lane: the lanes are closed — no later run is compared with, or waits for an event of, this table —
@@ -1399,6 +1425,7 @@ static void rows_classify(const znippy_ctx *ctx, znippy_rows *r, const RowCols &
         if (e[6] == 0) {
             r->ext_min_bo = e[0]; r->ext_max_bend = e[1]; r->ext_max_oend = e[2]; r->ext_wrap = e[3] != 0;
             r->n_compressed = n; r->bx_bytes = e[4]; k.nblk = e[5];
+            r->xxh_forms = 1;  // (no row above 64 KiB: the checksum stage's quad form alone)
             return;
         }
     }
@@ -1418,6 +1445,7 @@ static void rows_classify(const znippy_ctx *ctx, znippy_rows *r, const RowCols &
         r->bx_bytes += us;
         if (us > 65536 && us < (1ull << 30)) r->rx_words_small += (us + 1023) & ~1023ull;
         if (us >= zn::RX_MIN && us < (1ull << 30)) r->rx_words += (us + 1023) & ~1023ull;
+        r->xxh_forms |= us < zn::XXH_WAVE_MIN ? 1 : 2;
         if (us <= 64 * 1024) continue;
         k.big_bytes += us;
         k.big_blob += bs;
@@ -1955,6 +1983,8 @@ static BxArgs rows_bx_args(znippy_ctx *ctx, const znippy_rows *r, const RunPlan 
         x.rx_bound = std::min<uint64_t>(r->rx_words, ctx->rx_cap);
         x.rx_min = r->rx_min;
     }
+    x.xxh_on = ctx->batch_checksums && r->bx_cand_ck;
+    x.xxh_forms = r->xxh_forms; x.cand_ck = r->bx_cand_ck; x.xxh_stat = r->ctl_at<unsigned long long>(CTL_BX_XXH);
     x.small_frames = r->n_compressed && r->bx_bytes / r->n_compressed <= 65536;
     if (ctx->sw.ddbg)  // diagnostic: where the previous run's table kernel spent its waves' time
         x.dbg = diag_cycle<128>(ctx, znippy_ctx::DIAG_BX, ctx->stream, nullptr, [](const unsigned long long *h) {
@@ -2040,6 +2070,8 @@ static int run_batch_path(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
     if (p.third) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join2, 0));
     if (p.rx) { const int rc = run_resolve(ctx, r, x); if (rc) return rc; }
     else bx_stage(ctx, x, BX_EXEC, s);
+    // frames with a content checksum that were decoded above: a wrong trailer makes the frame undecoded again (the finish stage lists it)
+    if (x.xxh_on) timed(ctx, "zstd_batch_checksum", s, [&] { launch_bx_stage(x, ctx->cus, BX_XXH, s); });
     bx_stage(ctx, x, BX_FINISH, s);
     decode_rest(ctx, r, a, r->n_compressed);
     return ZNIPPY_OK;
@@ -2202,6 +2234,7 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         rc = ensure_fz_pools(ctx, r->bx_bytes, r->bx_item_cap);
         if (!rc) rc = ensure_bx_pools(ctx, r->bx_bytes, r->bx_item_cap);
         if (!rc && r->rx_base && rows_route_hint(r, plain) != 0) rc = ensure_rx_pool(ctx, r->rx_words);
+        if (!rc && ctx->batch_checksums && !r->bx_cand_ck && tmalloc(ctx, &r->bx_cand_ck, 4 * (size_t)r->bx_slots) != hipSuccess) rc = ZNIPPY_E_NOMEM;
     }
     if (rc) return rc;
     if (r->n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;

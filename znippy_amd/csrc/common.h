@@ -272,12 +272,21 @@ struct BxArgs {
     uint32_t *rx_pending;               // [round]: words still unresolved after that round (zeroed per run)
     uint64_t rx_bound;                  // host's bound on the words a run can use (grid sizing)
     uint32_t rx_min;                    // frames of at least this many bytes are resolved (RX_MIN; less for tables with few rows above 64 KiB)
+    // The checksum stage (k_bx_xxh_*, znippy_ctx_set_batch_checksums).  xxh_on is the context's switch as this run found it: the scan
+    // then takes frames that end with a Content_Checksum trailer and notes them in cand_ck; the stage hashes what was decoded here
+    // and hands a frame whose trailer differs back to the serial decoder (row_flag / rx_fail), which reports it.
+    int xxh_on;
+    int xxh_forms;                      // the forms the table's row sizes call for: bit 0 four lanes per frame (rows below XXH_WAVE_MIN), bit 1 a wave per frame
+    uint32_t *cand_ck;                  // per candidate slot (written by the scan when xxh_on): 1 = the frame's last 4 bytes are its checksum
+    unsigned long long *xxh_stat;       // [0] frames checked and right, [1] checked and wrong, [2] content bytes hashed (zeroed per run)
 };
+constexpr uint32_t XXH_WAVE_MIN = (64u << 10) + 1;  // checksum stage: frames of at least this many bytes get a wave, smaller ones four lanes
 constexpr uint32_t RX_NONE = 0xFFFFFFFFu, RX_DONE = 0x80000000u, RX_MIN = 256u << 10, RX_ROUNDS = 12, RX_JUMPS = 6;
 // the batch path's launches, in the order of a run: scan, prep (the tables), sort the work lists, fse (wave = block) beside huf
-// and fse (lane = block), then exec — or the resolve path: plan, exec beside expand, jump round r, store —, finish
+// and fse (lane = block), then exec — or the resolve path: plan, exec beside expand, jump round r, store —, the content checksums
+// (xxh: only with BxArgs::xxh_on), finish
 enum BxStage : int { BX_SCAN = 0, BX_PREP = 1, BX_HUF = 2, BX_FSE = 3, BX_EXEC = 4, BX_FINISH = 5, BX_FSE_WAVE = 6, BX_SORT = 7, BX_RX_PLAN = 8, BX_RX_EXPAND = 9,
-                     BX_RX_JUMP = 10 /* + r */, BX_RX_STORE = 30 };
+                     BX_RX_JUMP = 10 /* + r */, BX_RX_STORE = 30, BX_XXH = 31 };
 void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s);  // stage: a BxStage
 void bx_predefined_tables(uint16_t cells[160]);  // host: the three predefined tables as pool cells
 

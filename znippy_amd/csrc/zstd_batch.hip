@@ -2,6 +2,7 @@
 // (znippy-common/src/codec.rs:L67-78) for frames another writer produced.  See the section comments.
 #include <algorithm>
 #include "zstd_dev.h"
+#include "xxh64_lanes.h"
 
 namespace zn {
 
@@ -780,6 +781,8 @@ void launch_fz_exec(const FzArgs &a, hipStream_t s) {
 //   k_bx_fse    lane = block: the sequence bitstream -> 8-byte records, repeat offsets resolved on the way (against a
 //               symbolic incoming history for blocks that are not the first of their frame, as k_fz_entropy does)
 //   k_bx_exec   wave = frame: fz_exec_frame
+//   k_bx_xxh_*  (only with the context's batch-checksum switch) frames with a content checksum: XXH64 of what was decoded
+//               against the trailer; a frame that fails is undecoded again (the section in front of k_bx_finish)
 //   k_bx_finish lane = candidate: decoded -> status 2, anything else -> the serial decoder's list
 // Any error or anything unsupported leaves the frame to the serial decoder, which also produces the error code.
 // =============================================================================================
@@ -1102,7 +1105,7 @@ __global__ __launch_bounds__(64) void k_bx_scan(BxArgs a) {
             else { row = a.bc_row[t - a.n_list_a - n_pend]; take = a.row_flag[row] != 0; }
             if (take && a.preset && a.status[row] < 0) take = false;  // the host has ruled on this row
         }
-        uint32_t nb = 0;
+        uint32_t nb = 0, ck = 0;
         uint64_t first = 0, n = 0;
         const uint8_t *src = a.blobs;
         if (take) {
@@ -1116,7 +1119,11 @@ __global__ __launch_bounds__(64) void k_bx_scan(BxArgs a) {
                 const uint32_t fhd = src[4];
                 const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did_flag = fhd & 3;
                 const uint32_t fcs_bytes = fcs_flag == 0 ? single : (1u << fcs_flag);
-                ok = !(fhd & 8) && !((fhd >> 2) & 1) && did_flag == 0 && fcs_bytes != 0;  // a checksum trailer is the serial decoder's
+                // a checksum trailer is the serial decoder's — or, with the context's switch on, the checksum stage's: the blocks
+                // then end 4 bytes in front of the frame's end (n >= 9 holds; a frame too short for its trailer fails the walk)
+                ck = (fhd >> 2) & 1;
+                ok = !(fhd & 8) && (!ck || a.xxh_on) && did_flag == 0 && fcs_bytes != 0;
+                if (ok && ck) n -= 4;
                 if (ok) {
                     if (!single) pos++;
                     ok = pos + fcs_bytes <= n;
@@ -1156,6 +1163,7 @@ __global__ __launch_bounds__(64) void k_bx_scan(BxArgs a) {
             }
         }
         if (t < n_slots) { a.cand_row[t] = take ? row : 0xFFFFFFFFu; a.cand_base[t] = base; a.cand_nb[t] = nb; }
+        if (a.xxh_on && t < n_slots) a.cand_ck[t] = nb ? ck : 0u;
     }
 }
 
@@ -2150,6 +2158,128 @@ __global__ __launch_bounds__(256) void k_rx_store(BxArgs a) {
     }
 }
 
+// =============================================================================================
+// The checksum stage (BxArgs::xxh_on): frames that end with a Content_Checksum trailer — the low 32 bits of XXH64 over the
+// content — are checked here, behind the execute / resolve stages and in front of k_bx_finish, instead of going to the serial
+// decoder for it.  XXH64 is four serial chains, one step per 32-byte stripe (xxh64_lanes.h), so a frame cannot be spread
+// over more than four lanes; what can be is the work around the chain:
+//   k_bx_xxh_quad  frames below XXH_WAVE_MIN bytes: four lanes per frame, one accumulator each, 16 frames per wave; the
+//                  merge reads across the quad, the quad's first lane does the tail and the compare
+//   k_bx_xxh_wave  bigger frames: a wave per frame; all 64 lanes load 16 stripes (512 contiguous bytes) and premultiply them,
+//                  then the chain steps through the 16 premultiplied words by cross-lane reads — add, rotate and one multiply
+//                  per step are all that is left on the chain (every lane walks the chain of accumulator lane & 3: the
+//                  instruction stream is the same with four lanes or 64, and nothing diverges)
+// Both take their slots by a static stride, keep every trip count wave-uniform (the quad form runs to the longest of its 16
+// frames with the others predicated) and have no cross-lane operation under a divergent branch (k_rx_expand's comment).
+// A frame whose trailer differs is not reported here: it goes back to being undecoded (row_flag, or rx_fail for a resolved
+// frame), k_bx_finish lists it for the serial decoder, and that one decodes it again and reports ZNIPPY_E_CHECKSUM.
+// =============================================================================================
+// slot t holds a frame the stage checks: taken by the scan with a trailer, and decoded by this run's execute / resolve stage
+__device__ __forceinline__ bool bx_xxh_takes(const BxArgs &a, const uint32_t t, uint32_t &row, bool &resolved) {
+    row = a.cand_row[t];
+    if (row == 0xFFFFFFFFu || !a.cand_nb[t] || !a.cand_ck[t]) return false;
+    resolved = a.rx_base && a.rx_base[t] != RX_NONE;
+    return resolved ? a.rx_fail[t] == 0 : a.row_flag[row] == 0;
+}
+// one lane: everything behind the stripes, the compare with the trailer, and what a mismatch undoes; true = the trailer is right
+__device__ __forceinline__ bool bx_xxh_close(const BxArgs &a, const uint32_t t, const uint32_t row, const bool resolved, const uint64_t v[4],
+                                             const uint8_t *p, const uint64_t fcs) {
+    const uint64_t h = xxl::finish(v, p, fcs);
+    const uint8_t *const tr = a.blobs + (a.blob_off[row] - a.blob_base) + (a.blob_size[row] - 4);
+    const uint32_t want = tr[0] | (tr[1] << 8) | (tr[2] << 16) | ((uint32_t)tr[3] << 24);
+    const bool good = (uint32_t)h == want;
+    if (!good) {
+        if (resolved) a.rx_fail[t] = 1;
+        else { a.row_flag[row] = 1; atomicAdd(&a.pool_used[2], ~0ull); }  // (the execute stage had counted it as decoded)
+    }
+    return good;
+}
+
+__global__ __launch_bounds__(64) void k_bx_xxh_quad(BxArgs a) {
+    const uint32_t lane = threadIdx.x, j = lane & 3;
+    const uint32_t n_slots = uni(a.ctr[0]);
+    unsigned long long n_good = 0, n_bad = 0, n_bytes = 0;
+    for (uint32_t t0 = blockIdx.x * 16; t0 < n_slots; t0 += gridDim.x * 16) {
+        const uint32_t t = t0 + (lane >> 2);
+        uint32_t row = 0xFFFFFFFFu;
+        bool resolved = false;
+        bool on = t < n_slots && bx_xxh_takes(a, t, row, resolved);
+        uint64_t fcs = on ? a.usize[row] : 0;
+        on = on && fcs < XXH_WAVE_MIN;
+        if (!on) fcs = 0;
+        const uint8_t *const p = on ? a.out + a.out_off[row] : a.out;
+        const uint32_t stripes = (uint32_t)(fcs / xxl::STRIPE);
+        uint32_t trips = stripes;
+        for (int d = 32; d >= 4; d >>= 1) trips = max(trips, (uint32_t)__shfl_xor((int)trips, d));
+        trips = uni(trips);
+        uint64_t acc = xxl::acc_init(j);
+        const uint8_t *const q = p + 8 * j;
+        for (uint32_t i = 0; i < trips; i += 4) {  // four loads in flight in front of four steps
+            uint64_t in[4];
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) in[k] = i + k < stripes ? xxl::load64(q + (uint64_t)xxl::STRIPE * (i + k)) : 0ull;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) acc = i + k < stripes ? xxl::stripe_round(acc, in[k]) : acc;
+        }
+        uint64_t v[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) v[k] = __shfl(acc, (int)((lane & ~3u) + k));
+        if (on && j == 0) {
+            if (bx_xxh_close(a, t, row, resolved, v, p, fcs)) n_good++; else n_bad++;
+            n_bytes += fcs;
+        }
+    }
+    for (int d = 32; d >= 1; d >>= 1) { n_good += __shfl_xor(n_good, d); n_bad += __shfl_xor(n_bad, d); n_bytes += __shfl_xor(n_bytes, d); }
+    if (lane == 0) {
+        if (n_good) atomicAdd(&a.xxh_stat[0], n_good);
+        if (n_bad) atomicAdd(&a.xxh_stat[1], n_bad);
+        if (n_bytes) atomicAdd(&a.xxh_stat[2], n_bytes);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_bx_xxh_wave(BxArgs a) {
+    const uint32_t lane = threadIdx.x, j = lane & 3;
+    const uint32_t n_slots = uni(a.ctr[0]);
+    for (uint32_t t = blockIdx.x; t < n_slots; t += gridDim.x) {
+        uint32_t row = 0xFFFFFFFFu;
+        bool resolved = false;
+        const bool takes = bx_xxh_takes(a, t, row, resolved);  // (every lane reads the same words)
+        if (!uni(takes ? 1u : 0u)) continue;
+        row = uni(row);
+        resolved = uni(resolved ? 1u : 0u) != 0;
+        const uint64_t fcs = uni64(a.usize[row]);
+        if (fcs < XXH_WAVE_MIN) continue;  // the quad form's
+        const uint8_t *const p = a.out + uni64(a.out_off[row]);
+        const uint64_t stripes = fcs / xxl::STRIPE, body = stripes * xxl::STRIPE, groups = (stripes + 15) / 16;
+        // the lane's word of group g: bytes [512 g + 8 lane, + 8) of the frame, zero behind the last stripe
+        auto word = [&](uint64_t g) { const uint64_t o = 512 * g + 8 * lane; return o + 8 <= body ? xxl::load64(p + o) : 0ull; };
+        uint64_t acc = xxl::acc_init(j);
+        uint64_t next = word(0);
+        for (uint64_t g = 0; g < groups; g++) {
+            const uint64_t pre = xxl::premul(next);
+            next = word(g + 1);  // in flight while the chain walks this group
+            const uint32_t cnt = uni((uint32_t)(stripes - 16 * g < 16 ? stripes - 16 * g : 16));
+            if (cnt == 16) {
+                uint64_t w[16];  // all 16 cross-lane reads first: none of them waits for the chain
+#pragma unroll
+                for (uint32_t s = 0; s < 16; s++) w[s] = __shfl(pre, (int)(4 * s + j));
+#pragma unroll
+                for (uint32_t s = 0; s < 16; s++) acc = xxl::chain(acc, w[s]);
+            } else {
+                for (uint32_t s = 0; s < cnt; s++) acc = xxl::chain(acc, __shfl(pre, (int)(4 * s + j)));
+            }
+        }
+        uint64_t v[4];
+#pragma unroll
+        for (uint32_t k = 0; k < 4; k++) v[k] = __shfl(acc, (int)k);
+        if (lane == 0) {
+            const bool good = bx_xxh_close(a, t, row, resolved, v, p, fcs);
+            atomicAdd(&a.xxh_stat[good ? 0 : 1], 1ull);
+            atomicAdd(&a.xxh_stat[2], (unsigned long long)fcs);
+        }
+    }
+}
+
 __global__ __launch_bounds__(64) void k_bx_finish(BxArgs a) {
     const uint32_t lane = threadIdx.x;
     const uint32_t n_slots = a.ctr[0];
@@ -2202,6 +2332,10 @@ void launch_bx_stage(const BxArgs &a, int cus, int stage, hipStream_t s) {
     case BX_RX_PLAN: hipLaunchKernelGGL(k_rx_plan, cap(slots, 8), dim3(64), 0, s, a); break;
     case BX_RX_EXPAND: hipLaunchKernelGGL(k_rx_expand, cap(a.item_cap, 32), dim3(64), 0, s, a); break;  // (static stride over the list; lone chains: the more the better, 54 VGPRs, no LDS)
     case BX_RX_STORE: hipLaunchKernelGGL(k_rx_store, cap((uint32_t)std::min<uint64_t>((a.rx_bound + 1023) / 1024, 1u << 30), 64), dim3(256), 0, s, a); break;
+    case BX_XXH:  // (the forms the table's row sizes call for: bit 0 the quad form, bit 1 the wave form)
+        if (a.xxh_on && (a.xxh_forms & 1)) hipLaunchKernelGGL(k_bx_xxh_quad, cap((slots + 15) / 16, 16), dim3(64), 0, s, a);
+        if (a.xxh_on && (a.xxh_forms & 2)) hipLaunchKernelGGL(k_bx_xxh_wave, cap(slots, 16), dim3(64), 0, s, a);
+        break;
     case BX_FINISH: hipLaunchKernelGGL(k_bx_finish, dim3(lane_grid), dim3(64), 0, s, a); break;
     default:
         if (stage >= BX_RX_JUMP && stage < BX_RX_JUMP + (int)RX_ROUNDS)

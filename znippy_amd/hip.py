@@ -101,6 +101,15 @@ class Context:
     def window_log(self):
         return int(self.L.znippy_ctx_window_log(self.h))
 
+    def set_batch_checksums(self, on):
+        """Opt-in: zstd frames with a content checksum (XXH64 trailer) go through the batch and resolve paths of later read
+        runs, and a stage of its own checks the trailer; a mismatch is handed to the serial decoder, which reports it.
+        0 (default) or 1.  See znippy_hip.h."""
+        self._chk(self.L.znippy_ctx_set_batch_checksums(self.h, int(on)), "znippy_ctx_set_batch_checksums")
+
+    def batch_checksums(self):
+        return int(self.L.znippy_ctx_batch_checksums(self.h))
+
     def set_kernel_timing(self, level):
         """2 = HIP events around every kernel (default), 1 = around the dominant read kernels only, 0 = none."""
         self._chk(self.L.znippy_ctx_set_kernel_timing(self.h, int(level)), "znippy_ctx_set_kernel_timing")
@@ -390,6 +399,12 @@ class RowTable:
         self.ctx._chk(self.ctx.L.znippy_rows_foreign_stats(self.ctx.h, self.h, st), "znippy_rows_foreign_stats")
         return dict(lit_pool_bytes=int(st[0]), seq_pool_records=int(st[1]), frames=int(st[2]), blocks_given_up=int(st[3]),
                     given_up_error=int(st[4]), given_up_table_far=int(st[5]), given_up_pool=int(st[6]), given_up_range=int(st[7]))
+
+    def checksum_stats(self):
+        """Last run's checksum stage (Context.set_batch_checksums): frames whose trailer it found right / wrong, bytes it hashed."""
+        st = (C.c_uint64 * 4)()
+        self.ctx._chk(self.ctx.L.znippy_rows_checksum_stats(self.ctx.h, self.h, st), "znippy_rows_checksum_stats")
+        return dict(verified=int(st[0]), mismatched=int(st[1]), bytes=int(st[2]))
 
     def decode_verify(self, d_blobs, d_out, blob_base=0, out_cap=None, blob_cap=None):
         self.decode_verify_async(d_blobs, d_out, blob_base, out_cap, blob_cap)
