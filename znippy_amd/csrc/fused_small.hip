@@ -1192,6 +1192,10 @@ struct alignas(16) RolesShared {
     uint32_t next_iter;                  // the loaders' iteration counter (an iteration = one group of four slots)
     uint32_t cnt[R_SLOTS / R_GROUP];     // hashed slots of the group's current use
     uint32_t gen[R_SLOTS / R_GROUP];     // completed uses of the group (a loader refills it when gen == its next use)
+    // constants of roles_hash_6x10, written once per workgroup: the parent lanes' offset | stride << 11 | gap << 22 at
+    // their three level changes (roles_parent_level), and the BLAKE3 IV, which a hasher wave carries in scalar registers
+    uint32_t plevel[3][4];
+    uint32_t iv[8];
 };
 
 // One recognised row written by the whole wave from its window (R_LOADER_EMITS; lane = byte / 16-byte piece).
@@ -1370,7 +1374,8 @@ __device__ __forceinline__ bool tree_op_6x10(uint32_t n, uint32_t &l, uint32_t &
     return false;
 }
 
-// The leaf pass of a 6 x 10 tile staged in `slot` (windows extended by the caller), rows stored from the message registers;
+// The leaf pass of a 6 x 10 tile staged in `slot` (windows extended by the caller), rows stored from the message registers,
+// the 60 leaf chaining values left in `tree` by the last pass;
 // lanes 60..63 fold the previous tile's tree (have_prev) in `tree` and write its digests — as VIRTUAL LEAVES: a parent's
 // message is its two children's chaining values, which sit
 // in the node array at a fixed distance from each other on every level — so lanes 60..63 fetch their 64 message bytes with
@@ -1381,10 +1386,19 @@ __device__ __forceinline__ bool tree_op_6x10(uint32_t n, uint32_t &l, uint32_t &
 //   level 3, passes 11..12   row = 4(b-11) + s:     10 row | + 4               320 s (+1280), gap 96
 //   root,    passes 13..14   row = 4(b-13) + s:     10 row | + 8  -> digest    320 s (+1280), gap 224
 // A result goes over its left child (the address just read).  What is left per pass for the parent lanes is the reset of
-// their chaining value, one select for the flags and the result's two stores.
+// their chaining value, one AND for the flags and the result's two stores: a level's offset, stride and gap come from
+// RolesShared::plevel, read by lanes 60..63 alone in the three passes that fetch a new level's first message (a scalar
+// branch in the other passes), and the IV of the reset waits in scalar registers (`iv`: RolesShared::iv).
+// The loop runs two passes per iteration over two message sets: one is hashed while the other is fetched, then the
+// other way round, so that no message word moves from register to register between passes.
+__device__ __forceinline__ constexpr uint32_t roles_parent_level(uint32_t lv, uint32_t ps) {  // lv 0..2 = tree levels 2, 3, root
+    return lv == 0 ? (320 * (ps >> 1) + 128 * (ps & 1)) | 640u << 11 | 32u << 22
+                   : (320 * ps) | 1280u << 11 | (lv == 1 ? 96u : 224u) << 22;
+}
+
 template <bool STORE>
 __device__ __forceinline__ void roles_hash_6x10(const FusedArgs &a, RolesShared &S, uint32_t slot, uint32_t *tree, bool have_prev,
-                                                   uint32_t prev_first, uint32_t cv[8]) {
+                                                   uint32_t prev_first) {
     typedef __attribute__((address_space(3))) uint8_t lds8b;
     const uint32_t lane = threadIdx.x & 63;
     const bool leaf = lane < 60;
@@ -1401,10 +1415,13 @@ __device__ __forceinline__ void roles_hash_6x10(const FusedArgs &a, RolesShared 
     // passes in which this parent lane has an operation: all of 0..14, less the last pass of levels 1, 3 and 4 for lanes 2, 3
     const uint32_t vmask = (leaf || !have_prev) ? 0u : (ps < 2 ? 0x7FFFu : 0x7FFFu & ~((1u << 7) | (1u << 12) | (1u << 14)));
     const bool store = STORE && leaf && !(a.dbg & 16);  // (verify-only: loads from LDS, compression and the tree ride, nothing else)
-    b3::set_iv(cv);
-    uint4 n0, n1, n2, n3;
-    uint32_t wq = 0, wq_next = 0;  // where the pass's result goes: the offset its message was read from
-    auto fetch = [&]() {
+    // a pass's flags are the leaves' and the parents' ORed together (uniform), less the bits that are not the lane's kind's
+    const uint32_t fmask = leaf ? (b3::CHUNK_START | b3::CHUNK_END) : (b3::PARENT | b3::ROOT);
+    uint32_t cv[8], iv[8];  // the IV in scalar registers (read, not written as literals: a literal is a constant again in every use)
+#pragma unroll
+    for (int i = 0; i < 8; i++) cv[i] = iv[i] = lds_ld(&S.iv[i]);
+    struct Msg { u4v w0, w1, w2, w3; uint32_t q; };  // a pass's 64 message bytes and the offset they were read from (where a parent's result goes)
+    auto fetch = [&](Msg &M) {
         uint32_t q = p;
         if (p > yL0) {
             q = yB + r;
@@ -1412,27 +1429,23 @@ __device__ __forceinline__ void roles_hash_6x10(const FusedArgs &a, RolesShared 
             if (r >= yoff) r -= yoff;
         }
         const lds_u4 *q3 = (const lds_u4 *)(Y + q), *q4 = (const lds_u4 *)(Y + q + 32 + gap);
-        const u4v a0 = q3[0], a1 = q3[1], a2 = q4[0], a3 = q4[1];
-        n0 = make_uint4(a0.x, a0.y, a0.z, a0.w); n1 = make_uint4(a1.x, a1.y, a1.z, a1.w);
-        n2 = make_uint4(a2.x, a2.y, a2.z, a2.w); n3 = make_uint4(a3.x, a3.y, a3.z, a3.w);
-        wq_next = q;
+        M.w0 = q3[0]; M.w1 = q3[1]; M.w2 = q4[0]; M.w3 = q4[1];
+        M.q = q;
         p += step;
     };
-    fetch();
-#pragma unroll 1
-    for (uint32_t b = 0; b < 16; b++) {
-        uint32_t m[16] = {n0.x, n0.y, n0.z, n0.w, n1.x, n1.y, n1.z, n1.w, n2.x, n2.y, n2.z, n2.w, n3.x, n3.y, n3.z, n3.w};
-        wq = wq_next;
-        if (b < 15) {
-            if (b == 7 || b == 10 || b == 12) {  // the parent lanes' next level (uniform branch; three passes of sixteen)
+    // pass b: fetches the message of pass b + 1 into N, stores and hashes M
+    auto pass = [&](const uint32_t b, const bool odd, const Msg &M, Msg &N) {
+        if (odd ? b < 15 : true) {
+            if (odd ? b == 7 : (b == 10 || b == 12)) {  // the parent lanes' next level (uniform branch; three passes of sixteen)
                 if (!leaf) {
-                    if (b == 7) { p = 320 * (ps >> 1) + 128 * (ps & 1); step = 640; gap = 32; }
-                    else if (b == 10) { p = 320 * ps; step = 1280; gap = 96; }
-                    else { p = 320 * ps; gap = 224; }
+                    const uint32_t w = *(const volatile lds_u32 *)&S.plevel[odd ? 0 : (b >> 1) - 4][ps];
+                    p = w & 0x7FFu; step = (w >> 11) & 0x7FFu; gap = w >> 22;
                 }
             }
-            fetch();
+            fetch(N);
         }
+        const uint32_t m[16] = {M.w0.x, M.w0.y, M.w0.z, M.w0.w, M.w1.x, M.w1.y, M.w1.z, M.w1.w,
+                                M.w2.x, M.w2.y, M.w2.z, M.w2.w, M.w3.x, M.w3.y, M.w3.z, M.w3.w};
         if (store) {
             uint8_t *d = dst + b * 64;
             st16(d, make_uint4(m[0], m[1], m[2], m[3]));
@@ -1440,21 +1453,42 @@ __device__ __forceinline__ void roles_hash_6x10(const FusedArgs &a, RolesShared 
             st16(d + 32, make_uint4(m[8], m[9], m[10], m[11]));
             st16(d + 48, make_uint4(m[12], m[13], m[14], m[15]));
         }
-        const uint32_t fl = (b == 0 ? b3::CHUNK_START : 0u) | (b == 15 ? b3::CHUNK_END : 0u);
+        const uint32_t fl = odd ? (b == 15 ? b3::CHUNK_END : 0u) : (b == 0 ? b3::CHUNK_START : 0u);
         const uint32_t fp = b3::PARENT | (b >= 13 ? b3::ROOT : 0u);
-        if (!leaf) b3::set_iv(cv);
-        b3::compress(cv, m, kk, 0, 64, leaf ? fl : fp);
-        if ((vmask >> b) & 1u) {
-            if (b >= 13) {
-                uint4 *o = reinterpret_cast<uint4 *>(dig + (b - 13) * 32);
-                o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
-                o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
-            } else {
-                lds_u4a *o = (lds_u4a *)(Y + wq);
+        b3::compress(cv, m, kk, 0, 64, (fl | fp) & fmask);
+        if (!leaf) {
+            if ((vmask >> b) & 1u) {
+                if (b >= 13) {
+                    uint4 *o = reinterpret_cast<uint4 *>(dig + (b - 13) * 32);
+                    o[0] = make_uint4(cv[0], cv[1], cv[2], cv[3]);
+                    o[1] = make_uint4(cv[4], cv[5], cv[6], cv[7]);
+                } else {
+                    lds_u4a *o = (lds_u4a *)(Y + M.q);
+                    o[0] = u4v{cv[0], cv[1], cv[2], cv[3]};
+                    o[1] = u4v{cv[4], cv[5], cv[6], cv[7]};
+                }
+            }
+            // a parent's chaining value is the IV in every pass (set here, beside the stores: on its own the
+            // assignment becomes a select over all lanes)
+#pragma unroll
+            for (int i = 0; i < 8; i++) cv[i] = iv[i];
+        }
+        if (odd && b == 15) {
+            // the previous tree is done (its last node ran in pass 14): this tile's leaves take its place.  (Written here
+            // and not behind the loop: a chaining value that lives past the loop is copied at the end of every iteration.)
+            if (leaf) {
+                lds_u4a *o = (lds_u4a *)(tree + lane * 8);
                 o[0] = u4v{cv[0], cv[1], cv[2], cv[3]};
                 o[1] = u4v{cv[4], cv[5], cv[6], cv[7]};
             }
         }
+    };
+    Msg A, B;
+    fetch(A);
+#pragma unroll 1
+    for (uint32_t b = 0; b < 16; b += 2) {
+        pass(b, false, A, B);
+        pass(b + 1, true, B, A);
     }
 }
 
@@ -1538,13 +1572,7 @@ __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S)
             const bool shape610 = inline_tree && !R_LOADER_EMITS && nu == 6 && t.n_leaves == 60 && !(a.dbg & 8192) &&
                                   __ballot(lane < 6 && S.len[slot][lu] != 10240u) == 0ull;
             if (shape610) {
-                uint32_t cv[8];
-                roles_hash_6x10<STORE>(a, S, slot, tree, have_prev, prev_first, cv);
-                if (lane < 60) {  // the previous tree is done (its last node ran in pass 14): this tile's leaves take its place
-                    lds_u4a *o = (lds_u4a *)(tree + lane * 8);
-                    o[0] = u4v{cv[0], cv[1], cv[2], cv[3]};
-                    o[1] = u4v{cv[4], cv[5], cv[6], cv[7]};
-                }
+                roles_hash_6x10<STORE>(a, S, slot, tree, have_prev, prev_first);  // (leaves this tile's leaf CVs in `tree`)
                 have_prev = true;
                 prev_first = t.first_unit;
                 if (lane < WROWS) S.tn[slot][lane] = 0u;  // nothing left for the group's fold
@@ -1610,6 +1638,11 @@ __global__ __launch_bounds__(R_WAVES * 64) void k_fused_roles(FusedArgs a) {
     RolesShared &S = *reinterpret_cast<RolesShared *>(s_roles_raw);
     if (threadIdx.x == 0) { S.ready = 0; S.take = 0; S.finished = 0; S.next_iter = 0; }
     if (threadIdx.x < R_SLOTS / R_GROUP) { S.cnt[threadIdx.x] = 0; S.gen[threadIdx.x] = 0; }
+    if (threadIdx.x < 12) S.plevel[threadIdx.x >> 2][threadIdx.x & 3] = roles_parent_level(threadIdx.x >> 2, threadIdx.x & 3);
+    if (threadIdx.x < 8) {
+        constexpr uint32_t ivw[8] = {b3::IV0, b3::IV1, b3::IV2, b3::IV3, b3::IV4, b3::IV5, b3::IV6, b3::IV7};
+        S.iv[threadIdx.x] = ivw[threadIdx.x];
+    }
     __syncthreads();
     const bool clk = (a.dbg & 32768) && a.dbg_buf && blockIdx.x == 7 && threadIdx.x == 64 * R_LOADERS;
     const unsigned long long c0 = clk ? __builtin_amdgcn_s_memtime() : 0, r0 = clk ? __builtin_amdgcn_s_memrealtime() : 0;
