@@ -5,6 +5,7 @@
 #include "common.h"
 #include "encode.h"
 #include "../../include/znippy_hip.h"
+#include "host/enc_plan.h"
 #include "host/range_plan.h"
 #include "host/run_overlap.h"
 
@@ -617,7 +618,6 @@ struct znippy_rounds {
     uint32_t n = 0;
     uint64_t *src_off = nullptr, *len = nullptr;
     uint8_t *skip = nullptr;
-    uint32_t *digests = nullptr;
     std::vector<uint8_t> h_skip;  // empty: no round is a store-path round
     void *plan_scratch[3] = {nullptr, nullptr, nullptr};  // per-round prefix sums of the plan kernels (freed with the table)
     uint64_t in_bytes = 0, enc_bytes = 0;  // all rounds / rounds that go through the encoder
@@ -636,11 +636,13 @@ struct znippy_rounds {
     uint64_t prov_bytes = 0;
     uint32_t *piece_len = nullptr, *piece_len_init = nullptr;
     uint64_t *piece_start = nullptr, *local_excl = nullptr, *block_tot = nullptr;
-    // results live in ONE device slab (one D2H per call): [total u64][overflow u64][blob_offset n][blob_size n][digests 32n]
-    // Two slabs + two mirrors + one event each: run k uses slot k & 1 and its D2H copy rides the context's copy
+    // results live in ONE device slab (one copy out per call: ResSlab)
+    // Two slabs + two mirrors + one event each: run k uses slot k & 1 and its copy rides the context's copy
     // stream, so run k + 1 encodes while run k's results travel (and are read: znippy_rounds_results_lagged).
-    uint8_t *res = nullptr, *h_res = nullptr;  // device slab + pinned host mirror of the CURRENT run's slot
-    uint8_t *res_m[2] = {nullptr, nullptr}, *h_res_m[2] = {nullptr, nullptr};
+    uint8_t *res_m[2] = {nullptr, nullptr}, *h_res_m[2] = {nullptr, nullptr};  // device slabs + their pinned host mirrors
+    unsigned slot = 0;  // of the run queued last (0 before the first): znippy_rounds_results reads it, znippy_hash_rounds writes its digests
+    ResSlab dev(unsigned k) const { return ResSlab{res_m[k], n}; }
+    ResSlab host(unsigned k) const { return ResSlab{h_res_m[k], n}; }
     size_t h_res_cap_m[2] = {0, 0}, h_stored_cap = 0;
     hipEvent_t ev_enc[2] = {nullptr, nullptr}, ev_res[2] = {nullptr, nullptr};
     uint64_t run_seq = 0;
@@ -651,8 +653,6 @@ struct znippy_rounds {
     uint32_t blob_align = 1;            // opt-in (znippy_rounds_set_blob_align): every blob offset is a multiple of it
     uint32_t *piece_pad = nullptr;      // zero bytes behind every piece (made by the first alignment above 1; only the rounds' last pieces are ever written)
     uint8_t *stored = nullptr, *h_stored = nullptr;  // per round: turned into a raw payload by the opt-in pass
-    uint64_t *blob_offset = nullptr, *blob_size = nullptr, *total = nullptr;
-    uint32_t *overflow = nullptr;
     // far window: the rounds longer than one block and their regions of the index (found at creation; the device copies
     // are made by the first windowed encode call)
     std::vector<LdmRound> h_ldm;
@@ -2855,17 +2855,6 @@ int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
 }
 
 // ---- rounds -------------------------------------------------------------------------------------
-static void rounds_select(znippy_rounds *r, unsigned slot) {  // the result slab the next run writes
-    const size_t n = r->n;
-    r->res = r->res_m[slot];
-    r->h_res = r->h_res_m[slot];
-    r->total = reinterpret_cast<uint64_t *>(r->res);
-    r->overflow = reinterpret_cast<uint32_t *>(r->res + 8);
-    r->blob_offset = reinterpret_cast<uint64_t *>(r->res + 16);
-    r->blob_size = r->blob_offset + n;
-    r->digests = reinterpret_cast<uint32_t *>(r->res + 16 + n * 16);
-}
-
 void znippy_rounds_destroy(znippy_rounds *r) {
     if (!r) return;
     (void)hipSetDevice(r->ctx->device);
@@ -2890,6 +2879,82 @@ void znippy_rounds_destroy(znippy_rounds *r) {
     table_released(c);
 }
 
+// The stages of znippy_rounds_create, in its order.  Every failure returns; the constructor's scope guard frees what was made.
+static int rounds_columns_h2d(znippy_ctx *ctx, znippy_rounds *r, const uint64_t *src_offset, const uint64_t *len, const uint8_t *skip) {
+    const size_t n = r->n;
+    int rc;
+    if ((rc = dev_upload(ctx, &r->src_off, src_offset, n)) || (rc = dev_upload(ctx, &r->len, len, n)) ||
+        (skip ? (rc = dev_upload(ctx, &r->skip, skip, n)) : (tmalloc(ctx, &r->skip, std::max<size_t>(n, 16)) != hipSuccess ? (rc = ZNIPPY_E_NOMEM) : 0)))
+        return rc;
+    if (!skip && n) HIPCHK(ctx, hipMemsetAsync(r->skip, 0, n, ctx->stream));
+    return ZNIPPY_OK;
+}
+
+static int rounds_slabs(znippy_ctx *ctx, znippy_rounds *r) {
+    r->res_bytes = ResSlab::bytes(r->n);
+    for (int k = 0; k < 2; k++)
+        if (tmalloc(ctx, &r->res_m[k], r->res_bytes) != hipSuccess ||
+            !(r->h_res_m[k] = (uint8_t *)pinned_take(ctx, r->res_bytes, &r->h_res_cap_m[k])) ||
+            !(r->ev_enc[k] = event_take(ctx)) || !(r->ev_res[k] = event_take(ctx)))
+            return ZNIPPY_E_NOMEM;
+    return ZNIPPY_OK;
+}
+
+static int rounds_hash_plan(znippy_ctx *ctx, znippy_rounds *r, const uint64_t *len) {
+    const uint32_t n = r->n;
+    PlanBuf p;
+    build_plan([&](uint32_t u) { return len[u]; }, n, p);
+    const int rc = upload_plan(ctx, p, r->plan);
+    if (rc) return rc;
+    if (r->n_items == n && r->n_wide == 0 && r->enc_bytes == r->in_bytes && n) {
+        uint32_t max_units = 0;
+        for (const Tile &t : p.tiles) max_units = std::max(max_units, t.n_units);
+        r->fuse_tiles = 1;  // one tile per dequeue (C2: 6 rounds): 0.77 ms against 0.86 for two and 1.12 for ten on one box — with ~4 tiles per wave the finest grain balances best
+        if (const char *e = getenv("ZNIPPY_FUSE_TILES")) { const int v = atoi(e); if (v >= 1 && v * (int)max_units <= 64) r->fuse_tiles = v; }  // A/B
+    }
+    return ZNIPPY_OK;
+}
+
+// far window: regions of the index for the encoded rounds longer than one block (rounds of 4 GiB and more are not
+// indexed: the index holds 32-bit positions).  Every round has at least one piece: with no more pieces than rounds
+// there is no such round, and the pass is skipped (100k small rounds: no host pass of its own)
+static void rounds_far_regions(znippy_rounds *r, const uint64_t *len, const uint8_t *skip) {
+    const uint64_t n = r->n;
+    if (r->n_items > n) {
+        for (uint64_t i = 0; i < n; i++)
+            if (len[i] > BLOCK_BYTES && len[i] < (1ull << 32) && !(skip && skip[i])) {
+                const uint32_t lg = ldm_log2(len[i]);
+                r->h_ldm.push_back(LdmRound{(uint32_t)i, r->ldm_chunks, r->ldm_entries | ((uint64_t)lg << 48)});
+                r->ldm_entries += 1ull << lg;
+                r->ldm_chunks += (uint32_t)((len[i] + LDM_CHUNK - 1) / LDM_CHUNK);
+            }
+    }
+}
+
+// encoder plan: one item per output piece, in round order — counted, scanned and filled on the device
+static int rounds_encoder_plan(znippy_ctx *ctx, znippy_rounds *r, bool has_skip) {
+    const size_t n = r->n, ni = std::max<size_t>(r->n_items, 1), nsb = (ni + 255) / 256;
+    const uint32_t nblk = ((uint32_t)n + 1023) / 1024;
+    RoundSums *sums = nullptr;
+    auto take = [&](auto **p, size_t bytes) { return tmalloc(ctx, p, bytes) == hipSuccess; };  // (at least 16 bytes each)
+    const bool ok = take(&r->first_item, 4 * n) && take(&sums, std::max<size_t>(sizeof(RoundSums) * (size_t)nblk, 64)) &&
+                    take(&r->order_small, 4 * (size_t)r->n_small) && take(&r->order_wide, 4 * (size_t)r->n_wide) &&
+                    take(&r->retry_list, 4 * (size_t)r->n_small) && take(&r->retry_count, 64) && take(&r->stored, n) &&
+                    (r->h_stored = (uint8_t *)pinned_take(ctx, std::max<size_t>(n, 16), &r->h_stored_cap)) != nullptr &&
+                    take(&r->items, sizeof(EncItem) * ni) && take(&r->piece_len_init, 4 * ni) && take(&r->piece_len, 4 * ni) &&
+                    take(&r->piece_start, 8 * ni) && take(&r->local_excl, 8 * ni) && take(&r->block_tot, 8 * nsb);
+    r->plan_scratch[0] = sums;  // (parked until the table goes: the kernels below are still queued then)
+    if (!ok) return ZNIPPY_E_NOMEM;
+    if (n) {
+        const uint8_t *const d_skip = has_skip ? r->skip : (const uint8_t *)nullptr;
+        hipLaunchKernelGGL(k_rounds_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->len, d_skip, (uint32_t)n, sums);
+        hipLaunchKernelGGL(k_rounds_scan, dim3(1), dim3(256), 0, ctx->stream, sums, nblk);
+        hipLaunchKernelGGL(k_rounds_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->len, d_skip, (uint32_t)n, sums, r->first_item, r->items, r->piece_len_init,
+                           r->order_small, r->order_wide);
+    }
+    return ZNIPPY_OK;
+}
+
 int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint64_t *len,
                          const uint8_t *skip, uint64_t n, znippy_rounds **out) {
     if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
@@ -2910,65 +2975,14 @@ int znippy_rounds_create(znippy_ctx *ctx, const uint64_t *src_offset, const uint
     r->n_items = (uint32_t)tot[0]; r->prov_bytes = tot[1]; r->n_small = (uint32_t)tot[2]; r->n_wide = (uint32_t)tot[3];
     td.mark("totals");
     int rc;
-    if ((rc = dev_upload(ctx, &r->src_off, src_offset, n)) || (rc = dev_upload(ctx, &r->len, len, n)) ||
-        (skip ? (rc = dev_upload(ctx, &r->skip, skip, n)) : (tmalloc(ctx, &r->skip, std::max<size_t>(n, 16)) != hipSuccess ? (rc = ZNIPPY_E_NOMEM) : 0)))
-        return rc;
-    if (!skip && n) HIPCHK(ctx, hipMemsetAsync(r->skip, 0, n, ctx->stream));
+    if ((rc = rounds_columns_h2d(ctx, r, src_offset, len, skip))) return rc;
     td.mark("columns_h2d");
-    r->res_bytes = 16 + (size_t)n * (8 + 8 + 32);
-    for (int k = 0; k < 2; k++)
-        if (tmalloc(ctx, &r->res_m[k], r->res_bytes) != hipSuccess ||
-            !(r->h_res_m[k] = (uint8_t *)pinned_take(ctx, r->res_bytes, &r->h_res_cap_m[k])) ||
-            !(r->ev_enc[k] = event_take(ctx)) || !(r->ev_res[k] = event_take(ctx)))
-            return ZNIPPY_E_NOMEM;
-    rounds_select(r, 0);
+    if ((rc = rounds_slabs(ctx, r))) return rc;
     td.mark("slabs");
-    PlanBuf p;
-    build_plan([&](uint32_t u) { return len[u]; }, (uint32_t)n, p);
-    if ((rc = upload_plan(ctx, p, r->plan))) return rc;
-    if (r->n_items == n && r->n_wide == 0 && r->enc_bytes == r->in_bytes && n) {
-        uint32_t max_units = 0;
-        for (const Tile &t : p.tiles) max_units = std::max(max_units, t.n_units);
-        r->fuse_tiles = 1;  // one tile per dequeue (C2: 6 rounds): 0.77 ms against 0.86 for two and 1.12 for ten on one box — with ~4 tiles per wave the finest grain balances best
-        if (const char *e = getenv("ZNIPPY_FUSE_TILES")) { const int v = atoi(e); if (v >= 1 && v * (int)max_units <= 64) r->fuse_tiles = v; }  // A/B
-    }
+    if ((rc = rounds_hash_plan(ctx, r, len))) return rc;
     td.mark("hash_plan");
-    // far window: regions of the index for the encoded rounds longer than one block (rounds of 4 GiB and more are not
-    // indexed: the index holds 32-bit positions).  Every round has at least one piece: with no more pieces than rounds
-    // there is no such round, and the pass is skipped (100k small rounds: no host pass of its own)
-    if (r->n_items > n) {
-        for (uint64_t i = 0; i < n; i++)
-            if (len[i] > BLOCK_BYTES && len[i] < (1ull << 32) && !(skip && skip[i])) {
-                const uint32_t lg = ldm_log2(len[i]);
-                r->h_ldm.push_back(LdmRound{(uint32_t)i, r->ldm_chunks, r->ldm_entries | ((uint64_t)lg << 48)});
-                r->ldm_entries += 1ull << lg;
-                r->ldm_chunks += (uint32_t)((len[i] + LDM_CHUNK - 1) / LDM_CHUNK);
-            }
-    }
-    // encoder plan: one item per output piece, in round order — counted, scanned and filled on the device
-    const size_t ni = std::max<size_t>(r->n_items, 1), nsb = (ni + 255) / 256;
-    RoundSums *sums = nullptr;
-    const uint32_t nblk = ((uint32_t)n + 1023) / 1024;
-    if (tmalloc(ctx, &r->first_item, std::max<size_t>(4 * (size_t)n, 16)) != hipSuccess || tmalloc(ctx, &sums, std::max<size_t>(sizeof(RoundSums) * (size_t)nblk, 64)) != hipSuccess ||
-        tmalloc(ctx, &r->order_small, std::max<size_t>(4 * (size_t)r->n_small, 16)) != hipSuccess ||
-        tmalloc(ctx, &r->order_wide, std::max<size_t>(4 * (size_t)r->n_wide, 16)) != hipSuccess ||
-        tmalloc(ctx, &r->retry_list, std::max<size_t>(4 * (size_t)r->n_small, 16)) != hipSuccess || tmalloc(ctx, &r->retry_count, 64) != hipSuccess ||
-        tmalloc(ctx, &r->stored, std::max<size_t>(n, 16)) != hipSuccess ||
-        !(r->h_stored = (uint8_t *)pinned_take(ctx, std::max<size_t>(n, 16), &r->h_stored_cap)) ||
-        tmalloc(ctx, &r->items, sizeof(EncItem) * ni) != hipSuccess || tmalloc(ctx, &r->piece_len_init, 4 * ni) != hipSuccess ||
-        tmalloc(ctx, &r->piece_len, 4 * ni) != hipSuccess || tmalloc(ctx, &r->piece_start, 8 * ni) != hipSuccess ||
-        tmalloc(ctx, &r->local_excl, 8 * ni) != hipSuccess || tmalloc(ctx, &r->block_tot, 8 * nsb) != hipSuccess) {
-        tfree(ctx, sums);
-        return ZNIPPY_E_NOMEM;
-    }
-    if (n) {
-        const uint8_t *const d_skip = skip ? r->skip : (const uint8_t *)nullptr;
-        hipLaunchKernelGGL(k_rounds_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->len, d_skip, (uint32_t)n, sums);
-        hipLaunchKernelGGL(k_rounds_scan, dim3(1), dim3(256), 0, ctx->stream, sums, nblk);
-        hipLaunchKernelGGL(k_rounds_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->len, d_skip, (uint32_t)n, sums, r->first_item, r->items, r->piece_len_init,
-                           r->order_small, r->order_wide);
-    }
-    r->plan_scratch[0] = sums;  // (parked until the table goes: the kernels above are still queued)
+    rounds_far_regions(r, len, skip);
+    if ((rc = rounds_encoder_plan(ctx, r, skip != nullptr))) return rc;
     td.mark("encoder_plan");
     // store-path pieces keep their fixed lengths for the table's lifetime; encoded pieces are rewritten by
     // the encoder on every run, so one copy at creation is enough
@@ -2984,42 +2998,43 @@ uint64_t znippy_rounds_blob_bound(const znippy_rounds *r) {
     return r->blob_bound + (r->n ? (uint64_t)(r->n - 1) * (r->blob_align - 1) : 0);
 }
 
-// d_copy_out != nullptr: the stored (skip) rounds are copied to d_copy_out + blob_offset[round] while they are hashed
-// (store-heavy tables; blob_offset must have been computed on the stream before)
-// copy_align: the alignment of the run's blob offsets (16 and more: every destination is as aligned as d_copy_out is)
-// tree_out != nullptr: the run's block tree entries (znippy_rounds_emit_block_tree), made from the tile CVs behind the merge
-static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, hipStream_t on = nullptr,
-                             void *d_copy_out = nullptr, uint64_t copy_cap = 0, uint32_t copy_align = 1, uint32_t *tree_out = nullptr) {
-    hipStream_t s = on ? on : ctx->stream;
+// the rounds as hash input, digests into `res` (the hash kernel's arguments, and the encoder's where its waves hash: EncodeArgs::h)
+static HashArgs rounds_hash_args(const znippy_rounds *r, const ResSlab &res, const void *d_src) {
     HashArgs h{};
     h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
     h.len = r->len;
     h.srcA = (const uint8_t *)d_src; h.offA = r->src_off; h.baseA = 0;
-    h.digests = r->digests; h.tile_cv = r->plan.tile_cv;
+    h.digests = res.digests(); h.tile_cv = r->plan.tile_cv;
+    return h;
+}
+// res: the slab the digests go to (and whose blob offsets a copying launch reads)
+// d_copy_out != nullptr: the stored (skip) rounds are copied to d_copy_out + blob_offset[round] while they are hashed
+// (store-heavy tables; blob_offset must have been computed on the stream before)
+// copy_align: the alignment of the run's blob offsets (16 and more: every destination is as aligned as d_copy_out is)
+// tree_out != nullptr: the run's block tree entries (znippy_rounds_emit_block_tree), made from the tile CVs behind the merge
+static int hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const ResSlab &res, const void *d_src, hipStream_t on = nullptr,
+                             void *d_copy_out = nullptr, uint64_t copy_cap = 0, uint32_t copy_align = 1, uint32_t *tree_out = nullptr) {
+    hipStream_t s = on ? on : ctx->stream;
+    HashArgs h = rounds_hash_args(r, res, d_src);
     if (d_copy_out) {
-        h.srcB = (uint8_t *)d_copy_out; h.offB = r->blob_offset; h.copy_to_B = 1;
+        h.srcB = (uint8_t *)d_copy_out; h.offB = res.blob_offset(); h.copy_to_B = 1;
         h.store_tiles = ctx->sw.store_g;
         h.copy_mask = r->skip; h.copy_cap = copy_cap;
         h.misaligned_dst = !((r->all_stored_aligned || copy_align >= 16) && ((uintptr_t)d_copy_out & 15) == 0);
     }
     // next to a busy encoder (auxiliary stream) the hash keeps out of LDS: the encoder's residency depends on it
     if (on && r->enc_bytes * 4 >= r->in_bytes) h.fold_tiles_max = 1;
-    ktime_begin(ctx, "blake3_tiles", s);
-    launch_hash_tiles(h, s);
-    ktime_end(ctx, s);
+    timed(ctx, "blake3_tiles", s, [&] { launch_hash_tiles(h, s); });
     if (r->plan.n_big) {
-        ktime_begin(ctx, "blake3_merge_big", s);
         // beside the persistent encoder (auxiliary stream) the merge stays with its one-wave workgroups: a four-wave one waits for
         // four free wave slots on one CU, which the encoder's waves leave only when they retire (seen: 53 ms behind a 65 ms encode)
-        launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, r->digests, r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, on ? 0xFFFFFFFFu : r->plan.max_cvs, s);
-        ktime_end(ctx, s);
+        timed(ctx, "blake3_merge_big", s, [&] {
+            launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, res.digests(), r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, on ? 0xFFFFFFFFu : r->plan.max_cvs, s);
+        });
         // same stream, directly behind the merge: whatever orders the merge (ev_join, the main stream) orders this too, and the
         // next run's hash, which overwrites tile_cv, is behind it as it is behind the merge
-        if (tree_out) {
-            ktime_begin(ctx, "block_tree_entries", s);
-            launch_round_block_entries(r->tree_units, r->n_tree_units, r->n_tree_entries, r->plan.tile_cv, tree_out, s);
-            ktime_end(ctx, s);
-        }
+        if (tree_out)
+            timed(ctx, "block_tree_entries", s, [&] { launch_round_block_entries(r->tree_units, r->n_tree_units, r->n_tree_entries, r->plan.tile_cv, tree_out, s); });
     }
     HIPCHK(ctx, hipGetLastError());
     return ZNIPPY_OK;
@@ -3030,10 +3045,11 @@ int znippy_hash_rounds(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, uin
     if (!ctx || !r || r->ctx != ctx || !digests || (r->n && !d_src)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->n_ktimes = 0;
-    int rc = hash_rounds_async(ctx, r, d_src);
+    const ResSlab res = r->dev(r->slot);
+    int rc = hash_rounds_async(ctx, r, res, d_src);
     if (rc) return rc;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (r->n) HIPCHK(ctx, hipMemcpy(digests, r->digests, 32 * (size_t)r->n, hipMemcpyDeviceToHost));
+    if (r->n) HIPCHK(ctx, hipMemcpy(digests, res.digests(), 32 * (size_t)r->n, hipMemcpyDeviceToHost));
     return ZNIPPY_OK;
 }
 
@@ -3147,170 +3163,217 @@ static bool ensure_ldm(znippy_ctx *ctx, znippy_rounds *r) {
     return true;
 }
 
-extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out,
-                                               uint64_t blob_cap) {
-    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
-    if (!ctx || !r || r->ctx != ctx || (r->n && (!d_src || !d_blob_out))) return ZNIPPY_E_INVAL;
-    HIPCHK(ctx, hipSetDevice(ctx->device));
+// ---- one run of a rounds table: the plan (host/enc_plan.cc), then the stages in the order rounds_launch queues them ----------
+// what the caller gave a run, and what of the table is the run's own: its slot's slab and tree buffer, the alignment it was queued with
+struct EncRun { const void *d_src; void *d_blob_out; uint64_t blob_cap; unsigned slot; ResSlab res; uint32_t *tree_out; uint32_t align; const uint32_t *pad; };
+static_assert(ENC_HIGH_TIER_LEVEL == HIGH_TIER_LEVEL, "host/enc_plan.h restates the tier boundary of encode.h");
+
+static EncShape rounds_shape(const znippy_rounds *r) {
+    return EncShape{r->n, r->n_items, r->n_small, r->n_wide, r->in_bytes, r->enc_bytes, r->fuse_tiles, r->plan.n_tiles, r->n_tree_entries, r->ldm_entries,
+                    r->store_incompressible, r->emit_tree, r->blob_align};
+}
+static EncodeArgs rounds_encode_args(znippy_ctx *ctx, const znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    EncodeArgs a{};
+    a.items = r->items;
+    a.src = (const uint8_t *)run.d_src; a.src_off = r->src_off; a.len = r->len;
+    a.prov = ctx->enc_prov; a.seq_scratch = ctx->enc_seq;
+    a.piece_len = r->piece_len; a.piece_start = r->piece_start; a.tabs = ctx->enc_tabs;
+    a.high = p.high;
+    a.tail_mark = p.tail_mark;
+    a.window_log = p.window_log;
+    if (p.far) { a.ldm = ctx->ldm; a.ldm_desc = r->d_ldm_desc; }
+    if (ctx->sw.edbg)  // diagnostic: phase shares of the previous run's wide-variant blocks
+        a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_ENCODE, ctx->stream, nullptr, [](const unsigned long long *h) {
+            if (h[0]) fprintf(stderr, "[znippy edbg] wide blocks=%llu  cycles per block: setup=%.0f matching=%.0f literals=%.0f sequences=%.0f\n", h[0],
+                              (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0]);
+        });
+    return a;
+}
+static GatherArgs rounds_gather_args(znippy_ctx *ctx, const znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    GatherArgs g{};
+    g.items = r->items; g.n_pieces = r->n_items; g.piece_len = r->piece_len; g.piece_start = r->piece_start;
+    g.local_excl = r->local_excl; g.block_tot = r->block_tot; g.prov = ctx->enc_prov;
+    g.src = (const uint8_t *)run.d_src; g.src_off = r->src_off;
+    g.blob_out = (uint8_t *)run.d_blob_out; g.blob_cap = run.blob_cap;
+    g.blob_offset = run.res.blob_offset(); g.blob_size = run.res.blob_size(); g.total = run.res.total(); g.overflow = run.res.overflow();
+    g.stored = p.store_decide ? r->stored : nullptr;
+    g.skip_stored_copy = p.fuse_store ? 1 : 0;
+    g.pad = run.pad;
+    g.small_pieces = p.small_pieces ? 1 : 0;
+    return g;
+}
+
+static int enc_clear(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &, const EncRun &run) {
     hipStream_t s = ctx->stream;
-    ctx->n_ktimes = 0;
-    if (!r->n) return ZNIPPY_OK;
-    { const int rc0 = ensure_encoder(ctx); if (rc0) return rc0; }
-    const bool high = ctx->level >= HIGH_TIER_LEVEL;
-    const int window_log = high ? ctx->window_log : 0;  // (the fast tier keeps its frames)
-    const bool far = window_log && ensure_ldm(ctx, r);  // allocations before the first stream operation of the call
-    const uint32_t align = r->blob_align;  // this run's value: a later znippy_rounds_set_blob_align does not reach it
-    const uint32_t *const pad = align > 1 ? r->piece_pad : nullptr;
-    const bool emit_tree = r->emit_tree && !ctx->sw.nohash;  // this run's setting, as for the alignment (the diagnostic no-hash switch leaves nothing to make entries from)
-    if (r->prov_bytes + 64 > ctx->enc_prov_cap) {
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
-        ctx->enc_prov = nullptr; ctx->enc_prov_cap = 0;
-        HIPCHK(ctx, hipMalloc(&ctx->enc_prov, r->prov_bytes + 64));
-        ctx->enc_prov_cap = r->prov_bytes + 64;
-    }
-    const unsigned slot = (unsigned)(r->run_seq & 1);
-    rounds_select(r, slot);
-    r->tree_run[slot] = emit_tree;
-    uint32_t *const tree_out = emit_tree && r->n_tree_entries ? r->tree_m[slot] : nullptr;
-    if (r->run_seq >= 2) HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_res[slot], 0));  // the slab's previous results have left
-    HIPCHK(ctx, hipMemsetAsync(r->res, 0, 16 + 16 * (size_t)r->n, s));  // total, overflow, blob_offset, blob_size
+    if (r->run_seq >= 2) HIPCHK(ctx, hipStreamWaitEvent(s, r->ev_res[run.slot], 0));  // the slab's previous results have left
+    HIPCHK(ctx, hipMemsetAsync(run.res.base, 0, ResSlab::clear_bytes(r->n), s));  // total, overflow, blob_offset, blob_size
     HIPCHK(ctx, hipMemsetAsync(ctx->cursor, 0, 64, s));  // work cursors + (last word) the count of blocks handed to the wide variant
     // The fork comes AFTER the clears.  The hash kernel on the auxiliary stream starts at the fork and fills the chip; a
     // clear issued behind it is one tiny fill kernel that then waits ~100 us for its turn (kernel trace of the C2 write
     // step: two of them, 88 + 125 us, between the previous run's gather and this run's encoder).
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
-    EncodeArgs a{};
-    a.items = r->items;
-    a.src = (const uint8_t *)d_src; a.src_off = r->src_off; a.len = r->len;
-    a.prov = ctx->enc_prov; a.seq_scratch = ctx->enc_seq;
-    a.piece_len = r->piece_len; a.piece_start = r->piece_start; a.tabs = ctx->enc_tabs;
-    a.high = high;
-    a.tail_mark = high && !window_log;  // the empty closing block says every block stands alone: not with a window
-    a.window_log = window_log;
-    if (far) {
-        a.ldm = ctx->ldm; a.ldm_desc = r->d_ldm_desc;
-        ktime_begin(ctx, "ldm_index");
-        HIPCHK(ctx, hipMemsetAsync(ctx->ldm, 0xFF, 4 * r->ldm_entries, s));
-        launch_ldm_index(r->d_ldm, (uint32_t)r->h_ldm.size(), r->ldm_chunks, (const uint8_t *)d_src, r->src_off, r->len, ctx->ldm, s);
-        ktime_end(ctx);
+    return ZNIPPY_OK;
+}
+
+static int enc_far_index(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    if (!p.far) return ZNIPPY_OK;
+    ktime_begin(ctx, "ldm_index");
+    HIPCHK(ctx, hipMemsetAsync(ctx->ldm, 0xFF, 4 * r->ldm_entries, ctx->stream));
+    launch_ldm_index(r->d_ldm, (uint32_t)r->h_ldm.size(), r->ldm_chunks, (const uint8_t *)run.d_src, r->src_off, r->len, ctx->ldm, ctx->stream);
+    ktime_end(ctx);
+    return ZNIPPY_OK;
+}
+
+// the wide share first (its blocks are the long ones), the small share, then whatever the small variant handed over
+static void enc_blocks(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    hipStream_t s = ctx->stream;
+    EncodeArgs a = rounds_encode_args(ctx, r, p, run);
+    ktime_begin(ctx, p.fuse_hash ? "zstd_encode_hash" : "zstd_encode");
+    if (p.wide.on) {
+        a.n_items = p.wide.n_items; a.order = p.wide.use_order ? r->order_wide : nullptr;
+        a.cursor = ctx->cursor + 8; a.batch = p.wide.batch;
+        launch_encode(a, p.wide.grid, false, p.high, s);
     }
-    if (ctx->sw.edbg)  // diagnostic: phase shares of the previous run's wide-variant blocks
-        a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_ENCODE, s, nullptr, [](const unsigned long long *h) {
-            if (h[0]) fprintf(stderr, "[znippy edbg] wide blocks=%llu  cycles per block: setup=%.0f matching=%.0f literals=%.0f sequences=%.0f\n", h[0],
-                              (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0]);
-        });
-    // Tables of small encoded rounds only: the encoder's waves hash the rounds they are about to encode (EncodeArgs::fuse_tiles)
-    // (Block tree: fuse_tiles is only set for tables whose every round is one piece, at most one 128 KiB block — n_items == n,
-    // znippy_rounds_create — and a round of at most one block has no entries: such a table's tree is empty, and the entry kernel,
-    // which hash_rounds_async queues behind the merge of big units, has nothing to do on this route.)
-    const bool fuse_hash = r->fuse_tiles && !r->store_incompressible && !ctx->sw.nohash && !ctx->sw.no_fuse_hash;
-    ktime_begin(ctx, fuse_hash ? "zstd_encode_hash" : "zstd_encode");
-    for (int wide = 1; wide >= 0; wide--) {  // the wide share first: its blocks are the long ones
-        a.n_items = wide ? r->n_wide : r->n_small;
-        if (!a.n_items) continue;
-        a.order = a.n_items == r->n_items ? nullptr : (wide ? r->order_wide : r->order_small);  // all of one kind: no indirection
-        a.cursor = ctx->cursor + (wide ? 8 : 0);
-        const int g = wide ? ctx->encode_grid : ctx->encode_grid_small;
-        a.batch = std::max<uint32_t>(1, std::min<uint32_t>(16, a.n_items / (uint32_t)(g * 2)));
-        if (!wide) { a.retry_list = r->retry_list; a.retry_count = ctx->cursor + 15; }
-        int grid = std::min<int>(g, (int)a.n_items);
-        if (!wide && fuse_hash) {
-            a.fuse_tiles = r->fuse_tiles;
-            a.h = HashArgs{};
-            a.h.tiles = r->plan.tiles; a.h.n_tiles = r->plan.n_tiles;
-            a.h.len = r->len;
-            a.h.srcA = (const uint8_t *)d_src; a.h.offA = r->src_off; a.h.baseA = 0;
-            a.h.digests = r->digests; a.h.tile_cv = r->plan.tile_cv;
-            grid = std::min<int>(g, (int)((r->plan.n_tiles + r->fuse_tiles - 1) / r->fuse_tiles));
-        }
-        launch_encode(a, grid, !wide, high, s);
+    if (p.small.on) {
+        a.n_items = p.small.n_items; a.order = p.small.use_order ? r->order_small : nullptr;
+        a.cursor = ctx->cursor; a.batch = p.small.batch;
+        a.retry_list = r->retry_list; a.retry_count = ctx->cursor + 15;
+        if (p.fuse_hash) { a.fuse_tiles = r->fuse_tiles; a.h = rounds_hash_args(r, run.res, run.d_src); }
+        launch_encode(a, p.small.grid, true, p.high, s);
         a.fuse_tiles = 0;
     }
-    if (r->n_small) {  // second wide launch: whatever the small variant handed over (count on the device)
-        a.order = r->retry_list; a.n_items = r->n_small; a.n_items_dev = ctx->cursor + 15;
+    if (p.retry.on) {
+        a.order = r->retry_list; a.n_items = p.retry.n_items; a.n_items_dev = ctx->cursor + 15;
         a.retry_list = nullptr; a.retry_count = nullptr;
-        a.cursor = ctx->cursor + 12;
-        a.batch = 1;
-        launch_encode(a, std::min<int>(ctx->encode_grid, (int)r->n_small), false, high, s);
+        a.cursor = ctx->cursor + 12; a.batch = p.retry.batch;
+        launch_encode(a, p.retry.grid, false, p.high, s);
     }
     ktime_end(ctx);
-    // checksum over the ORIGINAL bytes (stream_packer.rs:L219): VALU-bound, submitted to the
-    // auxiliary stream right after the persistent (latency-bound) encoder so both share the CUs
-    // Store-heavy table (most bytes are skip rounds): hashing and copying the stored bytes are one pass over them once
-    // their blob offsets are known — scan and gather run first (the gather leaves the stored pieces alone), then the
-    // hash kernel copies what it hashes.  Otherwise the hash runs beside the encoder on the auxiliary stream.
-    // (Blobs are packed without gaps by default, so behind a compressed round the offsets are odd: unless every round is
-    // stored and every length a multiple of 16 — or the table asks for blob offsets aligned to 16 bytes or more — the
-    // launch uses the kernel variant that re-cuts the bytes to 16-byte boundaries on their way out: plain 16-byte stores
-    // at odd addresses cost more than the pass they save.)
-    const bool heavy = r->in_bytes && (r->in_bytes - r->enc_bytes) * 2 >= r->in_bytes;
-    const bool fuse_store = heavy && !r->store_incompressible &&
-                            !ctx->sw.no_fused_store && !ctx->sw.nohash;
-    int rc = ZNIPPY_OK;
-    if (!fuse_store && !fuse_hash) {
-        HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
-        rc = ctx->sw.nohash ? ZNIPPY_OK : hash_rounds_async(ctx, r, d_src, ctx->aux, nullptr, 0, 1, tree_out);  // diagnostic switch
-        if (rc) return rc;
-        HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
-    }
-    if (r->store_incompressible) {
-        ktime_begin(ctx, "store_decide");
-        launch_store_decide(r->first_item, r->items, r->len, r->skip, r->n, r->piece_len, r->stored, s);
-        ktime_end(ctx);
-    }
-    if (pad) {
-        ktime_begin(ctx, "round_pad");
-        launch_round_pad(r->first_item, r->items, r->len, r->skip, r->store_incompressible ? r->stored : nullptr, r->n, r->piece_len, align,
-                         r->piece_pad, s);
-        ktime_end(ctx);
-    }
-    ktime_begin(ctx, "piece_scan");
-    launch_piece_scan(r->piece_len, pad, r->n_items, r->local_excl, r->block_tot, s);
-    ktime_end(ctx);
-    GatherArgs g{};
-    g.items = r->items; g.n_pieces = r->n_items; g.piece_len = r->piece_len; g.piece_start = r->piece_start;
-    g.local_excl = r->local_excl; g.block_tot = r->block_tot; g.prov = ctx->enc_prov;
-    g.src = (const uint8_t *)d_src; g.src_off = r->src_off;
-    g.blob_out = (uint8_t *)d_blob_out; g.blob_cap = blob_cap;
-    g.blob_offset = r->blob_offset; g.blob_size = r->blob_size; g.total = r->total; g.overflow = r->overflow;
-    g.stored = r->store_incompressible ? r->stored : nullptr;
-    g.skip_stored_copy = fuse_store ? 1 : 0;
-    g.pad = pad;
-    // lane-per-piece gather (64 consecutive pieces per wave): only for tables without blocks above 16 KiB — the consecutive
-    // blocks of one big round land in one wave, which then copies them one after the other (a table of 4,900 text files, a
-    // few of them above 1 MiB: 0.29 ms against 0.03 for a wave per piece).  Store-heavy table: the stored rounds' 64 KiB
-    // slices are not copied here (the hash kernel does it) — only their bookkeeping is left, a lane's work.
-    g.small_pieces = r->n_items && r->n_wide == 0 && (fuse_store || r->in_bytes / r->n_items <= 16384) ? 1 : 0;
-    ktime_begin(ctx, "gather");
-    launch_gather(g, s);
-    ktime_end(ctx);
-    if (fuse_store) {
-        rc = hash_rounds_async(ctx, r, d_src, nullptr, d_blob_out, blob_cap, align, tree_out);
-        if (rc) return rc;
-    } else if (!fuse_hash) {
-        HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));  // digests are complete once the main stream drains
-    }
-    // the results leave on the copy stream (one DMA into the slot's pinned mirror) while the main stream is free for
-    // the next run
-    HIPCHK(ctx, hipEventRecord(r->ev_enc[slot], s));
-    HIPCHK(ctx, hipStreamWaitEvent(ctx->copy, r->ev_enc[slot], 0));
-    {
-        const uint32_t n16 = (uint32_t)((r->res_bytes + 15) / 16);  // both buffers are allocated in whole 16-byte units and more
-        // few workgroups: the copy only has to be done before the next run but one needs the slab, and it shares the chip with
-        // the next run's kernels (4-16 workgroups: 0.84 ms per C2 write step, 64: 0.88, 1,024: 0.90)
-        hipLaunchKernelGGL(k_results_out, dim3(std::min<uint32_t>((n16 + 255) / 256, 8)), dim3(256), 0, ctx->copy,
-                           reinterpret_cast<uint4 *>(r->h_res), reinterpret_cast<const uint4 *>(r->res), n16);
-        if (tree_out) {  // the tree leaves with the results, in front of ev_res: the slab-reuse wait covers its buffer too
-            const uint32_t t16 = 2 * r->n_tree_entries;
-            hipLaunchKernelGGL(k_results_out, dim3(std::min<uint32_t>((t16 + 255) / 256, 8)), dim3(256), 0, ctx->copy,
-                               reinterpret_cast<uint4 *>(r->h_tree_m[slot]), reinterpret_cast<const uint4 *>(tree_out), t16);
-        }
-    }
-    HIPCHK(ctx, hipEventRecord(r->ev_res[slot], ctx->copy));
-    r->run_seq++;
-    HIPCHK(ctx, hipGetLastError());
+}
+
+static int enc_hash_beside(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    if (!p.fork_aux) return ZNIPPY_OK;
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
+    const int rc = p.hash_beside ? hash_rounds_async(ctx, r, run.res, run.d_src, ctx->aux, nullptr, 0, 1, run.tree_out) : ZNIPPY_OK;
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
     return ZNIPPY_OK;
+}
+
+// where every piece goes: the opt-in passes that change lengths, then the scan
+static void enc_layout(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    hipStream_t s = ctx->stream;
+    if (p.store_decide)
+        timed(ctx, "store_decide", s, [&] { launch_store_decide(r->first_item, r->items, r->len, r->skip, r->n, r->piece_len, r->stored, s); });
+    if (p.pad)
+        timed(ctx, "round_pad", s, [&] {
+            launch_round_pad(r->first_item, r->items, r->len, r->skip, p.store_decide ? r->stored : nullptr, r->n, r->piece_len, run.align, r->piece_pad, s);
+        });
+    timed(ctx, "piece_scan", s, [&] { launch_piece_scan(r->piece_len, run.pad, r->n_items, r->local_excl, r->block_tot, s); });
+}
+
+static void enc_gather(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    const GatherArgs g = rounds_gather_args(ctx, r, p, run);
+    timed(ctx, "gather", ctx->stream, [&] { launch_gather(g, ctx->stream); });
+}
+
+// the fused-store hash behind the gather, or the join of the hash beside
+static int enc_hash_store(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &p, const EncRun &run) {
+    if (p.fuse_store) return hash_rounds_async(ctx, r, run.res, run.d_src, nullptr, run.d_blob_out, run.blob_cap, run.align, run.tree_out);
+    if (p.fork_aux) HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));  // digests are complete once the main stream drains
+    return ZNIPPY_OK;
+}
+
+// the results leave on the copy stream (into the slot's pinned mirror) while the main stream is free for the next run
+static int enc_results_out(znippy_ctx *ctx, znippy_rounds *r, const EncPlan &, const EncRun &run) {
+    HIPCHK(ctx, hipEventRecord(r->ev_enc[run.slot], ctx->stream));
+    HIPCHK(ctx, hipStreamWaitEvent(ctx->copy, r->ev_enc[run.slot], 0));
+    const uint32_t n16 = (uint32_t)((r->res_bytes + 15) / 16);  // both buffers are allocated in whole 16-byte units and more
+    // few workgroups: the copy only has to be done before the next run but one needs the slab, and it shares the chip with
+    // the next run's kernels (4-16 workgroups: 0.84 ms per C2 write step, 64: 0.88, 1,024: 0.90)
+    hipLaunchKernelGGL(k_results_out, dim3(std::min<uint32_t>((n16 + 255) / 256, 8)), dim3(256), 0, ctx->copy,
+                       reinterpret_cast<uint4 *>(r->h_res_m[run.slot]), reinterpret_cast<const uint4 *>(run.res.base), n16);
+    if (run.tree_out) {  // the tree leaves with the results, in front of ev_res: the slab-reuse wait covers its buffer too
+        const uint32_t t16 = 2 * r->n_tree_entries;
+        hipLaunchKernelGGL(k_results_out, dim3(std::min<uint32_t>((t16 + 255) / 256, 8)), dim3(256), 0, ctx->copy,
+                           reinterpret_cast<uint4 *>(r->h_tree_m[run.slot]), reinterpret_cast<const uint4 *>(run.tree_out), t16);
+    }
+    HIPCHK(ctx, hipEventRecord(r->ev_res[run.slot], ctx->copy));
+    return ZNIPPY_OK;
+}
+
+// Queues one run of the table into slot `slot`.  Every allocation the run needs is made before its first stream operation
+// (*queued): an error return after that point is a HIP runtime error, which the caller turns into a table whose latest run is
+// still the one before (rounds_abandon).  Only a run queued to its end enters the table's books.
+static int rounds_launch(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out, uint64_t blob_cap, unsigned slot, bool *queued) {
+    ctx->n_ktimes = 0;
+    if (!r->n) return ZNIPPY_OK;
+    int rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    EncEnv env{ctx->level, ctx->window_log, ctx->encode_grid, ctx->encode_grid_small, (bool)ctx->sw.nohash, (bool)ctx->sw.no_fuse_hash, (bool)ctx->sw.no_fused_store, false};
+    env.ldm_ok = enc_window_log(env) && ensure_ldm(ctx, r);
+    if (r->prov_bytes + 64 > ctx->enc_prov_cap) {
+        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+        if (ctx->enc_prov) (void)hipFree(ctx->enc_prov);
+        ctx->enc_prov = nullptr; ctx->enc_prov_cap = 0;
+        HIPCHK(ctx, hipMalloc(&ctx->enc_prov, r->prov_bytes + 64));
+        ctx->enc_prov_cap = r->prov_bytes + 64;
+    }
+    const EncPlan p = enc_plan(rounds_shape(r), env);
+    // the alignment and the tree switch are this run's values: a later znippy_rounds_set_blob_align / _emit_block_tree does not reach it
+    const EncRun run{d_src, d_blob_out, blob_cap, slot, r->dev(slot), p.tree_out ? r->tree_m[slot] : nullptr, r->blob_align, p.pad ? r->piece_pad : nullptr};
+    *queued = true;
+    if ((rc = enc_clear(ctx, r, p, run)) || (rc = enc_far_index(ctx, r, p, run))) return rc;
+    enc_blocks(ctx, r, p, run);
+    if ((rc = enc_hash_beside(ctx, r, p, run))) return rc;
+    enc_layout(ctx, r, p, run);
+    enc_gather(ctx, r, p, run);
+    if ((rc = enc_hash_store(ctx, r, p, run)) || (rc = enc_results_out(ctx, r, p, run))) return rc;
+    HIPCHK(ctx, hipGetLastError());
+    r->tree_run[slot] = p.emit_tree;
+    r->slot = slot;
+    r->run_seq++;
+    return ZNIPPY_OK;
+}
+
+// A run that failed after its first stream operation: the auxiliary stream is joined back into the main one, the copy stream
+// gets behind the run's end if that was recorded (a wait for an event never recorded is none), everything is waited for and
+// the sticky error cleared.  The table's books are as before the call; the failed run's slot — the run before last — may hold
+// a part of it.
+static void rounds_abandon(znippy_ctx *ctx, znippy_rounds *r, unsigned slot) {
+    if (hipEventRecord(ctx->ev_join, ctx->aux) == hipSuccess) (void)hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0);
+    (void)hipStreamWaitEvent(ctx->copy, r->ev_enc[slot], 0);
+    (void)hipStreamSynchronize(ctx->stream);
+    (void)hipStreamSynchronize(ctx->copy);
+    (void)hipGetLastError();
+}
+static int rounds_queue(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out, uint64_t blob_cap) {
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    const unsigned slot = (unsigned)(r->run_seq & 1);
+    bool queued = false;
+    const int rc = rounds_launch(ctx, r, d_src, d_blob_out, blob_cap, slot, &queued);
+    if (rc && queued) rounds_abandon(ctx, r, slot);
+    return rc;
+}
+
+extern "C" int znippy_encode_hash_rounds_async(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out,
+                                               uint64_t blob_cap) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || !r || r->ctx != ctx || (r->n && (!d_src || !d_blob_out))) return ZNIPPY_E_INVAL;
+    return rounds_queue(ctx, r, d_src, d_blob_out, blob_cap);
+}
+
+// The header of a finished run's mirror: the blob bytes, or ZNIPPY_E_DST_SMALL when the run ran out of blob_cap.
+static int res_header(const ResSlab &h, uint64_t *total) {
+    uint32_t ovf;
+    memcpy(total, h.total(), 8);
+    memcpy(&ovf, h.overflow(), 4);
+    return ovf ? ZNIPPY_E_DST_SMALL : ZNIPPY_OK;
+}
+static void res_view(const ResSlab &h, const uint64_t **blob_offset, const uint64_t **blob_size, const uint8_t **checksum) {
+    if (blob_offset) *blob_offset = h.blob_offset();
+    if (blob_size) *blob_size = h.blob_size();
+    if (checksum) *checksum = reinterpret_cast<const uint8_t *>(h.digests());
 }
 
 // Results of the run `lag` runs before the latest one (0 or 1) as pointers into that run's pinned mirror; waits for
@@ -3322,16 +3385,10 @@ extern "C" int znippy_rounds_results_lagged(znippy_ctx *ctx, znippy_rounds *r, u
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const unsigned slot = (unsigned)((r->run_seq - 1 - lag) & 1);
     HIPCHK(ctx, hipEventSynchronize(r->ev_res[slot]));
-    const uint8_t *h = r->h_res_m[slot];
     uint64_t total;
-    uint32_t ovf;
-    memcpy(&total, h, 8);
-    memcpy(&ovf, h + 8, 4);
-    if (ovf) return ZNIPPY_E_DST_SMALL;
-    const size_t n = r->n;
-    if (blob_offset) *blob_offset = reinterpret_cast<const uint64_t *>(h + 16);
-    if (blob_size) *blob_size = reinterpret_cast<const uint64_t *>(h + 16 + 8 * n);
-    if (checksum) *checksum = h + 16 + 16 * n;
+    const int rc = res_header(r->host(slot), &total);
+    if (rc) return rc;
+    res_view(r->host(slot), blob_offset, blob_size, checksum);
     if (blob_bytes) *blob_bytes = total;
     return ZNIPPY_OK;
 }
@@ -3344,20 +3401,19 @@ extern "C" int znippy_rounds_results(znippy_ctx *ctx, znippy_rounds *r, uint64_t
     if (blob_bytes) *blob_bytes = 0;
     if (!r->n) return ZNIPPY_OK;
     if (!r->run_seq) return ZNIPPY_E_INVAL;  // nothing has been encoded on this table yet
-    HIPCHK(ctx, hipEventSynchronize(r->ev_res[(r->run_seq - 1) & 1]));  // the latest run's results have arrived
+    HIPCHK(ctx, hipEventSynchronize(r->ev_res[r->slot]));  // the latest run's results have arrived
     if (r->store_incompressible) {
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         HIPCHK(ctx, hipMemcpy(r->h_stored, r->stored, r->n, hipMemcpyDeviceToHost));
     }
+    const ResSlab h = r->host(r->slot);
     uint64_t total;
-    uint32_t ovf;
-    memcpy(&total, r->h_res, 8);
-    memcpy(&ovf, r->h_res + 8, 4);
-    if (ovf) return ZNIPPY_E_DST_SMALL;
+    const int rc = res_header(h, &total);
+    if (rc) return rc;
     const size_t n = r->n;
-    if (blob_offset) memcpy(blob_offset, r->h_res + 16, 8 * n);
-    if (blob_size) memcpy(blob_size, r->h_res + 16 + 8 * n, 8 * n);
-    if (checksum) memcpy(checksum, r->h_res + 16 + 16 * n, 32 * n);
+    if (blob_offset) memcpy(blob_offset, h.blob_offset(), 8 * n);
+    if (blob_size) memcpy(blob_size, h.blob_size(), 8 * n);
+    if (checksum) memcpy(checksum, h.digests(), 32 * n);
     if (compressed)
         for (uint32_t i = 0; i < r->n; i++)
             compressed[i] = ((!r->h_skip.empty() && r->h_skip[i]) || (r->store_incompressible && r->h_stored[i])) ? 0 : 1;
@@ -3372,10 +3428,7 @@ extern "C" int znippy_rounds_results_view(znippy_ctx *ctx, znippy_rounds *r, con
     if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     int rc = znippy_rounds_results(ctx, r, nullptr, nullptr, nullptr, nullptr, blob_bytes);
     if (rc) return rc;
-    const size_t n = r->n;
-    if (blob_offset) *blob_offset = reinterpret_cast<const uint64_t *>(r->h_res + 16);
-    if (blob_size) *blob_size = reinterpret_cast<const uint64_t *>(r->h_res + 16 + 8 * n);
-    if (checksum) *checksum = r->h_res + 16 + 16 * n;
+    res_view(r->host(r->slot), blob_offset, blob_size, checksum);
     return ZNIPPY_OK;
 }
 
