@@ -8,7 +8,8 @@ its HIP events, and step minus that kernel — except on a side whose runs went 
 and the kernel's time includes its wait for CUs the run in front still holds: there the step alone counts, and the line says so
 (with the context's lane counters).  c2 is the headline
 table (100k x 10 KiB, libzstd -19 frames); the other workloads are this build's own archives and are there to show that nothing
-gets slower: each side must stay within the other build's A/A spread.
+gets slower: each side must stay within the other build's A/A spread.  Table build time (create + the stream drained, median of
+the rounds, the sides taking turns) is printed per side under the same rule.
 
 A side's place in the order in which contexts and tables are created moves its step by a few tenths of a percent on the big
 workloads (four sides of one build: 0.5 % on c5); `this_first` as the fourth argument creates this build's sides in front of the
@@ -94,6 +95,16 @@ for name in names:
     for j in made:
         rts[j] = hip.RowTable(ctxs[j], A["bo"], A["bs"], A["us"], oo, bitmap, A["ck"])
     d_out = torch.zeros(total + 64, dtype=torch.uint8, device="cuda")
+    build = [[] for _ in ctxs]  # table build time: create + the context's stream drained, the sides taking turns
+    for i in range(rounds + 2):
+        for j in [(i + k) % len(ctxs) for k in range(len(ctxs))]:
+            ctxs[j].sync()
+            t0 = time.perf_counter()
+            tmp = hip.RowTable(ctxs[j], A["bo"], A["bs"], A["us"], oo, bitmap, A["ck"])
+            ctxs[j].sync()
+            if i >= 2:
+                build[j].append((time.perf_counter() - t0) * 1e3)
+            tmp.close()
     level = 1 if name in ("c2", "c2small") else 2  # as bench.py's timed region
     t = [[] for _ in ctxs]
     main = [[] for _ in ctxs]
@@ -137,6 +148,12 @@ for name in names:
             print(f"  {side:15s} step {med[j]:.4f} ms   main kernel {mk[j]:.4f} ms INCLUDING its wait on the lane   lanes {lanes}{verdict}")
         else:
             print(f"  {side:15s} step {med[j]:.4f} ms   main kernel {mk[j]:.4f} ms   step - main kernel {(med[j] - mk[j]) * 1e3:6.1f} us{verdict}")
+    bm = [float(np.median(x)) for x in build]
+    bspread = abs(bm[0] / bm[1] - 1.0)
+    for j, (side, _) in enumerate(SIDES):
+        slower = j >= 2 and bm[j] > max(bm[0], bm[1]) * (1.0 + bspread)
+        ok_all &= not slower
+        print(f"  {side:15s} table_build_ms {bm[j]:.4f}" + (f"  (A/A spread of the other build {bspread * 100:.2f} %)" if j == 1 else "") + ("  SLOWER than its margin" if slower else ""))
     for j in (0, 2):
         print(f"  kernels of {SIDES[j][0]}: " + "  ".join(f"{k} {v:.4f}" for k, v in kall[j].items()))
     for r in rts:

@@ -7,6 +7,7 @@
 #include "../../include/znippy_hip.h"
 #include "host/enc_plan.h"
 #include "host/range_plan.h"
+#include "host/rows_plan.h"
 #include "host/run_overlap.h"
 
 #include <algorithm>
@@ -47,6 +48,7 @@ extern "C" int zn_rows_pack32(const uint64_t *bo, const uint64_t *bs, const uint
     try { return (call); } catch (const std::bad_alloc &) { return ZNIPPY_E_NOMEM; } catch (const std::length_error &) { return ZNIPPY_E_NOMEM; }
 static_assert(RP_OK == ZNIPPY_OK && RP_E_INVAL == ZNIPPY_E_INVAL && RP_E_NOMEM == ZNIPPY_E_NOMEM && RP_E_DST_SMALL == ZNIPPY_E_DST_SMALL &&
               RP_E_CORRUPT == ZNIPPY_E_CORRUPT && RP_E_DIGEST == ZNIPPY_E_DIGEST, "host/range_plan.h gives out the codes of znippy_hip.h");
+static_assert(RowsSwitches{}.bx_big == BX_BIG_SEQ, "host/rows_plan.h: the default of ZNIPPY_BX_BIG");
 
 // diagnostic (ZNIPPY_TDBG): wall time of the sections of a table constructor
 struct TDbg {
@@ -136,17 +138,10 @@ struct znippy_ctx {
     size_t dev_pool_bytes = 0;
     // diagnostic switches (ZNIPPY_* environment), read ONCE when the context is created: nothing on the hot path
     // calls getenv
-    struct {
-        int dbg = 0;             // ZNIPPY_DBG bit set (FusedArgs::dbg)
+    struct : RowsSwitches {  // (the ones the read side's plan goes by: host/rows_plan.h)
         unsigned lds_pad = 0;    // ZNIPPY_LDS_PAD
         int store_g = 0;         // ZNIPPY_STORE_G: tiles per wave of the store path kernel (0 = from the tile count)
-        bool no_block_items = false, no_fused_blocks = false, ddbg = false, edbg = false, no_fused_store = false,
-             no_fork_verify = false, no_run_lanes = false, nohash = false, no_roles = false, no_fz = false, fz_only = false, no_bx = false, tdbg = false, no_fuse_hash = false, trace = false, no_rx = false, no_pack = false, no_lean = false, no_stored_only = false;
-        // ZNIPPY_ROLES_MIN: small tiles from which the role-split persistent kernel takes the table (0 = never; below
-        // a few CU-fillings a persistent grid only adds start-up latency)
-        unsigned roles_min = 2048;
-        unsigned bx_big = BX_BIG_SEQ;  // ZNIPPY_BX_BIG
-        bool bx_big_set = false;
+        bool edbg = false, no_fused_store = false, no_fork_verify = false, no_run_lanes = false, nohash = false, fz_only = false, tdbg = false, no_fuse_hash = false, trace = false, no_pack = false;
         int ktime = 2;  // per-kernel HIP events: 2 = every kernel, 1 = the dominant read kernels only, 0 = none
     } sw;
     int cus = 256;
@@ -342,70 +337,6 @@ struct SyncFree {
     }
 };
 
-struct PlanBuf {
-    std::vector<Tile> tiles;
-    std::vector<BigUnit> big;
-    uint32_t n_tile_cv = 0;
-    // units with more than 64 tile CVs: their CVs are first folded in groups of 64 by independent waves
-    // (group g of big unit b: grp_big[g] = b, first CV = big[b].cv_base + 64 * grp_k[g]); results live behind the
-    // tile CVs, from BigUnit::pad on
-    std::vector<uint32_t> grp_big, grp_k;
-};
-
-// Greedy tile plan over unit lengths: whole small units are packed until a wave's 64 lanes are
-// full; a unit with more than 64 leaves becomes ceil(leaves/64) slice tiles + one BigUnit.
-template <class LenOf>
-static void build_plan(LenOf len_of, uint32_t n, PlanBuf &p) {
-    p.tiles.reserve((size_t)n / 4 + 16);
-    uint32_t cur_first = 0, cur_units = 0, cur_leaves = 0;
-    auto flush = [&]() {
-        if (cur_units) p.tiles.push_back(Tile{cur_first, cur_units, 0, cur_leaves, 0, 0});
-        cur_units = 0;
-        cur_leaves = 0;
-    };
-    for (uint32_t u = 0; u < n; u++) {
-        const uint64_t len_u = len_of(u);
-        uint64_t leaves64 = len_u ? (len_u + 1023) >> 10 : 1;
-        if (leaves64 > 64) {
-            flush();
-            uint32_t n_cvs = (uint32_t)((leaves64 + 63) / 64);
-            p.big.push_back(BigUnit{u, p.n_tile_cv, n_cvs, 0});
-            if (n_cvs > 64)
-                for (uint32_t g = 0; g < (n_cvs + 63) / 64; g++) { p.grp_big.push_back((uint32_t)p.big.size() - 1); p.grp_k.push_back(g); }
-            for (uint32_t t = 0; t < n_cvs; t++) {
-                uint32_t first = t * 64;
-                uint32_t nl = (uint32_t)std::min<uint64_t>(64, leaves64 - first);
-                p.tiles.push_back(Tile{u, 0, first, nl, p.n_tile_cv + t, 0});
-            }
-            p.n_tile_cv += n_cvs;
-        } else {
-            uint32_t leaves = (uint32_t)leaves64;
-            if (cur_units == 64 || cur_leaves + leaves > 64) flush();
-            if (!cur_units) cur_first = u;
-            cur_units++;
-            cur_leaves += leaves;
-            // a run of units of this same size (archives of fixed-size chunks: every BASELINE config): whole tiles at once —
-            // exactly the tiles the unit-by-unit rule above would cut
-            if (cur_units == 1 && u + 1 < n && len_of(u + 1) == len_u) {
-                uint32_t v = u + 1;
-                while (v < n && len_of(v) == len_u) v++;
-                const uint32_t per = std::min<uint32_t>(64 / leaves, 64), run = v - u, full = run / per;
-                if (full >= 1) {
-                    for (uint32_t t = 0; t < full; t++) p.tiles.push_back(Tile{u + t * per, per, 0, per * leaves, 0, 0});
-                    cur_units = 0; cur_leaves = 0;
-                    const uint32_t rest = run - full * per;
-                    if (rest) { cur_first = u + full * per; cur_units = rest; cur_leaves = rest * leaves; }
-                    u = v - 1;
-                }
-            }
-        }
-    }
-    flush();
-    uint32_t gb = 0;  // where each grouped unit's group CVs start (behind all tile CVs)
-    for (BigUnit &b : p.big)
-        if (b.n_cvs > 64) { b.pad = p.n_tile_cv + gb; gb += (b.n_cvs + 63) / 64; }
-}
-
 struct DevPlan {
     Tile *tiles = nullptr;
     BigUnit *big = nullptr;
@@ -419,8 +350,7 @@ struct DevPlan {
 static int upload_plan(znippy_ctx *ctx, const PlanBuf &p, DevPlan &d) {
     d.n_tiles = (uint32_t)p.tiles.size();
     d.n_big = (uint32_t)p.big.size();
-    d.max_cvs = 0;
-    for (const BigUnit &b : p.big) d.max_cvs = std::max(d.max_cvs, b.n_cvs);
+    d.max_cvs = plan_max_cvs(p);
     if (d.n_tiles) {
         HIPCHK(ctx, tmalloc(ctx, &d.tiles, sizeof(Tile) * d.n_tiles));
         HIPCHK(ctx, hipMemcpy(d.tiles, p.tiles.data(), sizeof(Tile) * d.n_tiles, hipMemcpyHostToDevice));
@@ -483,8 +413,8 @@ static_assert(CTL_FLAG < 8 && H_FLAGGED == H_SERIAL + 4 && H_FLAGGED < 8 && CUR_
 struct znippy_rows {
     znippy_ctx *ctx = nullptr;
     uint64_t row_begin = 0;
-    uint32_t n = 0;
-    uint32_t n_compressed = 0;
+    RowsShape shape;  // what creation learnt about the rows (host/rows_plan.h: rows_classify)
+    RowsHints hints;  // what the last finished run and the host's validation left (rows_note_hint, rows_validate)
     uint64_t *blob_off = nullptr, *blob_size = nullptr, *usize = nullptr, *out_off = nullptr;
     uint8_t *compressed = nullptr, *checksum = nullptr, *d_bitmap = nullptr;
     uint32_t *h_pack = nullptr, *d_pack = nullptr;  // front-to-back tables: the two size columns as 32-bit values (page-locked / device)
@@ -516,31 +446,12 @@ struct znippy_rows {
     // pinned mirror of the counters, filled by the run's own D2H copy.  Two slots + one event each: run k uses slot
     // k & 1, so the counters of run k can be read while run k + 1 is already executing (znippy_rows_results_lagged)
     uint64_t *h_counters = nullptr;  // per slot CTL_MIRROR bytes (16 x u64): the counters, then the 16 hand-over counts (u32)
-    const uint32_t *mirror_hand(unsigned slot) const { return reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(h_counters + 16 * slot) + CTL_HAND.at); }
+    HandCounts mirror_hand(unsigned slot) const {  // the hand-over counts a finished run left in its mirror slot
+        const uint32_t *left = reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(h_counters + 16 * slot) + CTL_HAND.at);
+        return HandCounts{left[H_FUSED], left[H_SERIAL], left[H_FLAGGED], left[H_TILES], left[H_ITEMS]};
+    }
     size_t h_counters_cap = 0;
-    // Does the batch path have anything to do?  Its six launches cost ~0.1 ms even when every list is empty (the BASELINE
-    // archives: every row is taken by the fused kernels), so a table remembers what its last finished run found: -1 not
-    // known yet (launch it), 0 nothing handed over (the serial decoder alone stands behind the fused kernels, as a
-    // safety net), 1 something was.
-    int bx_hint = -1;
-    // Lean runs.  A table of small rows whose last finished run left nothing behind the role-split kernel — no tile on its
-    // list, no row handed over — is run as memset + that kernel + verify: the three launches behind it (left-over tiles,
-    // serial decoder, second hash pass) cost ~25 us of a 0.5 ms step for looking at empty lists.  The verify kernel checks
-    // the lists; if this run did leave something (the blobs changed), its counters come back flagged and whoever reads the
-    // run's results first runs it again in full (rows_settle) — same inputs, the results the caller would have had.
-    bool lean_ok = false;      // the table's shape allows it (set at creation)
-    int lean_hint = -1;        // last finished run: 1 nothing left behind the roles kernel, 0 something was, -1 not known
-    bool lean_blocks_ok = false;  // the same for tables of big multi-block rows only (the fused block kernel in front)
-    bool lean_mixed_ok = false;   // small rows beside big stored / hashed units: the small rows' kernel beside the second hash pass
-    bool roles_off = false;       // a run of the role-split kernel left every tile on its list (rows of no shape it takes: 0.15 ms of looking)
-    bool small_ok = false, small_off = false;  // the fused kernels handed over every row: later runs skip them (all_rows = the batch path's list)
-    uint32_t *all_rows = nullptr;
-    int lean_hint2 = -1;
-    // Decode-only runs neither use up nor update the hints above (they cannot be flagged, so nothing they skip may be something a row
-    // needs).  What they do keep is their own answer to bx_hint's question — did the last finished decode-only run hand anything to the
-    // decoders behind the store kernels? — which only ROUTES the undecoded frames (batch path, or the serial decoders alone, which take
-    // whatever is handed over): a wrong answer costs time, never a row.  -1: not known (the table's bx_hint is consulted)
-    int plain_hint = -1;
+    uint32_t *all_rows = nullptr;  // RowsHints::small_off: the batch path's list of every row (made by the first run that needs it)
     struct RunArgs { const void *blobs = nullptr; void *out = nullptr; uint64_t base = 0, cap = 0, blob_cap = ~0ull; bool verify = false, plain = false; } run_args[2];  // per mirror slot: what the run was given, and its kind (plain: decode-only)
     // verify-only runs: the second output column — a 16-byte aligned slot in the context's scratch for every compressed row with bytes
     // (stored rows and empty rows: none) — built on the device at the table's first verify run; vs_bytes = the slots' extent
@@ -553,10 +464,8 @@ struct znippy_rows {
     // Host copies of the columns a run is validated against (one pass per distinct (blob_base, blob_cap, out_cap)):
     // a row whose blob lies outside the blob region, or whose bytes would land outside the output region, gets its
     // status from the host (status_init) and no kernel touches it — a crafted index is an error code, not a fault.
-    // extents of the table's rows (one pass at creation): a run whose regions contain them has no bad row; otherwise the
-    // columns come back from the device for the per-row pass (h_*: filled then)
-    uint64_t ext_min_bo = 0, ext_max_bend = 0, ext_max_oend = 0;
-    bool ext_wrap = false;
+    // A run whose regions contain the table's extents has no bad row; otherwise the columns come back from the device for
+    // the per-row pass (h_*: filled then)
     std::vector<uint64_t> h_blob_off, h_blob_size, h_len, h_out_off;
     std::vector<uint8_t> h_comp;  // range reads: the byte-per-row flags beside the three columns above (rows_host_columns)
     uint64_t blob_cap = ~0ull;  // size of the caller's blob region (znippy_rows_set_blob_cap); ~0 = not declared
@@ -568,47 +477,28 @@ struct znippy_rows {
     std::vector<uint8_t> h_checksum;
     uint64_t val_base = 0, val_bcap = 0, val_ocap = 0;
     bool val_done = false, val_verify = false;
-    uint32_t n_bad = 0;
-    bool force_full = false;  // a lean run came back flagged: this table runs in full from now on
     uint8_t *status_init = nullptr;  // image of ctl with the host-decided statuses (rows_validate)
-    bool odd_out = false;  // some stored row's output offset is not a multiple of 16 (store-path kernel variant)
     uint64_t *corrupt = nullptr;
     uint32_t corrupt_cap = 0;
     uint32_t *list_a = nullptr;   // compressed rows with > 64 leaves: general decoder
-    uint32_t n_list_a = 0;
-    bool wide_rows = false;       // big rows average >= 1 MiB: 1024-thread workgroups
     uint32_t *pending = nullptr;  // rows the fused kernel hands over (count: H_FUSED)
     // block items: compressed rows of >= 2 blocks are tried block by block first
-    uint32_t n_cand = 0, n_items = 0;
     uint32_t *cand_row = nullptr, *cand_base = nullptr, *cand_nblocks = nullptr, *pending2 = nullptr;
-    // two-phase path for the candidates the block-item path gives up on (foreign frames): item slots per candidate
-    // (2 x the expected blocks + 8: a writer may split blocks), the work list of the run, pool demand
+    // two-phase path for the candidates the block-item path gives up on (foreign frames): item slots per candidate, the work list of the run
     uint32_t *fz_base = nullptr, *fz_cap = nullptr, *fz_it_cand = nullptr, *fz_nb = nullptr, *fz_work = nullptr;
     zn::FzItem *fz_items = nullptr;
-    uint32_t fz_total = 0;
-    uint64_t fz_bytes = 0;  // content bytes of all candidates
     // batch path (k_bx_*): candidate slots (one per compressed row at most), item slots, the two entropy work lists
-    uint32_t bx_slots = 0, bx_item_cap = 0;
-    uint64_t bx_bytes = 0;  // content bytes of all compressed rows
-    uint64_t bx_nblk = 0;   // their 128 KiB blocks, as the index columns have them
     uint32_t *bx_cand_ck = nullptr;  // checksum stage: which slots hold a frame with a trailer (allocated by the first run with the switch on)
-    int xxh_forms = 0;               // ... and the forms its rows call for (BxArgs::xxh_forms)
     uint32_t *bx_cand_row = nullptr, *bx_cand_base = nullptr, *bx_cand_nb = nullptr, *bx_huf_list = nullptr, *bx_seq_list = nullptr, *bx_sort_tmp = nullptr;
     zn::FzItem *bx_items = nullptr;
     zn::BxPrep *bx_prep = nullptr;
-    uint64_t rx_words = 0;  // resolve path: words its frames (compressed rows of >= RX_MIN bytes) can ask for
-    uint64_t rx_words_small = 0;  // ... counting every row above 64 KiB
-    uint32_t rx_min = zn::RX_MIN;  // a table whose rows above 64 KiB are few (<= 256 M words) resolves all of them: one wave per frame is the slower way
-                                   // when the frames do not fill the chip (the image's source text: its 64-256 KiB frames were 1.6 ms of one-wave execution)
-    uint32_t *rx_base = nullptr, *rx_fail = nullptr, *rx_blk = nullptr, *rx_list = nullptr;
+    uint32_t *rx_base = nullptr, *rx_fail = nullptr, *rx_blk = nullptr, *rx_list = nullptr;  // resolve path
     uint32_t *item_row = nullptr, *item_k = nullptr, *item_src = nullptr, *row_flag = nullptr;
     // fused block kernel: big-slice tiles of the candidate rows, the item each belongs to, and what it got done
-    uint32_t n_bt = 0;
     uint32_t *bt_tile = nullptr, *bt_item = nullptr;
     uint8_t *tile_done = nullptr, *item_done = nullptr;  // one allocation (item_done lies behind tile_done)
     size_t done_bytes = 0;
     uint32_t *todo = nullptr;  // items left to the block decoder (count: H_ITEMS)
-    uint32_t n_small_tiles = 0;     // tiles of whole small rows (the fused kernels' work)
     uint32_t *slow_list = nullptr;  // tiles the role-split kernel leaves to k_fused_small (count: H_TILES)
     DevPlan plan;
 };
@@ -753,106 +643,61 @@ static int ensure_decoder(znippy_ctx *ctx) {
     if (hipMalloc(&ctx->lit_scratch, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
     return ZNIPPY_OK;
 }
-// Pools of the two-phase foreign-frame path.  Literals: a block's literals never exceed what it regenerates, so the
-// candidates' content bytes (+ 80 bytes of slack per item) always suffice.  Sequence records (8 bytes each): real data
-// runs at one sequence per 8-20 bytes; 1.5 bytes of pool per content byte covers one per 5.3 bytes, and a block that
-// finds the pool empty simply stays with the serial decoder.  Both are capped (a 100 GB archive does not get 250 GB
-// of scratch): what does not fit is decoded serially.
+// One grow-only pool of the context (sizes: host/rows_plan.h): when `want` is more than it holds, the main stream is waited for
+// (runs in flight use the pool: the auxiliary streams have joined by the end of a run), its buffers are freed and made again.
+// false: no memory — nothing is left of the pool, which an optional one's users take as "no pool" and a required one's as
+// ZNIPPY_E_NOMEM.
+struct PoolBuf { void **p; uint64_t bytes; };
+static bool pool_grow(znippy_ctx *ctx, std::initializer_list<PoolBuf> bufs, uint64_t *cap, uint64_t want) {
+    if (want <= *cap) return true;
+    (void)hipStreamSynchronize(ctx->stream);
+    for (const PoolBuf &b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
+    *cap = 0;
+    for (const PoolBuf &b : bufs)
+        if (hipMalloc(b.p, b.bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *b.p = nullptr;
+            for (const PoolBuf &f : bufs) { if (*f.p) (void)hipFree(*f.p); *f.p = nullptr; }
+            return false;
+        }
+    *cap = want;
+    return true;
+}
+// the two-phase path's pools; without one of them the serial decoder keeps the frames
 static int ensure_fz_pools(znippy_ctx *ctx, uint64_t content_bytes, uint32_t items) {
-    constexpr uint64_t CAP = 16ull << 30;
-    const uint64_t lit = std::min<uint64_t>(content_bytes + 80ull * items + 4096, CAP);
-    const uint64_t seq = std::min<uint64_t>(content_bytes * 3 / 2 + 4096, CAP) / 8;
-    if (lit > ctx->fz_lit_cap) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->fz_lit_pool) (void)hipFree(ctx->fz_lit_pool);
-        ctx->fz_lit_pool = nullptr; ctx->fz_lit_cap = 0;
-        if (hipMalloc(&ctx->fz_lit_pool, lit) != hipSuccess) { (void)hipGetLastError(); ctx->fz_lit_pool = nullptr; return ZNIPPY_OK; }  // no pool: the serial decoder keeps the frames
-        ctx->fz_lit_cap = lit;
-    }
-    if (seq > ctx->fz_seq_cap) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->fz_seq_pool) (void)hipFree(ctx->fz_seq_pool);
-        ctx->fz_seq_pool = nullptr; ctx->fz_seq_cap = 0;
-        if (hipMalloc(&ctx->fz_seq_pool, seq * 8) != hipSuccess) { (void)hipGetLastError(); ctx->fz_seq_pool = nullptr; return ZNIPPY_OK; }
-        ctx->fz_seq_cap = seq;
-    }
+    const FzPoolSizes z = fz_pool_sizes(content_bytes, items);
+    if (pool_grow(ctx, {{(void **)&ctx->fz_lit_pool, z.lit_bytes}}, &ctx->fz_lit_cap, z.lit_bytes))
+        (void)pool_grow(ctx, {{(void **)&ctx->fz_seq_pool, z.seq_records * 8}}, &ctx->fz_seq_cap, z.seq_records);
     return ZNIPPY_OK;
 }
-// Table pools of the batch path: a 10 KiB text frame needs ~1.5 KB of FSE cells and ~2 KB of Huffman cells; half a byte of
-// each per content byte (+ 64 bytes per item) covers frames down to ~1 KiB, and a block that finds a pool empty stays with
-// the serial decoder.
+// the batch path's table pools, the predefined tables at the head of the FSE pool
 static int ensure_bx_pools(znippy_ctx *ctx, uint64_t content_bytes, uint32_t items) {
-    constexpr uint64_t CAP = 16ull << 30;
-    const uint64_t bytes = std::min<uint64_t>(content_bytes / 2 + 64ull * items + 4096, CAP);
-    const uint64_t fse = bytes / 2 + BX_POOL_FIRST, huf = bytes / 2;
-    if (fse > ctx->bx_fse_cap) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->bx_fse_pool) (void)hipFree(ctx->bx_fse_pool);
-        ctx->bx_fse_pool = nullptr; ctx->bx_fse_cap = 0;
-        if (hipMalloc(&ctx->bx_fse_pool, fse * 2) != hipSuccess) { (void)hipGetLastError(); ctx->bx_fse_pool = nullptr; return ZNIPPY_OK; }
+    const BxPoolSizes z = bx_pool_sizes(content_bytes, items);
+    const uint64_t had = ctx->bx_fse_cap;
+    if (!pool_grow(ctx, {{(void **)&ctx->bx_fse_pool, z.fse_cells * 2}}, &ctx->bx_fse_cap, z.fse_cells)) return ZNIPPY_OK;
+    if (ctx->bx_fse_cap != had) {
         uint16_t predef[BX_POOL_FIRST];
         bx_predefined_tables(predef);
-        if (hipMemcpy(ctx->bx_fse_pool, predef, sizeof predef, hipMemcpyHostToDevice) != hipSuccess) return ZNIPPY_E_HIP;
-        ctx->bx_fse_cap = fse;
+        if (hipMemcpy(ctx->bx_fse_pool, predef, sizeof predef, hipMemcpyHostToDevice) != hipSuccess) { ctx->bx_fse_cap = 0; return ZNIPPY_E_HIP; }
     }
-    if (huf > ctx->bx_huf_cap) {
-        (void)hipStreamSynchronize(ctx->stream);
-        if (ctx->bx_huf_pool) (void)hipFree(ctx->bx_huf_pool);
-        ctx->bx_huf_pool = nullptr; ctx->bx_huf_cap = 0;
-        if (hipMalloc(&ctx->bx_huf_pool, huf * 2) != hipSuccess) { (void)hipGetLastError(); ctx->bx_huf_pool = nullptr; return ZNIPPY_OK; }
-        ctx->bx_huf_cap = huf;
-    }
+    (void)pool_grow(ctx, {{(void **)&ctx->bx_huf_pool, z.huf_cells * 2}}, &ctx->bx_huf_cap, z.huf_cells);
     return ZNIPPY_OK;
 }
-// Word pool of the resolve path: 4 bytes per output byte of the frames it takes, at most 2^31 - 2^20 words (a word with bit 31
-// clear is an index).  hipMalloc of 8 GiB takes 0.3 ms on this system; frames that find no room are executed by a wave each.
+// the resolve path's word pool with its chunk tables (hipMalloc of 8 GiB takes 0.3 ms on this system); no pool: the frames are
+// executed by a wave each
 static int ensure_rx_pool(znippy_ctx *ctx, uint64_t words) {
-    constexpr uint64_t CAP = (1ull << 31) - (1ull << 20);
-    words = std::min<uint64_t>((words + 1023) & ~1023ull, CAP);
-    if (words <= ctx->rx_cap) return ZNIPPY_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->rx_pool) (void)hipFree(ctx->rx_pool);
-    if (ctx->rx_chunk) (void)hipFree(ctx->rx_chunk);
-    if (ctx->rx_cdone) (void)hipFree(ctx->rx_cdone);
-    ctx->rx_pool = nullptr; ctx->rx_chunk = nullptr; ctx->rx_cdone = nullptr; ctx->rx_cap = 0;
-    if (hipMalloc(&ctx->rx_pool, words * 4) != hipSuccess || hipMalloc(&ctx->rx_chunk, words / 1024 * 4) != hipSuccess || hipMalloc(&ctx->rx_cdone, words / 1024) != hipSuccess) {
-        (void)hipGetLastError();
-        if (ctx->rx_pool) (void)hipFree(ctx->rx_pool);
-        if (ctx->rx_chunk) (void)hipFree(ctx->rx_chunk);
-        ctx->rx_pool = nullptr; ctx->rx_chunk = nullptr; ctx->rx_cdone = nullptr;
-        return ZNIPPY_OK;  // no pool: the frames are executed by a wave each
-    }
-    ctx->rx_cap = words;
+    words = rx_pool_words(words);
+    (void)pool_grow(ctx, {{(void **)&ctx->rx_pool, words * 4}, {(void **)&ctx->rx_chunk, words / 1024 * 4}, {(void **)&ctx->rx_cdone, words / 1024}}, &ctx->rx_cap, words);
     return ZNIPPY_OK;
 }
-// Scratch of the verify-only runs: the slots of one table (+ slack for 16-byte reads behind the last one).  Unlike the pools above it is
-// not optional — the rows that need it have nowhere else to go — and it is capped like them: above the cap the run is refused.
-static int ensure_verify_scratch(znippy_ctx *ctx, uint64_t bytes) {
-    constexpr uint64_t CAP = 16ull << 30;
-    if (!bytes) return ZNIPPY_OK;
-    if (bytes > CAP) return ZNIPPY_E_NOMEM;
-    bytes += 4096;
-    if (bytes <= ctx->vs_cap) return ZNIPPY_OK;
-    (void)hipStreamSynchronize(ctx->stream);  // (runs in flight use the region: the auxiliary streams have joined by the end of a run)
-    if (ctx->vs_pool) (void)hipFree(ctx->vs_pool);
-    ctx->vs_pool = nullptr; ctx->vs_cap = 0;
-    if (hipMalloc(&ctx->vs_pool, bytes) != hipSuccess) { (void)hipGetLastError(); ctx->vs_pool = nullptr; return ZNIPPY_E_NOMEM; }
-    ctx->vs_cap = bytes;
-    return ZNIPPY_OK;
+// the verify-only runs' scratch and the range reads' two regions: not optional — a call that needs more than may be had is refused
+static int ensure_scratch(znippy_ctx *ctx, uint8_t **pool, uint64_t *cap, uint64_t bytes) {
+    if (bytes == POOL_REFUSED) return ZNIPPY_E_NOMEM;
+    return pool_grow(ctx, {{(void **)pool, bytes}}, cap, bytes) ? ZNIPPY_OK : ZNIPPY_E_NOMEM;
 }
-// Scratch of the range reads, capped the same way (both regions together): a call that needs more is refused.
+static int ensure_verify_scratch(znippy_ctx *ctx, uint64_t bytes) { return ensure_scratch(ctx, &ctx->vs_pool, &ctx->vs_cap, verify_scratch_bytes(bytes)); }
 static int ensure_range_scratch(znippy_ctx *ctx, int which, uint64_t bytes) {
-    constexpr uint64_t CAP = 16ull << 30;
-    if (!bytes) return ZNIPPY_OK;
-    if (bytes > CAP || bytes + ctx->rr_cap[which ^ 1] > CAP + 8192) return ZNIPPY_E_NOMEM;
-    bytes += 4096;
-    if (bytes <= ctx->rr_cap[which]) return ZNIPPY_OK;
-    (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->rr_pool[which]) (void)hipFree(ctx->rr_pool[which]);
-    ctx->rr_pool[which] = nullptr; ctx->rr_cap[which] = 0;
-    if (hipMalloc(&ctx->rr_pool[which], bytes) != hipSuccess) { (void)hipGetLastError(); ctx->rr_pool[which] = nullptr; return ZNIPPY_E_NOMEM; }
-    ctx->rr_cap[which] = bytes;
-    return ZNIPPY_OK;
+    return ensure_scratch(ctx, &ctx->rr_pool[which], &ctx->rr_cap[which], range_scratch_bytes(bytes, ctx->rr_cap[which ^ 1]));
 }
 static int ensure_encoder(znippy_ctx *ctx) {
     if (ctx->enc_tabs) return ZNIPPY_OK;
@@ -1213,7 +1058,7 @@ int znippy_rows_foreign_stats(znippy_ctx *ctx, znippy_rows *r, uint64_t stats[8]
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // the pool counters of the path that ran for this table: the batch path's or the round-2 two-phase path's
-    HIPCHK(ctx, hipMemcpy(stats, r->ctl + (r->bx_slots ? CTL_BX_POOL : CTL_FZ_POOL).at, 64, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(stats, r->ctl + (r->shape.bx_slots ? CTL_BX_POOL : CTL_FZ_POOL).at, 64, hipMemcpyDeviceToHost));
     return ZNIPPY_OK;
 }
 
@@ -1363,21 +1208,9 @@ void znippy_rows_destroy(znippy_rows *r) {
     table_released(c);
 }
 
-struct RowCols {  // the caller's columns from row_begin on (host memory)
-    const uint64_t *bo, *bs, *us, *oo;
-    const uint8_t *bitmap;
-    uint64_t row_begin, row_end;
-    bool allc;  // every row compressed (the usual archive): the per-row passes skip the bit column
-    uint32_t comp(uint32_t i) const { if (allc) return 1u; const uint64_t row = row_begin + i; return (bitmap[row >> 3] >> (row & 7)) & 1u; }
-};
-struct RowClasses {  // what the pass over the columns finds about the compressed rows above 64 KiB (rows_classify)
-    std::vector<uint32_t> la, cand_row, cand_base, cand_nb, item_row, item_k, fz_base, fz_cap, fz_it_cand;
-    uint64_t big_bytes = 0, big_blob = 0, n_big = 0, nblk = 0;
-};
-
 // the columns as they are (the device derives the byte-per-row flags and the stored rows' lengths), then the checksums
 static int rows_columns_h2d(znippy_ctx *ctx, znippy_rows *r, const RowCols &c, const uint8_t *checksum, TDbg &td) {
-    const uint32_t n = r->n;
+    const uint32_t n = (uint32_t)(c.row_end - c.row_begin);
     int rc = ZNIPPY_OK;
     const uint64_t bm0 = c.row_begin >> 3, bm1 = (c.row_end + 7) >> 3;  // (d_bitmap is kept until the table goes: k_rows_fixup reads it on the stream, uploads are not stream-ordered)
     // A table written front to back is its two size columns (zn_rows_pack32): 8 bytes per row go to the device, from
@@ -1412,90 +1245,28 @@ static int rows_columns_h2d(znippy_ctx *ctx, znippy_rows *r, const RowCols &c, c
     return ZNIPPY_OK;
 }
 
-// ONE pass over the caller's columns: the flags the runs need, the extents a run is validated against (rows_validate: a
-// table whose extents fit the run's regions has no bad row — the per-row pass is for the others), and the big rows.
-// Compressed rows above 64 KiB: frames of >= 2 blocks (and < 4 GiB) are tried block by block (each block a work item),
-// the others go straight to the general decoder.
-static void rows_classify(const znippy_ctx *ctx, znippy_rows *r, const RowCols &c, RowClasses &k) {
-    constexpr uint64_t BLK = 128 * 1024;
-    const uint32_t n = r->n;
-    if (c.allc) {  // the vectorised pass; the row-by-row one below only if the table has big rows
-        uint64_t e[8];
-        zn_rows_extents(c.bo, c.bs, c.oo, c.us, n, e);
-        if (e[6] == 0) {
-            r->ext_min_bo = e[0]; r->ext_max_bend = e[1]; r->ext_max_oend = e[2]; r->ext_wrap = e[3] != 0;
-            r->n_compressed = n; r->bx_bytes = e[4]; k.nblk = e[5];
-            r->xxh_forms = 1;  // (no row above 64 KiB: the checksum stage's quad form alone)
-            return;
-        }
-    }
-    uint64_t min_bo = ~0ull, max_bend = 0, max_oend = 0;
-    bool wrap = false;
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t comp = c.comp(i);
-        const uint64_t bo = c.bo[i], bs = c.bs[i], oo = c.oo[i], us = comp ? c.us[i] : bs;
-        r->n_compressed += comp;
-        if (!comp && (oo & 15)) r->odd_out = true;
-        min_bo = std::min(min_bo, bo);
-        wrap |= bo + bs < bo || oo + us < oo;
-        max_bend = std::max(max_bend, bo + bs);
-        max_oend = std::max(max_oend, oo + us);
-        if (!comp) continue;
-        k.nblk += us ? (us + BLK - 1) / BLK : 1;
-        r->bx_bytes += us;
-        if (us > 65536 && us < (1ull << 30)) r->rx_words_small += (us + 1023) & ~1023ull;
-        if (us >= zn::RX_MIN && us < (1ull << 30)) r->rx_words += (us + 1023) & ~1023ull;
-        r->xxh_forms |= us < zn::XXH_WAVE_MIN ? 1 : 2;
-        if (us <= 64 * 1024) continue;
-        k.big_bytes += us;
-        k.big_blob += bs;
-        k.n_big++;
-        const uint64_t nb = (us + BLK - 1) / BLK;
-        if (nb >= 2 && us < 0xFFFFFFFFull && k.item_row.size() + nb < 0x7FFFFFFFull && !ctx->sw.no_block_items) {
-            k.cand_row.push_back(i);
-            k.cand_base.push_back((uint32_t)k.item_row.size());
-            k.cand_nb.push_back((uint32_t)nb);
-            for (uint32_t b = 0; b < nb; b++) { k.item_row.push_back(i); k.item_k.push_back(b); }
-            if (!ctx->sw.no_fz && ctx->sw.no_bx && k.fz_it_cand.size() + 2 * nb + 8 < 0x7FFFFFFFull) {
-                const uint32_t cap = (uint32_t)(2 * nb + 8);
-                k.fz_base.push_back((uint32_t)k.fz_it_cand.size());
-                k.fz_cap.push_back(cap);
-                k.fz_it_cand.insert(k.fz_it_cand.end(), cap, (uint32_t)k.cand_row.size() - 1);
-                r->fz_bytes += us;
-            } else { k.fz_base.push_back(0); k.fz_cap.push_back(0); }
-        } else k.la.push_back(i);
-    }
-    r->ext_min_bo = min_bo; r->ext_max_bend = max_bend; r->ext_max_oend = max_oend; r->ext_wrap = wrap;
-}
-
 // what the block-item path, the batch path and the serial decoder tell each other about a row, the serial decoder's list,
-// and the batch / resolve paths' per-table buffers
-static int rows_batch_buffers(znippy_ctx *ctx, znippy_rows *r, uint64_t nblk) {
-    if (tmalloc(ctx, &r->row_flag, std::max<size_t>(4 * (size_t)r->n, 16)) != hipSuccess ||
-        tmalloc(ctx, &r->pending2, std::max<size_t>(4 * (size_t)r->n_compressed, 16)) != hipSuccess)
+// and the batch / resolve paths' per-table buffers (capacities: rows_classify)
+static int rows_batch_buffers(znippy_ctx *ctx, znippy_rows *r) {
+    const RowsShape &s = r->shape;
+    if (tmalloc(ctx, &r->row_flag, std::max<size_t>(4 * (size_t)s.n, 16)) != hipSuccess ||
+        tmalloc(ctx, &r->pending2, std::max<size_t>(4 * (size_t)s.n_compressed, 16)) != hipSuccess)
         return ZNIPPY_E_NOMEM;
-    if (ctx->sw.no_bx) return ZNIPPY_OK;
-    // a writer may split blocks (libzstd's high levels cut a 128 KiB block into 2-5; runs of equal bytes come as
-    // strings of small RLE blocks): half as many again + up to 64k more, shared by all frames.  Frames that find no
-    // slot stay with the serial decoder.
-    r->bx_nblk = nblk;
-    if (r->rx_words_small && r->rx_words_small <= (256ull << 20)) { r->rx_min = 65537; r->rx_words = r->rx_words_small; }
-    const uint64_t cap = nblk + nblk / 2 + std::min<uint64_t>(3 * nblk, 65536) + 1024;
-    if (cap >= 0x7FFFFFFFull) return ZNIPPY_OK;
-    r->bx_slots = r->n_compressed;
-    r->bx_item_cap = (uint32_t)cap;
-    if (tmalloc(ctx, &r->bx_cand_row, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_cand_base, 4 * (size_t)r->bx_slots) != hipSuccess ||
-        tmalloc(ctx, &r->bx_cand_nb, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_huf_list, 4 * (size_t)cap) != hipSuccess ||
-        tmalloc(ctx, &r->bx_seq_list, 4 * 4 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->bx_sort_tmp, 5 * 4 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->bx_items, sizeof(zn::FzItem) * (size_t)cap) != hipSuccess ||
-        tmalloc(ctx, &r->bx_prep, sizeof(zn::BxPrep) * (size_t)cap) != hipSuccess ||
-        ((r->rx_words || r->rx_words_small) && !ctx->sw.no_rx &&
-         (tmalloc(ctx, &r->rx_base, 4 * (size_t)r->bx_slots) != hipSuccess || tmalloc(ctx, &r->rx_fail, 4 * (size_t)r->bx_slots) != hipSuccess ||
-          tmalloc(ctx, &r->rx_blk, 16 * (size_t)cap) != hipSuccess || tmalloc(ctx, &r->rx_list, 4 * (size_t)cap) != hipSuccess)))
+    if (!s.bx_slots) return ZNIPPY_OK;
+    const size_t cap = s.bx_item_cap;
+    if (tmalloc(ctx, &r->bx_cand_row, 4 * (size_t)s.bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_cand_base, 4 * (size_t)s.bx_slots) != hipSuccess ||
+        tmalloc(ctx, &r->bx_cand_nb, 4 * (size_t)s.bx_slots) != hipSuccess || tmalloc(ctx, &r->bx_huf_list, 4 * cap) != hipSuccess ||
+        tmalloc(ctx, &r->bx_seq_list, 4 * 4 * cap) != hipSuccess || tmalloc(ctx, &r->bx_sort_tmp, 5 * 4 * cap) != hipSuccess || tmalloc(ctx, &r->bx_items, sizeof(zn::FzItem) * cap) != hipSuccess ||
+        tmalloc(ctx, &r->bx_prep, sizeof(zn::BxPrep) * cap) != hipSuccess ||
+        (s.rx_frames &&
+         (tmalloc(ctx, &r->rx_base, 4 * (size_t)s.bx_slots) != hipSuccess || tmalloc(ctx, &r->rx_fail, 4 * (size_t)s.bx_slots) != hipSuccess ||
+          tmalloc(ctx, &r->rx_blk, 16 * cap) != hipSuccess || tmalloc(ctx, &r->rx_list, 4 * cap) != hipSuccess)))
         return ZNIPPY_E_NOMEM;
     return ZNIPPY_OK;
 }
 // block items: the candidates, their items, and the round-2 two-phase path's item slots
 static int rows_item_buffers(znippy_ctx *ctx, znippy_rows *r, const RowClasses &k) {
+    const RowsShape &s = r->shape;
     int rc;
     if ((rc = dev_upload(ctx, &r->cand_row, k.cand_row.data(), k.cand_row.size())) ||
         (rc = dev_upload(ctx, &r->cand_base, k.cand_base.data(), k.cand_base.size())) ||
@@ -1503,39 +1274,27 @@ static int rows_item_buffers(znippy_ctx *ctx, znippy_rows *r, const RowClasses &
         (rc = dev_upload(ctx, &r->item_row, k.item_row.data(), k.item_row.size())) ||
         (rc = dev_upload(ctx, &r->item_k, k.item_k.data(), k.item_k.size())))
         return rc;
-    if (tmalloc(ctx, &r->item_src, 4 * (size_t)r->n_items) != hipSuccess) return ZNIPPY_E_NOMEM;
-    r->fz_total = (uint32_t)k.fz_it_cand.size();
-    if (!r->fz_total) return ZNIPPY_OK;
+    if (tmalloc(ctx, &r->item_src, 4 * (size_t)s.n_items) != hipSuccess) return ZNIPPY_E_NOMEM;
+    if (!s.fz_total) return ZNIPPY_OK;
     if ((rc = dev_upload(ctx, &r->fz_base, k.fz_base.data(), k.fz_base.size())) ||
         (rc = dev_upload(ctx, &r->fz_cap, k.fz_cap.data(), k.fz_cap.size())) ||
         (rc = dev_upload(ctx, &r->fz_it_cand, k.fz_it_cand.data(), k.fz_it_cand.size())))
         return rc;
-    if (tmalloc(ctx, &r->fz_nb, 4 * (size_t)r->n_cand) != hipSuccess || tmalloc(ctx, &r->fz_work, 4 * (size_t)r->fz_total) != hipSuccess ||
-        tmalloc(ctx, &r->fz_items, sizeof(zn::FzItem) * (size_t)r->fz_total) != hipSuccess)
+    if (tmalloc(ctx, &r->fz_nb, 4 * (size_t)s.n_cand) != hipSuccess || tmalloc(ctx, &r->fz_work, 4 * (size_t)s.fz_total) != hipSuccess ||
+        tmalloc(ctx, &r->fz_items, sizeof(zn::FzItem) * (size_t)s.fz_total) != hipSuccess)
         return ZNIPPY_E_NOMEM;
     return ZNIPPY_OK;
 }
-// fused block kernel: the big-slice tiles of the candidate rows and the item each belongs to
-static int rows_fused_block_buffers(znippy_ctx *ctx, znippy_rows *r, const RowClasses &k, const PlanBuf &p) {
-    std::vector<uint32_t> row_base(r->n, 0xFFFFFFFFu), bt_tile, bt_item;
-    for (size_t c = 0; c < k.cand_row.size(); c++) row_base[k.cand_row[c]] = k.cand_base[c];
-    for (uint32_t ti = 0; ti < (uint32_t)p.tiles.size(); ti++) {
-        const Tile &t = p.tiles[ti];
-        if (t.n_units == 0 && row_base[t.first_unit] != 0xFFFFFFFFu) {
-            bt_tile.push_back(ti);
-            bt_item.push_back(row_base[t.first_unit] + (t.first_leaf >> 7));
-        }
-    }
-    r->n_bt = (uint32_t)bt_tile.size();
+// fused block kernel: the big-slice tiles of the candidate rows and the item each belongs to, its done flags, what it leaves
+static int rows_fused_block_buffers(znippy_ctx *ctx, znippy_rows *r, const RowClasses &k) {
     int rc;
-    if ((rc = dev_upload(ctx, &r->bt_tile, bt_tile.data(), bt_tile.size())) || (rc = dev_upload(ctx, &r->bt_item, bt_item.data(), bt_item.size()))) return rc;
-    // (the two arrays of done flags in one allocation: one clear per run instead of two)
-    const size_t td_bytes = (std::max<size_t>(p.tiles.size(), 16) + 15) & ~(size_t)15;
-    r->done_bytes = td_bytes + std::max<size_t>(r->n_items, 16);
+    if ((rc = dev_upload(ctx, &r->bt_tile, k.bt_tile.data(), k.bt_tile.size())) || (rc = dev_upload(ctx, &r->bt_item, k.bt_item.data(), k.bt_item.size()))) return rc;
+    size_t items_at;
+    r->done_bytes = rows_done_bytes(r->shape, &items_at);
     if (tmalloc(ctx, &r->tile_done, r->done_bytes) != hipSuccess ||
-        tmalloc(ctx, &r->todo, std::max<size_t>(4 * (size_t)r->n_items, 16)) != hipSuccess)
+        tmalloc(ctx, &r->todo, std::max<size_t>(4 * (size_t)r->shape.n_items, 16)) != hipSuccess)
         return ZNIPPY_E_NOMEM;
-    r->item_done = r->tile_done + td_bytes;
+    r->item_done = r->tile_done + items_at;
     return ZNIPPY_OK;
 }
 
@@ -1554,15 +1313,8 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
     r->ctx = ctx;
     ctx->live_tables++;
     r->row_begin = row_begin;
-    r->n = (uint32_t)(row_end - row_begin);
-    const uint32_t n = r->n;
-    bool allc = true;
-    if (compressed_bitmap) {
-        uint64_t row = row_begin;
-        for (; row < row_end && (row & 7); row++) allc &= (compressed_bitmap[row >> 3] >> (row & 7)) & 1;
-        for (; row + 8 <= row_end && allc; row += 8) allc &= compressed_bitmap[row >> 3] == 0xFF;
-        for (; row < row_end && allc; row++) allc &= (compressed_bitmap[row >> 3] >> (row & 7)) & 1;
-    }
+    const uint32_t n = (uint32_t)(row_end - row_begin);
+    const bool allc = rows_all_compressed(compressed_bitmap, row_begin, row_end);
     // a table without output offsets can only be verified (znippy_verify_rows): its output column is a packed layout of its own, so that
     // everything below that looks at the column finds a consistent one
     std::vector<uint64_t> own_oo;
@@ -1593,27 +1345,14 @@ int znippy_rows_create(znippy_ctx *ctx, const uint64_t *blob_offset, const uint6
     td.mark("plan");
     if ((rc = upload_plan(ctx, p, r->plan))) return rc;
     td.mark("plan_h2d");
-    for (const Tile &t : p.tiles) r->n_small_tiles += t.n_units != 0;
-    if (r->n_small_tiles && tmalloc(ctx, &r->slow_list, 4 * (size_t)p.tiles.size()) != hipSuccess) return ZNIPPY_E_NOMEM;
+    RowsShape &s = r->shape;
     RowClasses k;
-    rows_classify(ctx, r, c, k);
-    r->n_list_a = (uint32_t)k.la.size();
+    rows_classify(c, ctx->sw, p, s, k);
+    if (s.n_small_tiles && tmalloc(ctx, &r->slow_list, 4 * (size_t)s.n_tiles) != hipSuccess) return ZNIPPY_E_NOMEM;
     td.mark("big_rows");
-    if (r->n_compressed && (rc = rows_batch_buffers(ctx, r, k.nblk))) return rc;
-    // 1024-thread workgroups pay off where a few very long copies dominate (multi-MiB frames of periodic or stored
-    // data: a frame that is < 2 % of its content); entropy-coded frames are a serial bitstream and want the narrow
-    // variant's window execution instead, whatever their size
-    r->wide_rows = k.n_big && k.big_bytes / k.n_big >= (1u << 20) && k.big_blob * 50 < k.big_bytes;
-    r->n_cand = (uint32_t)k.cand_row.size();
-    r->n_items = (uint32_t)k.item_row.size();
-    const bool hints = !ctx->sw.no_lean && r->n_list_a == 0;  // what the lean forms of a run have in common
-    const uint32_t n_tiles = (uint32_t)p.tiles.size();
-    r->small_ok = allc && hints && !ctx->sw.no_bx && r->n_cand == 0 && r->n_small_tiles == n_tiles && r->n_small_tiles > 0 && r->bx_slots;
-    r->lean_mixed_ok = hints && r->n_cand == 0 && r->n_small_tiles > 0 && r->n_small_tiles < n_tiles;
-    r->lean_blocks_ok = allc && hints && r->n_cand > 0 && r->n_small_tiles == 0;
-    r->lean_ok = allc && hints && r->n_cand == 0 && p.big.empty() && r->n_small_tiles == n_tiles && r->n_small_tiles > 0;
-    if (r->n_cand && (rc = rows_item_buffers(ctx, r, k))) return rc;
-    if (r->n_cand && !ctx->sw.no_fused_blocks && (rc = rows_fused_block_buffers(ctx, r, k, p))) return rc;
+    if (s.n_compressed && (rc = rows_batch_buffers(ctx, r))) return rc;
+    if (s.n_cand && (rc = rows_item_buffers(ctx, r, k))) return rc;
+    if (s.n_bt && (rc = rows_fused_block_buffers(ctx, r, k))) return rc;
     if ((rc = dev_upload(ctx, &r->list_a, k.la.data(), k.la.size()))) return rc;
     if (tmalloc(ctx, &r->pending, std::max<size_t>(4 * (size_t)n, 16)) != hipSuccess) return ZNIPPY_E_NOMEM;
     td.mark("rest");
@@ -1634,42 +1373,29 @@ static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, ui
     if (verify) out_cap = ~0ull;
     if (r->val_done && r->val_verify == verify && r->val_base == blob_base && r->val_bcap == r->blob_cap && r->val_ocap == out_cap) return ZNIPPY_OK;
     std::vector<int32_t> init;
-    uint32_t bad = 0;
-    const uint64_t bcap = r->blob_cap;
-    const bool fits = !r->ext_wrap && (r->n == 0 || (r->ext_min_bo >= blob_base && (bcap == ~0ull || r->ext_max_bend - blob_base <= bcap) && (verify || r->ext_max_oend <= out_cap)));
-    if (!fits && r->h_blob_off.empty() && r->n) {  // the columns, for the per-row verdicts (the device copies hold the effective lengths)
-        r->h_blob_off.resize(r->n); r->h_blob_size.resize(r->n); r->h_len.resize(r->n);
+    const bool fits = rows_fit(r->shape, blob_base, r->blob_cap, out_cap, verify);
+    if (!fits && r->h_blob_off.empty() && r->shape.n) {  // the columns, for the per-row verdicts (the device copies hold the effective lengths)
+        r->h_blob_off.resize(r->shape.n); r->h_blob_size.resize(r->shape.n); r->h_len.resize(r->shape.n);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipMemcpy(r->h_blob_off.data(), r->blob_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(r->h_blob_size.data(), r->blob_size, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(r->h_len.data(), r->usize, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(r->h_blob_off.data(), r->blob_off, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(r->h_blob_size.data(), r->blob_size, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(r->h_len.data(), r->usize, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
     }
-    if (!fits && !verify && r->h_out_off.empty() && r->n) {
-        r->h_out_off.resize(r->n);
+    if (!fits && !verify && r->h_out_off.empty() && r->shape.n) {
+        r->h_out_off.resize(r->shape.n);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipMemcpy(r->h_out_off.data(), r->out_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(r->h_out_off.data(), r->out_off, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
     }
-    for (uint32_t i = 0; i < (fits ? 0u : r->n); i++) {
-        const uint64_t bo = r->h_blob_off[i], bs = r->h_blob_size[i], len = verify ? 0 : r->h_len[i], oo = verify ? 0 : r->h_out_off[i];
-        int code = 0;
-        if (bo < blob_base) code = ZNIPPY_E_CORRUPT;
-        else if (bcap != ~0ull && (bs > bcap || bo - blob_base > bcap - bs)) code = ZNIPPY_E_CORRUPT;
-        else if (len > out_cap || oo > out_cap - len) code = ZNIPPY_E_DST_SMALL;
-        if (code) {
-            if (init.empty()) init.assign(r->n, 0);
-            init[i] = code;
-            bad++;
-        }
-    }
+    const uint32_t bad = fits ? 0 : rows_verdicts(r->h_blob_off.data(), r->h_blob_size.data(), r->h_len.data(), r->h_out_off.data(), r->shape.n, blob_base, r->blob_cap, out_cap, verify, init);
     if (bad) {
         // image of the whole control block: zero head + the preset status column
         if (!r->status_init) {
             if (tmalloc(ctx, &r->status_init, r->ctl_bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
             HIPCHK(ctx, hipMemset(r->status_init, 0, r->ctl_bytes));
         }
-        HIPCHK(ctx, hipMemcpy(r->status_init + CTL_HEAD, init.data(), 4 * (size_t)r->n, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(r->status_init + CTL_HEAD, init.data(), 4 * (size_t)r->shape.n, hipMemcpyHostToDevice));
     }
-    r->n_bad = bad;
+    r->hints.n_bad = bad;
     r->val_base = blob_base; r->val_bcap = r->blob_cap; r->val_ocap = out_cap;
     r->val_done = true; r->val_verify = verify;
     return ZNIPPY_OK;
@@ -1679,107 +1405,36 @@ static int rows_validate(znippy_ctx *ctx, znippy_rows *r, uint64_t blob_base, ui
 // read — a stored row's length there is its blob, and it gets no slot — and the extent comes back for the pool.
 static int rows_verify_slots(znippy_ctx *ctx, znippy_rows *r) {
     if (r->vs_built) return ZNIPPY_OK;
-    if (r->n && r->n_compressed) {
-        const uint32_t nblk = (r->n + 1023) / 1024;
+    if (r->shape.n && r->shape.n_compressed) {
+        const uint32_t nblk = (r->shape.n + 1023) / 1024;
         unsigned long long *sums = nullptr;
-        if (tmalloc(ctx, &r->vs_off, 8 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
+        if (tmalloc(ctx, &r->vs_off, 8 * (size_t)r->shape.n) != hipSuccess) return ZNIPPY_E_NOMEM;
         if (tmalloc(ctx, &sums, 16 * ((size_t)nblk + 1)) != hipSuccess) return ZNIPPY_E_NOMEM;
-        hipLaunchKernelGGL(k_rows_slot_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->compressed, r->usize, r->n, sums);
+        hipLaunchKernelGGL(k_rows_slot_sums, dim3(nblk), dim3(256), 0, ctx->stream, r->compressed, r->usize, r->shape.n, sums);
         hipLaunchKernelGGL(k_rows_unpack_scan, dim3(1), dim3(256), 0, ctx->stream, sums, nblk);
-        hipLaunchKernelGGL(k_rows_slot_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->compressed, r->usize, r->n, sums, nblk, r->vs_off);
+        hipLaunchKernelGGL(k_rows_slot_fill, dim3(nblk), dim3(256), 0, ctx->stream, r->compressed, r->usize, r->shape.n, sums, nblk, r->vs_off);
         unsigned long long total = 0;
         const hipError_t e1 = hipStreamSynchronize(ctx->stream), e2 = hipMemcpy(&total, sums + 2 * (size_t)nblk, 8, hipMemcpyDeviceToHost);
         tfree(ctx, sums);
         HIPCHK(ctx, e1);
         HIPCHK(ctx, e2);
         r->vs_bytes = total;
-    } else if (r->n) {  // no compressed row: no slot, no scratch — the column exists (every row: position 0) because the kernels load it
-        if (tmalloc(ctx, &r->vs_off, 8 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
-        HIPCHK(ctx, hipMemsetAsync(r->vs_off, 0, 8 * (size_t)r->n, ctx->stream));
+    } else if (r->shape.n) {  // no compressed row: no slot, no scratch — the column exists (every row: position 0) because the kernels load it
+        if (tmalloc(ctx, &r->vs_off, 8 * (size_t)r->shape.n) != hipSuccess) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, hipMemsetAsync(r->vs_off, 0, 8 * (size_t)r->shape.n, ctx->stream));
     }
     r->vs_built = true;
     return ZNIPPY_OK;
 }
 
-// what a finished run's mirror says about the batch path's work: rows the fused kernel handed over + block candidates left
-// flagged + the host's own list of big single-block rows
-static void rows_note_hint(znippy_rows *r, unsigned slot) {
-    const uint32_t *left = r->mirror_hand(slot);
-    const bool handed = left[H_FUSED] || left[H_SERIAL] || left[H_FLAGGED];
-    r->bx_hint = (handed || r->n_list_a) ? 1 : 0;
-    r->lean_hint = (handed || left[H_TILES]) ? 0 : 1;
-    r->lean_hint2 = (handed || left[H_ITEMS]) ? 0 : 1;
-    if (r->n_small_tiles && left[H_TILES] >= r->n_small_tiles) r->roles_off = true;  // the role-split kernel took not one tile: not this table's kernel
-    // ... and when the fused kernels handed over every row of a table of small compressed rows, the next runs give the rows to the
-    // batch path themselves (100k rows of real text: 0.26 ms of parsing each frame only to pass it on)
-    if (r->small_ok && left[H_FUSED] >= r->n) r->small_off = true;
-    if (r->small_off) r->bx_hint = 1;
+// ---- one run of a row table: the plan (host/rows_plan.h: rows_plan), then the stages in the order rows_launch queues them ----------
+// the context and the table's optional buffers as this run finds them; nothing here or in the plan calls HIP
+static RunEnv rows_run_env(const znippy_ctx *ctx, const znippy_rows *r, const void *d_out) {
+    return RunEnv{ctx->fz_lit_pool != nullptr, ctx->fz_seq_pool != nullptr, ctx->bx_fse_pool != nullptr, ctx->bx_huf_pool != nullptr, ctx->rx_pool != nullptr, r->rx_base != nullptr,
+                  ctx->rx_cap, ctx->cus, ctx->decode_grid, ctx->gen_share, ctx->batch_checksums && r->bx_cand_ck, ctx->fork_verify, ((uintptr_t)d_out & 15) != 0, &ctx->sw};
 }
 
-static void rows_note_plain(znippy_rows *r, unsigned slot) {  // the same reading of a decode-only run's mirror, into its own field
-    const uint32_t *left = r->mirror_hand(slot);
-    r->plain_hint = (left[H_FUSED] || left[H_SERIAL] || left[H_FLAGGED] || r->n_list_a) ? 1 : 0;
-}
-// the routing hint a run goes by: a decode-only run's own once it has one
-static int rows_route_hint(const znippy_rows *r, bool plain) { return plain && r->plain_hint >= 0 ? r->plain_hint : r->bx_hint; }
-
-// ---- one run of a row table: the plan, then the stages in the order rows_launch queues them -----------------------
-// Which kernels a run launches and on which streams.  Everything here is known before the run's first launch — the context's
-// switches and pools, the table's shape, the hints of its last finished run — and nothing in rows_plan calls HIP.
-struct RunPlan {
-    bool bx;           // the batch path takes the undecoded frames (its pools exist, the last run did not find its lists empty)
-    bool small_off;    // ... every row of the table: the fused small-row kernels are left out, all_rows is its list
-    bool stored_only;  // no compressed row: one pass of the store path kernel over ALL tiles instead of stages 1 and 2
-    bool roles;        // the role-split persistent kernel in front of k_fused_small
-    bool lean;         // nothing behind the roles kernel but the verify, which checks the lists (rows_settle repeats a flagged run)
-    bool lean_mixed;   // small rows beside big stored units: the small rows' kernels on the auxiliary stream beside the second hash pass
-    bool decode;       // stage 2 runs: block items and the decoders behind the fused kernels
-    bool one_stream;   // block items on the main stream: nothing else is expected there
-    bool lean_blocks;  // ... and neither the block decoder nor the serial decoders behind the fused block kernel
-    bool behind;       // round-2 flow: the general decoder behind the block items instead of beside them
-    bool rx;           // batch path: big frames through the resolve stages
-    bool third;        // batch path: the lane-per-block sequence kernel on a third stream beside the Huffman streams
-};
-static RunPlan rows_plan(const znippy_ctx *ctx, const znippy_rows *r, int preset, bool plain) {
-    const auto &sw = ctx->sw;
-    RunPlan p{};
-    const int route = rows_route_hint(r, plain);  // bx_hint, or a decode-only run's own copy of it
-    p.bx = r->bx_slots && ctx->fz_lit_pool && ctx->fz_seq_pool && ctx->bx_fse_pool && ctx->bx_huf_pool && route != 0;
-    p.small_off = p.bx && r->small_off && !r->n_bad && !r->force_full && !sw.dbg;
-    // (a repository of small files the reference stores as they are — png, jpg, gz —, or one big jar.  The fused small-row kernel
-    // copies a stored row with each lane's own 64-byte stores: 100k x 10 KiB stored rows 0.85 ms there, 0.63 through the store path kernel)
-    p.stored_only = r->n_compressed == 0 && !preset && !sw.dbg && !sw.no_stored_only && !r->force_full;
-    // (a decode-only run is never a lean run: nothing it queues could flag it, so it leaves nothing out that a row might need — and it has
-    //  no use for the role-split kernel, whose loaders feed hashers)
-    const bool may_skip = !preset && !r->force_full && !plain;  // a run may leave out what the table's last finished run had no use for
-    if (!p.small_off && !p.stored_only) {
-        // Tables with enough small tiles go to the role-split persistent kernel first (loader + hasher waves: tiles whose rows are all whole-leaf rows of
-        // the recognised periodic shape); what it leaves on its list — and small tables, where a persistent grid only adds start-up latency — is k_fused_small's.
-        p.roles = !sw.no_roles && sw.roles_min != 0 && r->n_small_tiles >= sw.roles_min && r->n_small_tiles > 0 && !(sw.dbg & (1 | 2 | 4 | 8 | 128)) && !r->roles_off && !plain;
-        // A table of small rows AND big stored / hashed units (BASELINE configs[4]: 3,500 small files beside 6 GB of jars) whose
-        // last run handed nothing over: nothing of the small rows' kernel and the second hash pass depends on the other (C5:
-        // 0.28 ms of a 3.45 ms step ran in front of the pass).
-        p.lean_mixed = r->lean_mixed_ok && r->lean_hint == 1 && r->bx_hint == 0 && may_skip && !sw.dbg && !sw.ddbg;
-        p.lean = p.roles && r->lean_ok && r->lean_hint == 1 && r->bx_hint == 0 && may_skip && !sw.dbg;
-    }
-    p.decode = !p.lean && !p.lean_mixed && !p.stored_only;
-    if (!p.decode) return p;
-    // a table of big rows only whose last run handed nothing over: the main stream has nothing for the block items to run beside, and
-    // the fork and the join between two streams were ~0.1 ms of C3's 1.09 ms step
-    p.one_stream = r->n_cand && route == 0 && r->n_small_tiles == 0;
-    // ... and when its last run needed neither the serial block decoder nor the serial decoder behind it (every block item was written and hashed by the
-    // fused block kernel), those three launches are left out, the way a lean run of a table of small rows leaves out what stands behind the roles kernel.
-    p.lean_blocks = p.one_stream && r->lean_blocks_ok && r->lean_hint2 == 1 && may_skip && r->n_bt && !sw.ddbg && !r->fz_total;
-    if (!r->n_compressed) return p;
-    // (the serial decoder's launch then returns at once instead of waiting for CUs next to the block kernels: C3's 0.25 ms that only waited)
-    p.behind = !p.bx && r->n_cand && route == 0;
-    p.rx = p.bx && r->rx_base && ctx->rx_pool && r->rx_words;
-    // (only where the chip is not full of blocks anyway: 100k blocks, both kernels chip-wide: 2.98 ms together against 1.85 + 0.96 in a row)
-    p.third = p.bx && r->bx_nblk <= 32768;
-    return p;
-}
-
-static HashArgs rows_hash_args(const znippy_ctx *ctx, const znippy_rows *r, const RowsRun &run) {
+static HashArgs rows_hash_args(const znippy_ctx *ctx, const znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     HashArgs h{};
     h.tiles = r->plan.tiles; h.n_tiles = r->plan.n_tiles;
     h.len = r->usize;
@@ -1790,13 +1445,13 @@ static HashArgs rows_hash_args(const znippy_ctx *ctx, const znippy_rows *r, cons
     // the stores left out were measured in its place: equal on big slices, 8 % slower on C5 and on tables of small stored rows.)
     h.copy_to_B = run.verify ? 0 : 1;
     h.store_tiles = ctx->sw.store_g;
-    h.misaligned_dst = !run.verify && (r->odd_out || ((uintptr_t)run.d_out & 15) != 0);
+    h.misaligned_dst = p.misaligned_dst;
     h.digests = r->digests; h.tile_cv = r->plan.tile_cv;
     return h;
 }
 static BlockScanArgs rows_scan_args(const znippy_rows *r, const RowsRun &run) {
     BlockScanArgs b{};
-    b.cand_row = r->cand_row; b.cand_base = r->cand_base; b.cand_nblocks = r->cand_nblocks; b.n_cand = r->n_cand;
+    b.cand_row = r->cand_row; b.cand_base = r->cand_base; b.cand_nblocks = r->cand_nblocks; b.n_cand = r->shape.n_cand;
     fill_row_args(b, r, run);
     b.item_src = r->item_src; b.row_flag = r->row_flag;
     b.pending = r->pending2; b.pending_count = r->hand(H_SERIAL);  // its own hand-over list
@@ -1806,10 +1461,10 @@ static BlockScanArgs rows_scan_args(const znippy_rows *r, const RowsRun &run) {
 static DecodeArgs rows_decode_args(znippy_ctx *ctx, const znippy_rows *r, const RowsRun &run) {
     DecodeArgs a{};
     fill_row_args(a, r, run);
-    a.list_a = r->list_a; a.n_list_a = r->n_list_a;
+    a.list_a = r->list_a; a.n_list_a = r->shape.n_list_a;
     a.pending = r->pending; a.pending_count = r->hand(H_FUSED);
     a.compressed = r->compressed;
-    a.n_rows = r->n; a.cursor = r->cur(CUR_GENERAL);
+    a.n_rows = r->shape.n; a.cursor = r->cur(CUR_GENERAL);
     a.lit_scratch = ctx->lit_scratch;
     if (ctx->sw.ddbg)  // diagnostic: phase shares of the previous general-decoder launch
         a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_GENERAL, ctx->stream, nullptr, [](const unsigned long long *h) {
@@ -1818,12 +1473,12 @@ static DecodeArgs rows_decode_args(znippy_ctx *ctx, const znippy_rows *r, const 
         });
     return a;
 }
-static void decode_rest(znippy_ctx *ctx, const znippy_rows *r, DecodeArgs a, uint32_t rows) {  // what every path left: pending2
+static void decode_rest(znippy_ctx *ctx, const znippy_rows *r, const RunPlan &p, DecodeArgs a) {  // what every path left: pending2
     a.list_a = nullptr; a.n_list_a = 0;
     a.pending = r->pending2; a.pending_count = r->hand(H_SERIAL);
     a.cursor = r->cur(CUR_FALLBACK);
     timed(ctx, "zstd_decode_fallback", ctx->stream, [&] {
-        if (!ctx->sw.fz_only) launch_decode(a, std::min<int>(ctx->decode_grid, (int)rows), r->wide_rows, ctx->stream);
+        if (!ctx->sw.fz_only) launch_decode(a, p.fallback_grid, r->shape.wide_rows, ctx->stream);
     });
 }
 
@@ -1835,7 +1490,7 @@ static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const Ro
     if (run.preset) HIPCHK(ctx, hipMemcpyAsync(r->ctl, r->status_init, r->ctl_bytes, hipMemcpyDeviceToDevice, s));
     else HIPCHK(ctx, hipMemsetAsync(r->ctl, 0, r->ctl_bytes, s));
     // (the second hash pass looks at small tiles only when rows were handed over)
-    if (p.small_off) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)r->hand(H_FUSED), (int)r->n, 1, s));
+    if (p.small_off) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)r->hand(H_FUSED), (int)r->shape.n, 1, s));
     return ZNIPPY_OK;
 }
 
@@ -1843,13 +1498,13 @@ static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const Ro
 static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     hipStream_t s = run.on;
     FusedArgs f{};
-    f.h = rows_hash_args(ctx, r, run);
+    f.h = rows_hash_args(ctx, r, p, run);
     f.h.pass = 1;  // PASS_FUSED
     f.blob_size = r->blob_size; f.out_cap = run.out_cap; f.status = r->status;
     f.preset = run.preset;
     f.pending = r->pending; f.pending_count = r->hand(H_FUSED);
     if (run.plain) {  // store-only: one kernel over the plan's small tiles, no diagnostics
-        if (r->n_small_tiles) timed(ctx, "decode_small", s, [&] { launch_decode_small(f, s); });
+        if (p.small) timed(ctx, "decode_small", s, [&] { launch_decode_small(f, s); });
         return ZNIPPY_OK;
     }
     f.dbg = ctx->sw.dbg;
@@ -1877,7 +1532,7 @@ static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
         f.tile_count = r->hand(H_TILES);
         timed(ctx, run.verify ? "verify_roles" : "decode_verify_roles", fs, [&] { launch_fused_roles(f, ctx->cus, fs, run.verify); });
     }
-    if (r->n_small_tiles && !p.lean) timed(ctx, run.verify ? "verify_small" : "decode_verify_fused", fs, [&] { launch_fused_small(f, fs, p.roles ? ctx->cus * 5 : 0, run.verify); });
+    if (p.small) timed(ctx, run.verify ? "verify_small" : "decode_verify_fused", fs, [&] { launch_fused_small(f, fs, p.small_grid_cap, run.verify); });
     if (p.lean_mixed) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));  // (joined in front of the verify)
     return ZNIPPY_OK;
 }
@@ -1888,8 +1543,8 @@ static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
 // 7.0 + 10.6 ms).
 static void run_two_phase(znippy_ctx *ctx, znippy_rows *r, const RowsRun &run, hipStream_t ba) {
     FzArgs z{};
-    z.cand_row = r->cand_row; z.cand_fzbase = r->fz_base; z.cand_fzcap = r->fz_cap; z.n_cand = r->n_cand;
-    z.it_cand = r->fz_it_cand; z.total_items = r->fz_total; z.cand_nb = r->fz_nb; z.items = r->fz_items;
+    z.cand_row = r->cand_row; z.cand_fzbase = r->fz_base; z.cand_fzcap = r->fz_cap; z.n_cand = r->shape.n_cand;
+    z.it_cand = r->fz_it_cand; z.total_items = r->shape.fz_total; z.cand_nb = r->fz_nb; z.items = r->fz_items;
     fill_row_args(z, r, run);
     z.row_flag = r->row_flag;
     z.lit_pool = ctx->fz_lit_pool; z.lit_cap = ctx->fz_lit_cap; z.seq_pool = ctx->fz_seq_pool; z.seq_cap = ctx->fz_seq_cap;
@@ -1919,73 +1574,71 @@ static int run_block_items(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, co
         HIPCHK(ctx, hipStreamWaitEvent(ba, ctx->ev_fork, 0));
     }
     timed(ctx, "zstd_block_scan", ba, [&] { launch_scan_blocks(b, ba); });
-    if (r->n_bt) {  // blocks of the common shape: written and hashed in one go, skipped by the block decoder and the second hash pass
+    if (p.fused_blocks) {  // blocks of the common shape: written and hashed in one go, skipped by the block decoder and the second hash pass
         HIPCHK(ctx, hipMemsetAsync(r->tile_done, 0, r->done_bytes, ba));
         FusedBlocksArgs fb{};
-        fb.h = rows_hash_args(ctx, r, run);
+        fb.h = rows_hash_args(ctx, r, p, run);
         fb.h.pass = 0;  // PASS_ALL
         fb.blob_size = r->blob_size;
-        fb.bt_tile = r->bt_tile; fb.bt_item = r->bt_item; fb.n_bt = r->n_bt;
+        fb.bt_tile = r->bt_tile; fb.bt_item = r->bt_item; fb.n_bt = r->shape.n_bt;
         fb.item_src = r->item_src; fb.row_flag = r->row_flag;
         fb.tile_done = r->tile_done; fb.item_done = r->item_done;
         fb.dbg = ctx->sw.dbg;
         if (run.plain) timed(ctx, "decode_blocks", ba, [&] { launch_decode_blocks(fb, ba); });
         else timed(ctx, run.verify ? "verify_blocks" : "decode_verify_fused_blocks", ba, [&] { launch_fused_blocks(fb, ba, run.verify); });
-        launch_compact_items(r->item_done, r->n_items, r->todo, r->hand(H_ITEMS), ba);
+        launch_compact_items(r->item_done, r->shape.n_items, r->todo, r->hand(H_ITEMS), ba);
     }
     DecodeArgs a{};
     fill_row_args(a, r, run);
     a.block_mode = 1;
-    a.item_row = r->item_row; a.item_k = r->item_k; a.item_src = r->item_src; a.n_items = r->n_items; a.row_flag = r->row_flag;
-    a.item_done = r->n_bt ? r->item_done : nullptr;
-    a.todo = r->n_bt ? r->todo : nullptr; a.n_todo = r->hand(H_ITEMS);
+    a.item_row = r->item_row; a.item_k = r->item_k; a.item_src = r->item_src; a.n_items = r->shape.n_items; a.row_flag = r->row_flag;
+    a.item_done = p.fused_blocks ? r->item_done : nullptr;
+    a.todo = p.fused_blocks ? r->todo : nullptr; a.n_todo = r->hand(H_ITEMS);
     a.pending_count = r->hand(H_FUSED);
     a.compressed = r->compressed;
-    a.n_rows = r->n; a.cursor = r->cur(CUR_ITEMS);
+    a.n_rows = r->shape.n; a.cursor = r->cur(CUR_ITEMS);
     a.lit_scratch = ctx->lit_scratch_b;
     if (ctx->sw.ddbg)  // diagnostic: phase shares of the previous block-item launch
         a.dbg = diag_cycle<8>(ctx, znippy_ctx::DIAG_ITEMS, s, ba, [](const unsigned long long *h) {
             if (h[0]) fprintf(stderr, "[znippy ddbg] block items=%llu  cycles per item: literals=%.0f seq-tables=%.0f seq-decode=%.0f execute=%.0f tail=%.0f\n", h[0],
                               (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], (double)h[4] / h[0], (double)h[5] / h[0]);
         });
-    if (!p.lean_blocks) timed(ctx, "zstd_decode_blocks", ba, [&] { launch_decode(a, std::min<int>(ctx->decode_grid, (int)r->n_items), false, ba); });
-    if (r->fz_total) run_two_phase(ctx, r, run, ba);
+    if (p.block_decoder) timed(ctx, "zstd_decode_blocks", ba, [&] { launch_decode(a, p.items_grid, false, ba); });
+    if (p.two_phase) run_two_phase(ctx, r, run, ba);
     if (!p.one_stream) HIPCHK(ctx, hipEventRecord(ctx->ev_join, ctx->aux));
     return ZNIPPY_OK;
 }
 
 static BxArgs rows_bx_args(znippy_ctx *ctx, const znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     BxArgs x{};
-    x.list_a = r->list_a; x.n_list_a = r->n_list_a;
+    x.list_a = r->list_a; x.n_list_a = r->shape.n_list_a;
     x.pending = r->pending; x.pending_count = r->hand(H_FUSED);
     if (p.small_off) {  // every row is the batch path's: its list is all rows, nothing was handed over (a word that stays zero)
-        x.list_a = r->all_rows; x.n_list_a = r->n;
+        x.list_a = r->all_rows; x.n_list_a = r->shape.n;
         x.pending_count = r->ctl_at<uint32_t>(CTL_RX, RX_ZERO);
     }
-    x.bc_row = r->cand_row; x.n_bc = r->n_cand;
+    x.bc_row = r->cand_row; x.n_bc = r->shape.n_cand;
     fill_row_args(x, r, run);
     x.row_flag = r->row_flag;
-    x.cand_row = r->bx_cand_row; x.cand_base = r->bx_cand_base; x.cand_nb = r->bx_cand_nb; x.slot_cap = r->bx_slots;
-    x.items = r->bx_items; x.prep = r->bx_prep; x.item_cap = r->bx_item_cap;
+    x.cand_row = r->bx_cand_row; x.cand_base = r->bx_cand_base; x.cand_nb = r->bx_cand_nb; x.slot_cap = r->shape.bx_slots;
+    x.items = r->bx_items; x.prep = r->bx_prep; x.item_cap = r->shape.bx_item_cap;
     x.ctr = r->ctl_at<uint32_t>(CTL_BX_CTR);
     x.huf_list = r->bx_huf_list; x.seq_list = r->bx_seq_list; x.sort_tmp = r->bx_sort_tmp;
     x.lit_pool = ctx->fz_lit_pool; x.lit_cap = ctx->fz_lit_cap; x.seq_pool = ctx->fz_seq_pool; x.seq_cap = ctx->fz_seq_cap;
     x.fse_pool = ctx->bx_fse_pool; x.fse_cap = ctx->bx_fse_cap; x.huf_pool = ctx->bx_huf_pool; x.huf_cap = ctx->bx_huf_cap;
     x.pool_used = r->ctl_at<unsigned long long>(CTL_BX_POOL);
     x.pending2 = r->pending2; x.pending2_count = r->hand(H_SERIAL);
-    // 0: the blocks that get a wave of their own are picked from the table's histogram (k_bx_split: one workgroup per
-    // list, worth its ~0.1-0.4 ms where the chip is not full of blocks anyway); big tables keep the fixed threshold
-    x.big_seq = ctx->sw.bx_big_set || r->bx_nblk > 32768 ? ctx->sw.bx_big : 0u;
+    x.big_seq = p.big_seq;
     if (p.rx) {
         x.rx_ptr = ctx->rx_pool; x.rx_cap = ctx->rx_cap; x.rx_chunk = ctx->rx_chunk; x.rx_cdone = ctx->rx_cdone;
         x.rx_base = r->rx_base; x.rx_fail = r->rx_fail; x.rx_blk = r->rx_blk; x.rx_list = r->rx_list;
         x.rx_pending = r->ctl_at<uint32_t>(CTL_RX);
-        x.rx_bound = std::min<uint64_t>(r->rx_words, ctx->rx_cap);
-        x.rx_min = r->rx_min;
+        x.rx_bound = p.rx_bound;
+        x.rx_min = r->shape.rx_min;
     }
-    x.xxh_on = ctx->batch_checksums && r->bx_cand_ck;
-    x.xxh_forms = r->xxh_forms; x.cand_ck = r->bx_cand_ck; x.xxh_stat = r->ctl_at<unsigned long long>(CTL_BX_XXH);
-    x.small_frames = r->n_compressed && r->bx_bytes / r->n_compressed <= 65536;
+    x.xxh_on = p.xxh;
+    x.xxh_forms = r->shape.xxh_forms; x.cand_ck = r->bx_cand_ck; x.xxh_stat = r->ctl_at<unsigned long long>(CTL_BX_XXH);
+    x.small_frames = p.small_frames;
     if (ctx->sw.ddbg)  // diagnostic: where the previous run's table kernel spent its waves' time
         x.dbg = diag_cycle<128>(ctx, znippy_ctx::DIAG_BX, ctx->stream, nullptr, [](const unsigned long long *h) {
             if (h[64]) {
@@ -2015,7 +1668,7 @@ static int run_resolve(znippy_ctx *ctx, znippy_rows *r, const BxArgs &x) {
         (void)hipMemcpy(g, r->ctl + CTL_BX_CTR.at, CTL_BX_CTR.bytes, hipMemcpyDeviceToHost);
         (void)hipMemcpy(pu, r->ctl + CTL_BX_POOL.at, CTL_BX_POOL.bytes, hipMemcpyDeviceToHost);
         fprintf(stderr, "[znippy trace] resolve plan: slots %u items %u list %u frames %u words %llu extent %llu cap %llu item_cap %u\n", g[0], g[1], g[9], g[11], pu[10], pu[11],
-                (unsigned long long)ctx->rx_cap, r->bx_item_cap);
+                (unsigned long long)ctx->rx_cap, r->shape.bx_item_cap);
     }
     HIPCHK(ctx, hipEventRecord(ctx->ev_fork, s));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->aux, ctx->ev_fork, 0));
@@ -2042,7 +1695,7 @@ static int run_resolve(znippy_ctx *ctx, znippy_rows *r, const BxArgs &x) {
 static int run_batch_path(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     hipStream_t s = ctx->stream;
     const DecodeArgs a = rows_decode_args(ctx, r, run);
-    if (r->n_cand) {
+    if (p.items) {
         HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
         launch_finish_blocks(rows_scan_args(r, run), s, true);  // unflagged candidates are done; flagged ones wait for the batch path's verdict
     }
@@ -2073,7 +1726,7 @@ static int run_batch_path(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
     // frames with a content checksum that were decoded above: a wrong trailer makes the frame undecoded again (the finish stage lists it)
     if (x.xxh_on) timed(ctx, "zstd_batch_checksum", s, [&] { launch_bx_stage(x, ctx->cus, BX_XXH, s); });
     bx_stage(ctx, x, BX_FINISH, s);
-    decode_rest(ctx, r, a, r->n_compressed);
+    decode_rest(ctx, r, p, a);
     return ZNIPPY_OK;
 }
 // 2b') round-2 flow (no batch path: ZNIPPY_NO_BX, no pools, or a table whose last run handed nothing over): the serial
@@ -2087,28 +1740,24 @@ static int run_serial_flow(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, co
         launch_finish_blocks(rows_scan_args(r, run), s, false);
     }
     if (p.lean_blocks) return ZNIPPY_OK;
-    // A full grid of this kernel (4 workgroups per CU at 128 VGPRs) is the whole register file: whatever the auxiliary
-    // stream launches then waits until workgroups run out of rows.  With candidates for the block / foreign-frame
-    // paths it leaves them a quarter.
-    const int gen_grid = r->n_cand && !p.behind ? ctx->decode_grid / 4 * ctx->gen_share : ctx->decode_grid;
-    timed(ctx, "zstd_decode_general", s, [&] { launch_decode(a, std::min<int>(gen_grid, (int)r->n_compressed), r->wide_rows, s); });
-    if (!r->n_cand) return ZNIPPY_OK;
+    timed(ctx, "zstd_decode_general", s, [&] { launch_decode(a, p.general_grid, r->shape.wide_rows, s); });
+    if (!p.items) return ZNIPPY_OK;
     if (!p.behind) {  // join (block items and the foreign-frame path on the auxiliary stream), then what both gave up on
         HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
         launch_finish_blocks(rows_scan_args(r, run), s, false);
     }
-    decode_rest(ctx, r, a, r->n_cand);
+    decode_rest(ctx, r, p, a);
     return ZNIPPY_OK;
 }
 
 // 3) second hash pass: slices of big rows + rows the decoders finished (stored_only: every tile), then the big rows' trees
 static void run_second_hash(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     hipStream_t s = ctx->stream;
-    HashArgs h = rows_hash_args(ctx, r, run);
+    HashArgs h = rows_hash_args(ctx, r, p, run);
     h.pass = p.stored_only ? 0 : 2;  // PASS_ALL : PASS_SECOND
-    h.tile_done = r->n_bt && !p.stored_only ? r->tile_done : nullptr;
+    h.tile_done = p.hash_skips_done ? r->tile_done : nullptr;
     timed(ctx, run.verify ? "blake3_hash_only" : "blake3_second_pass", s, [&] { launch_hash_tiles(h, s); });
-    if (r->plan.n_big)
+    if (p.merge_big)
         timed(ctx, "blake3_merge_big", s, [&] {
             launch_merge_big(r->plan.big, r->plan.n_big, r->plan.tile_cv, r->digests, r->plan.grp_big, r->plan.grp_k, r->plan.n_grp, r->plan.max_cvs, s);
         });
@@ -2117,8 +1766,8 @@ static void run_second_hash(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, c
 // 3') decode-only runs: no hash pass — what is left of it is the copy of the stored rows no kernel in front has written (stored rows
 //     above a tile; stored_only: every row)
 static void run_copy_stored(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
-    if (!p.stored_only && !r->plan.n_big) return;
-    const HashArgs h = rows_hash_args(ctx, r, run);
+    if (!p.copy_stored) return;
+    const HashArgs h = rows_hash_args(ctx, r, p, run);
     timed(ctx, "copy_stored", ctx->stream, [&] { launch_copy_stored(h, p.stored_only, ctx->stream); });
 }
 
@@ -2126,11 +1775,9 @@ static void run_copy_stored(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, c
 static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const RowsRun &run) {
     hipStream_t s = run.on;
     if (p.lean_mixed) HIPCHK(ctx, hipStreamWaitEvent(s, ctx->ev_join, 0));
-    const bool skipped = p.lean || p.lean_blocks || p.lean_mixed;
-    // A lean run has nothing between its one kernel and the verify, and nothing of the NEXT run's kernels reads what the verify
-    // writes (the other slot is theirs): verify, result copy and the run's event go to the auxiliary stream behind an event, and
-    // the next run's kernel follows this run's directly.  The slot's next run is ordered behind ev_done (run_clear).
-    if (ctx->fork_verify && p.lean) {
+    // (a lean run's) verify, result copy and the run's event go to the auxiliary stream behind an event, and the next run's kernel
+    // follows this run's directly.  The slot's next run is ordered behind ev_done (run_clear).
+    if (p.verify_aux) {
         HIPCHK(ctx, hipEventRecord(r->ev_main[run.slot], s));
         if (run.lane_ev) HIPCHK(ctx, hipEventRecord(run.lane_ev, s));  // (what later lane runs and the main stream wait for: lane_begin)
         s = ctx->aux;
@@ -2139,8 +1786,8 @@ static int run_verify(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const R
     }
     // (decode-only: the counters pass alone — no checksum column, no digest read, every decoded row counts as verified)
     timed(ctx, run.plain ? "count_rows" : "verify", s, [&] {
-        launch_verify(r->digests, run.plain ? nullptr : r->checksum, r->usize, r->status, r->n, r->row_begin, r->counters, r->corrupt, r->corrupt_cap, s,
-                      skipped ? r->ctl_at<uint32_t>(CTL_HAND) : nullptr, (p.lean || p.lean_mixed) ? LEAN_SMALL : LEAN_BLOCKS);
+        launch_verify(r->digests, run.plain ? nullptr : r->checksum, r->usize, r->status, r->shape.n, r->row_begin, r->counters, r->corrupt, r->corrupt_cap, s,
+                      p.check_lists ? r->ctl_at<uint32_t>(CTL_HAND) : nullptr, p.lists_small ? LEAN_SMALL : LEAN_BLOCKS);
     });
     HIPCHK(ctx, hipMemcpyAsync(r->h_counters + 16 * run.slot, r->counters, CTL_MIRROR, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipEventRecord(r->ev_done[run.slot], s));
@@ -2229,28 +1876,28 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         d_out = ctx->vs_pool; out_cap = r->vs_bytes;
     }
     if (!rc) rc = rows_validate(ctx, r, blob_base, out_cap, verify);
-    if (!rc && r->fz_total) rc = ensure_fz_pools(ctx, r->fz_bytes, r->fz_total);
-    if (!rc && r->bx_slots) {
-        rc = ensure_fz_pools(ctx, r->bx_bytes, r->bx_item_cap);
-        if (!rc) rc = ensure_bx_pools(ctx, r->bx_bytes, r->bx_item_cap);
-        if (!rc && r->rx_base && rows_route_hint(r, plain) != 0) rc = ensure_rx_pool(ctx, r->rx_words);
-        if (!rc && ctx->batch_checksums && !r->bx_cand_ck && tmalloc(ctx, &r->bx_cand_ck, 4 * (size_t)r->bx_slots) != hipSuccess) rc = ZNIPPY_E_NOMEM;
+    if (!rc && r->shape.fz_total) rc = ensure_fz_pools(ctx, r->shape.fz_bytes, r->shape.fz_total);
+    if (!rc && r->shape.bx_slots) {
+        rc = ensure_fz_pools(ctx, r->shape.bx_bytes, r->shape.bx_item_cap);
+        if (!rc) rc = ensure_bx_pools(ctx, r->shape.bx_bytes, r->shape.bx_item_cap);
+        if (!rc && r->rx_base && rows_route_hint(r->hints, plain) != 0) rc = ensure_rx_pool(ctx, r->shape.rx_words);
+        if (!rc && ctx->batch_checksums && !r->bx_cand_ck && tmalloc(ctx, &r->bx_cand_ck, 4 * (size_t)r->shape.bx_slots) != hipSuccess) rc = ZNIPPY_E_NOMEM;
     }
     if (rc) return rc;
-    if (r->n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
-    if (r->run_seq && rows_route_hint(r, plain) < 0 && r->n) {  // a run of this table has finished meanwhile?
+    if (r->shape.n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
+    if (r->run_seq && rows_route_hint(r->hints, plain) < 0 && r->shape.n) {  // a run of this table has finished meanwhile?
         const unsigned last = (unsigned)((r->run_seq - 1) & 1);
         const bool last_plain = r->run_args[last].plain;  // (a decode-only run teaches the table's own hints nothing)
         if (last_plain && !plain) (void)0;
         else if (hipEventQuery(r->ev_done[last]) != hipSuccess) (void)hipGetLastError();
-        else if (last_plain) rows_note_plain(r, last);
-        else rows_note_hint(r, last);
+        else if (last_plain) rows_note_plain(r->shape, r->hints, r->mirror_hand(last));
+        else rows_note_hint(r->shape, r->hints, r->mirror_hand(last));
     }
-    RowsRun run{d_blobs, blob_base, d_out, out_cap, r->n_bad ? 1 : 0, slot, verify, plain, ctx->stream, nullptr};
-    const RunPlan p = rows_plan(ctx, r, run.preset, plain);
+    RowsRun run{d_blobs, blob_base, d_out, out_cap, r->hints.n_bad ? 1 : 0, slot, verify, plain, ctx->stream, nullptr};
+    const RunPlan p = rows_plan(r->shape, r->hints, rows_run_env(ctx, r, d_out), run.preset, verify, plain);
     if (p.small_off && !r->all_rows) {
-        if (tmalloc(ctx, &r->all_rows, 4 * (size_t)r->n) != hipSuccess) return ZNIPPY_E_NOMEM;
-        hipLaunchKernelGGL(k_iota32, dim3((r->n + 255) / 256), dim3(256), 0, ctx->stream, r->all_rows, r->n);
+        if (tmalloc(ctx, &r->all_rows, 4 * (size_t)r->shape.n) != hipSuccess) return ZNIPPY_E_NOMEM;
+        hipLaunchKernelGGL(k_iota32, dim3((r->shape.n + 255) / 256), dim3(256), 0, ctx->stream, r->all_rows, r->shape.n);
     }
     { auto &ra = r->run_args[slot]; ra.blobs = d_blobs; ra.base = blob_base; ra.out = verify ? nullptr : d_out; ra.cap = verify ? 0 : out_cap; ra.blob_cap = r->blob_cap; ra.verify = verify; ra.plain = plain; }
     r->select(slot);
@@ -2261,10 +1908,10 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         if (p.lean) ctx->lane_stats[3]++;  // a lean run kept off the lanes: a caller's stream, or a switch
         lanes_close(ctx);                  // what this run queues on the main stream stands behind every lane run
     }
-    if ((rc = run_clear(ctx, r, p, run)) || !r->n) return rc;
+    if ((rc = run_clear(ctx, r, p, run)) || p.empty) return rc;
     if (!p.small_off && !p.stored_only && (rc = run_small_rows(ctx, r, p, run))) return rc;
-    if (p.decode && r->n_cand && (rc = run_block_items(ctx, r, p, run))) return rc;
-    if (p.decode && r->n_compressed && (rc = p.bx ? run_batch_path(ctx, r, p, run) : run_serial_flow(ctx, r, p, run))) return rc;
+    if (p.items && (rc = run_block_items(ctx, r, p, run))) return rc;
+    if (p.decoders && (rc = p.bx ? run_batch_path(ctx, r, p, run) : run_serial_flow(ctx, r, p, run))) return rc;
     if (plain) run_copy_stored(ctx, r, p, run);
     else if (!p.lean) run_second_hash(ctx, r, p, run);
     return run_verify(ctx, r, p, run);
@@ -2290,8 +1937,7 @@ static void rows_abandon(znippy_ctx *ctx, znippy_rows *r) {
     (void)hipStreamSynchronize(ctx->stream);
     (void)hipGetLastError();
     r->run_seq = 0;
-    r->force_full = true;
-    r->lean_hint = 0; r->lean_hint2 = 0;
+    rows_force_full(r->hints);
 }
 
 int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs,
@@ -2299,7 +1945,7 @@ int znippy_decode_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void 
     if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
-    if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
+    if (r->shape.n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
     return rows_queue(ctx, r, d_blobs, blob_base, d_out, out_cap, false);
 }
 
@@ -2308,7 +1954,7 @@ int znippy_decode_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blob
     if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
     if (r->no_out) return ZNIPPY_E_INVAL;  // created without output offsets: verify-only
-    if (r->n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
+    if (r->shape.n && (!d_blobs || !d_out)) return ZNIPPY_E_INVAL;
     return rows_queue(ctx, r, d_blobs, blob_base, d_out, out_cap, false, true);
 }
 
@@ -2317,7 +1963,7 @@ int znippy_decode_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blob
 int znippy_verify_rows_async(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base) {
     if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
-    if (r->n && !d_blobs) return ZNIPPY_E_INVAL;
+    if (r->shape.n && !d_blobs) return ZNIPPY_E_INVAL;
     return rows_queue(ctx, r, d_blobs, blob_base, nullptr, 0, true);
 }
 
@@ -2330,14 +1976,14 @@ int znippy_rows_verify_scratch(znippy_ctx *ctx, znippy_rows *r, const void **d_b
     if (rc) return rc;
     *d_base = r->vs_bytes ? ctx->vs_pool : nullptr;
     *bytes = r->vs_bytes;
-    if (row_offset && r->n) {
-        std::vector<uint8_t> comp(r->n);
-        std::vector<uint64_t> len(r->n);
+    if (row_offset && r->shape.n) {
+        std::vector<uint8_t> comp(r->shape.n);
+        std::vector<uint64_t> len(r->shape.n);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        HIPCHK(ctx, hipMemcpy(row_offset, r->vs_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(comp.data(), r->compressed, r->n, hipMemcpyDeviceToHost));
-        HIPCHK(ctx, hipMemcpy(len.data(), r->usize, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < r->n; i++)
+        HIPCHK(ctx, hipMemcpy(row_offset, r->vs_off, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(comp.data(), r->compressed, r->shape.n, hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(len.data(), r->usize, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < r->shape.n; i++)
             if (!comp[i] || !len[i]) row_offset[i] = ~0ull;
     }
     return ZNIPPY_OK;
@@ -2353,13 +1999,12 @@ int znippy_rows_verify_scratch(znippy_ctx *ctx, znippy_rows *r, const void **d_b
 // clear: no slot is repeated twice.  Only runs over changed blobs get here, so the cost of the second repeat does not matter.
 // Called by everything that hands a run's results to the caller.
 static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
-    if (!r->n || !r->run_seq || !(r->h_counters[16 * slot + 7])) return ZNIPPY_OK;
+    if (!r->shape.n || !r->run_seq || !(r->h_counters[16 * slot + 7])) return ZNIPPY_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, lanes_sync(ctx));                 // the latest run's kernel may be queued there
     HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
-    r->force_full = true;
-    r->lean_hint = 0; r->lean_hint2 = 0;
+    rows_force_full(r->hints);
     const unsigned latest = (unsigned)((r->run_seq - 1) & 1);
     const unsigned order[2] = {slot, latest};
     for (int i = 0; i < (slot == latest ? 1 : 2); i++) {
@@ -2383,13 +2028,13 @@ int znippy_rows_results_lagged(znippy_ctx *ctx, znippy_rows *r, unsigned lag, zn
     if (!ctx_enter(ctx, ENTER_RUN)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx || !counters || lag > 1 || r->run_seq <= lag) return ZNIPPY_E_INVAL;
     uint64_t c[8] = {0};
-    if (r->n) {
+    if (r->shape.n) {
         const unsigned slot = (unsigned)((r->run_seq - 1 - lag) & 1);
         HIPCHK(ctx, hipEventSynchronize(r->ev_done[slot]));
         { const int rc = rows_settle(ctx, r, slot); if (rc) return rc; }
         memcpy(c, r->h_counters + 16 * slot, 64);
-        if (r->run_args[slot].plain) rows_note_plain(r, slot);
-        else rows_note_hint(r, slot);
+        if (r->run_args[slot].plain) rows_note_plain(r->shape, r->hints, r->mirror_hand(slot));
+        else rows_note_hint(r->shape, r->hints, r->mirror_hand(slot));
     }
     counters->total_chunks = c[0]; counters->total_written_bytes = c[1]; counters->verified_bytes = c[2];
     counters->corrupt_bytes = c[3]; counters->corrupt_rows = c[4]; counters->decode_errors = c[5];
@@ -2405,11 +2050,12 @@ int znippy_rows_results(znippy_ctx *ctx, znippy_rows *r, znippy_verify_counters 
     if (r->lane_used) HIPCHK(ctx, lanes_sync(ctx));
     if (r->aux_used) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     uint64_t c[8] = {0};
-    if (r->n && r->run_seq) {
+    if (r->shape.n && r->run_seq) {
         { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
         memcpy(c, r->h_counters + 16 * ((r->run_seq - 1) & 1), 64);  // copied by the run itself (pinned)
-        if (r->run_args[(r->run_seq - 1) & 1].plain) rows_note_plain(r, (unsigned)((r->run_seq - 1) & 1));
-        else rows_note_hint(r, (unsigned)((r->run_seq - 1) & 1));
+        const unsigned slot = (unsigned)((r->run_seq - 1) & 1);
+        if (r->run_args[slot].plain) rows_note_plain(r->shape, r->hints, r->mirror_hand(slot));
+        else rows_note_hint(r->shape, r->hints, r->mirror_hand(slot));
     }
     if (counters) {
         counters->total_chunks = c[0]; counters->total_written_bytes = c[1]; counters->verified_bytes = c[2];
@@ -2422,9 +2068,9 @@ int znippy_rows_results(znippy_ctx *ctx, znippy_rows *r, znippy_verify_counters 
         std::sort(tmp.begin(), tmp.end());
         memcpy(corrupt_rows, tmp.data(), 8 * std::min<uint64_t>(k, corrupt_cap));
     }
-    if (row_status && r->n) {
-        HIPCHK(ctx, hipMemcpy(row_status, r->status, 4 * (size_t)r->n, hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < r->n; i++)
+    if (row_status && r->shape.n) {
+        HIPCHK(ctx, hipMemcpy(row_status, r->status, 4 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+        for (uint32_t i = 0; i < r->shape.n; i++)
             if (row_status[i] > 0) row_status[i] = 0;  // internal routing states (1, 2) are successes
     }
     return ZNIPPY_OK;
@@ -2460,15 +2106,15 @@ int znippy_verify_rows(znippy_ctx *ctx, znippy_rows *rows, const void *d_blobs, 
 // The columns a call validates and plans against, on the host: fetched once per table from the device copies, which hold the
 // effective lengths (a stored row's length is its blob).  The same three vectors rows_validate fills for its per-row pass.
 static int rows_host_columns(znippy_ctx *ctx, znippy_rows *r) {
-    if (!r->n || (!r->h_blob_off.empty() && !r->h_comp.empty())) return ZNIPPY_OK;
+    if (!r->shape.n || (!r->h_blob_off.empty() && !r->h_comp.empty())) return ZNIPPY_OK;
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     // (into temporaries: a copy that fails leaves the table without a half-filled cache)
-    std::vector<uint64_t> bo(r->n), bs(r->n), len(r->n);
-    std::vector<uint8_t> comp(r->n);
-    HIPCHK(ctx, hipMemcpy(bo.data(), r->blob_off, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(bs.data(), r->blob_size, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(len.data(), r->usize, 8 * (size_t)r->n, hipMemcpyDeviceToHost));
-    HIPCHK(ctx, hipMemcpy(comp.data(), r->compressed, r->n, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> bo(r->shape.n), bs(r->shape.n), len(r->shape.n);
+    std::vector<uint8_t> comp(r->shape.n);
+    HIPCHK(ctx, hipMemcpy(bo.data(), r->blob_off, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(bs.data(), r->blob_size, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(len.data(), r->usize, 8 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(comp.data(), r->compressed, r->shape.n, hipMemcpyDeviceToHost));
     if (r->h_blob_off.empty()) { r->h_blob_off.swap(bo); r->h_blob_size.swap(bs); r->h_len.swap(len); }
     r->h_comp.swap(comp);
     return ZNIPPY_OK;
@@ -2476,14 +2122,14 @@ static int rows_host_columns(znippy_ctx *ctx, znippy_rows *r) {
 
 // What a call plans against (host/range_plan.h): the host columns above and, where they exist, the tree's layout and verdicts.
 static RrTable rows_table_view(const znippy_rows *r) {
-    return RrTable{r->n, r->row_begin, r->blob_cap, r->h_blob_off.data(), r->h_blob_size.data(), r->h_len.data(), r->h_comp.data(),
+    return RrTable{r->shape.n, r->row_begin, r->blob_cap, r->h_blob_off.data(), r->h_blob_size.data(), r->h_len.data(), r->h_comp.data(),
                    r->tree_first.data(), r->tree_first.size(), r->tree_accept.data(), r->tree_accept.size()};
 }
 
 // The checksum column on the host (verified range reads give the private tables of their whole-row passes the rows' checksums).
 static int rows_host_checksum(znippy_ctx *ctx, znippy_rows *r) {
-    if (!r->n || !r->checksum || !r->h_checksum.empty()) return ZNIPPY_OK;
-    std::vector<uint8_t> ck((size_t)32 * r->n);
+    if (!r->shape.n || !r->checksum || !r->h_checksum.empty()) return ZNIPPY_OK;
+    std::vector<uint8_t> ck((size_t)32 * r->shape.n);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(ck.data(), r->checksum, ck.size(), hipMemcpyDeviceToHost));
     r->h_checksum.swap(ck);
@@ -2539,8 +2185,8 @@ static int rr_decode_whole(znippy_ctx *ctx, const znippy_rows *r, std::vector<Rr
 static int rows_tree_layout(znippy_ctx *ctx, znippy_rows *r) {
     const int rc = rows_host_columns(ctx, r);
     if (rc || !r->tree_first.empty()) return rc;
-    std::vector<uint64_t> first((size_t)r->n + 1, 0);
-    for (uint32_t i = 0; i < r->n; i++) first[i + 1] = first[i] + tree_entries_of(r->h_len[i]);
+    std::vector<uint64_t> first((size_t)r->shape.n + 1, 0);
+    for (uint32_t i = 0; i < r->shape.n; i++) first[i + 1] = first[i] + tree_entries_of(r->h_len[i]);
     r->tree_first.swap(first);
     return ZNIPPY_OK;
 }
@@ -2668,7 +2314,7 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
                             uint64_t out_cap, int32_t *range_status, uint64_t *decoded_bytes, bool verified = false, uint64_t *hashed_bytes = nullptr) {
     if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
     if (!ctx || !r || r->ctx != ctx) return ZNIPPY_E_INVAL;
-    if (verified && !r->checksum && r->n) return ZNIPPY_E_INVAL;  // nothing to verify against
+    if (verified && !r->checksum && r->shape.n) return ZNIPPY_E_INVAL;  // nothing to verify against
     if (decoded_bytes) *decoded_bytes = 0;
     if (hashed_bytes) *hashed_bytes = 0;
     if (!n_ranges) return ZNIPPY_OK;
@@ -2737,8 +2383,8 @@ static int rows_block_tree_layout(znippy_ctx *ctx, znippy_rows *r, uint64_t *n_e
     HIPCHK(ctx, hipSetDevice(ctx->device));
     const int rc = rows_tree_layout(ctx, r);
     if (rc) return rc;
-    *n_entries = r->tree_first[r->n];
-    if (row_first) memcpy(row_first, r->tree_first.data(), 8 * ((size_t)r->n + 1));
+    *n_entries = r->tree_first[r->shape.n];
+    if (row_first) memcpy(row_first, r->tree_first.data(), 8 * ((size_t)r->shape.n + 1));
     return ZNIPPY_OK;
 }
 
@@ -2750,10 +2396,10 @@ static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_
     HIPCHK(ctx, hipSetDevice(ctx->device));
     int rc = rows_tree_layout(ctx, r);
     if (rc) return rc;
-    const uint64_t n_entries = r->tree_first[r->n];
+    const uint64_t n_entries = r->tree_first[r->shape.n];
     if (n_entries && (!d_blobs || !tree)) return ZNIPPY_E_INVAL;
-    std::vector<int32_t> st(r->n, 0);
-    if (row_status && r->n) memset(row_status, 0, 4 * (size_t)r->n);
+    std::vector<int32_t> st(r->shape.n, 0);
+    if (row_status && r->shape.n) memset(row_status, 0, 4 * (size_t)r->shape.n);
     if (!n_entries) return ZNIPPY_OK;
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
@@ -2789,9 +2435,9 @@ static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_
     }
     HIPCHK(ctx, hipMemcpyAsync(tree, g.a, 32 * (size_t)n_entries, hipMemcpyDeviceToHost, s));
     HIPCHK(ctx, hipStreamSynchronize(s));
-    for (uint32_t ri = 0; ri < r->n; ri++)  // a row that failed has no entries to offer
+    for (uint32_t ri = 0; ri < r->shape.n; ri++)  // a row that failed has no entries to offer
         if (st[ri]) memset(tree + 32 * r->tree_first[ri], 0, 32 * (size_t)(r->tree_first[ri + 1] - r->tree_first[ri]));
-    if (row_status) memcpy(row_status, st.data(), 4 * (size_t)r->n);
+    if (row_status) memcpy(row_status, st.data(), 4 * (size_t)r->shape.n);
     return ZNIPPY_OK;
 }
 
@@ -2803,7 +2449,7 @@ static int rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *t
     if (!r->checksum) return ZNIPPY_E_INVAL;  // nothing could authenticate the entries
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    if (row_status && r->n) memset(row_status, 0, 4 * (size_t)r->n);
+    if (row_status && r->shape.n) memset(row_status, 0, 4 * (size_t)r->shape.n);
     if (!tree) {
         HIPCHK(ctx, hipStreamSynchronize(s));
         tfree(ctx, r->tree_dev);
@@ -2813,15 +2459,15 @@ static int rows_set_block_tree(znippy_ctx *ctx, znippy_rows *r, const uint8_t *t
     }
     int rc = rows_tree_layout(ctx, r);
     if (rc) return rc;
-    const uint64_t n_entries = r->tree_first[r->n];
+    const uint64_t n_entries = r->tree_first[r->shape.n];
     ctx->n_ktimes = 0;
     SyncFree<uint32_t> g{ctx};  // a = the tree on the device
-    std::vector<uint8_t> accept(r->n, 0);
+    std::vector<uint8_t> accept(r->shape.n, 0);
     if (n_entries) {
         if (tmalloc(ctx, &g.a, 32 * (size_t)n_entries) != hipSuccess) return ZNIPPY_E_NOMEM;
         HIPCHK(ctx, hipMemcpyAsync(g.a, tree, 32 * (size_t)n_entries, hipMemcpyHostToDevice, s));
         std::vector<uint32_t> sel, ok;
-        for (uint32_t ri = 0; ri < r->n; ri++)
+        for (uint32_t ri = 0; ri < r->shape.n; ri++)
             if (r->tree_first[ri + 1] != r->tree_first[ri]) sel.push_back(ri);
         if ((rc = tree_fold_check(ctx, r, g.a, sel, ok))) return rc;
         for (size_t i = 0; i < sel.size(); i++) {
@@ -2848,9 +2494,9 @@ int znippy_rows_digests(znippy_ctx *ctx, znippy_rows *r, uint8_t *digests) {
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     if (r->lane_used) HIPCHK(ctx, lanes_sync(ctx));
     if (r->aux_used) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
-    if (r->n && r->run_seq) { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
+    if (r->shape.n && r->run_seq) { const int rc = rows_settle(ctx, r, (unsigned)((r->run_seq - 1) & 1)); if (rc) return rc; }
     if (r->run_seq && r->run_args[(r->run_seq - 1) & 1].plain) return ZNIPPY_E_INVAL;  // a decode-only run computes no digest
-    if (r->n) HIPCHK(ctx, hipMemcpy(digests, r->digests, 32 * (size_t)r->n, hipMemcpyDeviceToHost));
+    if (r->shape.n) HIPCHK(ctx, hipMemcpy(digests, r->digests, 32 * (size_t)r->shape.n, hipMemcpyDeviceToHost));
     return ZNIPPY_OK;
 }
 

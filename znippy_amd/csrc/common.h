@@ -5,30 +5,9 @@
 #include <stdint.h>
 #include <stddef.h>
 #include "host/range_plan.h"
+#include "host/rows_plan.h"  // Tile, BigUnit and the constants the read side's host plan shares with the kernels
 
 namespace zn {
-
-// A hash work item = one wavefront's worth of BLAKE3 leaves (<= 64 x 1 KiB).
-//   n_units >= 1 : `n_units` whole small units (each <= 64 leaves) packed so their leaves fill
-//                  the wave's lanes; digests are finished inside the wave.
-//   n_units == 0 : leaves [first_leaf, first_leaf+n_leaves) of big unit `first_unit`
-//                  (first_leaf is a multiple of 64 -> a complete subtree); the subtree CV goes
-//                  to tile_cv[cv_index] and the big-unit merge kernel finishes the tree.
-struct Tile {
-    uint32_t first_unit;
-    uint32_t n_units;
-    uint32_t first_leaf;
-    uint32_t n_leaves;
-    uint32_t cv_index;
-    uint32_t pad;
-};
-
-struct BigUnit {  // a unit with more than 64 leaves
-    uint32_t unit;
-    uint32_t cv_base;  // first tile CV of this unit in tile_cv
-    uint32_t n_cvs;    // ceil(leaves/64) >= 2
-    uint32_t pad;      // n_cvs > 64: index (in CVs) of this unit's group CVs in tile_cv, ceil(n_cvs/64) of them
-};
 
 // Where each unit's bytes live.  Units with sel==0 (or all units when sel==nullptr) are hashed
 // from srcA+offA[u]; when copy_to_B is set those bytes are also copied to srcB+offB[u] (store
@@ -231,7 +210,6 @@ struct BxPrep {            // per block item, written by k_bx_prep
     uint32_t bs_len;       // bytes
 };
 constexpr uint32_t BX_BIG_SEQ = 2048;  // blocks of this many sequences get a wave of their own in the sequence stage
-constexpr uint32_t BX_PREDEF_LL = 0, BX_PREDEF_OF = 64, BX_PREDEF_ML = 96, BX_POOL_FIRST = 160;  // predefined tables at the head of the FSE pool
 // FSE pool cell (2 bytes): symbol:6 | ns:10 << 6 (zstd_batch.hip)
 struct BxArgs {
     const uint32_t *list_a; uint32_t n_list_a;
@@ -280,8 +258,7 @@ struct BxArgs {
     uint32_t *cand_ck;                  // per candidate slot (written by the scan when xxh_on): 1 = the frame's last 4 bytes are its checksum
     unsigned long long *xxh_stat;       // [0] frames checked and right, [1] checked and wrong, [2] content bytes hashed (zeroed per run)
 };
-constexpr uint32_t XXH_WAVE_MIN = (64u << 10) + 1;  // checksum stage: frames of at least this many bytes get a wave, smaller ones four lanes
-constexpr uint32_t RX_NONE = 0xFFFFFFFFu, RX_DONE = 0x80000000u, RX_MIN = 256u << 10, RX_ROUNDS = 12, RX_JUMPS = 6;
+constexpr uint32_t RX_NONE = 0xFFFFFFFFu, RX_DONE = 0x80000000u, RX_ROUNDS = 12, RX_JUMPS = 6;
 // the batch path's launches, in the order of a run: scan, prep (the tables), sort the work lists, fse (wave = block) beside huf
 // and fse (lane = block), then exec — or the resolve path: plan, exec beside expand, jump round r, store —, the content checksums
 // (xxh: only with BxArgs::xxh_on), finish
@@ -298,7 +275,6 @@ void launch_range_gather(const RangePiece *pieces, uint32_t n_pieces, hipStream_
 void launch_range_status(const uint32_t *row_flag, const uint64_t *block_bytes, uint32_t n_rows, uint8_t *late, unsigned long long *decoded, hipStream_t s);
 
 // Block tree (block_tree.hip): one 32-byte entry per 128 KiB block of a row of more than one block (and below 4 GiB).
-constexpr uint32_t BLOCK_TREE_BLK = 128u << 10;
 // write mode: out != NULL; compare mode: expect != NULL, verdict[item] = 1 if the block's chaining value equals expect[slot]
 void launch_block_cvs(const BlockCvItem *items, uint32_t n_items, uint32_t *out, const uint32_t *expect, uint32_t *verdict, hipStream_t s);
 // verdict[i] = 1 if rows[i]'s entries fold to checksum[32 * row ..]
