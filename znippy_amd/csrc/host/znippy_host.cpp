@@ -5,6 +5,7 @@
 #include "../../../include/znippy_host.h"
 #include "../../../include/znippy_hip.h"
 #include "arrow_ipc.h"
+#include "read_plan.h"
 #include "zip_dir.h"
 
 #include <hip/hip_runtime.h>
@@ -58,9 +59,8 @@ uint32_t blob_align() {
     const unsigned long a = v && *v ? strtoul(v, nullptr, 10) : 1;
     return a >= 1 && a <= 4096 && !(a & (a - 1)) ? (uint32_t)a : 1u;
 }
-// File I/O helper threads.  Readers (compress_dir: open/pread/close, lstat) scale to ~16 threads; writers that
-// CREATE files in one directory contend on its lock and are fastest at ~4 (tmpfs, 100k files: 1 writer 0.50 s,
-// 2: 0.41 s, 4: 0.38 s, 8: 0.52 s, 16: 0.78 s, 32: 1.2 s).  ZNIPPY_HOST_READERS / ZNIPPY_HOST_WRITERS override.
+// File I/O helper threads.  Readers (compress_dir: open/pread/close, lstat) scale to ~16 threads; writers are fastest at ~4
+// (the table is beside cut_writers, read_plan.h).  ZNIPPY_HOST_READERS / ZNIPPY_HOST_WRITERS override.
 unsigned env_threads(const char *name, unsigned dflt) {
     unsigned hw = std::thread::hardware_concurrency();
     cpu_set_t set;
@@ -233,22 +233,9 @@ void mkdirs(const std::string &dir) {
     }
 }
 
-// Contiguous [begin,end) per rank, balanced by sum(weights)
-std::pair<uint64_t, uint64_t> split_rows(const std::vector<uint64_t> &w, uint32_t rank, uint32_t world) {
-    const uint64_t n = w.size();
-    if (world <= 1) return {0, n};
-    std::vector<long double> c(n);
-    long double acc = 0;
-    for (uint64_t i = 0; i < n; i++) { acc += (long double)std::max<uint64_t>(w[i], 1); c[i] = acc; }
-    std::vector<uint64_t> cuts(world + 1, n);
-    cuts[0] = 0;
-    for (uint32_t r = 1; r < world; r++) {
-        long double target = acc * r / world;
-        cuts[r] = (uint64_t)(std::lower_bound(c.begin(), c.end(), target) - c.begin());
-    }
-    for (uint32_t r = 1; r <= world; r++) cuts[r] = std::max(cuts[r], cuts[r - 1]);
-    return {cuts[rank], cuts[rank + 1]};
-}
+using zn::IndexView;
+using zn::RowTable;
+static_assert(zn::RDP_E_CORRUPT == ZNIPPY_E_CORRUPT, "read_plan.h gives out ZNIPPY_E_CORRUPT");
 
 }  // namespace
 
@@ -258,6 +245,14 @@ struct znippy_index {
     std::map<std::string, std::string> metadata;
     uint64_t blob_end = 0, file_size = 0;
     size_t n() const { return rows.rows(); }
+    IndexView view() const {  // the eight base columns by name (load_index_impl has put them in index_schema()'s order)
+        const auto &c = rows.cols;
+        IndexView v;
+        v.path = c[0].str.data(); v.chunk_seq = c[1].u32.data(); v.fdata_offset = c[2].u64.data(); v.compressed = c[3].u8.data();
+        v.usize = c[4].u64.data(); v.blob_offset = c[5].u64.data(); v.blob_size = c[6].u64.data(); v.checksum = c[7].u8.data();
+        v.n = n(); v.file_size = file_size;
+        return v;
+    }
 };
 
 // A file is untrusted input: every length is checked against the file before anything is allocated or indexed,
@@ -594,9 +589,9 @@ uint64_t write_metadata(int fd, uint64_t blob_end, const std::vector<RowMeta> &r
 
 // The block tree sidecar `<archive path>.b3t` (znippy_host.h): header + the rows' entries in the order the index numbers the rows —
 // sub-index by sub-index, batch by batch, as write_metadata lays them down.
-constexpr char B3T_MAGIC[9] = "ZNPYB3T1";
-constexpr uint32_t B3T_BLOCK_LOG = 17;
-constexpr size_t B3T_HEADER = 32;
+using zn::B3T_BLOCK_LOG;
+using zn::B3T_HEADER;
+using zn::B3T_MAGIC;
 
 bool write_sidecar(const std::string &archive_path, const std::vector<RowMeta> &rows, const std::vector<uint8_t> &tree, const std::vector<SubIndex> &subs) {
     std::vector<uint8_t> out(B3T_HEADER, 0);
@@ -986,64 +981,58 @@ struct ReadBufs {
     double t_read = 0, t_h2d = 0, t_kern = 0;
 };
 
+bool read_into_slab(int fd, uint8_t *slab, const std::vector<zn::SlabRead> &reads) {
+    for (const zn::SlabRead &r : reads)
+        if (!pread_all(fd, slab + r.at, r.len, r.fpos)) return false;
+    return true;
+}
+
+// A private device table of t's rows over a blob region of blob_cap bytes (~0: not declared): a row pointing outside what was
+// read is an error code, not a device fault.
+int create_rows(znippy_ctx *ctx, const RowTable &t, const uint64_t *out_off, uint64_t blob_cap, znippy_rows **rt) {
+    const int rc = znippy_rows_create(ctx, t.bo.data(), t.bs.data(), t.bitmap.data(), t.us.data(), out_off, t.ck.empty() ? nullptr : t.ck.data(), 0, t.n(), rt);
+    if (rc) return fail(rc, "znippy_rows_create failed");
+    znippy_rows_set_blob_cap(*rt, blob_cap);
+    return ZNIPPY_OK;
+}
+
+// "checksum mismatch" / "decompress failed" of the first row or range that has one
+int sweep_status(const std::vector<int32_t> &st, const char *rel) {
+    for (int32_t v : st) {
+        if (v == ZNIPPY_E_DIGEST) return fail(ZNIPPY_E_CHECKSUM, std::string("checksum mismatch in ") + rel);
+        if (v < 0) return fail(v, "OpenZL-equivalent decompress failed");
+    }
+    return ZNIPPY_OK;
+}
+
 // Blob bytes -> HBM -> decode+verify kernels; the decoded rows stay in bufs.d_out (the caller decides whether
 // they cross PCIe at all).  Stands for the worker loop body, decompress.rs:L135-190.  keep_out = false (save_data=false,
 // L186-189): no output region at all — the rows are checked by a verify-only run (znippy_verify_rows) and bufs.d_out is not touched.
 // decode_only (with keep_out and without verify: the extract path, archive.rs:L144-168): a decode-only run (znippy_decode_rows) — nothing is hashed.
 int decode_range(znippy_ctx *ctx, int arc_fd, const znippy_index &ix, const uint64_t *row_ids, size_t n, bool verify, ReadBufs &bufs,
                  DecodedRange *dr, bool keep_out = true, bool decode_only = false) {
-    std::vector<uint64_t> bo(n), bs(n), us(n);
-    std::vector<uint8_t> bitmap((n + 7) / 8, 0), ck(verify ? 32 * n : 0);
-    dr->out_off.assign(n, 0);
-    dr->len.assign(n, 0);
+    zn::RowsRead p = zn::plan_rows_read(ix.view(), row_ids, n, verify);
+    if (p.rc) return fail(p.rc, p.err);
+    dr->out_off.swap(p.out_off);
+    dr->len = p.t.us;
+    dr->total = p.total;
     dr->status.assign(n, 0);
-    dr->total = 0;
     dr->cnt = znippy_verify_counters{};
-    uint64_t lo = UINT64_MAX, hi = 0, sum = 0;
-    for (size_t k = 0; k < n; k++) {
-        const uint64_t r = row_ids[k];
-        bo[k] = ix.rows.cols[5].u64[r]; bs[k] = ix.rows.cols[6].u64[r];
-        us[k] = ix.rows.cols[3].u8[r] ? ix.rows.cols[4].u64[r] : bs[k];  // a stored row is its blob
-        dr->len[k] = us[k];
-        if (dr->total + us[k] < dr->total) return fail(ZNIPPY_E_CORRUPT, "row sizes overflow");
-        if (ix.rows.cols[3].u8[r]) bitmap[k >> 3] |= (uint8_t)(1u << (k & 7));
-        if (verify) std::memcpy(&ck[32 * k], &ix.rows.cols[7].u8[32 * r], 32);
-        dr->out_off[k] = dr->total;
-        dr->total += us[k];
-        if (bo[k] > ix.file_size || bs[k] > ix.file_size - bo[k]) return fail(ZNIPPY_E_CORRUPT, "blob range outside the archive");
-        lo = std::min(lo, bo[k]);
-        hi = std::max(hi, bo[k] + bs[k]);
-        sum += bs[k];
-    }
     if (!n) return ZNIPPY_OK;
     double t = now_s();
-    uint64_t base = lo, nblob = hi - lo;
-    if (nblob > 2 * sum + (1u << 20)) {  // scattered rows: pack them instead of reading the span between them
-        if (!bufs.blob_pin.reserve(sum + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
-        uint64_t pos = 0;
-        for (size_t k = 0; k < n; k++) {
-            if (bs[k] && !pread_all(arc_fd, bufs.blob_pin.p + pos, bs[k], bo[k])) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
-            bo[k] = pos;
-            pos += bs[k];
-        }
-        base = 0;
-        nblob = sum;
-    } else {
-        if (!bufs.blob_pin.reserve(nblob + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
-        if (nblob && !pread_all(arc_fd, bufs.blob_pin.p, nblob, lo)) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
-    }
+    if (!bufs.blob_pin.reserve(p.nblob + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+    if (!read_into_slab(arc_fd, bufs.blob_pin.p, p.reads)) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
     bufs.t_read += now_s() - t; t = now_s();
-    if (!bufs.d_blobs.reserve(nblob + 64) || (keep_out && !bufs.d_out.reserve(dr->total + 64))) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
-    if (nblob && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, nblob, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+    if (!bufs.d_blobs.reserve(p.nblob + 64) || (keep_out && !bufs.d_out.reserve(dr->total + 64))) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+    if (p.nblob && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, p.nblob, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
     bufs.t_h2d += now_s() - t; t = now_s();
     znippy_rows *rt = nullptr;
-    int rc = znippy_rows_create(ctx, bo.data(), bs.data(), bitmap.data(), us.data(), keep_out ? dr->out_off.data() : nullptr, verify ? ck.data() : nullptr, 0, n, &rt);
-    if (rc) return fail(rc, "znippy_rows_create failed");
-    znippy_rows_set_blob_cap(rt, nblob);  // a row pointing outside what was read is an error code, not a device fault
+    int rc = create_rows(ctx, p.t, keep_out ? dr->out_off.data() : nullptr, p.nblob, &rt);
+    if (rc) return rc;
     std::vector<uint64_t> cr(n);
-    if (keep_out && decode_only && !verify) rc = znippy_decode_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, dr->status.data());
-    else if (keep_out) rc = znippy_decode_verify_rows(ctx, rt, bufs.d_blobs.p, base, bufs.d_out.p, dr->total, &dr->cnt, cr.data(), n, dr->status.data());
-    else rc = znippy_verify_rows(ctx, rt, bufs.d_blobs.p, base, &dr->cnt, cr.data(), n, dr->status.data());
+    if (keep_out && decode_only && !verify) rc = znippy_decode_rows(ctx, rt, bufs.d_blobs.p, p.base, bufs.d_out.p, dr->total, &dr->cnt, dr->status.data());
+    else if (keep_out) rc = znippy_decode_verify_rows(ctx, rt, bufs.d_blobs.p, p.base, bufs.d_out.p, dr->total, &dr->cnt, cr.data(), n, dr->status.data());
+    else rc = znippy_verify_rows(ctx, rt, bufs.d_blobs.p, p.base, &dr->cnt, cr.data(), n, dr->status.data());
     znippy_rows_destroy(rt);
     if (rc) return fail(rc, std::string("decode failed: ") + znippy_last_error(ctx));
     bufs.t_kern += now_s() - t;
@@ -1055,11 +1044,11 @@ int decode_range(znippy_ctx *ctx, int arc_fd, const znippy_index &ix, const uint
 // when this rank owns the whole archive, truncated) at its first row; rows of one file are adjacent, so one
 // cached descriptor per writer replaces the reference's table of open files.
 struct RowWriter {
-    const znippy_index *ix;
+    IndexView ix;
     const char *out_dir;
     const std::vector<uint8_t> *first_touch;
     bool truncate;  // this process owns the whole archive: O_TRUNC on first touch, like the reference (L74-101)
-    const std::unordered_map<std::string, uint64_t> *final_size;  // several ranks share the files: first touch sets the final size
+    const std::unordered_map<std::string, uint64_t> *final_size;  // several ranks share the files: first touch sets the final size (read_plan_first_touch)
     std::atomic<int> *err;
     void operator()(const uint8_t *bytes, const DecodedRange *dr, uint64_t row0, uint64_t k0, uint64_t k1) const {
         std::string cur_dir;
@@ -1071,7 +1060,7 @@ struct RowWriter {
                 fprintf(stderr, "[decomp] row %llu error=%d\n", (unsigned long long)r, dr->status[k]);
                 continue;
             }
-            const std::string &p = ix->rows.cols[0].str[r];
+            const std::string &p = ix.path[r];
             if (!cur_path || *cur_path != p) {
                 if (fd >= 0) close(fd);
                 const std::string full = std::string(out_dir) + "/" + p;
@@ -1083,15 +1072,12 @@ struct RowWriter {
                 fd = open(full.c_str(), O_CREAT | O_WRONLY | ((first && truncate) ? O_TRUNC : 0), 0644);
                 cur_path = &p;
                 if (fd < 0) { err->store(1); g_open_failed(p); return; }
-                // Ranks write disjoint parts of a file in any order, so none of them may O_TRUNC; instead every rank
-                // sets the file to its final length when it first touches it (idempotent: every row lies inside
-                // that length) — a longer file left from an earlier run loses its stale tail.
                 if (first && !truncate && final_size) {
                     auto it = final_size->find(p);
                     if (it != final_size->end() && ftruncate(fd, (off_t)it->second) != 0) err->store(2);
                 }
             }
-            if (!pwrite_all(fd, bytes + dr->out_off[k], dr->len[k], ix->rows.cols[2].u64[r])) err->store(2);
+            if (!pwrite_all(fd, bytes + dr->out_off[k], dr->len[k], ix.fdata_offset[r])) err->store(2);
         }
         if (fd >= 0) close(fd);
     }
@@ -1111,40 +1097,11 @@ static int znippy_decompress_archive_impl(const char *index_path, int save_data,
     int rc = load_index(index_path, &ix);
     if (rc) return rc;
     const double t_index = now_s();
-    const uint64_t n_rows = ix.n();
-    const auto &paths = ix.rows.cols[0].str;
-    // unique paths (L64-69) + the first row of every path; rows of a path that are not adjacent (duplicate entries)
-    // force a single writer so that the first-touch truncate cannot race with a later row's write
-    std::vector<uint8_t> first_touch(n_rows, 0);
-    bool adjacent = true;
-    size_t n_unique = 0;
-    {
-        std::unordered_set<std::string> uniq;
-        uniq.reserve(n_rows * 2);
-        for (uint64_t r = 0; r < n_rows; r++) {
-            if (r && paths[r] == paths[r - 1]) continue;
-            if (uniq.insert(paths[r]).second) first_touch[r] = 1;
-            else adjacent = false;
-        }
-        n_unique = uniq.size();
-    }
-    const auto range = split_rows(ix.rows.cols[4].u64, rank, world);
-    std::unordered_map<std::string, uint64_t> final_size;
-    if (world > 1 && save_data) {
-        // first touch is per rank (the first row of a path inside MY range), and comes with the file's final length
-        std::fill(first_touch.begin(), first_touch.end(), 0);
-        std::unordered_set<std::string> seen;
-        for (uint64_t r = range.first; r < range.second; r++) {
-            if (r > range.first && paths[r] == paths[r - 1]) continue;
-            if (seen.insert(paths[r]).second) first_touch[r] = 1;
-        }
-        final_size.reserve(n_unique * 2);
-        for (uint64_t r = 0; r < n_rows; r++) {
-            const uint64_t len = ix.rows.cols[3].u8[r] ? ix.rows.cols[4].u64[r] : ix.rows.cols[6].u64[r];
-            uint64_t &fs = final_size[paths[r]];
-            fs = std::max(fs, ix.rows.cols[2].u64[r] + len);
-        }
-    }
+    const IndexView view = ix.view();
+    const std::string *paths = view.path;
+    const auto range = zn::split_rows(view.usize, view.n, rank, world);
+    const zn::FirstTouch touch = zn::read_plan_first_touch(view, range.first, range.second, world > 1 && save_data);
+    const size_t n_unique = touch.n_unique;
     if (save_data) mkdirs(out_dir);
     int arc = open(index_path, O_RDONLY);
     if (arc < 0) return fail(ZNIPPY_E_INVAL, "cannot open archive");
@@ -1169,21 +1126,18 @@ static int znippy_decompress_archive_impl(const char *index_path, int save_data,
         void join() { for (auto &t : writers) t.join(); writers.clear(); }
     } slabs[2];
     std::atomic<int> werr{0};
-    const RowWriter writer{&ix, out_dir, &first_touch, world == 1, world > 1 ? &final_size : nullptr, &werr};
-    const unsigned n_writers = adjacent ? writer_threads() : 1;
+    const RowWriter writer{view, out_dir, &touch.first, world == 1, world > 1 ? &touch.final_size : nullptr, &werr};
+    const unsigned n_writers = touch.adjacent ? writer_threads() : 1;
     const uint64_t batch_bytes = range_bytes(save_data != 0);
     // save_data=false: rows are verified without being written (ZNIPPY_NO_VERIFY_ONLY=1 in the environment: decoded into a region
-    // that is thrown away, as before — for A/B).  What such a range takes on the device is its blobs and the scratch of its
-    // compressed rows, so that is what a range is cut by.
+    // that is thrown away, as before — for A/B); cut_batch cuts such a range by what it takes on the device.
     const bool verify_only = !save_data && !env_on("ZNIPPY_NO_VERIFY_ONLY");
     double t_d2h = 0, t_wjoin = 0;
     int which = 0, n_ranges = 0;
     uint64_t i = range.first;
     std::vector<uint64_t> ids;
     while (i < range.second && rc == ZNIPPY_OK && !werr.load()) {
-        uint64_t j = i, nbytes = 0;
-        const auto row_cost = [&](uint64_t r) { return verify_only ? ix.rows.cols[6].u64[r] + (ix.rows.cols[3].u8[r] ? ix.rows.cols[4].u64[r] : 0) : ix.rows.cols[4].u64[r]; };
-        while (j < range.second && (j == i || nbytes + row_cost(j) <= batch_bytes)) nbytes += row_cost(j++);
+        const uint64_t j = zn::cut_batch(view, i, range.second, batch_bytes, verify_only);
         ids.resize(j - i);
         for (uint64_t k = i; k < j; k++) ids[k - i] = k;
         OutSlab &sl = slabs[which];
@@ -1207,20 +1161,8 @@ static int znippy_decompress_archive_impl(const char *index_path, int save_data,
             if (!sl.pin.reserve(sl.dr.total + 64)) { rc = fail(ZNIPPY_E_NOMEM, "page-locked allocation failed"); break; }
             if (sl.dr.total && hipMemcpy(sl.pin.p, bufs.d_out.p, sl.dr.total, hipMemcpyDeviceToHost) != hipSuccess) { rc = fail(ZNIPPY_E_HIP, "D2H failed"); break; }
             t_d2h += now_s() - t;
-            // split [i,j) into contiguous parts of about equal bytes, cut only where the path changes
-            const uint64_t n = j - i;
-            uint64_t k0 = 0;
-            for (unsigned w = 0; w < n_writers && k0 < n; w++) {
-                uint64_t k1 = n;
-                if (w + 1 < n_writers) {
-                    const uint64_t target = sl.dr.total / n_writers * (w + 1);
-                    k1 = (uint64_t)(std::lower_bound(sl.dr.out_off.begin() + k0, sl.dr.out_off.end(), target) - sl.dr.out_off.begin());
-                    k1 = std::max(k1, k0 + 1);
-                    while (k1 < n && paths[i + k1] == paths[i + k1 - 1]) k1++;
-                }
-                sl.writers.emplace_back(writer, sl.pin.p, &sl.dr, i, k0, k1);
-                k0 = k1;
-            }
+            for (const auto &part : zn::cut_writers(sl.dr.out_off.data(), sl.dr.total, paths, i, j - i, n_writers))
+                sl.writers.emplace_back(writer, sl.pin.p, &sl.dr, i, part.first, part.second);
             which ^= 1;
         }
         i = j;
@@ -1276,35 +1218,84 @@ struct znippy_archive {
 };
 
 namespace {
-uint64_t tree_entries_of(uint64_t n) { return n > (128u << 10) && n < (1ull << 32) ? (n + (128u << 10) - 1) / (128u << 10) : 0; }
-
-// A sidecar that is missing, malformed, or disagrees with the index in n_rows or n_entries is ignored.
+// A sidecar that is missing, malformed, or disagrees with the index in n_rows or n_entries is ignored (zn::sidecar_layout).
 void load_sidecar(znippy_archive *a) {
     const std::string path = a->path + ".b3t";
     const int fd = open(path.c_str(), O_RDONLY);
     if (fd < 0) return;
     struct stat st;
     std::vector<uint8_t> raw;
-    const bool ok = fstat(fd, &st) == 0 && (uint64_t)st.st_size >= B3T_HEADER && ((uint64_t)st.st_size - B3T_HEADER) % 32 == 0 &&
-                    (raw.resize((size_t)st.st_size), pread_all(fd, raw.data(), raw.size(), 0));
+    const bool ok = fstat(fd, &st) == 0 && (raw.resize((size_t)st.st_size), pread_all(fd, raw.data(), raw.size(), 0));
     close(fd);
-    if (!ok) return;
-    uint32_t log = 0, zero = 0;
-    uint64_t n_rows = 0, n_entries = 0;
-    std::memcpy(&log, raw.data() + 8, 4);
-    std::memcpy(&zero, raw.data() + 12, 4);
-    std::memcpy(&n_rows, raw.data() + 16, 8);
-    std::memcpy(&n_entries, raw.data() + 24, 8);
-    if (std::memcmp(raw.data(), B3T_MAGIC, 8) != 0 || log != B3T_BLOCK_LOG || zero != 0 || n_rows != a->ix.n() ||
-        n_entries != (raw.size() - B3T_HEADER) / 32)
-        return;
-    const auto &c = a->ix.rows.cols;
-    std::vector<uint64_t> first(a->ix.n() + 1, 0);
-    for (uint64_t r = 0; r < a->ix.n(); r++) first[r + 1] = first[r] + tree_entries_of(c[3].u8[r] ? c[4].u64[r] : c[6].u64[r]);
-    if (first.back() != n_entries) return;
+    std::vector<uint64_t> first;
+    if (!ok || !zn::sidecar_layout(raw.data(), raw.size(), a->ix.view(), &first)) return;
     a->side_tree.assign(raw.begin() + B3T_HEADER, raw.end());
+    a->tree_stats[0] = first.back();
     a->side_first.swap(first);
-    a->tree_stats[0] = n_entries;
+}
+
+int archive_ctx(znippy_archive *a) {  // the context is created at the first call that needs the GPU
+    if (a->ctx) return ZNIPPY_OK;
+    if (hipSetDevice(a->device) != hipSuccess) return fail(ZNIPPY_E_HIP, "hipSetDevice failed");
+    const int rc = znippy_ctx_create(a->device, nullptr, &a->ctx);
+    return rc ? fail(rc, "no usable GPU: the codec/hash path has no CPU fallback") : ZNIPPY_OK;
+}
+
+// Verified range reads: rows `fresh` of the read's table t (table row k is archive row arow[k]) have entries and no cached tree yet.
+// First the sidecar's entries for them are offered — as one private table over the same slab — and cached without any decode where
+// znippy_rows_set_block_tree accepts them against the index checksum; *fresh becomes the rows it refused.
+int offer_sidecar(znippy_archive *a, const RowTable &t, const std::vector<uint64_t> &arow, std::vector<size_t> *fresh) {
+    const RowTable ft = t.subset(*fresh);
+    std::vector<uint8_t> tree;
+    for (size_t k : *fresh) {  // (the sidecar's layout was checked against the index: this row has tree_entries_of(us[k]) there)
+        const uint64_t *first = &a->side_first[arow[k]];
+        zn::take_tree(a->side_tree.data(), 32 * (size_t)first[0], first[1] - first[0], &tree);
+    }
+    znippy_rows *bt = nullptr;
+    int rc = create_rows(a->ctx, ft, nullptr, ~0ull, &bt);
+    if (rc) return rc;
+    std::vector<int32_t> bst(ft.n(), 0);
+    rc = znippy_rows_set_block_tree(a->ctx, bt, tree.data(), bst.data());
+    znippy_rows_destroy(bt);
+    if (rc) return fail(rc, std::string("block tree check failed: ") + znippy_last_error(a->ctx));
+    std::vector<size_t> rest;
+    size_t at = 0;
+    for (size_t i = 0; i < ft.n(); i++) {
+        std::vector<uint8_t> entries;
+        at = zn::take_tree(tree.data(), at, zn::tree_entries_of(ft.us[i]), &entries);
+        if (bst[i] == 0) {
+            a->block_trees[arow[(*fresh)[i]]] = std::move(entries);
+            a->tree_stats[1]++;
+        } else {  // rejected: the whole-decode build
+            rest.push_back((*fresh)[i]);
+            a->tree_stats[2]++;
+        }
+    }
+    fresh->swap(rest);
+    return ZNIPPY_OK;
+}
+
+// ... the rest is built: one private table, one whole decode of its rows (their blobs are in bufs.d_blobs) whose digests must be
+// the index checksums.
+int build_trees(znippy_archive *a, const RowTable &t, const std::vector<uint64_t> &arow, const std::vector<size_t> &fresh, const char *rel) {
+    const RowTable ft = t.subset(fresh);
+    uint64_t n_entries = 0;
+    for (uint64_t us : ft.us) n_entries += zn::tree_entries_of(us);
+    znippy_rows *bt = nullptr;
+    int rc = create_rows(a->ctx, ft, nullptr, ft.sum, &bt);
+    if (rc) return rc;
+    std::vector<uint8_t> tree(32 * (size_t)n_entries);
+    std::vector<int32_t> bst(ft.n(), 0);
+    rc = znippy_rows_block_tree_build(a->ctx, bt, a->bufs.d_blobs.p, 0, tree.data(), bst.data());
+    znippy_rows_destroy(bt);
+    if (rc) return fail(rc, std::string("block tree build failed: ") + znippy_last_error(a->ctx));
+    if ((rc = sweep_status(bst, rel))) return rc;
+    size_t at = 0;
+    for (size_t i = 0; i < ft.n(); i++) {
+        at = zn::take_tree(tree.data(), at, zn::tree_entries_of(ft.us[i]), &a->block_trees[arow[fresh[i]]]);
+        a->tree_stats[3]++;
+    }
+    return ZNIPPY_OK;
 }
 }  // namespace
 
@@ -1318,11 +1309,10 @@ static int znippy_archive_open_impl(const char *path, int device, znippy_archive
     a->device = device;
     int rc = load_index(path, &a->ix);
     if (rc) return rc;
-    for (uint64_t r = 0; r < a->ix.n(); r++) a->files[a->ix.rows.cols[0].str[r]].push_back(r);
+    const IndexView v = a->ix.view();
+    for (uint64_t r = 0; r < v.n; r++) a->files[v.path[r]].push_back(r);
     for (auto &kv : a->files)
-        std::stable_sort(kv.second.begin(), kv.second.end(), [&](uint64_t x, uint64_t y) {
-            return a->ix.rows.cols[2].u64[x] < a->ix.rows.cols[2].u64[y];
-        });
+        std::stable_sort(kv.second.begin(), kv.second.end(), [&](uint64_t x, uint64_t y) { return v.fdata_offset[x] < v.fdata_offset[y]; });
     a->fd = open(path, O_RDONLY);
     if (a->fd < 0) return fail(ZNIPPY_E_INVAL, "cannot open archive");
     load_sidecar(a.get());
@@ -1337,7 +1327,7 @@ int64_t znippy_archive_file_size(const znippy_archive *a, const char *rel) {
     auto it = a->files.find(rel);
     if (it == a->files.end()) return -1;
     uint64_t s = 0;
-    for (uint64_t r : it->second) s += a->ix.rows.cols[4].u64[r];
+    for (uint64_t r : it->second) s += a->ix.view().usize[r];
     return (int64_t)s;
 }
 
@@ -1345,16 +1335,13 @@ static int znippy_archive_extract_file_impl(znippy_archive *a, const char *rel, 
     if (!a || !rel || !written) return fail(ZNIPPY_E_INVAL, "null argument");
     auto it = a->files.find(rel);
     if (it == a->files.end()) return fail(ZNIPPY_E_INVAL, std::string("file not found in archive: ") + rel);
-    if (!a->ctx) {
-        if (hipSetDevice(a->device) != hipSuccess) return fail(ZNIPPY_E_HIP, "hipSetDevice failed");
-        int rc = znippy_ctx_create(a->device, nullptr, &a->ctx);
-        if (rc) return fail(rc, "no usable GPU: the codec/hash path has no CPU fallback");
-    }
+    int rc = archive_ctx(a);
+    if (rc) return rc;
     DecodedRange dr;
     // the unverified extract hashes nothing (ZNIPPY_NO_DECODE_ONLY=1 in the environment: the decode + verify run without a checksum
     // column, as before — for A/B runs)
     const bool decode_only = !verify && !env_on("ZNIPPY_NO_DECODE_ONLY");
-    int rc = decode_range(a->ctx, a->fd, a->ix, it->second.data(), it->second.size(), verify != 0, a->bufs, &dr, true, decode_only);
+    rc = decode_range(a->ctx, a->fd, a->ix, it->second.data(), it->second.size(), verify != 0, a->bufs, &dr, true, decode_only);
     if (rc) return rc;
     for (int32_t st : dr.status)
         if (st < 0) return fail(st, "OpenZL-equivalent decompress failed");  // propagates (archive.rs:L160)
@@ -1378,140 +1365,46 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
     *written = 0;
     auto it = a->files.find(rel);
     if (it == a->files.end()) return fail(ZNIPPY_E_INVAL, std::string("file not found in archive: ") + rel);
-    const auto &c = a->ix.rows.cols;
-    const uint64_t end = offset + len < offset ? UINT64_MAX : offset + len;
-    std::vector<uint64_t> bo, bs, us, rr, rb, rl, arow;
-    std::vector<uint8_t> bitmap, ck;
-    uint64_t sum = 0, total = 0;
-    for (uint64_t r : it->second) {  // (sorted by fdata_offset)
-        const uint64_t lo = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];  // a stored row is its blob
-        const uint64_t x = std::max(offset, lo), y = std::min(end, lo + n);
-        if (x >= y) continue;
-        const size_t k = bo.size();
-        if (c[5].u64[r] > a->ix.file_size || c[6].u64[r] > a->ix.file_size - c[5].u64[r]) return fail(ZNIPPY_E_CORRUPT, "blob range outside the archive");
-        bo.push_back(sum); bs.push_back(c[6].u64[r]); us.push_back(n);
-        if ((k & 7) == 0) bitmap.push_back(0);
-        if (c[3].u8[r]) bitmap[k >> 3] |= (uint8_t)(1u << (k & 7));
-        rr.push_back(k); rb.push_back(x - lo); rl.push_back(y - x);
-        if (verify) { arow.push_back(r); ck.insert(ck.end(), &c[7].u8[32 * r], &c[7].u8[32 * r] + 32); }
-        sum += c[6].u64[r];
-        total += y - x;
-    }
-    if (bo.empty()) return ZNIPPY_OK;  // at or past the end of the file, or an empty range
-    if (!a->ctx) {
-        if (hipSetDevice(a->device) != hipSuccess) return fail(ZNIPPY_E_HIP, "hipSetDevice failed");
-        int rc = znippy_ctx_create(a->device, nullptr, &a->ctx);
-        if (rc) return fail(rc, "no usable GPU: the codec/hash path has no CPU fallback");
-    }
+    const zn::RangeRead p = zn::plan_range_read(a->ix.view(), it->second.data(), it->second.size(), offset, len, verify != 0);
+    if (p.rc) return fail(p.rc, "blob range outside the archive");
+    const RowTable &t = p.t;
+    if (!t.n()) return ZNIPPY_OK;  // at or past the end of the file, or an empty range
+    int rc = archive_ctx(a);
+    if (rc) return rc;
     ReadBufs &bufs = a->bufs;
-    if (!bufs.blob_pin.reserve(std::max<uint64_t>(sum, total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
-    {
-        size_t k = 0;
-        for (uint64_t r : it->second) {  // the same walk: the touched chunks' blobs, packed
-            const uint64_t lo = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];
-            if (std::max(offset, lo) >= std::min(end, lo + n)) continue;
-            if (bs[k] && !pread_all(a->fd, bufs.blob_pin.p + bo[k], bs[k], c[5].u64[r])) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
-            k++;
-        }
-    }
-    if (!bufs.d_blobs.reserve(sum + 64) || !bufs.d_out.reserve(total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
-    if (sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
-    int rc = ZNIPPY_OK;
-    if (verify) {  // chunks with entries that this handle has not built yet: one private table, one build
-        auto entries_of = [](uint64_t n) -> uint64_t { return tree_entries_of(n); };
+    if (!bufs.blob_pin.reserve(std::max<uint64_t>(t.sum, p.total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+    if (!read_into_slab(a->fd, bufs.blob_pin.p, t.reads())) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
+    if (!bufs.d_blobs.reserve(t.sum + 64) || !bufs.d_out.reserve(p.total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+    if (t.sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, t.sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+    if (verify) {  // chunks with entries that this handle has not built yet
         std::vector<size_t> fresh;
-        for (size_t k = 0; k < bo.size(); k++)
-            if (entries_of(us[k]) && !a->block_trees.count(arow[k])) fresh.push_back(k);
-        if (!fresh.empty() && !a->side_first.empty()) {  // the sidecar's entries for these chunks: offered, and cached without any decode if accepted
-            std::vector<uint64_t> fbo, fbs, fus;
-            std::vector<uint8_t> fbm((fresh.size() + 7) / 8, 0), fck, tree;
-            for (size_t i = 0; i < fresh.size(); i++) {
-                const size_t k = fresh[i];
-                fbo.push_back(bo[k]); fbs.push_back(bs[k]); fus.push_back(us[k]);
-                if ((bitmap[k >> 3] >> (k & 7)) & 1) fbm[i >> 3] |= (uint8_t)(1u << (i & 7));
-                fck.insert(fck.end(), &ck[32 * k], &ck[32 * k] + 32);
-                const uint64_t r = arow[k];  // (the sidecar's layout was checked against the index: this row has entries_of(us[k]) there)
-                tree.insert(tree.end(), a->side_tree.begin() + 32 * a->side_first[r], a->side_tree.begin() + 32 * a->side_first[r + 1]);
-            }
-            znippy_rows *bt = nullptr;
-            rc = znippy_rows_create(a->ctx, fbo.data(), fbs.data(), fbm.data(), fus.data(), nullptr, fck.data(), 0, fresh.size(), &bt);
-            if (rc) return fail(rc, "znippy_rows_create failed");
-            std::vector<int32_t> bst(fresh.size(), 0);
-            rc = znippy_rows_set_block_tree(a->ctx, bt, tree.data(), bst.data());
-            znippy_rows_destroy(bt);
-            if (rc) return fail(rc, std::string("block tree check failed: ") + znippy_last_error(a->ctx));
-            std::vector<size_t> rest;
-            size_t at = 0;
-            for (size_t i = 0; i < fresh.size(); i++) {
-                const size_t nb = 32 * (size_t)entries_of(fus[i]);
-                if (bst[i] == 0) {
-                    a->block_trees[arow[fresh[i]]].assign(tree.begin() + at, tree.begin() + at + nb);
-                    a->tree_stats[1]++;
-                } else {  // rejected: today's whole-decode build
-                    rest.push_back(fresh[i]);
-                    a->tree_stats[2]++;
-                }
-                at += nb;
-            }
-            fresh.swap(rest);
-        }
-        if (!fresh.empty()) {
-            std::vector<uint64_t> fbo, fbs, fus;
-            std::vector<uint8_t> fbm((fresh.size() + 7) / 8, 0), fck;
-            uint64_t n_entries = 0;
-            for (size_t i = 0; i < fresh.size(); i++) {
-                const size_t k = fresh[i];
-                fbo.push_back(bo[k]); fbs.push_back(bs[k]); fus.push_back(us[k]);
-                if ((bitmap[k >> 3] >> (k & 7)) & 1) fbm[i >> 3] |= (uint8_t)(1u << (i & 7));
-                fck.insert(fck.end(), &ck[32 * k], &ck[32 * k] + 32);
-                n_entries += entries_of(us[k]);
-            }
-            znippy_rows *bt = nullptr;
-            rc = znippy_rows_create(a->ctx, fbo.data(), fbs.data(), fbm.data(), fus.data(), nullptr, fck.data(), 0, fresh.size(), &bt);
-            if (rc) return fail(rc, "znippy_rows_create failed");
-            znippy_rows_set_blob_cap(bt, sum);
-            std::vector<uint8_t> tree(32 * (size_t)n_entries);
-            std::vector<int32_t> bst(fresh.size(), 0);
-            rc = znippy_rows_block_tree_build(a->ctx, bt, bufs.d_blobs.p, 0, tree.data(), bst.data());
-            znippy_rows_destroy(bt);
-            if (rc) return fail(rc, std::string("block tree build failed: ") + znippy_last_error(a->ctx));
-            for (int32_t v : bst) {
-                if (v == ZNIPPY_E_DIGEST) return fail(ZNIPPY_E_CHECKSUM, std::string("checksum mismatch in ") + rel);
-                if (v < 0) return fail(v, "OpenZL-equivalent decompress failed");
-            }
-            size_t at = 0;
-            for (size_t i = 0; i < fresh.size(); i++) {
-                const size_t nb = 32 * (size_t)entries_of(fus[i]);
-                a->block_trees[arow[fresh[i]]].assign(tree.begin() + at, tree.begin() + at + nb);
-                a->tree_stats[3]++;
-                at += nb;
-            }
-        }
+        for (size_t k = 0; k < t.n(); k++)
+            if (zn::tree_entries_of(t.us[k]) && !a->block_trees.count(p.arow[k])) fresh.push_back(k);
+        if (!fresh.empty() && !a->side_first.empty()) rc = offer_sidecar(a, t, p.arow, &fresh);
+        if (!rc && !fresh.empty()) rc = build_trees(a, t, p.arow, fresh, rel);
+        if (rc) return rc;
     }
     znippy_rows *rt = nullptr;
-    rc = znippy_rows_create(a->ctx, bo.data(), bs.data(), bitmap.data(), us.data(), nullptr, verify ? ck.data() : nullptr, 0, bo.size(), &rt);
-    if (rc) return fail(rc, "znippy_rows_create failed");
-    znippy_rows_set_blob_cap(rt, sum);
-    std::vector<int32_t> st(rr.size(), 0);
+    rc = create_rows(a->ctx, t, nullptr, t.sum, &rt);
+    if (rc) return rc;
+    const zn::RangeList &rg = p.rg;
+    std::vector<int32_t> st(rg.n(), 0);
     if (verify) {
-        std::vector<uint8_t> tree;
-        for (size_t k = 0; k < bo.size(); k++) {
-            auto bt = a->block_trees.find(arow[k]);
-            if (bt != a->block_trees.end()) tree.insert(tree.end(), bt->second.begin(), bt->second.end());
+        std::vector<uint8_t> tree;  // the tree of this table: its rows' cached entries, in row order
+        for (uint64_t r : p.arow) {
+            auto bt = a->block_trees.find(r);
+            if (bt != a->block_trees.end()) zn::take_tree(bt->second.data(), 0, bt->second.size() / 32, &tree);
         }
         tree.push_back(0);  // (never NULL: that would remove the tree)
         rc = znippy_rows_set_block_tree(a->ctx, rt, tree.data(), nullptr);
-        if (!rc) rc = znippy_rows_read_ranges_verified(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, st.data(), nullptr, nullptr);
+        if (!rc) rc = znippy_rows_read_ranges_verified(a->ctx, rt, bufs.d_blobs.p, 0, rg.row.data(), rg.begin.data(), rg.len.data(), nullptr, rg.n(), bufs.d_out.p, p.total, st.data(), nullptr, nullptr);
     } else
-        rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, st.data(), nullptr);
+        rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rg.row.data(), rg.begin.data(), rg.len.data(), nullptr, rg.n(), bufs.d_out.p, p.total, st.data(), nullptr);
     znippy_rows_destroy(rt);
     if (rc) return fail(rc, std::string("range read failed: ") + znippy_last_error(a->ctx));
-    for (int32_t v : st) {
-        if (v == ZNIPPY_E_DIGEST) return fail(ZNIPPY_E_CHECKSUM, std::string("checksum mismatch in ") + rel);
-        if (v < 0) return fail(v, "OpenZL-equivalent decompress failed");
-    }
-    if (hipMemcpy(dst, bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
-    *written = total;
+    if ((rc = sweep_status(st, rel))) return rc;
+    if (hipMemcpy(dst, bufs.d_out.p, p.total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+    *written = p.total;
     return ZNIPPY_OK;
 }
 
@@ -1520,81 +1413,36 @@ static int znippy_archive_read_range_impl(znippy_archive *a, const char *rel, ui
 // ---- entries of archived ZIP containers (znippy_archive_extract_zip_entries) ----------------------------
 namespace {
 
-struct FileRange {  // bytes [off, off + len) of one archived file, wholly inside it
-    const std::vector<uint64_t> *rows;  // the file's archive rows, sorted by fdata_offset
-    uint64_t off, len;
-};
+using zn::FileRange;  // bytes [off, off + len) of one archived file, wholly inside it
 
-// One range-read pass for many files: every request is mapped to the chunks it touches; of a stored chunk the requested bytes, of a
-// compressed chunk the whole frame (once per pass) are read from the archive and uploaded in one copy, ONE znippy_rows_read_ranges
-// over a private table of them gathers all requests packed back to back, and one copy brings them to the host: request i at
-// host[at[i] .. at[i] + len), st[i] = 0 or a chunk's ZNIPPY_E_*.  Nothing is kept between passes: a compressed chunk that two passes
-// touch is read and uploaded twice.
+// One range-read pass for many files (zn::plan_file_ranges): the planned blobs are read from the archive and uploaded in one copy,
+// ONE znippy_rows_read_ranges over a private table of them gathers all requests packed back to back, and one copy brings them to the
+// host: request i at host[at[i] .. at[i] + len), st[i] = 0 or a chunk's ZNIPPY_E_*.  Nothing is kept between passes: a compressed
+// chunk that two passes touch is read and uploaded twice.
 int read_file_ranges(znippy_archive *a, const std::vector<FileRange> &req, std::vector<uint8_t> *host, std::vector<uint64_t> *at,
                      std::vector<int32_t> *st) {
-    const auto &c = a->ix.rows.cols;
-    std::vector<uint64_t> bo, bs, us, fpos, rr, rb, rl;  // fpos: where a table row's blob bytes lie in the archive file
-    std::vector<uint8_t> bitmap;
-    std::vector<size_t> of_req;  // range -> request
-    std::unordered_map<uint64_t, uint64_t> row_at;
-    uint64_t sum = 0, total = 0;
-    at->assign(req.size(), 0);
-    st->assign(req.size(), 0);
-    for (size_t i = 0; i < req.size(); i++) {
-        (*at)[i] = total;
-        const uint64_t lo = req[i].off, hi = req[i].off + req[i].len;
-        uint64_t covered = 0;
-        const size_t first_range = rr.size();
-        for (uint64_t r : *req[i].rows) {
-            const uint64_t f0 = c[2].u64[r], n = c[3].u8[r] ? c[4].u64[r] : c[6].u64[r];  // a stored row is its blob
-            const uint64_t x = std::max(lo, f0), y = std::min(hi, f0 + n);
-            if (x >= y) continue;
-            if (c[5].u64[r] > a->ix.file_size || c[6].u64[r] > a->ix.file_size - c[5].u64[r]) { (*st)[i] = ZNIPPY_E_CORRUPT; break; }
-            if (!c[3].u8[r]) {
-                // a stored chunk is its blob: only the bytes asked for are read and uploaded, as a stored row of their own (a jar is
-                // stored by the extension rule, and of a jar of many MB the three passes want the tail, the directory and one entry)
-                const size_t k = bo.size();
-                bo.push_back(sum); bs.push_back(y - x); us.push_back(y - x); fpos.push_back(c[5].u64[r] + (x - f0));
-                if ((k & 7) == 0) bitmap.push_back(0);
-                sum += y - x;
-                rr.push_back(k); rb.push_back(0); rl.push_back(y - x); of_req.push_back(i);
-                covered += y - x;
-                continue;
-            }
-            auto it = row_at.find(r);
-            if (it == row_at.end()) {  // a compressed chunk: its whole frame, once per pass however many requests touch it
-                const size_t k = bo.size();
-                it = row_at.emplace(r, k).first;
-                bo.push_back(sum); bs.push_back(c[6].u64[r]); us.push_back(n); fpos.push_back(c[5].u64[r]);
-                if ((k & 7) == 0) bitmap.push_back(0);
-                bitmap[k >> 3] |= (uint8_t)(1u << (k & 7));
-                sum += c[6].u64[r];
-            }
-            rr.push_back(it->second); rb.push_back(x - f0); rl.push_back(y - x); of_req.push_back(i);
-            covered += y - x;
-        }
-        if ((*st)[i] == 0 && covered != req[i].len) (*st)[i] = ZNIPPY_E_CORRUPT;  // the index does not cover the file
-        if ((*st)[i]) { rr.resize(first_range); rb.resize(first_range); rl.resize(first_range); of_req.resize(first_range); continue; }
-        total += req[i].len;
-    }
+    zn::FileRangesRead p = zn::plan_file_ranges(a->ix.view(), req);
+    const RowTable &t = p.t;
+    const zn::RangeList &rg = p.rg;
+    const uint64_t total = p.total;
+    at->swap(p.at);
+    st->swap(p.st);
     host->assign((size_t)total, 0);
-    if (rr.empty()) return ZNIPPY_OK;
+    if (!rg.n()) return ZNIPPY_OK;
     ReadBufs &bufs = a->bufs;
-    if (!bufs.blob_pin.reserve(std::max<uint64_t>(sum, total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
-    for (size_t k = 0; k < bo.size(); k++)
-        if (bs[k] && !pread_all(a->fd, bufs.blob_pin.p + bo[k], bs[k], fpos[k])) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
-    if (!bufs.d_blobs.reserve(sum + 64) || !bufs.d_out.reserve(total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
-    if (sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
+    if (!bufs.blob_pin.reserve(std::max<uint64_t>(t.sum, total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+    if (!read_into_slab(a->fd, bufs.blob_pin.p, t.reads())) return fail(ZNIPPY_E_INVAL, "failed to read blob from archive");
+    if (!bufs.d_blobs.reserve(t.sum + 64) || !bufs.d_out.reserve(total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+    if (t.sum && hipMemcpy(bufs.d_blobs.p, bufs.blob_pin.p, t.sum, hipMemcpyHostToDevice) != hipSuccess) return fail(ZNIPPY_E_HIP, "H2D failed");
     znippy_rows *rt = nullptr;
-    int rc = znippy_rows_create(a->ctx, bo.data(), bs.data(), bitmap.data(), us.data(), nullptr, nullptr, 0, bo.size(), &rt);
-    if (rc) return fail(rc, "znippy_rows_create failed");
-    znippy_rows_set_blob_cap(rt, sum);
-    std::vector<int32_t> rst(rr.size(), 0);
-    rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rr.data(), rb.data(), rl.data(), nullptr, rr.size(), bufs.d_out.p, total, rst.data(), nullptr);
+    int rc = create_rows(a->ctx, t, nullptr, t.sum, &rt);
+    if (rc) return rc;
+    std::vector<int32_t> rst(rg.n(), 0);
+    rc = znippy_rows_read_ranges(a->ctx, rt, bufs.d_blobs.p, 0, rg.row.data(), rg.begin.data(), rg.len.data(), nullptr, rg.n(), bufs.d_out.p, total, rst.data(), nullptr);
     znippy_rows_destroy(rt);
     if (rc) return fail(rc, std::string("range read failed: ") + znippy_last_error(a->ctx));
     for (size_t k = 0; k < rst.size(); k++)
-        if (rst[k] < 0 && (*st)[of_req[k]] == 0) (*st)[of_req[k]] = rst[k];
+        if (rst[k] < 0 && (*st)[p.of_req[k]] == 0) (*st)[p.of_req[k]] = rst[k];
     if (total && hipMemcpy(host->data(), bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
     return ZNIPPY_OK;
 }
@@ -1609,17 +1457,15 @@ static int znippy_archive_extract_zip_entries_impl(znippy_archive *a, const char
     std::vector<int32_t> st(n, 0);
     std::vector<const std::vector<uint64_t> *> rows(n, nullptr);
     std::vector<uint64_t> fsize(n, 0);
+    const IndexView view = a->ix.view();
     for (size_t i = 0; i < n; i++) {
         auto it = paths[i] ? a->files.find(paths[i]) : a->files.end();
         if (it == a->files.end()) { st[i] = ZNIPPY_E_INVAL; continue; }
         rows[i] = &it->second;
-        for (uint64_t r : it->second) fsize[i] += a->ix.rows.cols[3].u8[r] ? a->ix.rows.cols[4].u64[r] : a->ix.rows.cols[6].u64[r];
+        for (uint64_t r : it->second) fsize[i] += view.row_len(r);
     }
-    if (!a->ctx) {
-        if (hipSetDevice(a->device) != hipSuccess) return fail(ZNIPPY_E_HIP, "hipSetDevice failed");
-        int rc = znippy_ctx_create(a->device, nullptr, &a->ctx);
-        if (rc) return fail(rc, "no usable GPU: the codec/hash path has no CPU fallback");
-    }
+    int rc = archive_ctx(a);
+    if (rc) return rc;
     std::vector<FileRange> req;
     std::vector<size_t> who;  // request -> file
     std::vector<uint8_t> bytes;
@@ -1641,7 +1487,7 @@ static int znippy_archive_extract_zip_entries_impl(znippy_archive *a, const char
         req.push_back(FileRange{rows[i], fsize[i] - tl, tl});
         who.push_back(i);
     }
-    int rc = pass();
+    rc = pass();
     if (rc) return rc;
     for (size_t k = 0; k < req.size(); k++) {
         const size_t i = who[k];
