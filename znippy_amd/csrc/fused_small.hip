@@ -20,6 +20,7 @@
 // The parent trees of a workgroup's four tiles are folded together by one of its waves (BlockFold).
 #include "common.h"
 #include "hash_dev.h"
+#include "zstd_rules.h"
 
 #include <algorithm>
 #include <cstring>
@@ -37,74 +38,26 @@ struct DTab {
     uint32_t base;
 };
 __constant__ DTab c_dll[64], c_dml[64], c_dof[32];
-__constant__ uint32_t c_llb[36] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18,
-                                   20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048,
-                                   4096, 8192, 16384, 32768, 65536};
-__constant__ uint8_t c_lla[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                  1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-__constant__ uint32_t c_mlb[53] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20,
-                                   21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 37,
-                                   39, 41, 43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051,
-                                   4099, 8195, 16387, 32771, 65539};
-__constant__ uint8_t c_mla[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                  0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                  1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11,
-                                  12, 13, 14, 15, 16};
 
 // ---- host: decoding tables of the predefined distributions -> __constant__ -----------------------
-static void host_fse_build(const int8_t *norm, int nsym, int log, int kind, DTab *t) {
-    static const uint32_t llb[36] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18,
-                                     20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048,
-                                     4096, 8192, 16384, 32768, 65536};
-    static const uint8_t lla[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                    1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-    static const uint32_t mlb[53] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20,
-                                     21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 37,
-                                     39, 41, 43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051,
-                                     4099, 8195, 16387, 32771, 65539};
-    static const uint8_t mla[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                    0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                    1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11,
-                                    12, 13, 14, 15, 16};
-    const int size = 1 << log;
-    uint8_t sym[512];
+static void predefined_table(int kind, DTab *t) {
+    const int log = zr::KIND[kind].def_log, size = 1 << log;
+    uint8_t sym[64];
     uint16_t next[64];
-    int high = size;
-    for (int s = 0; s < nsym; s++)
-        if (norm[s] == -1) { sym[--high] = (uint8_t)s; next[s] = 1; }
-    const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    int pos = 0;
-    for (int s = 0; s < nsym; s++) {
-        if (norm[s] <= 0) continue;
-        next[s] = (uint16_t)norm[s];
-        for (int i = 0; i < norm[s]; i++) {
-            sym[pos] = (uint8_t)s;
-            do { pos = (pos + step) & mask; } while (pos >= high);
-        }
-    }
+    const zr::Flat<uint16_t> nx{next};
+    zr::fse_spread(zr::Flat<const int8_t>{zr::default_norm(kind)}, nx, zr::default_nsym(kind), log, [&](uint32_t u, uint32_t s) { sym[u] = (uint8_t)s; });
     for (int i = 0; i < size; i++) {
-        uint32_t s = sym[i], ns = next[s]++;
-        int nb = log - (31 - __builtin_clz(ns));
-        t[i].next = (uint16_t)((ns << nb) - size);
-        t[i].nbits = (uint8_t)nb;
-        if (kind == 0) { t[i].base = llb[s]; t[i].addbits = lla[s]; }
-        else if (kind == 2) { t[i].base = mlb[s]; t[i].addbits = mla[s]; }
-        else { t[i].base = 1u << s; t[i].addbits = (uint8_t)s; }
+        const zr::FseCell c = zr::fse_cell(zr::fse_take_state(nx, sym[i]), (uint32_t)log);
+        const zr::SymValue v = zr::sym_value(kind, sym[i]);
+        t[i] = DTab{(uint16_t)c.next, (uint8_t)c.nbits, (uint8_t)v.bits, v.base};
     }
 }
 
 void init_fused_tables() {
-    static const int8_t ll[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
-                                  2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1, -1};
-    static const int8_t ml[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                  1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                  1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1};
-    static const int8_t of[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1,
-                                  1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
     DTab tl[64], tm[64], to[32];
-    host_fse_build(ll, 36, 6, 0, tl);
-    host_fse_build(ml, 53, 6, 2, tm);
-    host_fse_build(of, 29, 5, 1, to);
+    predefined_table(zr::K_LL, tl);
+    predefined_table(zr::K_ML, tm);
+    predefined_table(zr::K_OF, to);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(c_dll), tl, sizeof tl);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(c_dml), tm, sizeof tm);
     (void)hipMemcpyToSymbol(HIP_SYMBOL(c_dof), to, sizeof to);
@@ -485,7 +438,7 @@ __device__ int decode_simple(const uint8_t *src, uint32_t n, uint8_t *out, uint6
                     if (pos >= bend) return F_E_CORRUPT;
                     uint32_t s = (uint32_t)W.fwd(pos) & 0xFF; pos++;
                     if (s > 35) return F_E_CORRUPT;
-                    rl_base = c_llb[s]; rl_add = c_lla[s];
+                    rl_base = zr::LL_BASE[s]; rl_add = zr::LL_BITS[s];
                 }
                 if (m_of) {
                     if (pos >= bend) return F_E_CORRUPT;
@@ -497,7 +450,7 @@ __device__ int decode_simple(const uint8_t *src, uint32_t n, uint8_t *out, uint6
                     if (pos >= bend) return F_E_CORRUPT;
                     uint32_t s = (uint32_t)W.fwd(pos) & 0xFF; pos++;
                     if (s > 52) return F_E_CORRUPT;
-                    rm_base = c_mlb[s]; rm_add = c_mla[s];
+                    rm_base = zr::ML_BASE[s]; rm_add = zr::ML_BITS[s];
                 }
                 if (pos >= bend) return F_E_CORRUPT;
                 const uint32_t lastb = (uint32_t)W.bwd(bend - 1) & 0xFF;
@@ -887,8 +840,8 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
             T.ll = eL.base | (uint32_t)eL.addbits << 24;
             T.ml = eM.base | (uint32_t)eM.addbits << 24;
             T.of = eO.addbits;
-            T.lls = lane < 36 ? c_llb[lane] | (uint32_t)c_lla[lane] << 24 : 0u;
-            T.mls = lane < 53 ? c_mlb[lane] | (uint32_t)c_mla[lane] << 24 : 0u;
+            T.lls = lane < 36 ? zr::LL_BASE[lane] | (uint32_t)zr::LL_BITS[lane] << 24 : 0u;
+            T.mls = lane < 53 ? zr::ML_BASE[lane] | (uint32_t)zr::ML_BITS[lane] << 24 : 0u;
         }
 #pragma unroll 1
         for (uint32_t g0 = WROWS; g0 < t.n_units; g0 += WROWS) {
@@ -965,8 +918,8 @@ __device__ __forceinline__ void fused_tile(const FusedArgs &a, const uint32_t wa
             T.ll = eL.base | (uint32_t)eL.addbits << 24;
             T.ml = eM.base | (uint32_t)eM.addbits << 24;
             T.of = eO.addbits;
-            T.lls = lane < 36 ? c_llb[lane] | (uint32_t)c_lla[lane] << 24 : 0u;
-            T.mls = lane < 53 ? c_mlb[lane] | (uint32_t)c_mla[lane] << 24 : 0u;
+            T.lls = lane < 36 ? zr::LL_BASE[lane] | (uint32_t)zr::LL_BITS[lane] << 24 : 0u;
+            T.mls = lane < 53 ? zr::ML_BASE[lane] | (uint32_t)zr::ML_BITS[lane] << 24 : 0u;
         }
         const bool want = lane < t.n_units && lane < WROWS && c_sel && c_oo + c_len <= a.out_cap && c_st == 0;
         fr = parse_fast(WL + (lane < WROWS ? lane : 0) * WSTRIDE, c_bs, c_len, want, T);
@@ -1254,8 +1207,8 @@ __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S)
         T.ll = eL.base | (uint32_t)eL.addbits << 24;
         T.ml = eM.base | (uint32_t)eM.addbits << 24;
         T.of = eO.addbits;
-        T.lls = lane < 36 ? c_llb[lane] | (uint32_t)c_lla[lane] << 24 : 0u;
-        T.mls = lane < 53 ? c_mlb[lane] | (uint32_t)c_mla[lane] << 24 : 0u;
+        T.lls = lane < 36 ? zr::LL_BASE[lane] | (uint32_t)zr::LL_BITS[lane] << 24 : 0u;
+        T.mls = lane < 53 ? zr::ML_BASE[lane] | (uint32_t)zr::ML_BITS[lane] << 24 : 0u;
     }
     for (;;) {
         // iterations are numbered across the workgroup's loaders (their slots are published in that order); the tiles
@@ -1735,8 +1688,8 @@ __global__ __launch_bounds__(256, 4) void k_fused_blocks(FusedBlocksArgs a) {
                 T.ll = eL.base | (uint32_t)eL.addbits << 24;
                 T.ml = eM.base | (uint32_t)eM.addbits << 24;
                 T.of = eO.addbits;
-                T.lls = lane < 36 ? c_llb[lane] | (uint32_t)c_lla[lane] << 24 : 0u;
-                T.mls = lane < 53 ? c_mlb[lane] | (uint32_t)c_mla[lane] << 24 : 0u;
+                T.lls = lane < 36 ? zr::LL_BASE[lane] | (uint32_t)zr::LL_BITS[lane] << 24 : 0u;
+                T.mls = lane < 53 ? zr::ML_BASE[lane] | (uint32_t)zr::ML_BITS[lane] << 24 : 0u;
             }
             const uint32_t bh = uni(*reinterpret_cast<const uint32_t *>(WL)) & 0xFFFFFF;
             if (avail >= 3 && ((bh >> 1) & 3) == 0 && (bh >> 3) == 128 * 1024 && src_pos + 3 + 128 * 1024ull <= n) {
@@ -1902,8 +1855,8 @@ __global__ __launch_bounds__(256) void k_decode_blocks(FusedBlocksArgs a) {
         T.ll = eL.base | (uint32_t)eL.addbits << 24;
         T.ml = eM.base | (uint32_t)eM.addbits << 24;
         T.of = eO.addbits;
-        T.lls = lane < 36 ? c_llb[lane] | (uint32_t)c_lla[lane] << 24 : 0u;
-        T.mls = lane < 53 ? c_mlb[lane] | (uint32_t)c_mla[lane] << 24 : 0u;
+        T.lls = lane < 36 ? zr::LL_BASE[lane] | (uint32_t)zr::LL_BITS[lane] << 24 : 0u;
+        T.mls = lane < 53 ? zr::ML_BASE[lane] | (uint32_t)zr::ML_BITS[lane] << 24 : 0u;
     }
     const uint64_t tile_at = (uint64_t)t.first_leaf << 10;            // the tile's first byte inside the row
     const uint32_t rel = (uint32_t)(tile_at - origin);                // ... inside its block: 0 or 64 KiB

@@ -124,54 +124,35 @@ __device__ int fz_find_tree(FzTmp &T, const FzArgs &a, const uint8_t *src, const
 
 // Sequences_Section_Header of the section [q, q + n): number of sequences, then the three table descriptions.  Kinds in
 // `want` (bit 0 LL, 1 OF, 2 ML) that are described here are set up; those in Repeat_Mode come back in *missing.
+struct FzSeqTables {
+    FzShared &S;
+    FzTmp &T;
+    uint32_t want, miss;
+    __device__ bool wanted(int k) const { return (want >> k) & 1; }
+    __device__ int predefined(int k) { if (wanted(k)) { S.sel[k] = 0; S.log_[k] = zr::kind_def_log(k); } return 0; }
+    __device__ int rle(int k, uint32_t sym) {
+        if (!wanted(k)) return 0;
+        const int rc = fse_set_rle(&S.rle[k], sym, k);
+        if (!rc) { S.sel[k] = 1; S.log_[k] = 0; }
+        return rc;
+    }
+    __device__ int described(int k, const uint8_t *d, uint32_t n, uint32_t *used) {
+        int nsym, log;
+        // counts of a wanted table stay in norm[64 k ..] for the wave to build from (k_fz_entropy); a table that is only
+        // stepped over is read into the spare quarter
+        const int rc = fse_read_ncount(T, d, n, zr::kind_max_log(k), zr::kind_max_sym(k), &nsym, &log, used, wanted(k) ? 64 * k : 192);
+        if (!rc && wanted(k)) { T.bld[k] = (uint32_t)nsym; S.sel[k] = 2; S.log_[k] = log; }
+        return rc;
+    }
+    __device__ int repeat(int k) { if (wanted(k)) miss |= 1u << k; return 0; }
+};
 __device__ int fz_seq_tables(FzShared &S, FzTmp &T, const uint8_t *q, uint32_t n, uint32_t want, uint32_t *missing,
                              uint32_t *nseq_out, uint32_t *bits_at) {
-    if (n < 1) return E_TRUNC;
-    uint32_t p = 0, nseq = 0;
-    const uint32_t b0 = q[0];
-    if (b0 == 0) { nseq = 0; p = 1; }
-    else if (b0 < 128) { nseq = b0; p = 1; }
-    else if (b0 < 255) { if (n < 2) return E_TRUNC; nseq = ((b0 - 128) << 8) + q[1]; p = 2; }
-    else { if (n < 3) return E_TRUNC; nseq = q[1] + ((uint32_t)q[2] << 8) + 0x7F00; p = 3; }
-    *nseq_out = nseq;
+    FzSeqTables cb{S, T, want, 0};
     *missing = want;
-    *bits_at = p;
-    if (!nseq) return 0;
-    if (p >= n) return E_TRUNC;
-    const uint32_t modes = q[p++];
-    if (modes & 3) return E_CORRUPT;
-    const int shifts[3] = {6, 4, 2};
-    const int kinds[3] = {K_LL, K_OF, K_ML};
-    const int maxlog[3] = {9, 8, 9};
-    const int maxsym[3] = {35, 31, 52};
-    const int deflog[3] = {6, 5, 6};
-    uint32_t miss = 0;
-    for (int k = 0; k < 3; k++) {
-        const uint32_t mode = (modes >> shifts[k]) & 3;
-        const bool wanted = (want >> k) & 1;
-        if (mode == 0) { if (wanted) { S.sel[k] = 0; S.log_[k] = deflog[k]; } }
-        else if (mode == 1) {
-            if (p >= n) return E_TRUNC;
-            if (wanted) {
-                const int rc = fse_set_rle(&S.rle[k], q[p], kinds[k]);
-                if (rc) return rc;
-                S.sel[k] = 1; S.log_[k] = 0;
-            }
-            p++;
-        } else if (mode == 2) {
-            int nsym, log;
-            uint32_t used;
-            // counts of a wanted table stay in norm[64 k ..] for the wave to build from (k_fz_entropy); a table that is only
-            // stepped over is read into the spare quarter
-            int rc = fse_read_ncount(T, q + p, n - p, maxlog[k], maxsym[k], &nsym, &log, &used, wanted ? 64 * k : 192);
-            if (rc) return rc;
-            if (wanted) { T.bld[k] = (uint32_t)nsym; S.sel[k] = 2; S.log_[k] = log; }
-            p += used;
-        } else if (wanted) miss |= 1u << k;
-    }
-    *missing = miss;
-    *bits_at = p;
-    return 0;
+    const int rc = zr::seq_header(q, n, nseq_out, bits_at, cb);
+    if (!rc && *nseq_out) *missing = cb.miss;
+    return rc;
 }
 
 
@@ -329,14 +310,7 @@ __global__ __launch_bounds__(128, 4) void k_fz_entropy(FzArgs a, const uint32_t 
     const bool wave0 = tid < 64;
     const uint32_t n_work = *work_count;
     if (n_work == 0) return;
-    if (tid == 0) {
-        for (int i = 0; i < 36; i++) S.ta.norm[i] = c_ll_default[i];
-        fse_build(S.ta, S.dll, 36, 6, K_LL);
-        for (int i = 0; i < 53; i++) S.ta.norm[i] = c_ml_default[i];
-        fse_build(S.ta, S.dml, 53, 6, K_ML);
-        for (int i = 0; i < 29; i++) S.ta.norm[i] = c_of_default[i];
-        fse_build(S.ta, S.dof, 29, 5, K_OF);
-    }
+    if (tid == 0) fse_build_predefined(S.ta, S.dll, S.dof, S.dml);
     __syncthreads();
     for (;;) {
         if (tid == 0) S.claim = atomicAdd(a.cursor, 1u);
@@ -818,35 +792,15 @@ __device__ __forceinline__ uint64_t wave_alloc64(unsigned long long *counter, ui
     return rdlane64_u(base, 0) + incl - mine;
 }
 
-// forward bit reader with a 64-bit register window (table descriptions); bytes past n read as zero
-struct FwdW {
-    const uint8_t *p;
-    uint32_t n, bitpos, wbit;
-    uint64_t win;
-    __device__ __forceinline__ void fill(uint32_t byte) {
-        uint64_t v = 0;
-        if (byte + 8 <= n) __builtin_memcpy(&v, p + byte, 8);
-        else for (uint32_t i = 0; i < 8 && byte + i < n; i++) v |= (uint64_t)p[byte + i] << (8 * i);
-        win = v;
-        wbit = byte * 8;
-    }
-    __device__ __forceinline__ void init(const uint8_t *src, uint32_t len) { p = src; n = len; bitpos = 0; fill(0); }
-    __device__ __forceinline__ uint32_t peek(uint32_t nb) {  // nb <= 25
-        if (bitpos + nb > wbit + 64) fill(bitpos >> 3);
-        return (uint32_t)(win >> (bitpos - wbit)) & ((1u << nb) - 1u);
-    }
-    __device__ __forceinline__ uint32_t read(uint32_t nb) { const uint32_t v = peek(nb); bitpos += nb; return v; }
-};
-
 #define BX_NORM(i) S.norm[(i) * 64 + lane]
-#define BX_NXT(i) S.nxt[(i) * 64 + lane]
 #define BX_W(i) S.weights[(i) * 64 + lane]
 
-// fse_read_ncount for one lane (RFC 8878 4.1.1); at most 64 symbols (what a lane's scratch holds)
-__device__ int bx_read_ncount(BxScratch &S, const uint32_t lane, const uint8_t *src, uint32_t n, int max_log, int max_sym, int *nsym,
-                              int *log, uint32_t *consumed) {
+// zr::read_ncount for one lane's stripe, at most 64 symbols (what a lane's scratch holds); k < 0: the table of the Huffman weights.  It keeps a body
+// of its own: through the shared one k_bx_prep was 1.7 % slower on frames of many blocks (profiles/ab_zstd_rules_refactor.log); same rules, cap 64.
+__device__ int bx_read_ncount(BxScratch &S, const uint32_t lane, const uint8_t *src, uint32_t n, int k, int *nsym, int *log, uint32_t *consumed) {
+    const int max_log = k < 0 ? 6 : zr::kind_max_log(k), max_sym = k < 0 ? 255 : zr::kind_max_sym(k);
     if (n == 0) return E_TRUNC;
-    FwdW b;
+    zr::FwdW b;
     b.init(src, n);
     const int alog = 5 + (int)b.read(4);
     if (alog > max_log) return E_CORRUPT;
@@ -877,49 +831,24 @@ __device__ int bx_read_ncount(BxScratch &S, const uint32_t lane, const uint8_t *
     return 0;
 }
 
-// Spread of the symbols over the table cells (RFC 8878 4.1.1): put(cell, symbol); the lane's next-state counters are set.
-template <class Put>
-__device__ __forceinline__ int bx_fse_spread(BxScratch &S, const uint32_t lane, int nsym, int log, Put put) {
-    const int size = 1 << log;
-    int high = size;
-    for (int s = 0; s < nsym; s++)
-        if (BX_NORM(s) == -1) { put((uint32_t)--high, (uint32_t)s); BX_NXT(s) = 1; }
-    const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    int pos = 0;
-    for (int s = 0; s < nsym; s++) {
-        const int c = BX_NORM(s);
-        if (c <= 0) continue;
-        BX_NXT(s) = (uint16_t)c;
-        for (int i = 0; i < c; i++) {
-            put((uint32_t)pos, (uint32_t)s);
-            do { pos = (pos + step) & mask; } while (pos >= high);
-        }
-    }
-    return pos == 0 ? 0 : E_CORRUPT;
-}
-
 // FSE pool cell (2 bytes): symbol:6 | ns:10 << 6, ns = the state counter the table construction hands the cell
 // (RFC 8878 4.1.1): the bits to read are log - hibit(ns), the next state's base is (ns << bits) - (1 << log); base value and
 // extra bits follow from the symbol.  Half the size of a cell that spells these out: 64 blocks' tables fit one wave's LDS.
-__device__ __forceinline__ int bx_check_sym(int kind, uint32_t sym) {
-    return sym > (kind == K_LL ? 35u : (kind == K_ML ? 52u : 31u)) ? E_CORRUPT : 0;
-}
-
 // One sequence table of one lane's block, from its counts (BX_NORM) into cells[0 .. 1 << log) of the FSE pool (cells is
 // 16-byte aligned and has room for a multiple of 8 cells).
 __device__ int bx_build_seq_table(BxScratch &S, const uint32_t lane, int nsym, int log, int kind, uint16_t *cells) {
-    int rc = bx_fse_spread(S, lane, nsym, log, [&](uint32_t u, uint32_t sym) { S.sym[u * 64 + lane] = (uint8_t)sym; });
-    if (rc) return rc;
+    const zr::Stripe<uint16_t> nxt{S.nxt, lane};
+    if (zr::fse_spread(zr::Stripe<int16_t>{S.norm, lane}, nxt, nsym, log, [&](uint32_t u, uint32_t sym) { S.sym[u * 64 + lane] = (uint8_t)sym; }) != 0)
+        return E_CORRUPT;
     for (int s_ = 0; s_ < nsym; s_++)
-        if (BX_NORM(s_) != 0 && bx_check_sym(kind, (uint32_t)s_)) return E_CORRUPT;
+        if (BX_NORM(s_) != 0 && !zr::sym_in_range(kind, (uint32_t)s_)) return E_CORRUPT;
     const uint32_t size = 1u << log;
     for (uint32_t u0 = 0; u0 < size; u0 += 8) {  // (a table has at least 32 cells)
         uint32_t w[4];
 #pragma unroll
         for (uint32_t q = 0; q < 8; q++) {
             const uint32_t sym = S.sym[(u0 + q) * 64 + lane];
-            const uint32_t ns = BX_NXT(sym);
-            BX_NXT(sym) = (uint16_t)(ns + 1);
+            const uint32_t ns = zr::fse_take_state(nxt, sym);
             const uint32_t c = sym | (ns << 6);
             if (q & 1) w[q >> 1] |= c << 16; else w[q >> 1] = c;
         }
@@ -934,86 +863,41 @@ __device__ int bx_read_weights(BxScratch &S, const uint32_t lane, const uint8_t 
                                uint32_t *consumed, uint32_t *hlog, uint32_t *nsym_out) {
     if (n < 1) return E_TRUNC;
     const uint32_t hb = src[0];
+    const zr::Stripe<uint8_t> weights{S.weights, lane};
     uint32_t nw = 0;
     if (hb >= 128) {
-        nw = hb - 127;
-        const uint32_t bytes = (nw + 1) / 2;
-        if (1 + bytes > n) return E_TRUNC;
-        for (uint32_t i = 0; i < nw; i++) {
-            const uint8_t b = src[1 + i / 2];
-            BX_W(i) = (i & 1) ? (b & 15) : (b >> 4);
-        }
-        *consumed = 1 + bytes;
+        const int rc = zr::huf_direct_weights(src, n, weights, &nw, consumed);
+        if (rc) return rc;
     } else {
         if (hb == 0 || 1 + hb > n) return E_TRUNC;
         int nsym = 0, log = 0;
         uint32_t hdr = 0;
-        int rc = bx_read_ncount(S, lane, src + 1, hb, 6, 255, &nsym, &log, &hdr);
+        const int rc = bx_read_ncount(S, lane, src + 1, hb, -1, &nsym, &log, &hdr);
         if (rc) return rc;
-        rc = bx_fse_spread(S, lane, nsym, log, [&](uint32_t u, uint32_t sym) { S.wtab[u * 64 + lane] = (uint16_t)sym; });
-        if (rc) return rc;
+        const zr::Stripe<uint16_t> nxt{S.nxt, lane}, wtab{S.wtab, lane};
+        if (zr::fse_spread(zr::Stripe<int16_t>{S.norm, lane}, nxt, nsym, log, [&](uint32_t u, uint32_t sym) { wtab.set(u, (int)sym); }) != 0) return E_CORRUPT;
         const uint32_t size = 1u << log;
         for (uint32_t u = 0; u < size; u++) {
-            const uint32_t sym = S.wtab[u * 64 + lane];
-            const uint32_t ns = BX_NXT(sym);
-            BX_NXT(sym) = (uint16_t)(ns + 1);
-            const uint32_t nb = (uint32_t)log - (uint32_t)hibit(ns);
-            S.wtab[u * 64 + lane] = (uint16_t)((sym > 15 ? 15u : sym) | (nb << 4) | (((ns << nb) - size) << 7));  // a weight above 12 is rejected below
+            const uint32_t sym = (uint32_t)wtab.get(u);
+            const zr::FseCell c = zr::fse_cell(zr::fse_take_state(nxt, sym), (uint32_t)log);
+            wtab.set(u, (int)((sym > 15 ? 15u : sym) | (c.nbits << 4) | (c.next << 7)));  // a weight above 12 is rejected below
         }
         if (hdr >= hb) return E_CORRUPT;
         BitR b;
         if (!b.init(src + 1 + hdr, hb - hdr, blob_end)) return E_CORRUPT;
-        uint32_t s1 = b.read((uint32_t)log), s2 = b.read((uint32_t)log);
-        for (;;) {
-            const uint32_t e1 = S.wtab[s1 * 64 + lane];
-            if (nw >= 255) return E_CORRUPT;
-            BX_W(nw++) = (uint8_t)(e1 & 15);
-            s1 = (e1 >> 7) + b.read((e1 >> 4) & 7);
-            const uint32_t e2 = S.wtab[s2 * 64 + lane];
-            if (b.pos < 0) {
-                if (nw >= 255) return E_CORRUPT;
-                BX_W(nw++) = (uint8_t)(e2 & 15);
-                break;
-            }
-            if (nw >= 255) return E_CORRUPT;
-            BX_W(nw++) = (uint8_t)(e2 & 15);
-            s2 = (e2 >> 7) + b.read((e2 >> 4) & 7);
-            if (b.pos < 0) {
-                if (nw >= 255) return E_CORRUPT;
-                BX_W(nw++) = (uint8_t)(S.wtab[s1 * 64 + lane] & 15);
-                break;
-            }
-        }
+        const auto cell = [&](uint32_t s) { const uint32_t e = (uint32_t)wtab.get(s); return zr::HufCell{e & 15, (e >> 4) & 7, e >> 7}; };
+        const int rw = zr::huf_walk_weights<true>(b, (uint32_t)log, cell, weights, &nw);
+        if (rw) return rw;
         *consumed = 1 + hb;
     }
     // implied last weight, code lengths, first cell of every rank
-    uint32_t total = 0;
-    for (uint32_t i = 0; i < nw; i++) {
-        const uint32_t w = BX_W(i);
-        if (w > 12) return E_CORRUPT;
-        total += w ? 1u << (w - 1) : 0;
-    }
-    if (total == 0) return E_CORRUPT;
-    const uint32_t maxbits = (uint32_t)hibit(total) + 1;
-    if (maxbits > 11) return E_CORRUPT;
-    const uint32_t left = (1u << maxbits) - total;
-    if (left & (left - 1)) return E_CORRUPT;
-    BX_W(nw) = (uint8_t)(hibit(left) + 1);
+    uint32_t maxbits, lastw;
+    int rc = zr::huf_limits(weights, nw, &maxbits, &lastw);
+    if (rc) return rc;
+    BX_W(nw) = (uint8_t)lastw;
     const uint32_t nsym = nw + 1;
-    for (uint32_t i = 0; i < 16; i++) S.rank[i * 64 + lane] = 0;
-    for (uint32_t i = 0; i < nsym; i++) {
-        const uint32_t w = BX_W(i);
-        if (w) S.rank[(maxbits + 1 - w) * 64 + lane] += 1;  // count per code length
-    }
-    {   // counts -> first cells, longest codes first (as the table is laid out)
-        uint32_t start = 0;
-        for (uint32_t bits = maxbits; bits >= 1; bits--) {
-            const uint32_t cnt = S.rank[bits * 64 + lane];
-            S.rank[bits * 64 + lane] = (uint16_t)start;
-            start += cnt << (maxbits - bits);
-        }
-        if (start != (1u << maxbits)) return E_CORRUPT;
-    }
+    rc = zr::huf_rank_starts(weights, nsym, maxbits, zr::Stripe<uint16_t>{S.rank, lane});
+    if (rc) return rc;
     *hlog = maxbits;
     *nsym_out = nsym;
     return 0;
@@ -1044,50 +928,34 @@ struct BxSeqHdr {
     const uint8_t *desc[3];
     uint32_t desc_n[3];
 };
+struct BxSeqLocate {
+    BxScratch &S;
+    const uint32_t lane;
+    BxSeqHdr &H;
+    uint32_t want, miss;
+    __device__ bool wanted(int k) const { return (want >> k) & 1; }
+    __device__ int predefined(int k) { if (wanted(k)) { H.mode[k] = 0; H.log[k] = zr::kind_def_log(k); } return 0; }
+    __device__ int rle(int k, uint32_t sym) {
+        if (!wanted(k)) return 0;
+        if (!zr::sym_in_range(k, sym)) return E_CORRUPT;
+        H.mode[k] = 1; H.log[k] = 0; H.sym[k] = sym;
+        return 0;
+    }
+    __device__ int described(int k, const uint8_t *d, uint32_t n, uint32_t *used) {  // read for its length; phase 2 reads a wanted one again
+        int nsym = 0, log = 0;
+        const int rc = bx_read_ncount(S, lane, d, n, k, &nsym, &log, used);
+        if (!rc && wanted(k)) { H.mode[k] = 2; H.log[k] = (uint32_t)log; H.desc[k] = d; H.desc_n[k] = n; }
+        return rc;
+    }
+    __device__ int repeat(int k) { if (wanted(k)) miss |= 1u << k; return 0; }
+};
 __device__ int bx_seq_locate(BxScratch &S, const uint32_t lane, const uint8_t *q, uint32_t n, uint32_t want, uint32_t *missing,
                              uint32_t *nseq_out, uint32_t *bits_at, BxSeqHdr &H) {
-    if (n < 1) return E_TRUNC;
-    uint32_t p = 0, nseq = 0;
-    const uint32_t b0 = q[0];
-    if (b0 == 0) { nseq = 0; p = 1; }
-    else if (b0 < 128) { nseq = b0; p = 1; }
-    else if (b0 < 255) { if (n < 2) return E_TRUNC; nseq = ((b0 - 128) << 8) + q[1]; p = 2; }
-    else { if (n < 3) return E_TRUNC; nseq = q[1] + ((uint32_t)q[2] << 8) + 0x7F00; p = 3; }
-    *nseq_out = nseq;
+    BxSeqLocate cb{S, lane, H, want, 0};
     *missing = want;
-    *bits_at = p;
-    if (!nseq) return 0;
-    if (p >= n) return E_TRUNC;
-    const uint32_t modes = q[p++];
-    if (modes & 3) return E_CORRUPT;
-    uint32_t miss = 0;
-    for (int k = 0; k < 3; k++) {
-        const uint32_t mode = (modes >> (6 - 2 * k)) & 3;
-        const bool wanted = (want >> k) & 1;
-        const int kind = k == 0 ? K_LL : (k == 1 ? K_OF : K_ML);
-        if (mode == 0) {
-            if (wanted) { H.mode[k] = 0; H.log[k] = k == 1 ? 5 : 6; }
-        } else if (mode == 1) {
-            if (p >= n) return E_TRUNC;
-            if (wanted) {
-                const uint32_t sym = q[p];
-                const int rc = bx_check_sym(kind, sym);
-                if (rc) return rc;
-                H.mode[k] = 1; H.log[k] = 0; H.sym[k] = sym;
-            }
-            p++;
-        } else if (mode == 2) {
-            int nsym = 0, log = 0;
-            uint32_t used = 0;
-            const int rc = bx_read_ncount(S, lane, q + p, n - p, k == 1 ? 8 : 9, k == 0 ? 35 : (k == 1 ? 31 : 52), &nsym, &log, &used);
-            if (rc) return rc;
-            if (wanted) { H.mode[k] = 2; H.log[k] = (uint32_t)log; H.desc[k] = q + p; H.desc_n[k] = n - p; }
-            p += used;
-        } else if (wanted) miss |= 1u << k;
-    }
-    *missing = miss;
-    *bits_at = p;
-    return 0;
+    const int rc = zr::seq_header(q, n, nseq_out, bits_at, cb);
+    if (!rc && *nseq_out) *missing = cb.miss;
+    return rc;
 }
 
 __global__ __launch_bounds__(64) void k_bx_scan(BxArgs a) {
@@ -1338,7 +1206,7 @@ __global__ __launch_bounds__(64) void k_bx_prep(BxArgs a) {
                     else {
                         int nsym = 0, log = 0;
                         uint32_t used = 0;
-                        err = bx_read_ncount(S, lane, H.desc[j], H.desc_n[j], j == 1 ? 8 : 9, j == 0 ? 35 : (j == 1 ? 31 : 52), &nsym, &log, &used);
+                        err = bx_read_ncount(S, lane, H.desc[j], H.desc_n[j], j, &nsym, &log, &used);
                         if (!err) err = bx_build_seq_table(S, lane, nsym, log, kind, a.fse_pool + at);
                         pr.tab[j] = at; at += 1u << log;
                     }
@@ -1641,8 +1509,8 @@ __global__ __launch_bounds__(64) void k_bx_fse_wave(BxArgs a, const uint32_t *li
                 const uint32_t c = cells[u], sym = c & 63u, ns = c >> 6;
                 const uint32_t nb = log - (uint32_t)hibit(ns | 1u);
                 uint32_t ab, base;
-                if (k == 0) { ab = c_ll_bits[sym > 35 ? 35 : sym]; base = c_ll_base[sym > 35 ? 35 : sym]; }
-                else if (k == 2) { ab = c_ml_bits[sym > 52 ? 52 : sym]; base = c_ml_base[sym > 52 ? 52 : sym]; }
+                if (k == 0) { ab = zr::LL_BITS[sym > 35 ? 35 : sym]; base = zr::LL_BASE[sym > 35 ? 35 : sym]; }
+                else if (k == 2) { ab = zr::ML_BITS[sym > 52 ? 52 : sym]; base = zr::ML_BASE[sym > 52 ? 52 : sym]; }
                 else { ab = sym; base = 1u << (sym & 31); }
                 t[u] = make_uint2((((ns << nb) - size) & 0xFFFFu) | (nb << 16) | (ab << 24), base);
             }
@@ -1684,8 +1552,8 @@ __global__ __launch_bounds__(64) void k_bx_fse(BxArgs a, const uint32_t *list, c
     __shared__ uint32_t s_ll[64], s_ml[64];  // base value | extra bits << 24, by symbol
     typedef __attribute__((address_space(3))) uint16_t lds16;
     const uint32_t lane = threadIdx.x;
-    s_ll[lane] = lane < 36 ? c_ll_base[lane] | ((uint32_t)c_ll_bits[lane] << 24) : 0u;
-    s_ml[lane] = lane < 53 ? c_ml_base[lane] | ((uint32_t)c_ml_bits[lane] << 24) : 0u;
+    s_ll[lane] = lane < 36 ? zr::LL_BASE[lane] | ((uint32_t)zr::LL_BITS[lane] << 24) : 0u;
+    s_ml[lane] = lane < 53 ? zr::ML_BASE[lane] | ((uint32_t)zr::ML_BITS[lane] << 24) : 0u;
     __builtin_amdgcn_wave_barrier();
     const uint32_t n_list = *n_list_p;
     lds8 *const my = (lds8 *)T + (lane < LANES ? lane : 0) * STRIDE;

@@ -16,6 +16,22 @@
 
 namespace zn {
 
+// What lane 0 does with a Sequences_Section_Header (zr::seq_header): every table is chosen on the spot; the counts of a
+// described one wait in S.norm[64 k ..] for wave k to build from (S.bld[k] = alphabet size).
+template <class Shared>
+struct DecodeSeqTables {
+    Shared &S;
+    __device__ int predefined(int k) { S.sel[k] = 0; S.log_[k] = zr::kind_def_log(k); S.valid[k] = 1; return 0; }
+    __device__ int rle(int k, uint32_t sym) { S.sel[k] = 1; S.log_[k] = 0; S.valid[k] = 1; return fse_set_rle(&S.rle[k], sym, k); }
+    __device__ int described(int k, const uint8_t *d, uint32_t n, uint32_t *used) {
+        int nsym, log;
+        const int rc = fse_read_ncount(S, d, n, zr::kind_max_log(k), zr::kind_max_sym(k), &nsym, &log, used, 64 * k);
+        if (!rc) { S.sel[k] = 2; S.log_[k] = log; S.valid[k] = 1; S.bld[k] = (uint32_t)nsym; }
+        return rc;
+    }
+    __device__ int repeat(int k) { return S.valid[k] ? 0 : E_CORRUPT; }
+};
+
 // ---------------------------------------------------------------------------------------------
 // the kernel
 // ---------------------------------------------------------------------------------------------
@@ -37,14 +53,7 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 4 ? 4 : 1) void k_zstd_decod
     if (a.block_mode && n_work == 0) return;
 
     // predefined tables, once per workgroup (lane 0; tiny)
-    if (tid == 0) {
-        for (int i = 0; i < 36; i++) S.norm[i] = c_ll_default[i];
-        fse_build(S, S.dll, 36, 6, K_LL);
-        for (int i = 0; i < 53; i++) S.norm[i] = c_ml_default[i];
-        fse_build(S, S.dml, 53, 6, K_ML);
-        for (int i = 0; i < 29; i++) S.norm[i] = c_of_default[i];
-        fse_build(S, S.dof, 29, 5, K_OF);
-    }
+    if (tid == 0) fse_build_predefined(S, S.dll, S.dof, S.dml);
     __syncthreads();
 
     for (;;) {
@@ -306,48 +315,22 @@ __global__ __launch_bounds__(NWAVES * 64, NWAVES == 4 ? 4 : 1) void k_zstd_decod
                 S.bld[0] = S.bld[1] = S.bld[2] = 0;
                 if (p >= end) err = E_TRUNC;
                 else {
-                    uint32_t b0 = src[p];
-                    if (b0 == 0) { nseq = 0; p += 1; }
-                    else if (b0 < 128) { nseq = b0; p += 1; }
-                    else if (b0 < 255) { if (p + 2 > end) err = E_TRUNC; else { nseq = ((b0 - 128) << 8) + src[p + 1]; p += 2; } }
-                    else { if (p + 3 > end) err = E_TRUNC; else { nseq = src[p + 1] + ((uint32_t)src[p + 2] << 8) + 0x7F00; p += 3; } }
+                    DecodeSeqTables<Shared> cb{S};
+                    uint32_t bits_at = 0;
+                    err = zr::seq_header(src + p, (uint32_t)(end - p), &nseq, &bits_at, cb);
+                    p += bits_at;
                 }
                 if (!err && nseq) {
                     if (p >= end) err = E_TRUNC;
                     else {
-                        uint32_t modes = src[p++];
-                        if (modes & 3) err = E_CORRUPT;
-                        const int shifts[3] = {6, 4, 2};
-                        const int kinds[3] = {K_LL, K_OF, K_ML};
-                        const int maxlog[3] = {9, 8, 9};
-                        const int maxsym[3] = {35, 31, 52};
-                        const int deflog[3] = {6, 5, 6};
-                        for (int k = 0; k < 3 && !err; k++) {
-                            uint32_t mode = (modes >> shifts[k]) & 3;
-                            if (mode == 0) { S.sel[k] = 0; S.log_[k] = deflog[k]; S.valid[k] = 1; }
-                            else if (mode == 1) {
-                                if (p >= end) err = E_TRUNC;
-                                else { err = fse_set_rle(&S.rle[k], src[p++], kinds[k]); S.sel[k] = 1; S.log_[k] = 0; S.valid[k] = 1; }
-                            } else if (mode == 2) {
-                                int nsym, log;
-                                uint32_t used;
-                                err = fse_read_ncount(S, src + p, (uint32_t)(end - p), maxlog[k], maxsym[k], &nsym, &log, &used, 64 * k);
-                                if (!err) { p += used; S.sel[k] = 2; S.log_[k] = log; S.valid[k] = 1; S.bld[k] = (uint32_t)nsym; }
-                            } else if (!S.valid[k]) err = E_CORRUPT;
-                        }
-                        if (!err) {
-                            if (p >= end) err = E_TRUNC;
-                            else {
-                                BitR b;
-                                if (!b.init(src + p, (uint32_t)(end - p), blob_end)) err = E_CORRUPT;
-                                else {
-                                    S.st_ll = b.read(S.log_[0]);
-                                    S.st_of = b.read(S.log_[1]);
-                                    S.st_ml = b.read(S.log_[2]);
-                                    S.bs_pos = b.pos;
-                                    S.bs_off = (uint32_t)p;
-                                }
-                            }
+                        BitR b;
+                        if (!b.init(src + p, (uint32_t)(end - p), blob_end)) err = E_CORRUPT;
+                        else {
+                            S.st_ll = b.read(S.log_[0]);
+                            S.st_of = b.read(S.log_[1]);
+                            S.st_ml = b.read(S.log_[2]);
+                            S.bs_pos = b.pos;
+                            S.bs_off = (uint32_t)p;
                         }
                     }
                 } else if (!err && p != end) err = E_CORRUPT;

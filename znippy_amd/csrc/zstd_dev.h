@@ -1,11 +1,16 @@
-// Device helpers shared by the zstd decode kernels (zstd_decode.hip, zstd_batch.hip): constants and code tables of
-// RFC 8878, bit readers, wave-cooperative copies, the LDS output window.  Internal.
+// Device helpers shared by the zstd decode kernels (zstd_decode.hip, zstd_batch.hip): the table builders and tree readers
+// over the rules of zstd_rules.h (RFC 8878's constants, code tables and table descriptions, stated there once), the
+// backward bit reader, wave-cooperative copies, the LDS output window.  Internal.
 #pragma once
 #include "common.h"
+#include "zstd_rules.h"
 
 namespace zn {
 
-constexpr int E_TRUNC = -5, E_CORRUPT = -5, E_UNSUP = -6, E_DST = -4;
+using zr::E_TRUNC; using zr::E_CORRUPT; using zr::E_UNSUP;  // the table-description rules (zstd_rules.h) answer with these
+using zr::K_LL; using zr::K_OF; using zr::K_ML;
+using zr::FwdR;
+constexpr int E_DST = -4;
 constexpr uint32_t BLOCK_MAX = 128 * 1024;
 constexpr int LIT_SCRATCH_BYTES = 128 * 1024 + 64;
 constexpr int SEQ_BATCH = 256;
@@ -24,29 +29,6 @@ struct FseEntry {
     uint8_t addbits;  // extra bits of the value
     uint32_t base;    // value baseline
 };
-
-static __constant__ uint32_t c_ll_base[36] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 18,
-                                       20, 22, 24, 28, 32, 40, 48, 64, 128, 256, 512, 1024, 2048,
-                                       4096, 8192, 16384, 32768, 65536};
-static __constant__ uint8_t c_ll_bits[36] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                      1, 1, 2, 2, 3, 3, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16};
-static __constant__ uint32_t c_ml_base[53] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20,
-                                       21, 22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 37,
-                                       39, 41, 43, 47, 51, 59, 67, 83, 99, 131, 259, 515, 1027, 2051,
-                                       4099, 8195, 16387, 32771, 65539};
-static __constant__ uint8_t c_ml_bits[53] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                      0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, 1,
-                                      1, 1, 2, 2, 3, 3, 4, 4, 5, 7, 8, 9, 10, 11,
-                                      12, 13, 14, 15, 16};
-static __constant__ int8_t c_ll_default[36] = {4, 3, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 2, 1, 1, 1, 2, 2,
-                                        2, 2, 2, 2, 2, 2, 2, 3, 2, 1, 1, 1, 1, 1, -1, -1, -1, -1};
-static __constant__ int8_t c_ml_default[53] = {1, 4, 3, 2, 2, 2, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                        1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1,
-                                        1, 1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1, -1, -1};
-static __constant__ int8_t c_of_default[29] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 1, 1, 1, 1, 1, 1,
-                                        1, 1, 1, 1, 1, 1, 1, 1, 1, -1, -1, -1, -1, -1};
-
-enum { K_LL = 0, K_OF = 1, K_ML = 2 };
 
 // NW = waves of the workgroup: sizes the pattern buffer (16 bytes per thread per trip)
 template <int NW>
@@ -177,23 +159,6 @@ struct BitR {
     __device__ __forceinline__ uint32_t read(uint32_t nb) {
         uint32_t v = peek(nb);
         pos -= nb;
-        return v;
-    }
-};
-
-// Forward bit reader (FSE table descriptions).
-struct FwdR {
-    const uint8_t *p;
-    uint32_t n;
-    uint32_t bitpos;
-    __device__ __forceinline__ uint32_t read(uint32_t nb) {
-        uint32_t v = 0;
-        for (uint32_t i = 0; i < nb; i++) {
-            uint32_t bp = bitpos + i;
-            uint32_t bit = (bp >> 3) < n ? (p[bp >> 3] >> (bp & 7)) & 1u : 0u;
-            v |= bit << i;
-        }
-        bitpos += nb;
         return v;
     }
 };
@@ -640,39 +605,19 @@ __device__ __forceinline__ uint32_t fz_lit_section_bytes(const LitHdr &h) {
 template <class Shared>
 __device__ int fse_read_ncount(Shared &S, const uint8_t *src, uint32_t n, int max_log, int max_sym, int *nsym,
                                int *log, uint32_t *consumed, int nbase = 0) {
-    FwdR b{src, n, 0};
-    if (n == 0) return E_TRUNC;
-    int alog = 5 + (int)b.read(4);
-    if (alog > max_log) return E_CORRUPT;
-    int remaining = 1 << alog, s = 0;
-    while (remaining > 0 && s <= max_sym) {
-        int bits = hibit((uint32_t)remaining + 1) + 1;
-        uint32_t val = b.read(bits);
-        uint32_t lower_mask = (1u << (bits - 1)) - 1;
-        uint32_t threshold = (1u << bits) - 1 - ((uint32_t)remaining + 1);
-        if ((val & lower_mask) < threshold) {
-            b.bitpos -= 1;
-            val &= lower_mask;
-        } else if (val > lower_mask) {
-            val -= threshold;
-        }
-        int proba = (int)val - 1;
-        remaining -= proba < 0 ? -proba : proba;
-        S.norm[nbase + s++] = (int16_t)proba;
-        if (proba == 0) {
-            uint32_t rep = b.read(2);
-            for (;;) {
-                for (uint32_t i = 0; i < rep && s <= max_sym; i++) S.norm[nbase + s++] = 0;
-                if (rep == 3) rep = b.read(2); else break;
-            }
-        }
-    }
-    if (remaining != 0) return E_CORRUPT;
-    if ((b.bitpos + 7) / 8 > n) return E_TRUNC;
-    *nsym = s;
-    *log = alog;
-    *consumed = (b.bitpos + 7) / 8;
-    return 0;
+    return zr::read_ncount<FwdR>(src, n, zr::Flat<int16_t>{S.norm + nbase}, max_log, max_sym, 256, nsym, log, consumed);
+}
+
+// one table cell from its symbol and state counter (zstd_rules.h: fse_cell, sym_value); the symbol is in range
+__device__ __forceinline__ FseEntry fse_entry(uint32_t sym, uint32_t ns, uint32_t log, int kind) {
+    const zr::FseCell c = zr::fse_cell(ns, log);
+    const zr::SymValue v = zr::sym_value(kind, sym);
+    FseEntry e;
+    e.next = (uint16_t)c.next;
+    e.nbits = (uint8_t)c.nbits;
+    e.addbits = (uint8_t)v.bits;
+    e.base = v.base;
+    return e;
 }
 
 // Build a decoding table from S.norm[0..nsym).  kind selects how (symbol -> base, addbits) maps:
@@ -680,36 +625,29 @@ __device__ int fse_read_ncount(Shared &S, const uint8_t *src, uint32_t n, int ma
 // kind < 0 = plain symbols (Huffman weights).
 template <class Shared>
 __device__ int fse_build(Shared &S, FseEntry *t, int nsym, int log, int kind) {
+    const zr::Flat<uint16_t> next{S.fse_next};
+    if (zr::fse_spread(zr::Flat<int16_t>{S.norm}, next, nsym, log, [&](uint32_t u, uint32_t sym) { S.fse_sym[u] = (uint8_t)sym; }) != 0)
+        return E_CORRUPT;
     const int size = 1 << log;
-    int high = size;
-    for (int s = 0; s < nsym; s++)
-        if (S.norm[s] == -1) { S.fse_sym[--high] = (uint8_t)s; S.fse_next[s] = 1; }
-    const int step = (size >> 1) + (size >> 3) + 3, mask = size - 1;
-    int pos = 0;
-    for (int s = 0; s < nsym; s++) {
-        int c = S.norm[s];
-        if (c <= 0) continue;
-        S.fse_next[s] = (uint16_t)c;
-        for (int i = 0; i < c; i++) {
-            S.fse_sym[pos] = (uint8_t)s;
-            do { pos = (pos + step) & mask; } while (pos >= high);
-        }
-    }
-    if (pos != 0) return E_CORRUPT;
     for (int i = 0; i < size; i++) {
-        uint32_t sym = S.fse_sym[i];
-        uint32_t ns = S.fse_next[sym]++;
-        int nb = log - hibit(ns);
-        FseEntry e;
-        e.next = (uint16_t)((ns << nb) - size);
-        e.nbits = (uint8_t)nb;
-        if (kind == K_LL) { if (sym > 35) return E_CORRUPT; e.base = c_ll_base[sym]; e.addbits = c_ll_bits[sym]; }
-        else if (kind == K_ML) { if (sym > 52) return E_CORRUPT; e.base = c_ml_base[sym]; e.addbits = c_ml_bits[sym]; }
-        else if (kind == K_OF) { if (sym > 31) return E_CORRUPT; e.base = 1u << sym; e.addbits = (uint8_t)sym; }
-        else { e.base = sym; e.addbits = 0; }
-        t[i] = e;
+        const uint32_t sym = S.fse_sym[i];
+        if (!zr::sym_in_range(kind, sym)) return E_CORRUPT;
+        t[i] = fse_entry(sym, zr::fse_take_state(next, sym), (uint32_t)log, kind);
     }
     return 0;
+}
+
+// the three predefined tables, once per workgroup (one lane; tiny): T is the scratch fse_build works in
+template <int K, class Tmp>
+__device__ __forceinline__ void fse_build_default(Tmp &T, FseEntry *t) {
+    for (int i = 0; i < zr::default_nsym(K); i++) T.norm[i] = zr::default_norm(K)[i];
+    fse_build(T, t, zr::default_nsym(K), zr::KIND[K].def_log, K);
+}
+template <class Tmp>
+__device__ __forceinline__ void fse_build_predefined(Tmp &T, FseEntry *dll, FseEntry *dof, FseEntry *dml) {
+    fse_build_default<K_LL>(T, dll);
+    fse_build_default<K_ML>(T, dml);
+    fse_build_default<K_OF>(T, dof);
 }
 
 // fse_build by one wave, for alphabets of at most 64 symbols (the three sequence tables): lane = symbol for the
@@ -735,8 +673,8 @@ __device__ void fse_build_wave(const int16_t *norm, uint32_t nsym, uint32_t log,
         const uint32_t nb = log - (uint32_t)hibit(ns);
         e.next = (uint16_t)((ns << nb) - size);
         e.nbits = (uint8_t)nb;
-        if (kind == K_LL) { e.base = c_ll_base[sym > 35 ? 35 : sym]; e.addbits = c_ll_bits[sym > 35 ? 35 : sym]; }
-        else if (kind == K_ML) { e.base = c_ml_base[sym > 52 ? 52 : sym]; e.addbits = c_ml_bits[sym > 52 ? 52 : sym]; }
+        if (kind == K_LL) { e.base = zr::LL_BASE[sym > 35 ? 35 : sym]; e.addbits = zr::LL_BITS[sym > 35 ? 35 : sym]; }
+        else if (kind == K_ML) { e.base = zr::ML_BASE[sym > 52 ? 52 : sym]; e.addbits = zr::ML_BITS[sym > 52 ? 52 : sym]; }
         else if (kind == K_OF) { e.base = 1u << (sym & 31); e.addbits = (uint8_t)sym; }
         else { e.base = sym; e.addbits = 0; }  // kind < 0: plain symbols (Huffman weights)
         return e;
@@ -780,96 +718,64 @@ __device__ void fse_build_wave(const int16_t *norm, uint32_t nsym, uint32_t log,
 }
 
 __device__ int fse_set_rle(FseEntry *e, uint32_t sym, int kind) {
-    e->next = 0; e->nbits = 0;
-    if (kind == K_LL) { if (sym > 35) return E_CORRUPT; e->base = c_ll_base[sym]; e->addbits = c_ll_bits[sym]; }
-    else if (kind == K_ML) { if (sym > 52) return E_CORRUPT; e->base = c_ml_base[sym]; e->addbits = c_ml_bits[sym]; }
-    else { if (sym > 31) return E_CORRUPT; e->base = 1u << sym; e->addbits = (uint8_t)sym; }
+    if (!zr::sym_in_range(kind, sym)) return E_CORRUPT;
+    *e = fse_entry(sym, 1, 0, kind);  // one cell: no bits, next state 0
     return 0;
 }
+
+// the FSE table of the Huffman weights as zr::huf_walk_weights reads it: a cell's symbol is the weight
+struct FseWeightTab {
+    const FseEntry *t;
+    __device__ __forceinline__ zr::HufCell operator()(uint32_t s) const { return zr::HufCell{t[s].base, t[s].nbits, t[s].next}; }
+};
 
 // Huffman tree description -> S.weights / S.sym_start / S.sym_len / S.huf_log (lane 0).
 template <class Shared>
 __device__ int huf_read_tree(Shared &S, const uint8_t *src, uint32_t n, const uint8_t *blob_end, uint32_t *consumed) {
     if (n < 1) return E_TRUNC;
-    uint32_t hb = src[0];
-    int nw = 0;
+    const uint32_t hb = src[0];
+    const zr::Flat<uint8_t> weights{S.weights};
+    uint32_t nw = 0;
     if (hb >= 128) {
-        int num = (int)hb - 127;
-        uint32_t bytes = (uint32_t)(num + 1) / 2;
-        if (1 + bytes > n) return E_TRUNC;
-        for (int i = 0; i < num; i++) {
-            uint8_t b = src[1 + i / 2];
-            S.weights[i] = (i & 1) ? (b & 15) : (b >> 4);
-        }
-        nw = num;
-        *consumed = 1 + bytes;
+        const int rc = zr::huf_direct_weights(src, n, weights, &nw, consumed);
+        if (rc) return rc;
     } else {
         if (hb == 0 || 1 + hb > n) return E_TRUNC;
         int nsym, log;
         uint32_t hdr;
         int rc = fse_read_ncount(S, src + 1, hb, 6, 255, &nsym, &log, &hdr);
         if (rc) return rc;
-        // weights table reuses the `of` slot region? no: keep sequence tables intact (repeat mode) -> use ll? also live.
-        // A 64-entry table fits in the dml slot only if ML is not in default mode later, so build into a
-        // private region: the seq_ll batch buffer is free while literals are being decoded.
+        // the weights' table goes where no sequence table lives (Repeat_Mode keeps those): the seq_ll batch buffer is free
+        // while literals are being decoded
         FseEntry *t = reinterpret_cast<FseEntry *>(S.seq_ll);
         rc = fse_build(S, t, nsym, log, -1);
         if (rc) return rc;
         if (hdr >= hb) return E_CORRUPT;
         BitR b;
         if (!b.init(src + 1 + hdr, hb - hdr, blob_end)) return E_CORRUPT;
-        uint32_t s1 = b.read(log), s2 = b.read(log);
-        for (;;) {
-            if (nw >= 255) return E_CORRUPT;
-            S.weights[nw++] = (uint8_t)t[s1].base;
-            s1 = t[s1].next + b.read(t[s1].nbits);
-            if (b.pos < 0) {
-                if (nw >= 255) return E_CORRUPT;
-                S.weights[nw++] = (uint8_t)t[s2].base;
-                break;
-            }
-            if (nw >= 255) return E_CORRUPT;
-            S.weights[nw++] = (uint8_t)t[s2].base;
-            s2 = t[s2].next + b.read(t[s2].nbits);
-            if (b.pos < 0) {
-                if (nw >= 255) return E_CORRUPT;
-                S.weights[nw++] = (uint8_t)t[s1].base;
-                break;
-            }
-        }
+        rc = zr::huf_walk_weights<false>(b, (uint32_t)log, FseWeightTab{t}, weights, &nw);
+        if (rc) return rc;
         *consumed = 1 + hb;
     }
     // implied last weight, code lengths, canonical start index per symbol
-    uint32_t total = 0;
-    for (int i = 0; i < nw; i++) {
-        uint32_t w = S.weights[i];
-        if (w > 12) return E_CORRUPT;
-        total += w ? 1u << (w - 1) : 0;
-    }
-    if (total == 0) return E_CORRUPT;
-    int maxbits = hibit(total) + 1;
-    if (maxbits > 11) return E_CORRUPT;
-    uint32_t left = (1u << maxbits) - total;
-    if (left & (left - 1)) return E_CORRUPT;
-    S.weights[nw] = (uint8_t)(hibit(left) + 1);
-    int nsym = nw + 1;
-    uint32_t rank_count[13], rank_idx[13];
-    for (int i = 0; i < 13; i++) rank_count[i] = 0;
-    for (int i = 0; i < nsym; i++) {
-        uint32_t w = S.weights[i];
-        rank_count[w ? maxbits + 1 - w : 0]++;
-    }
-    rank_idx[maxbits] = 0;
-    for (int i = maxbits; i >= 1; i--) rank_idx[i - 1] = rank_idx[i] + rank_count[i] * (1u << (maxbits - i));
-    if (rank_idx[0] != (1u << maxbits)) return E_CORRUPT;
+    uint32_t maxbits, lastw;
+    int rc = zr::huf_limits(weights, nw, &maxbits, &lastw);
+    if (rc) return rc;
+    S.weights[nw] = (uint8_t)lastw;
+    const uint32_t nsym = nw + 1;
+    // 16 entries of the table builder's scratch, free again (an array in registers is indexed by select chains).  S.fse_next must be the
+    // calling lane's alone until this function returns: one lane runs it over its wave's own scratch (k_fz_entropy: wave 0 S.ta, wave 1 S.tb)
+    uint16_t *const rank_idx = S.fse_next;
+    rc = zr::huf_rank_starts(weights, nsym, maxbits, zr::Flat<uint16_t>{rank_idx});
+    if (rc) return rc;
     for (int i = 0; i < 256; i++) S.sym_len[i] = 0;
-    for (int i = 0; i < nsym; i++) {
+    for (uint32_t i = 0; i < nsym; i++) {
         uint32_t w = S.weights[i];
         if (!w) continue;
         uint32_t bits = maxbits + 1 - w, len = 1u << (maxbits - bits);
         S.sym_start[i] = (uint16_t)rank_idx[bits];
         S.sym_len[i] = (uint16_t)len;
-        rank_idx[bits] += len;
+        rank_idx[bits] = (uint16_t)(rank_idx[bits] + len);
     }
     S.huf_log = maxbits;
     return 0;
@@ -913,27 +819,7 @@ __device__ int huf_read_tree_wave(Shared &S, const uint8_t *src, uint32_t n, con
         if (lane == 0) {
             BitR b;
             if (!b.init(src + 1 + hdr, hb - hdr, blob_end)) rc = E_CORRUPT;
-            else {
-                uint32_t s1 = b.read(log), s2 = b.read(log);
-                for (;;) {
-                    if (nw >= 255) { rc = E_CORRUPT; break; }
-                    S.weights[nw++] = (uint8_t)t[s1].base;
-                    s1 = t[s1].next + b.read(t[s1].nbits);
-                    if (b.pos < 0) {
-                        if (nw >= 255) { rc = E_CORRUPT; break; }
-                        S.weights[nw++] = (uint8_t)t[s2].base;
-                        break;
-                    }
-                    if (nw >= 255) { rc = E_CORRUPT; break; }
-                    S.weights[nw++] = (uint8_t)t[s2].base;
-                    s2 = t[s2].next + b.read(t[s2].nbits);
-                    if (b.pos < 0) {
-                        if (nw >= 255) { rc = E_CORRUPT; break; }
-                        S.weights[nw++] = (uint8_t)t[s1].base;
-                        break;
-                    }
-                }
-            }
+            else rc = zr::huf_walk_weights<false>(b, (uint32_t)log, FseWeightTab{t}, zr::Flat<uint8_t>{S.weights}, &nw);
         }
         rc = (int)uni((uint32_t)rc); nw = uni(nw);
         if (rc) return rc;
