@@ -23,6 +23,8 @@
  *   znippy_hash_rounds           blake3-only / store path      slot_packer.rs:L553-560 (skip branch)
  *   znippy_inflate_batch         ljar::decompress_jar_filter   znippy-plugin-maven/src/native.rs:L28-31,L47 (the inflate of the
  *                                over a batch of containers     entry the filter chose), znippy-plugin-python/src/native.rs:L85-89
+ *   znippy_targz_find_batch      parse_deps_from_tarball        znippy-common/src/plugins/cargo_native.rs:L46-71 (gunzip a .crate, walk
+ *                                over a batch of tarballs       the tar to the first .../Cargo.toml); sdists: znippy-plugin-python/src/native.rs:L17-21
  *
  * Codec wire format: one standard Zstandard frame (RFC 8878) per chunk.  (The reference's
  * OpenZL framing cannot be reproduced or checked offline — see DESIGN.md "Oracle".)
@@ -46,6 +48,7 @@ extern "C" {
 #define ZNIPPY_E_CHECKSUM (-7)    /* frame content checksum (XXH64) mismatch */
 #define ZNIPPY_E_DIGEST (-8)      /* BLAKE3 of the bytes does not match the index checksum or block tree */
 #define ZNIPPY_E_NOENT (-9)       /* no entry of the container matches */
+#define ZNIPPY_E_MORE (-10)       /* the answer lies behind the bytes given */
 
 typedef struct znippy_ctx znippy_ctx;
 typedef struct znippy_rows znippy_rows;     /* read side: a range of index rows, device-resident */
@@ -386,6 +389,49 @@ int znippy_rows_read_ranges_verified(znippy_ctx *ctx, znippy_rows *rows, const v
 int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
                          const uint8_t *method, void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
                          const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out);
+
+/* ---- one tar member out of gzip-compressed tars the engine already holds ----------------------------------------------------
+ * The third registry type of the reference (znippy-common/src/plugins/cargo_native.rs:L46-71: a .crate is gunzipped and its tar walked to
+ * the first .../Cargo.toml; znippy-plugin-python/src/native.rs:L17-21 lists .tar.gz sdists beside wheels).  Such files sit in the archive as
+ * stored gzip streams.  A tar has no directory — where a member lies is known only while the stream is inflated — so this call decodes
+ * each stream only until the tar it produces answers the question: "the filter happens before any decompression work"
+ * (TODO_NOW.md:L200-213) becomes "stop the moment the answer is known".  Plain .tar, bzip2 / xz tarballs and multi-member gzip are out of
+ * scope.
+ *   d_src, src_cap     DEVICE: the region that holds the files; item i is the gzip member d_src[src_off[i] .. + src_len[i])
+ *   whole              HOST, optional (NULL: every item is whole): 0 = item i is only the head of its file
+ *   name_prefix/suffix the filter, compared as bytes as in znippy_zip_find_entry: the first regular member (typeflag '0', '\0', '7') in
+ *                      stream order whose name starts with the one and ends with the other wins
+ *   scan_cap           at least 512: the most inflated bytes one item may take.  Item i gets min(scan_cap, 1032 * src_len + 512) bytes (no
+ *                      valid DEFLATE expands more; below 4 GiB - 16 in any case), rounded up to 16, of the context's grow-only range
+ *                      scratch, capped at 16 GiB: a batch that needs more returns ZNIPPY_E_NOMEM with nothing queued
+ *   d_out, out_cap     DEVICE: the members with status 0 are packed back to back in array order
+ *   out_off, out_len   HOST out: where member i lies in d_out; 0, 0 for an item with another status
+ *   status             HOST, optional: per item, see below
+ *   scanned            HOST, optional: bytes inflated per item
+ * Per item: 0; ZNIPPY_E_NOENT — the tar ended (two zero blocks, or the final block ends at a header boundary) and no member matched;
+ * ZNIPPY_E_CORRUPT — no gzip magic, a DEFLATE stream zlib's raw inflate refuses, a tar header that fails its checksum or whose size is
+ * no number, a final block that ends inside a header or member, input of a whole item that ends first; ZNIPPY_E_MORE — input of an item
+ * that is not whole ends first (inside the gzip header, inside the stream, or so closely behind it that a following member could not
+ * be seen): ask again with more of the file; ZNIPPY_E_UNSUPPORTED — a method other than 8 or reserved flag bits in the gzip header,
+ * a GNU sparse member, a long-name or pax payload above 8 KiB, or 10 or more bytes that start another gzip member behind the 8-byte
+ * trailer (multi-member files are not guessed at); ZNIPPY_E_DST_SMALL — the member is not complete within the item's scan bytes (an
+ * item ends at once when the walk needs bytes beyond them: nothing is inflated up to the cap first), or it no longer fits into out_cap
+ * (it takes no room, and members behind it may still fit).  The rules of the walk, with Python's tarfile as arbiter: csrc/tar_rules.h.
+ * The gzip trailer (CRC-32, ISIZE) is never checked: the call usually stops long before it.  The archive's BLAKE3 is the integrity
+ * check of the container.
+ * Host validation, per item, before any kernel runs: source not inside [0, src_cap), or off + len overflowing: ZNIPPY_E_INVAL; src_len
+ * of 4 GiB or more: ZNIPPY_E_UNSUPPORTED.  No kernel touches such an item and the call returns ZNIPPY_OK whatever the items report.
+ * ZNIPPY_E_INVAL is returned only for NULL required arguments, a filter string of 64 KiB or more, scan_cap below 512, a closed context
+ * or n of 2^32 - 16 or more; n == 0 is ZNIPPY_OK.
+ * Writes: no byte of d_out outside the packed members is written.  Not a run, and synchronous on the context's stream, exactly as
+ * znippy_inflate_batch; no table is touched; every allocation is made before the first stream operation
+ * (znippy_last_kernel_times: targz_find, targz_gather).
+ * Kernels: one wave decodes one stream with the decoder of znippy_inflate_batch and steps the tar walk on what it has produced
+ * (csrc/targz.hip); the members are moved by the range reads' gather. */
+int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
+                            const uint8_t *whole, uint64_t n, const char *name_prefix, uint64_t prefix_len, const char *name_suffix,
+                            uint64_t suffix_len, uint64_t scan_cap, void *d_out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len,
+                            int32_t *status, uint64_t *scanned);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,

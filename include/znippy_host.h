@@ -178,6 +178,23 @@ int znippy_zip_local_data_offset(const uint8_t *header, size_t header_len, uint6
 int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files,
                                        const char *name_prefix, const char *name_suffix, void *dst, size_t cap,
                                        uint64_t *entry_off /* n_files + 1 */, int32_t *status);
+/* For every archived file of relative_paths (each a gzip-compressed tar: a .crate, a .tar.gz sdist, a .tgz): the content of its first
+ * regular member whose name starts with name_prefix and ends with name_suffix (either may be NULL or empty) — what the reference's
+ * cargo plugin does per crate (znippy-common/src/plugins/cargo_native.rs:L46-71), on the read side and for all files at once.
+ * Pass 1 gathers bytes [0, min(file size, head)) of every file on the device — one range-read pass whose result is not copied to the
+ * host — and runs the znippy_targz_find_batch of include/znippy_hip.h on them there, a file shorter than head as a whole one; pass 2 does
+ * the same with the whole file for exactly the files that reported ZNIPPY_E_MORE.  Only the members come back to the host.  head is
+ * 64 KiB; ZNIPPY_HOST_TARGZ_HEAD in the environment, read at the call, overrides it.  scan_cap (at least 512): the most inflated bytes
+ * one file may take.
+ * Results as in znippy_archive_extract_zip_entries: file i at dst[entry_off[i] .. entry_off[i + 1]) (entry_off: n_files + 1 values), of
+ * length 0 when its status is not 0.  status (optional), per file: 0; ZNIPPY_E_INVAL an unknown path; ZNIPPY_E_UNSUPPORTED a file of
+ * 4 GiB or more; the per-item codes of that call (ZNIPPY_E_NOENT, ZNIPPY_E_CORRUPT — an empty file too —, ZNIPPY_E_UNSUPPORTED,
+ * ZNIPPY_E_DST_SMALL for a member not complete within scan_cap); ZNIPPY_E_DST_SMALL when cap does not hold it (the files in front of
+ * it are unaffected); a chunk's decode error.  The call returns ZNIPPY_OK whatever the files report; NULL arguments and a scan_cap
+ * below 512 give ZNIPPY_E_INVAL. */
+int znippy_archive_extract_tar_members(znippy_archive *a, const char *const *relative_paths, uint64_t n_files,
+                                       const char *name_prefix, const char *name_suffix, uint64_t scan_cap, void *dst, size_t cap,
+                                       uint64_t *entry_off /* n_files + 1 */, int32_t *status);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

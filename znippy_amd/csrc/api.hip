@@ -3300,3 +3300,115 @@ extern "C" int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t
                                     const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out) {
     ZN_NO_THROW(inflate_batch(ctx, d_src, src_cap, src_off, src_len, method, d_out, out_cap, out_off, out_len, crc32, n, status, crc_out))
 }
+
+// ---- one tar member out of gzip-compressed tars (znippy_targz_find_batch) ----------------------------
+// Not a run, like the call above: the items are validated on the host, the ones that pass get a slice of the context's range scratch
+// (sized before anything is queued) and are walked by one launch (wave = stream, targz.hip); status, place and length come back in one
+// copy; the members that were found and fit are packed into d_out by the range reads' gather.
+static int targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, const uint8_t *whole,
+                            uint64_t n, const char *name_prefix, uint64_t prefix_len, const char *name_suffix, uint64_t suffix_len, uint64_t scan_cap,
+                            void *d_out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len, int32_t *status, uint64_t *scanned) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
+    if (!n) return ZNIPPY_OK;
+    if (!src_off || !src_len || !out_off || !out_len || !d_src || (out_cap && !d_out) || (prefix_len && !name_prefix) || (suffix_len && !name_suffix) ||
+        prefix_len >= (1u << 16) || suffix_len >= (1u << 16) || scan_cap < 512)
+        return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ctx->n_ktimes = 0;
+
+    // 1) every item against the source region; its slice of the scratch
+    std::vector<int32_t> st(n, 0);
+    std::vector<TargzItem> items;
+    std::vector<uint64_t> slice;    // list entry -> offset of its slice
+    std::vector<uint32_t> item_of;  // list entry -> item
+    uint64_t need = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t so = src_off[i], sl = src_len[i];
+        out_off[i] = out_len[i] = 0;
+        if (scanned) scanned[i] = 0;
+        if (so > src_cap || sl > src_cap - so) { st[i] = ZNIPPY_E_INVAL; continue; }
+        if (sl >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
+        // no valid DEFLATE expands more than 1032 : 1, and one item walks at most 4 GiB - 16 bytes of tar
+        const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>(scan_cap, 1032 * sl + 512), 0xFFFFFFF0ull);
+        TargzItem it;
+        it.src = (const uint8_t *)d_src + so;
+        it.scratch = nullptr;
+        it.src_len = (uint32_t)sl; it.cap = (uint32_t)cap;
+        it.whole = whole ? whole[i] != 0 : 1; it.pad = 0;
+        items.push_back(it);
+        slice.push_back(need);
+        item_of.push_back((uint32_t)i);
+        need += (cap + 15) & ~15ull;
+        if (need > (1ull << 40)) return ZNIPPY_E_NOMEM;  // (far beyond the scratch's cap: the sum stays small)
+    }
+    const uint32_t n_items = (uint32_t)items.size();
+    std::vector<TargzResult> res(n_items);
+    if (n_items) {
+        // 2) every allocation, then the stream
+        int rc;
+        if ((rc = ensure_range_scratch(ctx, 0, need))) return rc;
+        for (uint32_t k = 0; k < n_items; k++) items[k].scratch = ctx->rr_pool[0] + slice[k];
+        struct Guard {
+            znippy_ctx *ctx;
+            TargzItem *items = nullptr; TargzResult *res = nullptr; uint8_t *filter = nullptr; RangePiece *pieces = nullptr;
+            ~Guard() { tfree(ctx, items); tfree(ctx, res); tfree(ctx, filter); tfree(ctx, pieces); }
+        } g{ctx};
+        std::vector<uint8_t> filter(prefix_len + suffix_len + 16, 0);
+        if (prefix_len) memcpy(filter.data(), name_prefix, prefix_len);
+        if (suffix_len) memcpy(filter.data() + prefix_len, name_suffix, suffix_len);
+        // the gather's list is cut once the results are known: at most one piece per RANGE_PIECE bytes of output and one more per item
+        const size_t max_pieces = (size_t)(out_cap / RANGE_PIECE) + 2 * (size_t)n_items;
+        if (max_pieces > RR_ITEMS_MAX) return ZNIPPY_E_NOMEM;
+        HIPCHK(ctx, tmalloc(ctx, &g.items, sizeof(TargzItem) * n_items));
+        HIPCHK(ctx, tmalloc(ctx, &g.res, sizeof(TargzResult) * n_items));
+        HIPCHK(ctx, tmalloc(ctx, &g.filter, filter.size()));
+        HIPCHK(ctx, tmalloc(ctx, &g.pieces, sizeof(RangePiece) * max_pieces));
+        std::vector<RangePiece> pieces;
+        pieces.reserve(2 * (size_t)n_items);
+        HIPCHK(ctx, hipMemcpyAsync(g.items, items.data(), sizeof(TargzItem) * n_items, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(g.filter, filter.data(), filter.size(), hipMemcpyHostToDevice, s));
+        timed(ctx, "targz_find", s, [&] { launch_targz_find(g.items, n_items, g.filter, (uint32_t)prefix_len, (uint32_t)suffix_len, g.res, s); });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(res.data(), g.res, sizeof(TargzResult) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        // 3) the members found, back to back in array order; one that no longer fits takes no room, and those behind it may still fit
+        uint64_t packed = 0;
+        for (uint32_t k = 0; k < n_items; k++) {
+            const uint32_t i = item_of[k];
+            const TargzResult &r = res[k];
+            st[i] = r.status;
+            if (scanned) scanned[i] = r.scanned;
+            if (r.status != 0) continue;
+            if (r.off > items[k].cap || r.len > items[k].cap - r.off) { st[i] = ZNIPPY_E_CORRUPT; continue; }  // (the kernel's word is checked, not trusted)
+            if (r.len > out_cap - packed) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+            out_off[i] = packed; out_len[i] = r.len;
+            const uint8_t *from = items[k].scratch + r.off;
+            uint8_t *to = (uint8_t *)d_out + packed;
+            for (uint64_t left = r.len; left;) {  // from the second piece of a member on, a destination starts on a 128-byte line
+                const uint64_t room = RANGE_PIECE - ((uintptr_t)to & 127), len = std::min(left, room);
+                pieces.push_back(RangePiece{from, to, (uint32_t)len, 0});
+                from += len; to += len; left -= len;
+            }
+            packed += r.len;
+        }
+        if (!pieces.empty()) {
+            if (pieces.size() > max_pieces) return ZNIPPY_E_NOMEM;  // (cannot happen: the bound above counts them)
+            HIPCHK(ctx, hipMemcpyAsync(g.pieces, pieces.data(), sizeof(RangePiece) * pieces.size(), hipMemcpyHostToDevice, s));
+            timed(ctx, "targz_gather", s, [&] { launch_range_gather(g.pieces, (uint32_t)pieces.size(), s); });
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+    }
+    if (status) memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
+                                       const uint8_t *whole, uint64_t n, const char *name_prefix, uint64_t prefix_len, const char *name_suffix,
+                                       uint64_t suffix_len, uint64_t scan_cap, void *d_out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len,
+                                       int32_t *status, uint64_t *scanned) {
+    ZN_NO_THROW(targz_find_batch(ctx, d_src, src_cap, src_off, src_len, whole, n, name_prefix, prefix_len, name_suffix, suffix_len, scan_cap, d_out, out_cap,
+                                 out_off, out_len, status, scanned))
+}

@@ -305,4 +305,24 @@ void launch_inflate(const InflateItem *items, uint32_t n_items, int32_t *status,
 // for every item with status 0: crc_out[i] = CRC-32 of its out_len bytes; status[i] = ZNIPPY_E_CHECKSUM where has_crc and it is not want_crc
 void launch_inflate_crc(const InflateItem *items, uint32_t n_items, int32_t *status, uint32_t *crc_out, hipStream_t s);
 
+// One tar member out of gzip-compressed tars (targz.hip, znippy_targz_find_batch): one item the host has validated, decoded by one
+// wave only as far as the tar has to be read
+struct TargzItem {
+    const uint8_t *src;  // the gzip member, any alignment
+    uint8_t *scratch;    // where the tar is inflated to: 16-byte aligned, cap rounded up to 16 bytes long
+    uint32_t src_len;    // below 4 GiB
+    uint32_t cap;        // inflated bytes the item may take: 512 .. 4 GiB - 16
+    uint32_t whole;      // src is the whole file: input that ends inside the stream is damage, not "more"
+    uint32_t pad;
+};
+struct TargzResult {
+    int32_t status;    // 0 or ZNIPPY_E_*
+    uint32_t pad;
+    uint64_t off, len;  // status 0: the member is scratch[off .. off + len)
+    uint64_t scanned;   // bytes inflated
+};
+// filter: name_prefix then name_suffix, in device memory.  res[i] for every item; no byte outside [scratch, scratch + cap) is written
+void launch_targz_find(const TargzItem *items, uint32_t n_items, const uint8_t *filter, uint32_t prefix_len, uint32_t suffix_len, TargzResult *res,
+                       hipStream_t s);
+
 }  // namespace zn

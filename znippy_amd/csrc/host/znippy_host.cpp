@@ -1419,15 +1419,18 @@ using zn::FileRange;  // bytes [off, off + len) of one archived file, wholly ins
 // ONE znippy_rows_read_ranges over a private table of them gathers all requests packed back to back, and one copy brings them to the
 // host: request i at host[at[i] .. at[i] + len), st[i] = 0 or a chunk's ZNIPPY_E_*.  Nothing is kept between passes: a compressed
 // chunk that two passes touch is read and uploaded twice.
+// host == NULL: the copy to the host is skipped and the requests stay on the device, request i at a->bufs.d_out.p + at[i], *on_device
+// bytes in all (for a caller that goes on working on them there).
 int read_file_ranges(znippy_archive *a, const std::vector<FileRange> &req, std::vector<uint8_t> *host, std::vector<uint64_t> *at,
-                     std::vector<int32_t> *st) {
+                     std::vector<int32_t> *st, uint64_t *on_device = nullptr) {
     zn::FileRangesRead p = zn::plan_file_ranges(a->ix.view(), req);
     const RowTable &t = p.t;
     const zn::RangeList &rg = p.rg;
     const uint64_t total = p.total;
     at->swap(p.at);
     st->swap(p.st);
-    host->assign((size_t)total, 0);
+    if (host) host->assign((size_t)total, 0);
+    if (on_device) *on_device = total;
     if (!rg.n()) return ZNIPPY_OK;
     ReadBufs &bufs = a->bufs;
     if (!bufs.blob_pin.reserve(std::max<uint64_t>(t.sum, total) + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
@@ -1443,7 +1446,7 @@ int read_file_ranges(znippy_archive *a, const std::vector<FileRange> &req, std::
     if (rc) return fail(rc, std::string("range read failed: ") + znippy_last_error(a->ctx));
     for (size_t k = 0; k < rst.size(); k++)
         if (rst[k] < 0 && (*st)[p.of_req[k]] == 0) (*st)[p.of_req[k]] = rst[k];
-    if (total && hipMemcpy(host->data(), bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+    if (host && total && hipMemcpy(host->data(), bufs.d_out.p, total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
     return ZNIPPY_OK;
 }
 
@@ -1575,11 +1578,108 @@ static int znippy_archive_extract_zip_entries_impl(znippy_archive *a, const char
     return ZNIPPY_OK;
 }
 
+// ---- one member of archived gzip-compressed tars (znippy_archive_extract_tar_members) ----------------------------
+// Pass 1 gathers the first `head` bytes of every file on the device (one range read, no copy to the host) and runs
+// znippy_targz_find_batch on them there; pass 2 does the same with the whole file for exactly the files whose head did not hold the
+// answer (ZNIPPY_E_MORE).  Only the members come back to the host.
+static int znippy_archive_extract_tar_members_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, const char *name_prefix,
+                                                   const char *name_suffix, uint64_t scan_cap, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {
+    if (!a || !entry_off || (n_files && !paths) || (cap && !dst) || scan_cap < 512) return fail(ZNIPPY_E_INVAL, "null argument or scan_cap below 512");
+    const char *prefix = name_prefix ? name_prefix : "", *suffix = name_suffix ? name_suffix : "";
+    uint64_t head = 64 << 10;
+    if (const char *v = getenv("ZNIPPY_HOST_TARGZ_HEAD")) {  // (read at the call)
+        char *end = nullptr;
+        const unsigned long long h = strtoull(v, &end, 0);
+        if (end != v && *end == 0 && h) head = h;
+    }
+    const size_t n = (size_t)n_files;
+    std::vector<int32_t> st(n, 0);
+    std::vector<const std::vector<uint64_t> *> rows(n, nullptr);
+    std::vector<uint64_t> fsize(n, 0);
+    const IndexView view = a->ix.view();
+    for (size_t i = 0; i < n; i++) {
+        auto it = paths[i] ? a->files.find(paths[i]) : a->files.end();
+        if (it == a->files.end()) { st[i] = ZNIPPY_E_INVAL; continue; }
+        rows[i] = &it->second;
+        for (uint64_t r : it->second) fsize[i] += view.row_len(r);
+        if (fsize[i] >= (1ull << 32)) st[i] = ZNIPPY_E_UNSUPPORTED;
+        else if (fsize[i] == 0) st[i] = ZNIPPY_E_CORRUPT;  // no gzip member
+    }
+    int rc = archive_ctx(a);
+    if (rc) return rc;
+    std::vector<std::vector<uint8_t>> member(n);
+    ReadBufs &bufs = a->bufs;
+    // one pass over the files of `who`, the first take(i) bytes of each
+    auto pass = [&](const std::vector<size_t> &who, bool whole_files) -> int {
+        if (who.empty()) return ZNIPPY_OK;
+        std::vector<FileRange> req;
+        for (size_t i : who) req.push_back(FileRange{rows[i], 0, whole_files ? fsize[i] : std::min(fsize[i], head)});
+        std::vector<uint64_t> at;
+        std::vector<int32_t> rst;
+        uint64_t total = 0;
+        int rc = read_file_ranges(a, req, nullptr, &at, &rst, &total);
+        if (rc) return rc;
+        std::vector<uint64_t> s_off, s_len;
+        std::vector<uint8_t> whole;
+        std::vector<size_t> item_file;
+        uint64_t bound = 0;  // what the members of this pass can come to
+        for (size_t k = 0; k < who.size(); k++) {
+            const size_t i = who[k];
+            if (rst[k]) { st[i] = rst[k]; continue; }
+            s_off.push_back(at[k]); s_len.push_back(req[k].len); whole.push_back(req[k].len == fsize[i]); item_file.push_back(i);
+            bound += std::min<uint64_t>(scan_cap, 1032 * req[k].len + 512);
+        }
+        if (item_file.empty()) return ZNIPPY_OK;
+        const uint64_t out_cap = std::min<uint64_t>(bound, cap);
+        if (!bufs.d_blobs.reserve(out_cap + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");  // (the chunks in it have been gathered from)
+        std::vector<uint64_t> o_off(item_file.size(), 0), o_len(item_file.size(), 0);
+        std::vector<int32_t> ist(item_file.size(), 0);
+        rc = znippy_targz_find_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), whole.data(), item_file.size(), prefix, strlen(prefix), suffix,
+                                     strlen(suffix), scan_cap, bufs.d_blobs.p, out_cap, o_off.data(), o_len.data(), ist.data(), nullptr);
+        if (rc) return fail(rc, std::string("tar member search failed: ") + znippy_last_error(a->ctx));
+        uint64_t found = 0;
+        for (size_t j = 0; j < item_file.size(); j++) found = std::max(found, o_off[j] + o_len[j]);
+        if (!bufs.blob_pin.reserve(found + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+        if (found && hipMemcpy(bufs.blob_pin.p, bufs.d_blobs.p, found, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+        for (size_t j = 0; j < item_file.size(); j++) {
+            st[item_file[j]] = ist[j];
+            if (ist[j] == 0) member[item_file[j]].assign(bufs.blob_pin.p + o_off[j], bufs.blob_pin.p + o_off[j] + o_len[j]);
+        }
+        return ZNIPPY_OK;
+    };
+    std::vector<size_t> who;
+    for (size_t i = 0; i < n; i++)
+        if (st[i] == 0) who.push_back(i);
+    if ((rc = pass(who, false))) return rc;
+    who.clear();
+    for (size_t i = 0; i < n; i++)
+        if (st[i] == ZNIPPY_E_MORE) { st[i] = 0; who.push_back(i); }
+    if ((rc = pass(who, true))) return rc;
+    // the members, packed in file order; one that does not fit is left out and the ones behind it may still fit
+    uint64_t cursor = 0;
+    for (size_t i = 0; i < n; i++) {
+        entry_off[i] = cursor;
+        if (st[i]) continue;
+        const uint64_t len = member[i].size();
+        if (len > cap - cursor) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (len) std::memcpy((uint8_t *)dst + cursor, member[i].data(), (size_t)len);
+        cursor += len;
+    }
+    entry_off[n] = cursor;
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
 extern "C" {
 
 int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
                                        const char *name_suffix, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {
     return guarded([&] { return znippy_archive_extract_zip_entries_impl(a, relative_paths, n_files, name_prefix, name_suffix, dst, cap, entry_off, status); });
+}
+
+int znippy_archive_extract_tar_members(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
+                                       const char *name_suffix, uint64_t scan_cap, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {
+    return guarded([&] { return znippy_archive_extract_tar_members_impl(a, relative_paths, n_files, name_prefix, name_suffix, scan_cap, dst, cap, entry_off, status); });
 }
 
 int znippy_archive_block_tree_stats(const znippy_archive *a, uint64_t stats[4]) {

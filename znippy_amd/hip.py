@@ -175,6 +175,27 @@ class Context:
                                               opt(oo), np_ptr(ol), opt(cr), n, np_ptr(status), np_ptr(crc)), "znippy_inflate_batch")
         return status[:n], crc[:n]
 
+    # ---- one tar member out of gzip-compressed tars held in device memory ----
+    def targz_find_batch(self, d_src, src_off, src_len, d_out, suffix, prefix=b"", whole=None, scan_cap=8 << 20, src_cap=None, out_cap=None):
+        """znippy_targz_find_batch: item i is the gzip member d_src[src_off[i] .. + src_len[i]) of a tar (whole[i] = 0: only the head of
+        its file; None: all whole).  Each is inflated only until the first regular member whose name starts with `prefix` and ends with
+        `suffix` (bytes) is complete; the members found are packed back to back into d_out in array order.  scan_cap: the most
+        inflated bytes one item may take.  Synchronous and not a run.  Returns (status per item: 0 or ZNIPPY_E_* — ZNIPPY_E_MORE asks
+        for more of the file —, out_off, out_len, bytes inflated per item)."""
+        so, sl = as_np(src_off, np.uint64), as_np(src_len, np.uint64)
+        wh = as_np(whole, np.uint8) if whole is not None else None
+        n = len(so)
+        assert len(sl) == n and (wh is None or len(wh) == n), "item arrays differ in length"
+        prefix, suffix = bytes(prefix), bytes(suffix)
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        oo, ol, sc = (np.zeros(max(n, 1), dtype=np.uint64) for _ in range(3))
+        self._chk(self.L.znippy_targz_find_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), np_ptr(wh) if wh is not None else None, n,
+                                                 prefix, len(prefix), suffix, len(suffix), int(scan_cap), _dptr(d_out), int(out_cap),
+                                                 np_ptr(oo), np_ptr(ol), np_ptr(status), np_ptr(sc)), "znippy_targz_find_batch")
+        return status[:n], oo[:n], ol[:n], sc[:n]
+
 
 def get_decompressed_size(frame) -> int:
     a = np.frombuffer(frame, dtype=np.uint8)

@@ -29,7 +29,7 @@ class _ME(C.Structure):
 HOST_EXPORTS = [
     "znippy_host_last_error", "znippy_compress_stream", "znippy_stream_send", "znippy_stream_send_packed", "znippy_stream_finish",
     "znippy_compress_dir", "znippy_decompress_archive", "znippy_archive_open", "znippy_archive_file_count", "znippy_archive_file_size",
-    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
+    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
     "znippy_index_manifest_len", "znippy_index_manifest_entry", "znippy_index_row", "znippy_index_metadata",
     "znippy_index_close", "znippy_interpret_footer", "znippy_write_manifest_bytes",
 ]
@@ -61,6 +61,7 @@ def lib():
         L.znippy_archive_block_tree_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.znippy_archive_close.argtypes = [vp]
         L.znippy_archive_extract_zip_entries.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, vp, C.c_size_t, vp, vp]
+        L.znippy_archive_extract_tar_members.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp, vp]
         L.znippy_zip_end_of_directory.argtypes = [vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.znippy_zip_find_entry.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, vp]
         L.znippy_zip_local_data_offset.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64)]
@@ -249,6 +250,40 @@ class ZnippyArchive:
                     again.append(i)
             # (DEFLATE expands at most 1032-fold: more room than that for the containers left cannot help)
             most = sum(1032 * (self.file_size(paths[i]) or 0) + 64 for i in again)
+            if cap is not None or room >= most:
+                break
+            todo, room = again, min(8 * room, most)
+        return out, status
+
+    def extract_tar_members(self, paths, suffix, prefix="", scan_cap=8 << 20, cap=None):
+        """For every archived gzip-compressed tar of `paths` (.crate files, .tar.gz sdists): the content of its first regular member
+        whose name starts with `prefix` and ends with `suffix` — the Cargo.toml of a batch of crates — found on the device: the first
+        64 KiB of every file (ZNIPPY_HOST_TARGZ_HEAD overrides) are gathered there and inflated only until the tar answers, the files
+        whose head did not hold the answer go through once more whole, and only the members come back.  scan_cap: the most inflated
+        bytes one file may take.  cap: bytes of the result buffer of the one call made.  None: the first call gets 16 KiB per file +
+        1 MiB, and the files that did not fit (ZNIPPY_E_DST_SMALL) go through the call again with eight times the room, until they
+        fit or the room is what scan_cap lets them come to.  Returns (list of bytes, or None where the status is not 0; statuses)."""
+        paths = [str(p) for p in paths]
+        n = len(paths)
+        out, status = [None] * n, [0] * n
+        todo = list(range(n))
+        room = int(cap) if cap is not None else (16 << 10) * n + (1 << 20)
+        while todo:
+            m = len(todo)
+            arr = (C.c_char_p * m)(*[paths[i].encode() for i in todo])
+            buf = np.empty(max(room, 1), dtype=np.uint8)
+            off = np.zeros(m + 1, dtype=np.uint64)
+            st = np.zeros(m, dtype=np.int32)
+            _chk(lib().znippy_archive_extract_tar_members(self.h, arr, m, prefix.encode(), suffix.encode(), int(scan_cap), buf.ctypes.data_as(vp), room,
+                                                          off.ctypes.data_as(vp), st.ctypes.data_as(vp)), "extract_tar_members")
+            again = []
+            for k, i in enumerate(todo):
+                status[i] = int(st[k])
+                if st[k] == 0:
+                    out[i] = buf[int(off[k]):int(off[k + 1])].tobytes()
+                elif st[k] == _lib.E_DST_SMALL:
+                    again.append(i)
+            most = sum(min(int(scan_cap), 1032 * (self.file_size(paths[i]) or 0) + 512) for i in again)
             if cap is not None or room >= most:
                 break
             todo, room = again, min(8 * room, most)
