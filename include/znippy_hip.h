@@ -567,6 +567,16 @@ int znippy_measure_blake3_pass_ns(znippy_ctx *ctx, float *ns_per_pass_per_simd, 
 /* Shader clock (GHz) one wave of the read side's small-row kernel saw during the last run of a context created with
  * ZNIPPY_DBG bit 32768 set: its life in shader cycles / in 100 MHz ticks.  0 if nothing was recorded. */
 int znippy_last_shader_ghz(znippy_ctx *ctx, float *ghz);
+/* Diagnostic: the role-split read kernel as this library was built and as this context runs it.  geometry[0] waves per
+ * workgroup, [1] ring slots, [2] workgroups per CU, [3] bytes of dynamic LDS per workgroup, [4] registers per lane, [5] LDS
+ * bytes it holds of a CU, [6] 1 if a run's verify is queued beside the next run (it fits on a CU beside the kernel), [7] 1 if
+ * the run lanes are on.  From a context created with ZNIPPY_DBG bit 32768 also what the waves of the last run left: 8 words
+ * per wave, workgroup by workgroup (word 7 of each: the launch's workgroups) — its life in shader cycles; the cycles of its
+ * three waits (a hasher: before its first tile, between tiles, the last one that ends without a tile; the loader: for a free
+ * group, for its publish turn, and the length of its first iteration); the tiles (iterations) it got; its first and last
+ * 100 MHz tick.  At most cap_words words are copied to waves (HOST; may be NULL with cap_words 0), *n_words says how many.
+ * Synchronises. */
+int znippy_roles_wait_stats(znippy_ctx *ctx, uint32_t geometry[8], uint64_t *waves, uint64_t cap_words, uint64_t *n_words);
 
 /* Where a verify-only run (znippy_verify_rows) keeps the rows it has to materialise: the context's scratch region as it
  * is now (*d_base, DEVICE; NULL when the table needs none), the extent of this table's slots in it (*bytes) and, when

@@ -953,7 +953,9 @@ int znippy_ctx_create(int device, void *hip_stream, znippy_ctx **out) {
         ctx->encode_grid_small = cus * 16;  // 4 KiB hash table per wave
     }
     if (!ctx->sw.no_fork_verify) {
-        // gfx950: 512 registers per SIMD lane handed out in blocks of 8, 160 KiB of LDS per CU; a workgroup of k_verify is one wave per SIMD
+        // gfx950: 512 registers per SIMD lane handed out in blocks of 8, 160 KiB of LDS per CU; a workgroup of k_verify is one wave per SIMD.
+        // (The role-split kernel's side is what it holds of a CU with all its workgroups resident — two of eight waves and 74 KiB
+        // by default: 4 x 120 registers + 32, 148.3 KiB + 192 bytes, five waves per SIMD.  Its registers must stay <= 120 for this.)
         int rr = 0, rw = 0, rl = 0, vr = 0, vl = 0;
         if (roles_footprint(&rr, &rw, &rl) == 0 && verify_footprint(&vr, &vl) == 0)
             ctx->fork_verify = rw * ((rr + 7) / 8 * 8) + (vr + 7) / 8 * 8 <= 512 && rl + vl <= 160 * 1024 && rw + 1 <= 8;
@@ -1126,6 +1128,26 @@ int znippy_last_shader_ghz(znippy_ctx *ctx, float *ghz) {
     unsigned long long h[2] = {0, 0};
     HIPCHK(ctx, hipMemcpy(h, ctx->clk_buf, 16, hipMemcpyDeviceToHost));
     if (h[1]) *ghz = (float)((double)h[0] / (double)h[1] * 0.1);
+    return ZNIPPY_OK;
+}
+
+// The role-split read kernel's geometry and what decides whether a run's verify is forked, and — from a context created with
+// ZNIPPY_DBG bit 32768 — the wait counters its waves left in the last run (fused_small.hip: roles_clk_add).
+int znippy_roles_wait_stats(znippy_ctx *ctx, uint32_t geometry[8], uint64_t *waves, uint64_t cap_words, uint64_t *n_words) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || !geometry || !n_words || (cap_words && !waves)) return ZNIPPY_E_INVAL;
+    int rr = 0, rw = 0, rl = 0;
+    roles_geometry(geometry);
+    if (roles_footprint(&rr, &rw, &rl) != 0) return ZNIPPY_E_HIP;
+    geometry[4] = (uint32_t)rr; geometry[5] = (uint32_t)rl; geometry[6] = ctx->fork_verify; geometry[7] = ctx->lanes_on;
+    *n_words = 0;
+    if (!ctx->clk_buf) return ZNIPPY_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, lanes_sync(ctx));
+    const uint64_t have = roles_clk_bytes(ctx->cus) / 8 - 8;
+    *n_words = have < cap_words ? have : cap_words;
+    if (*n_words) HIPCHK(ctx, hipMemcpy(waves, ctx->clk_buf + 8, *n_words * 8, hipMemcpyDeviceToHost));
     return ZNIPPY_OK;
 }
 
@@ -1516,7 +1538,7 @@ static int run_small_rows(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, con
         set_fused_dbg(f.dbg_buf);
     }
     if (f.dbg & 32768) {
-        if (!ctx->clk_buf) { (void)hipMalloc(&ctx->clk_buf, 64); (void)hipMemset(ctx->clk_buf, 0, 64); }
+        if (!ctx->clk_buf) { (void)hipMalloc(&ctx->clk_buf, roles_clk_bytes(ctx->cus)); (void)hipMemset(ctx->clk_buf, 0, roles_clk_bytes(ctx->cus)); }
         f.dbg_buf = ctx->clk_buf;
     }
     if (f.dbg & (16 | 32 | 64)) set_fused_abl(f.dbg);

@@ -83,7 +83,7 @@ struct FusedArgs {
     // instead of their windows, 8 phase stamps -> dbg_buf, 16 no row stores, 32 no pattern expansion (scalar decoder),
     // 64 no s_setprio on the scalar decoder, 128 no lane-parallel recognition, 256 parent trees folded per wave
     int dbg;
-    unsigned long long *dbg_buf;  // diagnostic stamps (ZNIPPY_DBG & 8)
+    unsigned long long *dbg_buf;  // diagnostic stamps (ZNIPPY_DBG & 8); with bit 32768 the clock buffer of roles_clk_bytes() bytes
     uint32_t lds_pad;  // extra dynamic LDS per block: caps blocks/CU (in-flight footprint vs Infinity Cache)
     int preset;        // != 0: status[] was initialised with the host's verdicts — a row with status < 0 is left alone
     // role-split kernel (k_fused_roles): global work cursor over the plan's tiles, and the tiles it leaves to
@@ -124,6 +124,8 @@ void launch_verify(const uint32_t *digests, const uint8_t *checksum, const uint6
 // what the two kernels take of a CU, from hipFuncGetAttributes (-1: not known)
 int verify_footprint(int *regs, int *lds);
 int roles_footprint(int *regs, int *waves_per_simd, int *lds);
+size_t roles_clk_bytes(int cus);       // the ZNIPPY_DBG & 32768 buffer: 8 words, then 8 per wave of every workgroup a launch can have
+void roles_geometry(uint32_t g[4]);    // waves per workgroup, ring slots, workgroups per CU, sizeof(RolesShared)
 int decode_grid_size(int device);
 void launch_decode(const DecodeArgs &a, int grid, bool wide, hipStream_t s);
 // block-item path: header scan of the candidate frames, then (after the block-mode decode) the per-row verdict

@@ -1080,10 +1080,12 @@ __global__ __launch_bounds__(256, 5) void k_fused_small(FusedArgs a) {
 
 // ---- role-split persistent kernel ---------------------------------------------------------------------------
 // Tiles whose rows are ALL whole-leaf rows of the recognised periodic shape (every BASELINE text row) are taken by
-// persistent workgroups — one per CU — of a LOADER wave and fifteen HASHER waves around a ring of slots in LDS:
+// persistent workgroups — two per CU — of a LOADER wave and seven HASHER waves around a ring of sixteen slots in LDS
+// (ZN_R_WAVES = 8, ZN_R_SLOTS = 16; -DZN_R_WAVES=16 -DZN_R_SLOTS=32 builds the earlier geometry, one workgroup of one
+// loader and fifteen hashers around 32 slots per CU):
 //   loader : pulls four tiles at a time from a global cursor, loads their index columns and frames (lane = row),
 //            recognises the rows lane-parallel (parse_fast) and publishes the four windows as a group of slots.  It
-//            owns every global load of the workgroup and runs up to seven groups ahead of the hashers.
+//            owns every global load of the workgroup and runs up to three groups ahead of the hashers.
 //   hasher : takes the next ready slot, gives every row's window 64 more bytes of its period, hashes the tile's
 //            <= 64 leaves straight from the windows (an all-LDS loop) while its lanes store the message registers
 //            as the row's bytes, leaves the chaining values in the slot; the wave that completes a group folds the
@@ -1103,11 +1105,19 @@ __global__ __launch_bounds__(256, 5) void k_fused_small(FusedArgs a) {
 //    rate; so the hash lanes store their registers as in k_fused_small (R_LOADER_EMITS = 0);
 //  * a volatile access through a generic pointer is a FLAT instruction; the ring's control words are explicit LDS
 //    accesses.
+//  * the geometry (profiles/roles_geometry_waits.txt, per-wave waits under ZNIPPY_DBG & 32768, one run of the table alone):
+//    with 1 x (1 + 15) waves x 32 slots a hasher spent 6.0 % of its life waiting for its first tile, 12.4 % waiting
+//    between tiles — a group is refilled only when all four of its slots are hashed, and fifteen hashers drain the
+//    loader's lead — and a hasher slot stood empty for 7.8 % of its workgroup's life after the wave had left; the
+//    loader's first iteration is 12-14 us, a later one 15.5 us without its waits.  With 2 x (1 + 7) x 16 the three are
+//    4.3 %, 0.8 % and 4.5 %, and the pipelined step is 5.5-7 % shorter: eight busy hashers hold a CU's integer pipe, and a
+//    workgroup's ramp or tail runs beside another's steady state — the NEXT run's above all: with every run in queue
+//    order on one stream the step is the parent's (the time is then set by the workgroups that get the most tiles).
 #ifndef ZN_R_SLOTS
-#define ZN_R_SLOTS 32
+#define ZN_R_SLOTS 16
 #endif
 #ifndef ZN_R_WAVES
-#define ZN_R_WAVES 16
+#define ZN_R_WAVES 8
 #endif
 #ifndef ZN_R_LOADERS
 #define ZN_R_LOADERS 1
@@ -1149,7 +1159,42 @@ struct alignas(16) RolesShared {
     // their three level changes (roles_parent_level), and the BLAKE3 IV, which a hasher wave carries in scalar registers
     uint32_t plevel[3][4];
     uint32_t iv[8];
+    // diagnostic (ZNIPPY_DBG & 32768), per wave: shader cycles spent in its three kinds of wait and the tiles (a loader:
+    // iterations) it got — kept here and not in registers, so that nothing of it lives across the hash loop
+    unsigned long long clk[R_WAVES][4], clk0[R_WAVES][2];  // (clk0: the wave's first shader cycle and 100 MHz tick)
+    uint32_t clk_on;  // (read where it is needed: a flag held in scalar registers across the hash loop costs the kernel three registers)
 };
+// Progress of the ring.  Tickets (`take`) are handed out in order, so every published slot is claimed before any later one,
+// and a hasher that holds a published slot waits for nothing until it has counted the slot into `cnt`.  The loader waits
+// only for `gen` of the group it is about to refill, i.e. for the four slots it published R_SLOTS / R_GROUP iterations
+// ago, all of which are claimed or will be by the next free hasher: hashers alone complete it.  So the ring cannot
+// deadlock with any number of groups >= 1.  What the number of groups decides is whether the loader can work AHEAD:
+// H hashers hold H consecutive tickets, which lie in at most (H - 2) / R_GROUP + 2 groups (seven hashers: three, fifteen:
+// five); with one group more than that there is always a group no hasher is working in, which the loader fills while
+// every hasher is busy — with fewer, loader and hashers take turns.
+constexpr uint32_t R_HASHERS = R_WAVES - R_LOADERS;
+static_assert(R_WAVES > R_LOADERS && R_HASHERS >= 2, "a workgroup needs hashers");
+static_assert(R_SLOTS / R_GROUP >= (R_HASHERS - 2) / R_GROUP + 2 + 1,
+              "ring size: one group more than the hashers can hold slots of, or the loader never runs ahead");
+// two workgroups per CU where two fit beside each other (launch_fused_roles, roles_footprint): 160 KiB of LDS per CU, of which
+// the kernel's static part (hash_tile_leaves' scratch) is counted with 256 bytes per workgroup
+constexpr uint32_t R_PER_CU = sizeof(RolesShared) > 80 * 1024 ? 1u : 2u;
+constexpr uint32_t R_STATIC_LDS_MAX = 256;
+static_assert(R_PER_CU * (sizeof(RolesShared) + R_STATIC_LDS_MAX) <= 160 * 1024, "the CU's LDS");
+static_assert(R_PER_CU * R_WAVES <= 16, "four waves per SIMD: the kernel is compiled for that");
+
+// ZNIPPY_DBG & 32768: where the waves' time goes.  dbg_buf[0..1] stay one wave's life in shader cycles / 100 MHz ticks
+// (the shader clock); behind them 8 words per wave, indexed by workgroup and wave: its life in shader cycles, its three
+// waits (roles_clk_add; a loader's third: the length of its first iteration), its tiles (a loader: iterations), its first and
+// last 100 MHz tick, and the launch's workgroups.
+constexpr uint32_t R_CLK_HEAD = 8, R_CLK_WORDS = 8;
+size_t roles_clk_bytes(int cus) { return (R_CLK_HEAD + (size_t)cus * R_PER_CU * R_WAVES * R_CLK_WORDS) * sizeof(unsigned long long); }
+void roles_geometry(uint32_t g[4]) { g[0] = R_WAVES; g[1] = R_SLOTS; g[2] = R_PER_CU; g[3] = (uint32_t)sizeof(RolesShared); }
+// one wait of this wave has ended: its cycles go to kind k (lane 0 keeps the wave's books)
+__device__ __forceinline__ void roles_clk_add(RolesShared &S, uint32_t k, unsigned long long t0) {
+    const unsigned long long dt = __builtin_amdgcn_s_memtime() - t0;
+    if ((threadIdx.x & 63) == 0) S.clk[threadIdx.x >> 6][k] += dt;
+}
 
 // One recognised row written by the whole wave from its window (R_LOADER_EMITS; lane = byte / 16-byte piece).
 // Y = the row's window at its literals:
@@ -1201,6 +1246,8 @@ __device__ __forceinline__ void emit_periodic_row(uint8_t *Y, uint32_t L0, uint3
 template <bool STORE>
 __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S) {
     const uint32_t lane = threadIdx.x & 63, j = lane >> 4, u = lane & 15;  // 16 lanes per tile, lane u = row u of tile j
+    const bool tm = lds_ld(&S.clk_on) != 0;  // diagnostic: clk[0] waits for `gen`, [1] for its publish turn, [2] first iteration, [3] iterations
+    const unsigned long long tm0 = tm ? __builtin_amdgcn_s_memtime() : 0;
     FastTabs T;
     {
         const DTab eL = c_dll[lane], eM = c_dml[lane], eO = c_dof[lane & 31];
@@ -1248,7 +1295,9 @@ __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S)
         }
         const bool want = rowv && c_sel && c_st == 0 && c_len != 0 && (c_len & 1023) == 0 && c_len <= 0x10000 &&
                           (!STORE || c_oo + c_len <= a.out_cap) && c_bs >= 12 && c_bs <= WIN;
+        const unsigned long long tg = tm ? __builtin_amdgcn_s_memtime() : 0;
         while (lds_ld(&S.gen[grp]) != use) __builtin_amdgcn_s_sleep(4);  // the group's previous use has been folded
+        if (tm) roles_clk_add(S, 0, tg);
         asm volatile("" ::: "memory");  // (volatile accesses order only against one another: pin the window stores below)
         // ---- the frames, lane = row: 16 bytes per step into the row's window (the last partial piece bytewise: the
         // blob region promises nothing behind its last byte) ----
@@ -1298,8 +1347,14 @@ __device__ __forceinline__ void roles_loader(const FusedArgs &a, RolesShared &S)
             }
             lds_fence();
         }
+        const unsigned long long tp = tm ? __builtin_amdgcn_s_memtime() : 0;
         while (lds_ld(&S.ready) != iter * R_GROUP) __builtin_amdgcn_s_sleep(2);  // publish in iteration order
         if (lane == 0) lds_st(&S.ready, (iter + 1) * R_GROUP);
+        if (tm) {
+            roles_clk_add(S, 1, tp);
+            if (iter < R_LOADERS) roles_clk_add(S, 2, tm0);  // this loader's first group is out
+            if (lane == 0) S.clk[threadIdx.x >> 6][3] += 1;
+        }
         if (last) break;
     }
     lds_fence();
@@ -1486,14 +1541,23 @@ __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S)
     bool have_prev = false;       // `tree` holds the leaf CVs of a 6 x 10 tile whose parents are still to be computed
     uint32_t prev_first = 0;      // ... its first row
     const bool inline_tree = !(a.dbg & 524288);
+    // diagnostic: clk[0] the wait for the wave's first tile (ramp), [1] waits for later tiles (feed), [2] the wait that ends
+    // without a tile, because the loader is done (tail), [3] tiles
     for (;;) {
         const uint32_t take = uni(atomicAdd(&S.take, lane == 0 ? 1u : 0u));  // every lane executes it: see roles_loader
+        const bool tm = lds_ld(&S.clk_on) != 0;
+        const unsigned long long tw = tm ? __builtin_amdgcn_s_memtime() : 0;
         bool go = false;
         for (;;) {
             const uint32_t f = lds_ld(&S.finished);  // (read BEFORE ready: a loader's last slots are published before it says so)
             if (lds_ld(&S.ready) > take) { go = true; break; }
             if (f == R_LOADERS) break;               // nothing more will be published
             __builtin_amdgcn_s_sleep(2);
+        }
+        if (tm) {
+            const uint32_t got = (uint32_t)S.clk[threadIdx.x >> 6][3];
+            roles_clk_add(S, go ? (got ? 1u : 0u) : 2u, tw);
+            if (go && lane == 0) S.clk[threadIdx.x >> 6][3] = got + 1;
         }
         if (!go) {
             if (have_prev) roles_flush_tree_6x10(a, tree, prev_first);
@@ -1586,7 +1650,9 @@ __device__ __forceinline__ void roles_hasher(const FusedArgs &a, RolesShared &S)
 }
 
 template <bool STORE>
-__global__ __launch_bounds__(R_WAVES * 64) void k_fused_roles(FusedArgs a) {
+// (four waves per SIMD in either geometry, whatever the workgroup's size; and 120 registers, not the 128 that would give:
+// a workgroup of k_verify — 32 registers — must fit beside the four waves, or a run's verify is no longer forked, api.hip)
+__global__ __launch_bounds__(R_WAVES * 64, 4) __attribute__((amdgpu_num_vgpr(120))) void k_fused_roles(FusedArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t s_roles_raw[];  // dynamic: more than the 64 KiB a static array may take
     RolesShared &S = *reinterpret_cast<RolesShared *>(s_roles_raw);
     if (threadIdx.x == 0) { S.ready = 0; S.take = 0; S.finished = 0; S.next_iter = 0; }
@@ -1596,16 +1662,28 @@ __global__ __launch_bounds__(R_WAVES * 64) void k_fused_roles(FusedArgs a) {
         constexpr uint32_t ivw[8] = {b3::IV0, b3::IV1, b3::IV2, b3::IV3, b3::IV4, b3::IV5, b3::IV6, b3::IV7};
         S.iv[threadIdx.x] = ivw[threadIdx.x];
     }
+    if (threadIdx.x < R_WAVES * 4) S.clk[threadIdx.x >> 2][threadIdx.x & 3] = 0;
+    if (threadIdx.x == 0) S.clk_on = (a.dbg & 32768) && a.dbg_buf ? 1u : 0u;
     __syncthreads();
-    const bool clk = (a.dbg & 32768) && a.dbg_buf && blockIdx.x == 7 && threadIdx.x == 64 * R_LOADERS;
-    const unsigned long long c0 = clk ? __builtin_amdgcn_s_memtime() : 0, r0 = clk ? __builtin_amdgcn_s_memrealtime() : 0;
+    if (lds_ld(&S.clk_on) && (threadIdx.x & 63) == 0) {
+        S.clk0[threadIdx.x >> 6][0] = __builtin_amdgcn_s_memtime();
+        S.clk0[threadIdx.x >> 6][1] = __builtin_amdgcn_s_memrealtime();
+    }
     if (threadIdx.x < 64 * R_LOADERS) {
         // the loader's instruction stream is one long dependent chain with little VALU in it: at top priority it
         // issues whenever it is ready and costs the hashers a few per cent of the issue slots
         if (!(a.dbg & 64)) __builtin_amdgcn_s_setprio(3);
         roles_loader<STORE>(a, S);
     } else roles_hasher<STORE>(a, S);
-    if (clk) { a.dbg_buf[0] = __builtin_amdgcn_s_memtime() - c0; a.dbg_buf[1] = __builtin_amdgcn_s_memrealtime() - r0; }
+    if (lds_ld(&S.clk_on) && (threadIdx.x & 63) == 0) {  // (the grid is at most cus * R_PER_CU workgroups: roles_clk_bytes)
+        const uint32_t w = threadIdx.x >> 6;
+        unsigned long long *o = a.dbg_buf + R_CLK_HEAD + ((size_t)blockIdx.x * R_WAVES + w) * R_CLK_WORDS;
+        o[0] = __builtin_amdgcn_s_memtime() - S.clk0[w][0];
+        o[1] = S.clk[w][0]; o[2] = S.clk[w][1]; o[3] = S.clk[w][2]; o[4] = S.clk[w][3];
+        o[5] = S.clk0[w][1]; o[6] = __builtin_amdgcn_s_memrealtime();
+        o[7] = gridDim.x;
+        if (blockIdx.x == 7 && w == R_LOADERS) { a.dbg_buf[0] = o[0]; a.dbg_buf[1] = o[6] - o[5]; }  // the shader clock: one wave's life in both units
+    }
 }
 
 void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify) {
@@ -1617,8 +1695,7 @@ void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify)
         attr_set[verify] = true;
     }
     const uint32_t want = (a.h.n_tiles + R_GROUP - 1) / R_GROUP;  // one group per workgroup at least
-    const uint32_t per_cu = sizeof(RolesShared) > 80 * 1024 ? 1u : 2u;
-    uint32_t grid = std::min<uint32_t>((uint32_t)cus * per_cu, want);
+    uint32_t grid = std::min<uint32_t>((uint32_t)cus * R_PER_CU, want);
     if (a.lds_pad) grid = std::min<uint32_t>(grid, a.lds_pad);  // diagnostic: ZNIPPY_LDS_PAD caps the grid (one workgroup = a deterministic ring)
     if (verify) hipLaunchKernelGGL(k_fused_roles<false>, dim3(grid), dim3(R_WAVES * 64), sizeof(RolesShared), s, a);
     else hipLaunchKernelGGL(k_fused_roles<true>, dim3(grid), dim3(R_WAVES * 64), sizeof(RolesShared), s, a);
@@ -1629,7 +1706,8 @@ void launch_fused_roles(const FusedArgs &a, int cus, hipStream_t s, bool verify)
 int roles_footprint(int *regs, int *waves_per_simd, int *lds) {
     hipFuncAttributes fa;
     if (hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(k_fused_roles<true>)) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    const int per_cu = sizeof(RolesShared) > 80 * 1024 ? 1 : 2;
+    const int per_cu = (int)R_PER_CU;
+    if (fa.sharedSizeBytes > R_STATIC_LDS_MAX) return -1;  // (the static_assert above counted on it)
     *regs = fa.numRegs; *waves_per_simd = (int)(R_WAVES * per_cu + 3) / 4; *lds = per_cu * (int)(sizeof(RolesShared) + fa.sharedSizeBytes);
     return 0;
 }

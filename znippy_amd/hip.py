@@ -127,6 +127,17 @@ class Context:
         self._chk(self.L.znippy_last_shader_ghz(self.h, C.byref(g)), "znippy_last_shader_ghz")
         return float(g.value)
 
+    def roles_wait_stats(self, max_waves=1 << 14):
+        """Diagnostic (znippy_hip.h): the role-split read kernel's geometry as a dict, and the last run's per-wave wait
+        counters as an array [waves, 8] (empty unless the context was created with ZNIPPY_DBG & 32768)."""
+        import numpy as np
+        g = (C.c_uint32 * 8)()
+        buf = np.zeros((max_waves, 8), dtype=np.uint64)
+        n = C.c_uint64()
+        self._chk(self.L.znippy_roles_wait_stats(self.h, g, buf.ctypes.data, buf.size, C.byref(n)), "znippy_roles_wait_stats")
+        keys = ("waves", "slots", "per_cu", "lds_per_workgroup", "registers", "lds_per_cu", "fork_verify", "run_lanes")
+        return dict(zip(keys, (int(v) for v in g))), buf[:int(n.value) // 8]
+
     # ---- single-chunk shims (codec.rs semantics, host buffers) ----
     def compress_bound(self, n):
         return int(self.L.znippy_compress_bound(n))
