@@ -25,6 +25,8 @@
  *                                over a batch of containers     entry the filter chose), znippy-plugin-python/src/native.rs:L85-89
  *   znippy_targz_find_batch      parse_deps_from_tarball        znippy-common/src/plugins/cargo_native.rs:L46-71 (gunzip a .crate, walk
  *                                over a batch of tarballs       the tar to the first .../Cargo.toml); sdists: znippy-plugin-python/src/native.rs:L17-21
+ *   znippy_gunzip_batch          lgz::decompress_gz             znippy-common/src/plugins/wasm_loader.rs (host_decompress codec 1,
+ *                                over a batch of files          tar_gz_list_entries): the gunzip of a whole file
  *
  * Codec wire format: one standard Zstandard frame (RFC 8878) per chunk.  (The reference's
  * OpenZL framing cannot be reproduced or checked offline — see DESIGN.md "Oracle".)
@@ -432,6 +434,62 @@ int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
                             const uint8_t *whole, uint64_t n, const char *name_prefix, uint64_t prefix_len, const char *name_suffix,
                             uint64_t suffix_len, uint64_t scan_cap, void *d_out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len,
                             int32_t *status, uint64_t *scanned);
+
+/* ---- whole gzip files the engine already holds ---------------------------------------------------------------------------------
+ * The plain gunzip of the reference's ingest side (host_decompress codec 1 and tar_gz_list_entries of wasm_loader.rs, both through
+ * lgz::decompress_gz, which splits the stream at full-flush boundaries and decompresses the pieces in parallel): .gz logs, .tar.gz sdists,
+ * .crate files, BGZF files, all of which sit in the archive as stored rows.  The DEFLATE decoder of znippy_inflate_batch is one wave per
+ * stream; this call cuts a file where it can be cut — gzip members are independent, and behind the empty stored block 00 00 FF FF of a
+ * flush point (Z_FULL_FLUSH, Z_SYNC_FLUSH, pigz) symbol decoding needs nothing from before it — and gives every piece a wave.
+ *   d_src, src_cap     DEVICE: the region that holds the files; item i is the whole file d_src[src_off[i] .. + src_len[i])
+ *   d_out, out_cap     DEVICE: item i's content goes to d_out[out_off[i] .. + out_room[i]), its room
+ *   out_off            HOST, optional (NULL: the rooms lie back to back in array order)
+ *   out_room           HOST: the bytes item i may produce.  For a file of one member the trailer's ISIZE (its last 4 bytes) is exact
+ *   seg_min            the least distance in source bytes between two kept flush candidates of an item (below); 0 = the default,
+ *                      256 bytes (the best of the values swept in profiles/gunzip_report.log), which ZNIPPY_GZ_SEG_MIN (a decimal number
+ *                      of bytes) replaces for every call
+ *   out_len            HOST out: bytes produced; 0 for every status but 0
+ *   status             HOST, optional: per item, see below
+ *   members            HOST out, optional: gzip members decoded (status 0)
+ *   segments           HOST out, optional: the pieces of item i that a wave of its own decoded (status 0; empty pieces count)
+ * Per item, with Python's gzip.decompress as arbiter: the content of all members, concatenated.  Zero bytes behind a trailer are
+ * ignored; anything else there that is no member header is ZNIPPY_E_CORRUPT; an item of no bytes has no member and no content.  The
+ * header rule is that of znippy_targz_find_batch (csrc/tar_rules.h: gzip_header): FEXTRA, FNAME and FCOMMENT are skipped, FHCRC is
+ * skipped and not verified, and — the one deviation from the arbiter — a method other than 8 or reserved FLG bits are
+ * ZNIPPY_E_UNSUPPORTED.  A DEFLATE stream is valid exactly when zlib's raw inflate accepts it (the rules at znippy_inflate_batch);
+ * input that ends early — inside a header, a stream or a trailer — is ZNIPPY_E_CORRUPT.  More content than out_room is
+ * ZNIPPY_E_DST_SMALL.  Every member's CRC-32 is computed on the device from the bytes written and compared with its trailer, and its
+ * ISIZE with the member's length mod 2^32: a mismatch on an otherwise clean item is ZNIPPY_E_CHECKSUM.  The first failure in stream
+ * order decides the status; ZNIPPY_E_CHECKSUM is reported only if everything decoded.
+ * Host validation and ZNIPPY_E_INVAL exactly as znippy_targz_find_batch (required: src_off, src_len, out_room, out_len; d_src, and d_out
+ * when out_cap > 0); a room not inside out_cap is ZNIPPY_E_DST_SMALL; a src_len or room of 4 GiB or more is ZNIPPY_E_UNSUPPORTED.  The
+ * call returns ZNIPPY_OK whatever the items report.
+ * Writes: no byte of d_out outside the room of an item is written; inside the room of an item whose status is not 0 the bytes are
+ * unspecified; rooms must not overlap (not checked).  A damaged file is a status, never a fault, a hang or a stray write.
+ * Not a run, and synchronous on the context's stream, exactly as znippy_inflate_batch; no table is touched; every allocation (one,
+ * sized from the source lengths: about 0.7 bytes per source byte and 3 KiB per item) is made before the first stream operation.
+ * Stages (csrc/gunzip.hip, csrc/host/gz_plan.h; znippy_last_kernel_times: gunzip_scan, gunzip_probe, gunzip_single, gunzip_inflate,
+ * gunzip_crc — only those that were launched):
+ *   scan     finds candidate starts: every position behind 00 00 FF FF (a flush candidate) and every 1F 8B 08 (a member candidate,
+ *            always kept).  A flush candidate closer than seg_min to the candidate kept before it (byte 0 is one) is dropped.
+ *   probe    one wave per kept candidate decodes symbols and stored-block lengths and writes nothing.  It stops at the first block
+ *            boundary that is a kept flush candidate, at its member's trailer, on an error or beyond the room, and records where it
+ *            ended, the bytes it would produce and how far its matches reach in front of its first byte.
+ *   plan     (host) walks each item's chain of records from byte 0.  Only candidates the chain lands on count, so the pattern inside
+ *            compressed or stored data changes no result.  A piece whose matches reach back (a sync flush) joins the run in front of
+ *            it; a run never crosses a member.
+ *   inflate  one wave per run decodes into the final place, to the run's exact byte count.  Runs of no bytes are not launched.
+ *   crc      the CRC launch of znippy_inflate_batch, a workgroup per run; the host combines the CRCs of a member's runs (as zlib's
+ *            crc32_combine) and compares with the trailer.
+ * An item without a kept candidate behind byte 0 (a crate, an sdist: one member, no flush) is decoded once, not twice: one wave
+ * inflates it with the room as its limit and checks trailer and padding (single), its CRC goes to the crc launch, and a batch of such
+ * items launches no probe.  The same wave takes, member by member, an item whose candidates outnumber its slice of the list
+ * (16 + src_len / 256), so that no result depends on which candidates could be kept.
+ * Out of scope: decoding dependent pieces in parallel from their predecessors' last 32 KiB, guessing block boundaries inside streams
+ * without flush points, bzip2 and xz, and listing tar members. */
+int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
+                        void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len,
+                        int32_t *status, uint32_t *members, uint32_t *segments);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,

@@ -195,6 +195,22 @@ int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *rel
 int znippy_archive_extract_tar_members(znippy_archive *a, const char *const *relative_paths, uint64_t n_files,
                                        const char *name_prefix, const char *name_suffix, uint64_t scan_cap, void *dst, size_t cap,
                                        uint64_t *entry_off /* n_files + 1 */, int32_t *status);
+/* For every archived file of relative_paths (each a gzip file: a .gz log, a .tar.gz sdist, a .crate, a BGZF file): its whole content,
+ * all members concatenated — what the reference's host_decompress (codec 1) does per file through lgz::decompress_gz
+ * (znippy-common/src/plugins/wasm_loader.rs), on the read side and for all files at once.  Pass 1 reads the last four bytes of every
+ * file, the ISIZE of its last member, which is the content's size when the file has one member.  Pass 2 gathers the files whole on the
+ * device — one range-read pass whose result is not copied to the host — and runs the znippy_gunzip_batch of include/znippy_hip.h on
+ * them there with those rooms: members and flush segments are decoded in parallel, CRC-32 and ISIZE of every member are checked.  The
+ * files that report ZNIPPY_E_DST_SMALL (several members) go through that call again with eight times the room (4 KiB at least), until
+ * they fit or the room is what DEFLATE can expand the file to (1032 : 1).  Only the contents come back to the host.
+ * Results as in znippy_archive_extract_zip_entries: file i at dst[entry_off[i] .. entry_off[i + 1]) (entry_off: n_files + 1 values), of
+ * length 0 when its status is not 0.  status (optional), per file: 0; ZNIPPY_E_INVAL an unknown path; ZNIPPY_E_UNSUPPORTED a file of
+ * 4 GiB or more; the per-item codes of that call (ZNIPPY_E_CORRUPT — a file that is no gzip file too —, ZNIPPY_E_CHECKSUM,
+ * ZNIPPY_E_UNSUPPORTED); ZNIPPY_E_DST_SMALL when cap does not hold it (the files in front of it are unaffected); a chunk's decode
+ * error.  An empty file has no member and no content.  The call returns ZNIPPY_OK whatever the files report; NULL arguments give
+ * ZNIPPY_E_INVAL. */
+int znippy_archive_gunzip_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap,
+                                uint64_t *entry_off /* n_files + 1 */, int32_t *status);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

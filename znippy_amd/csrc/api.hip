@@ -6,6 +6,7 @@
 #include "encode.h"
 #include "../../include/znippy_hip.h"
 #include "host/enc_plan.h"
+#include "host/gz_plan.h"
 #include "host/range_plan.h"
 #include "host/rows_plan.h"
 #include "host/run_overlap.h"
@@ -3433,4 +3434,246 @@ extern "C" int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint6
                                        int32_t *status, uint64_t *scanned) {
     ZN_NO_THROW(targz_find_batch(ctx, d_src, src_cap, src_off, src_len, whole, n, name_prefix, prefix_len, name_suffix, suffix_len, scan_cap, d_out, out_cap,
                                  out_off, out_len, status, scanned))
+}
+
+// ---- whole gzip files (znippy_gunzip_batch) ----------------------------------------------------------
+// Not a run, like the two calls above.  The items that pass the host's validation are scanned for candidate starts; the host keeps
+// candidates (host/gz_plan.h: keep_candidates), the probe leaves a record per kept candidate, plan_item turns an item's records into
+// runs and members, and the decode and CRC launches follow.  Items without a kept candidate behind byte 0, and items whose candidates did
+// not fit their slice of the list, take the single pass instead.  One device allocation, sized from the source lengths before
+// anything is queued, holds every list.
+static_assert(gzp::OK == ZNIPPY_OK && gzp::E_DST_SMALL == ZNIPPY_E_DST_SMALL && gzp::E_CORRUPT == ZNIPPY_E_CORRUPT &&
+              gzp::E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED && gzp::E_CHECKSUM == ZNIPPY_E_CHECKSUM, "host/gz_plan.h gives out the codes of znippy_hip.h");
+static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n, void *d_out,
+                        uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len, int32_t *status,
+                        uint32_t *members, uint32_t *segments) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
+    if (!n) return ZNIPPY_OK;
+    if (!src_off || !src_len || !out_room || !out_len || !d_src || (out_cap && !d_out)) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ctx->n_ktimes = 0;
+    if (!seg_min) {
+        seg_min = gzp::SEG_MIN_DEFAULT;
+        if (const char *e = getenv("ZNIPPY_GZ_SEG_MIN")) {
+            const unsigned long long v = strtoull(e, nullptr, 10);
+            if (v) seg_min = v;
+        }
+    }
+
+    // 1) every item against the source region and the output region; its slice of the candidate list and its chunks of the scan
+    std::vector<int32_t> st(n, 0);
+    std::vector<GzItem> items;
+    std::vector<uint32_t> item_of;  // list entry -> item
+    std::vector<GzScanChunk> chunks;
+    uint64_t packed = 0, cand_total = 0;
+    bool packed_wrap = false;
+    for (uint64_t i = 0; i < n; i++) {
+        const uint64_t so = src_off[i], sl = src_len[i], room = out_room[i];
+        const bool dst_known = out_off || !packed_wrap;
+        const uint64_t dst = out_off ? out_off[i] : packed;
+        if (!out_off) { packed_wrap |= packed + room < packed; packed += room; }
+        out_len[i] = 0;
+        if (members) members[i] = 0;
+        if (segments) segments[i] = 0;
+        if (so > src_cap || sl > src_cap - so) { st[i] = ZNIPPY_E_INVAL; continue; }
+        if (!dst_known || room > out_cap || dst > out_cap - room) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (sl >= (1ull << 32) || room >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
+        if (!sl) continue;  // no member at all: nothing, as gzip.decompress(b"") gives
+        GzItem it;
+        it.src = (const uint8_t *)d_src + so;
+        it.dst = (uint8_t *)d_out + dst;
+        it.src_len = (uint32_t)sl; it.room = (uint32_t)room;
+        it.cand_base = (uint32_t)cand_total; it.cand_cap = (uint32_t)(16 + sl / 256);
+        cand_total += it.cand_cap;
+        if (cand_total > (1ull << 30) || chunks.size() + sl / GZ_SCAN_CHUNK + 1 > (1ull << 30)) return ZNIPPY_E_NOMEM;
+        for (uint64_t off = 0; off < sl; off += GZ_SCAN_CHUNK) chunks.push_back(GzScanChunk{(uint32_t)items.size(), (uint32_t)off});
+        items.push_back(it);
+        item_of.push_back((uint32_t)i);
+    }
+    const uint32_t n_items = (uint32_t)items.size();
+    if (n_items) {
+        // 2) the one allocation, then the stream.  A kept candidate list is never longer than the raw one plus byte 0 of every item
+        const size_t n_kept_max = (size_t)cand_total + n_items;
+        size_t bytes = 0;
+        auto carve = [&](size_t sz) { const size_t at = bytes; bytes += (sz + 15) & ~(size_t)15; return at; };
+        const size_t o_items = carve(sizeof(GzItem) * n_items), o_chunks = carve(sizeof(GzScanChunk) * chunks.size()),
+                     o_count = carve(sizeof(uint32_t) * n_items), o_raw = carve(sizeof(uint64_t) * cand_total),
+                     o_cands = carve(sizeof(GzCand) * n_kept_max), o_stops = carve(sizeof(uint32_t) * cand_total),
+                     o_recs = carve(sizeof(GzProbe) * n_kept_max), o_runs = carve(sizeof(GzRun) * n_kept_max),
+                     o_run_st = carve(sizeof(int32_t) * n_kept_max), o_mem = carve(sizeof(InflateItem) * n_kept_max),
+                     o_mem_st = carve(sizeof(int32_t) * n_kept_max), o_mem_crc = carve(sizeof(uint32_t) * n_kept_max),
+                     o_list = carve(sizeof(uint32_t) * n_items), o_single = carve(sizeof(GzSingle) * n_items);
+        struct Guard {
+            znippy_ctx *ctx;
+            uint8_t *p = nullptr;
+            ~Guard() { tfree(ctx, p); }
+        } g{ctx};
+        HIPCHK(ctx, tmalloc(ctx, &g.p, bytes));
+        GzItem *const d_items = (GzItem *)(g.p + o_items);
+        uint32_t *const d_count = (uint32_t *)(g.p + o_count);
+        uint64_t *const d_raw = (uint64_t *)(g.p + o_raw);
+        HIPCHK(ctx, hipMemcpyAsync(d_items, items.data(), sizeof(GzItem) * n_items, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(g.p + o_chunks, chunks.data(), sizeof(GzScanChunk) * chunks.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t) * n_items, s));
+        timed(ctx, "gunzip_scan", s, [&] { launch_gunzip_scan(d_items, (const GzScanChunk *)(g.p + o_chunks), (uint32_t)chunks.size(), d_count, d_raw, s); });
+        HIPCHK(ctx, hipGetLastError());
+        std::vector<uint32_t> count(n_items);
+        HIPCHK(ctx, hipMemcpyAsync(count.data(), d_count, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        // 3) the candidates kept; which items are probed and which take the single pass
+        std::vector<uint64_t> raw;
+        uint64_t raw_end = 0;  // the list is copied back as far as the last item that has candidates and room for them
+        for (uint32_t k = 0; k < n_items; k++)
+            if (count[k] && count[k] <= items[k].cand_cap) raw_end = (uint64_t)items[k].cand_base + count[k];
+        if (raw_end) {
+            raw.resize(raw_end);
+            HIPCHK(ctx, hipMemcpyAsync(raw.data(), d_raw, sizeof(uint64_t) * raw_end, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+        std::vector<GzCand> cands;
+        std::vector<uint32_t> stops, single, probed;  // probed: the items with records, in the order of their records
+        std::vector<size_t> first_cand;               // probed[j]'s first entry of cands
+        for (uint32_t k = 0; k < n_items; k++) {
+            size_t kept = 0;
+            if (count[k] && count[k] <= items[k].cand_cap) kept = gzp::keep_candidates(raw.data() + items[k].cand_base, count[k], seg_min);
+            if (!kept) { single.push_back(k); continue; }
+            const uint64_t *c = raw.data() + items[k].cand_base;
+            probed.push_back(k);
+            first_cand.push_back(cands.size());
+            const uint32_t stop_begin = (uint32_t)stops.size();
+            for (size_t j = 0; j < kept; j++)
+                if ((c[j] & 1) == gzp::K_FLUSH) stops.push_back((uint32_t)(c[j] >> 1));
+            const uint32_t stop_end = (uint32_t)stops.size();
+            cands.push_back(GzCand{k, 0, gzp::K_MEMBER, stop_begin, stop_end, 0});
+            uint32_t next_stop = stop_begin;  // the first flush candidate behind the position
+            for (size_t j = 0; j < kept; j++) {
+                const uint32_t pos = (uint32_t)(c[j] >> 1), kind = (uint32_t)(c[j] & 1);
+                while (next_stop < stop_end && stops[next_stop] <= pos) next_stop++;
+                cands.push_back(GzCand{k, pos, kind, next_stop, stop_end, 0});
+            }
+        }
+        first_cand.push_back(cands.size());
+        const uint32_t n_cands = (uint32_t)cands.size(), n_single = (uint32_t)single.size();
+        if (n_cands > n_kept_max || stops.size() > cand_total) return ZNIPPY_E_NOMEM;  // (cannot happen: the bound above counts them)
+        std::vector<GzProbe> recs(n_cands);
+        std::vector<GzSingle> sres(n_single);
+        if (n_cands) {
+            HIPCHK(ctx, hipMemcpyAsync(g.p + o_cands, cands.data(), sizeof(GzCand) * n_cands, hipMemcpyHostToDevice, s));
+            if (!stops.empty()) HIPCHK(ctx, hipMemcpyAsync(g.p + o_stops, stops.data(), sizeof(uint32_t) * stops.size(), hipMemcpyHostToDevice, s));
+            timed(ctx, "gunzip_probe", s, [&] {
+                launch_gunzip_probe(d_items, (const GzCand *)(g.p + o_cands), n_cands, (const uint32_t *)(g.p + o_stops), (GzProbe *)(g.p + o_recs), s);
+            });
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(recs.data(), g.p + o_recs, sizeof(GzProbe) * n_cands, hipMemcpyDeviceToHost, s));
+        }
+        if (n_single) {
+            HIPCHK(ctx, hipMemcpyAsync(g.p + o_list, single.data(), sizeof(uint32_t) * n_single, hipMemcpyHostToDevice, s));
+            timed(ctx, "gunzip_single", s, [&] { launch_gunzip_single(d_items, (const uint32_t *)(g.p + o_list), n_single, (GzSingle *)(g.p + o_single), s); });
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(sres.data(), g.p + o_single, sizeof(GzSingle) * n_single, hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        // 4) the plan of every probed item; the decode launch; the CRC launch over every non-empty run and over the first member of
+        //    every item of the single pass (the CRCs of a member's runs are combined on the host: a long member is many workgroups)
+        std::vector<int32_t> item_st(n_items, 0);
+        std::vector<InflateItem> crc_items;
+        std::vector<uint32_t> crc_item_of;  // CRC launch entry -> item, for the entries that carry the CRC to compare with
+        auto crc_item = [&](uint8_t *dst, uint64_t len, bool has, uint32_t want) {
+            InflateItem it;
+            it.src = nullptr; it.dst = dst; it.src_len = 0; it.out_len = (uint32_t)len;
+            it.method = 8; it.want_crc = want; it.has_crc = has ? 1 : 0; it.pad = 0;
+            crc_items.push_back(it);
+        };
+        for (uint32_t e = 0; e < n_single; e++) {
+            const uint32_t k = single[e];
+            const GzSingle &r = sres[e];
+            item_st[k] = r.status;
+            if (r.status == 0 && (r.out_len > items[k].room || r.len0 > r.out_len)) item_st[k] = ZNIPPY_E_CORRUPT;  // (the kernel's word is checked, not trusted)
+            if (item_st[k] != 0) continue;
+            crc_item(items[k].dst, r.len0, true, r.crc0);
+            crc_item_of.push_back(k);
+        }
+        const size_t n_first = crc_items.size();
+        std::vector<gzp::Run> runs;
+        std::vector<gzp::Member> mems;
+        std::vector<gzp::ItemPlan> plans(probed.size());
+        std::vector<gzp::Probe> pr;
+        for (size_t j = 0; j < probed.size(); j++) {
+            const uint32_t k = probed[j];
+            pr.clear();
+            for (size_t c = first_cand[j]; c < first_cand[j + 1]; c++) {
+                const GzProbe &r = recs[c];
+                pr.push_back(gzp::Probe{cands[c].pos, cands[c].kind, r.data_start, r.end_kind, r.end_pos, r.status, r.out, r.reach, r.crc, r.isize, r.next});
+            }
+            gzp::plan_item(pr.data(), pr.size(), k, items[k].src_len, items[k].room, runs, mems, &plans[j]);
+            item_st[k] = plans[j].status;
+        }
+        std::vector<GzRun> h_runs;
+        std::vector<uint32_t> run_item;
+        std::vector<size_t> crc_of_run(runs.size(), 0);  // run -> its entry of the CRC launch (non-empty runs)
+        for (size_t r = 0; r < runs.size(); r++)
+            if (runs[r].out_len) {
+                h_runs.push_back(GzRun{runs[r].item, runs[r].src_start, (uint32_t)runs[r].out_off, (uint32_t)runs[r].out_len});
+                run_item.push_back(runs[r].item);
+                crc_of_run[r] = crc_items.size();
+                crc_item(items[runs[r].item].dst + runs[r].out_off, runs[r].out_len, false, 0);
+            }
+        const uint32_t n_runs = (uint32_t)h_runs.size(), n_crc = (uint32_t)crc_items.size();
+        if (n_runs > n_kept_max || n_crc > n_kept_max) return ZNIPPY_E_NOMEM;  // (cannot happen: a run per record, a first member per item at most)
+        std::vector<int32_t> run_st(n_runs, 0), crc_st(n_crc, 0);
+        std::vector<uint32_t> crc_got(n_crc, 0);
+        if (n_runs) {
+            HIPCHK(ctx, hipMemcpyAsync(g.p + o_runs, h_runs.data(), sizeof(GzRun) * n_runs, hipMemcpyHostToDevice, s));
+            timed(ctx, "gunzip_inflate", s, [&] { launch_gunzip_inflate(d_items, (const GzRun *)(g.p + o_runs), n_runs, (int32_t *)(g.p + o_run_st), s); });
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(run_st.data(), g.p + o_run_st, sizeof(int32_t) * n_runs, hipMemcpyDeviceToHost, s));
+        }
+        if (n_crc) {
+            HIPCHK(ctx, hipMemcpyAsync(g.p + o_mem, crc_items.data(), sizeof(InflateItem) * n_crc, hipMemcpyHostToDevice, s));
+            HIPCHK(ctx, hipMemsetAsync(g.p + o_mem_st, 0, sizeof(int32_t) * n_crc, s));
+            timed(ctx, "gunzip_crc", s, [&] {
+                launch_inflate_crc((const InflateItem *)(g.p + o_mem), n_crc, (int32_t *)(g.p + o_mem_st), (uint32_t *)(g.p + o_mem_crc), s);
+            });
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(crc_st.data(), g.p + o_mem_st, sizeof(int32_t) * n_crc, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipMemcpyAsync(crc_got.data(), g.p + o_mem_crc, sizeof(uint32_t) * n_crc, hipMemcpyDeviceToHost, s));
+        }
+        if (n_runs || n_crc) HIPCHK(ctx, hipStreamSynchronize(s));
+        for (uint32_t r = 0; r < n_runs; r++)
+            if (run_st[r] != 0) item_st[run_item[r]] = ZNIPPY_E_CORRUPT;
+        for (size_t c = 0; c < n_first; c++)
+            if (crc_st[c] != 0 && item_st[crc_item_of[c]] == 0) item_st[crc_item_of[c]] = ZNIPPY_E_CHECKSUM;
+        for (const gzp::Member &m : mems) {
+            uint32_t crc = 0;
+            for (size_t r = m.run0; r < m.run1; r++)
+                if (runs[r].out_len) crc = gzp::crc32_combine(crc, crc_got[crc_of_run[r]], runs[r].out_len);
+            if (crc != m.crc && item_st[m.item] == 0) item_st[m.item] = ZNIPPY_E_CHECKSUM;
+        }
+        for (uint32_t e = 0; e < n_single; e++) {
+            const uint32_t k = single[e], i = item_of[k];
+            st[i] = item_st[k];
+            if (st[i] != 0) continue;
+            out_len[i] = sres[e].out_len;
+            if (members) members[i] = sres[e].members;
+            if (segments) segments[i] = 1;
+        }
+        for (size_t j = 0; j < probed.size(); j++) {
+            const uint32_t k = probed[j], i = item_of[k];
+            st[i] = item_st[k];
+            if (st[i] != 0) continue;
+            out_len[i] = plans[j].out_len;
+            if (members) members[i] = plans[j].members;
+            if (segments) segments[i] = plans[j].segments;
+        }
+    }
+    if (status) memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
+                                   void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len,
+                                   int32_t *status, uint32_t *members, uint32_t *segments) {
+    ZN_NO_THROW(gunzip_batch(ctx, d_src, src_cap, src_off, src_len, n, d_out, out_cap, out_off, out_room, seg_min, out_len, status, members, segments))
 }

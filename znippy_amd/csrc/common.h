@@ -327,4 +327,43 @@ struct TargzResult {
 void launch_targz_find(const TargzItem *items, uint32_t n_items, const uint8_t *filter, uint32_t prefix_len, uint32_t suffix_len, TargzResult *res,
                        hipStream_t s);
 
+// Whole gzip files (gunzip.hip, znippy_gunzip_batch): one item the host has validated
+struct GzItem {
+    const uint8_t *src;  // the file, any alignment
+    uint8_t *dst;        // its room
+    uint32_t src_len, room;  // both below 4 GiB
+    uint32_t cand_base, cand_cap;  // its slice of the scan's candidate list
+};
+constexpr uint32_t GZ_SCAN_CHUNK = 4096;
+struct GzScanChunk { uint32_t item, off; };  // bytes [off, off + GZ_SCAN_CHUNK) of the item: one wave of the scan
+// count[i] = candidates found in item i (byte 0 not among them); the first cand_cap of them, in no order, as pos << 1 | kind
+// (0: behind 00 00 FF FF, 1: at 1F 8B 08) in cands[cand_base ..]
+void launch_gunzip_scan(const GzItem *items, const GzScanChunk *chunks, uint32_t n_chunks, uint32_t *count, uint64_t *cands, hipStream_t s);
+struct GzCand {  // one kept candidate: one wave of the probe
+    uint32_t item, pos, kind;
+    uint32_t stop0, stop1;  // stops[stop0 .. stop1): the kept flush candidates of its item behind pos, ascending
+    uint32_t pad;
+};
+struct GzProbe {  // gzp::Probe without the candidate
+    uint32_t data_start, end_kind, end_pos;
+    int32_t status;
+    uint64_t out;
+    uint32_t reach, crc, isize;
+    int32_t next;
+};
+void launch_gunzip_probe(const GzItem *items, const GzCand *cands, uint32_t n_cands, const uint32_t *stops, GzProbe *recs, hipStream_t s);
+struct GzRun {  // one wave of the decode launch
+    uint32_t item, src_start;  // the first DEFLATE byte, relative to the item's source
+    uint32_t out_off, out_len; // relative to the item's room; out_len > 0, and exact
+};
+void launch_gunzip_inflate(const GzItem *items, const GzRun *runs, uint32_t n_runs, int32_t *status, hipStream_t s);
+struct GzSingle {  // what the single pass says about an item
+    int32_t status;       // ZNIPPY_E_CHECKSUM here: an ISIZE, or the CRC-32 of a member behind the first
+    uint32_t out_len, members;
+    uint32_t crc0, len0;  // the first member's CRC-32 as its trailer has it, and its length: left to the CRC launch
+    uint32_t pad;
+};
+// list[k]: an item decoded from its first byte to its last by one wave, its members one after the other, trailers and padding checked
+void launch_gunzip_single(const GzItem *items, const uint32_t *list, uint32_t n_list, GzSingle *res, hipStream_t s);
+
 }  // namespace zn

@@ -1670,6 +1670,109 @@ static int znippy_archive_extract_tar_members_impl(znippy_archive *a, const char
     return ZNIPPY_OK;
 }
 
+// ---- the content of archived gzip files (znippy_archive_gunzip_files) ----------------------------
+// Pass 1 reads the last four bytes of every file (ISIZE: exact for a file of one member); pass 2 gathers the files whole on the device
+// (one range read, no copy to the host) and runs znippy_gunzip_batch on them there with those rooms.  The files that report
+// ZNIPPY_E_DST_SMALL — several members, of which ISIZE names only the last — go through the call again with eight times the room,
+// until they fit or the room is what DEFLATE can expand the file to.  Only the contents come back to the host.
+static int znippy_archive_gunzip_files_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
+                                            int32_t *status) {
+    if (!a || !entry_off || (n_files && !paths) || (cap && !dst)) return fail(ZNIPPY_E_INVAL, "null argument");
+    const size_t n = (size_t)n_files;
+    std::vector<int32_t> st(n, 0);
+    std::vector<const std::vector<uint64_t> *> rows(n, nullptr);
+    std::vector<uint64_t> fsize(n, 0), room(n, 0);
+    const IndexView view = a->ix.view();
+    for (size_t i = 0; i < n; i++) {
+        auto it = paths[i] ? a->files.find(paths[i]) : a->files.end();
+        if (it == a->files.end()) { st[i] = ZNIPPY_E_INVAL; continue; }
+        rows[i] = &it->second;
+        for (uint64_t r : it->second) fsize[i] += view.row_len(r);
+        if (fsize[i] >= (1ull << 32)) st[i] = ZNIPPY_E_UNSUPPORTED;
+    }
+    int rc = archive_ctx(a);
+    if (rc) return rc;
+    // 1) the rooms
+    {
+        std::vector<FileRange> req;
+        std::vector<size_t> who;
+        for (size_t i = 0; i < n; i++)
+            if (st[i] == 0 && fsize[i] >= 4) { req.push_back(FileRange{rows[i], fsize[i] - 4, 4}); who.push_back(i); }
+        std::vector<uint8_t> bytes;
+        std::vector<uint64_t> at;
+        std::vector<int32_t> rst;
+        if ((rc = read_file_ranges(a, req, &bytes, &at, &rst))) return rc;
+        for (size_t k = 0; k < req.size(); k++) {
+            const uint8_t *p = bytes.data() + at[k];
+            if (rst[k]) st[who[k]] = rst[k];
+            else room[who[k]] = (uint64_t)p[0] | (uint64_t)p[1] << 8 | (uint64_t)p[2] << 16 | (uint64_t)p[3] << 24;
+        }
+    }
+    // 2) the files, whole, on the device
+    std::vector<size_t> who;
+    std::vector<FileRange> req;
+    for (size_t i = 0; i < n; i++)
+        if (st[i] == 0) { who.push_back(i); req.push_back(FileRange{rows[i], 0, fsize[i]}); }
+    std::vector<std::vector<uint8_t>> content(n);
+    if (!who.empty()) {
+        std::vector<uint64_t> at;
+        std::vector<int32_t> rst;
+        uint64_t total = 0;
+        if ((rc = read_file_ranges(a, req, nullptr, &at, &rst, &total))) return rc;
+        ReadBufs &bufs = a->bufs;
+        std::vector<size_t> todo;  // indexes into who
+        for (size_t k = 0; k < who.size(); k++) {
+            if (rst[k]) st[who[k]] = rst[k];
+            else todo.push_back(k);
+        }
+        // no valid DEFLATE expands more than 1032 : 1, and the call takes rooms below 4 GiB
+        auto most = [&](size_t i) { return std::min<uint64_t>(1032 * fsize[i] + 512, 0xFFFFFFF0ull); };
+        while (!todo.empty()) {
+            std::vector<uint64_t> s_off, s_len, o_room, o_len(todo.size(), 0);
+            uint64_t out_total = 0;
+            for (size_t k : todo) {
+                const size_t i = who[k];
+                room[i] = std::min(room[i], most(i));
+                s_off.push_back(at[k]); s_len.push_back(fsize[i]); o_room.push_back(room[i]);
+                out_total += room[i];
+            }
+            if (!bufs.d_blobs.reserve(out_total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");  // (the chunks in it have been gathered from)
+            std::vector<int32_t> ist(todo.size(), 0);
+            rc = znippy_gunzip_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), bufs.d_blobs.p, out_total, nullptr, o_room.data(), 0,
+                                     o_len.data(), ist.data(), nullptr, nullptr);
+            if (rc) return fail(rc, std::string("gunzip failed: ") + znippy_last_error(a->ctx));
+            if (!bufs.blob_pin.reserve(out_total + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+            if (out_total && hipMemcpy(bufs.blob_pin.p, bufs.d_blobs.p, out_total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+            std::vector<size_t> again;
+            uint64_t o = 0;
+            for (size_t j = 0; j < todo.size(); j++) {
+                const size_t i = who[todo[j]];
+                st[i] = ist[j];
+                if (ist[j] == 0) content[i].assign(bufs.blob_pin.p + o, bufs.blob_pin.p + o + o_len[j]);
+                else if (ist[j] == ZNIPPY_E_DST_SMALL && room[i] < most(i)) {
+                    room[i] = std::max<uint64_t>(8 * room[i], 4096);
+                    again.push_back(todo[j]);
+                }
+                o += o_room[j];
+            }
+            todo.swap(again);
+        }
+    }
+    // the contents, packed in file order; one that does not fit is left out and the ones behind it may still fit
+    uint64_t cursor = 0;
+    for (size_t i = 0; i < n; i++) {
+        entry_off[i] = cursor;
+        if (st[i]) continue;
+        const uint64_t len = content[i].size();
+        if (len > cap - cursor) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (len) std::memcpy((uint8_t *)dst + cursor, content[i].data(), (size_t)len);
+        cursor += len;
+    }
+    entry_off[n] = cursor;
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
 extern "C" {
 
 int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
@@ -1680,6 +1783,11 @@ int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *rel
 int znippy_archive_extract_tar_members(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
                                        const char *name_suffix, uint64_t scan_cap, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {
     return guarded([&] { return znippy_archive_extract_tar_members_impl(a, relative_paths, n_files, name_prefix, name_suffix, scan_cap, dst, cap, entry_off, status); });
+}
+
+int znippy_archive_gunzip_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
+                                int32_t *status) {
+    return guarded([&] { return znippy_archive_gunzip_files_impl(a, relative_paths, n_files, dst, cap, entry_off, status); });
 }
 
 int znippy_archive_block_tree_stats(const znippy_archive *a, uint64_t stats[4]) {

@@ -38,23 +38,6 @@ __device__ int inflate_stream(InflLds &S, const uint8_t *src, uint32_t src_len, 
     if (st == 0 && pos != out_len) st = E_CORRUPT;
     return st;
 }
-__device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b) {  // a * b mod P, reflected (zlib: multmodp)
-    uint32_t p = 0;
-    for (uint32_t i = 0; i < 32; i++) {
-        if (a & (0x80000000u >> i)) p ^= b;
-        b = b & 1 ? (b >> 1) ^ CRC_POLY : b >> 1;
-    }
-    return p;
-}
-__device__ __forceinline__ uint32_t crc_xpow(uint64_t n) {  // x^n mod P
-    uint32_t r = 0x80000000u, q = 0x40000000u;
-    for (uint32_t i = 0; i < 40; i++) {
-        if ((n >> i) & 1) r = crc_mulmod(r, q);
-        q = crc_mulmod(q, q);
-    }
-    return r;
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(64) void k_inflate(const InflateItem *items, uint32_t n_items, int32_t *status) {

@@ -400,6 +400,147 @@ __device__ int inflate_body(InflLds &S, BitIn &b, uint8_t *dst, uint32_t out_len
     return st;
 }
 
+// CRC-32 arithmetic on the reflected polynomial (k_inflate_crc, and the single pass of gunzip.hip)
+__device__ __forceinline__ uint32_t crc_mulmod(uint32_t a, uint32_t b) {  // a * b mod P, reflected (zlib: multmodp)
+    uint32_t p = 0;
+    for (uint32_t i = 0; i < 32; i++) {
+        if (a & (0x80000000u >> i)) p ^= b;
+        b = b & 1 ? (b >> 1) ^ CRC_POLY : b >> 1;
+    }
+    return p;
+}
+__device__ __forceinline__ uint32_t crc_xpow(uint64_t n) {  // x^n mod P
+    uint32_t r = 0x80000000u, q = 0x40000000u;
+    for (uint32_t i = 0; i < 40; i++) {
+        if ((n >> i) & 1) r = crc_mulmod(r, q);
+        q = crc_mulmod(q, q);
+    }
+    return r;
+}
+
+// A hook that ends the stream loop once `n` bytes (> 0) exist: the decoder of a piece whose exact byte count is known (gunzip.hip).
+struct StopAt {
+    static constexpr bool active = true;
+    uint32_t n;
+    __device__ __forceinline__ bool due(uint32_t pos) const { return pos >= n; }
+    __device__ __forceinline__ uint32_t run(const uint8_t *, uint32_t, uint32_t) { return 1; }
+};
+
+// The stream behind `b` decoded for its symbols and lengths alone: nothing is written (gunzip.hip: the probe of a candidate start).
+// Symbol decoding needs no window, so the count of bytes and the place where the stream ends are those of the real decoder even when
+// matches reach in front of the first byte; REACH says whether they may (a piece behind a flush point): then *reach is the longest
+// such reach, otherwise a distance beyond the bytes produced is E_CORRUPT as in inflate_body.
+// stops[0 .. n_stops): ascending byte positions of b.src.  The loop ends at the first block boundary behind a non-final stored block
+// that is one of them (PROBE_BOUNDARY; b.ip is that position), behind the final block (PROBE_FINAL), or when more than `limit` bytes
+// would exist (PROBE_LIMIT).  *how is defined when 0 is returned; otherwise E_CORRUPT, or E_INPUT_END where the input ends first.
+constexpr uint32_t PROBE_FINAL = 0, PROBE_BOUNDARY = 1, PROBE_LIMIT = 2;
+template <bool REACH>
+__device__ int probe_body(InflLds &S, BitIn &b, uint64_t limit, const uint32_t *stops, uint32_t n_stops, uint32_t lane, uint64_t *produced, uint32_t *reach,
+                          uint32_t *how) {
+    constexpr int TR = E_INPUT_END;
+    b.load_win(lane);
+    const Code lc = {S.lt, S.lsym, S.lcnt, (1u << LB) - 1}, dc = {S.dt, S.dsym, S.dcnt, (1u << DB) - 1};
+    int st = 0;
+    uint64_t pos = 0;
+    uint32_t far = 0, si = 0;
+    uint32_t done = 0, fixed_built = 0, stop = 0;
+    while (!done && !stop && st == 0) {
+        b.refill(lane);
+        const uint32_t final_block = b.take(1), type = b.take(2);
+        if (b.over()) {
+            st = TR;
+        } else if (type == 3) {
+            st = E_CORRUPT;
+        } else if (type == 0) {
+            b.drop(b.bc & 7);
+            b.refill(lane);
+            const uint32_t len = b.take(16), nlen = b.take(16);
+            if (b.over()) {
+                st = TR;
+            } else if (len != (nlen ^ 0xFFFFu)) {
+                st = E_CORRUPT;
+            } else {
+                const uint64_t at = b.ip - (b.bc >> 3);
+                const uint64_t avail = b.n - at;
+                pos += len < avail ? len : avail;
+                if (pos > limit) {
+                    stop = PROBE_LIMIT;
+                } else if (len > avail) {
+                    st = TR;
+                } else {
+                    b.ip = at + len; b.bb = 0; b.bc = 0;
+                    if (final_block) {
+                        done = 1;
+                    } else {
+                        // (the list is walked forward once over the whole stream: the positions only grow)
+                        while (si < n_stops && uni(stops[si]) < b.ip) si++;
+                        if (si < n_stops && uni(stops[si]) == b.ip) stop = PROBE_BOUNDARY;
+                    }
+                }
+            }
+        } else {
+            if (type == 1) {
+                if (!fixed_built) fixed_codes(S, lane);
+                fixed_built = 1;
+            } else {
+                fixed_built = 0;
+                st = dynamic_codes<TR>(S, b, lane);
+            }
+            uint32_t eob = 0;
+            while (!eob && !stop && st == 0) {
+                b.refill(lane);
+                uint32_t l = 0;
+                const uint32_t sym = decode_sym(lc, b.bb, &l);
+                if (sym == NO_SYM) {
+                    st = b.over_by(1) ? TR : E_CORRUPT;
+                } else if (sym < 256) {
+                    b.drop(l);
+                    if (b.over()) st = TR;
+                    else if (++pos > limit) stop = PROBE_LIMIT;
+                } else if (sym == 256) {
+                    b.drop(l);
+                    if (b.over()) st = TR;
+                    else eob = 1;
+                } else {
+                    b.drop(l);
+                    if (b.over()) {
+                        st = TR;
+                    } else if (sym > 285) {
+                        st = E_CORRUPT;
+                    } else {
+                        const uint32_t i = sym - 257;
+                        const uint32_t lx = i < 8 || i == 28 ? 0u : (i - 4) >> 2;
+                        const uint32_t len = (i < 8 ? 3 + i : i == 28 ? 258u : 3 + ((4 + (i & 3)) << lx)) + b.take(lx);
+                        uint32_t dl = 0;
+                        const uint32_t ds = decode_sym(dc, b.bb, &dl);
+                        if (ds == NO_SYM) {
+                            st = b.over_by(1) ? TR : E_CORRUPT;
+                        } else {
+                            b.drop(dl);
+                            const uint32_t dx = ds < 4 ? 0u : (ds - 2) >> 1;
+                            const uint32_t dist = (ds < 4 ? 1 + ds : 1 + ((2 + (ds & 1)) << dx)) + (ds > 29 ? 0u : b.take(dx));
+                            if (b.over()) {
+                                st = TR;
+                            } else if (ds > 29 || (!REACH && dist > pos)) {
+                                st = E_CORRUPT;
+                            } else {
+                                if (dist > pos && dist - (uint32_t)pos > far) far = dist - (uint32_t)pos;
+                                pos += len;
+                                if (pos > limit) stop = PROBE_LIMIT;
+                            }
+                        }
+                    }
+                }
+            }
+            if (st == 0 && !stop && final_block) done = 1;
+        }
+    }
+    *produced = pos;
+    *reach = far;
+    *how = stop;
+    return st;
+}
+
 }  // namespace
 
 }  // namespace zn

@@ -207,6 +207,28 @@ class Context:
                                                  np_ptr(oo), np_ptr(ol), np_ptr(status), np_ptr(sc)), "znippy_targz_find_batch")
         return status[:n], oo[:n], ol[:n], sc[:n]
 
+    # ---- whole gzip files held in device memory ----
+    def gunzip_batch(self, d_src, src_off, src_len, d_out, out_room, out_off=None, seg_min=0, src_cap=None, out_cap=None):
+        """znippy_gunzip_batch: item i is the whole gzip file d_src[src_off[i] .. + src_len[i]); the content of all its members goes to
+        d_out + out_off[i] (None: the rooms lie back to back in array order) and may take out_room[i] bytes — for a file of one member
+        its last four bytes, ISIZE, say how many.  Members and the pieces between flush points are decoded in parallel; seg_min: the
+        least distance in source bytes between two flush points that are used (0: the default).  CRC-32 and ISIZE of every member are
+        checked.  Synchronous and not a run.  Returns (status per item: 0 or ZNIPPY_E_*, out_off, out_len — 0 unless the status is 0 —,
+        members, segments: the pieces of the item that a wave of its own decoded)."""
+        so, sl, room = as_np(src_off, np.uint64), as_np(src_len, np.uint64), as_np(out_room, np.uint64)
+        n = len(so)
+        assert len(sl) == n and len(room) == n and (out_off is None or len(out_off) == n), "item arrays differ in length"
+        oo = as_np(out_off, np.uint64) if out_off is not None else np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.uint64)
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ol = np.zeros(max(n, 1), dtype=np.uint64)
+        mem, seg = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        self._chk(self.L.znippy_gunzip_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), n, _dptr(d_out), int(out_cap),
+                                             np_ptr(oo) if out_off is not None else None, np_ptr(room), int(seg_min), np_ptr(ol), np_ptr(status),
+                                             np_ptr(mem), np_ptr(seg)), "znippy_gunzip_batch")
+        return status[:n], oo[:n], ol[:n], mem[:n], seg[:n]
+
 
 def get_decompressed_size(frame) -> int:
     a = np.frombuffer(frame, dtype=np.uint8)

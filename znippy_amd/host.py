@@ -29,7 +29,7 @@ class _ME(C.Structure):
 HOST_EXPORTS = [
     "znippy_host_last_error", "znippy_compress_stream", "znippy_stream_send", "znippy_stream_send_packed", "znippy_stream_finish",
     "znippy_compress_dir", "znippy_decompress_archive", "znippy_archive_open", "znippy_archive_file_count", "znippy_archive_file_size",
-    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
+    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
     "znippy_index_manifest_len", "znippy_index_manifest_entry", "znippy_index_row", "znippy_index_metadata",
     "znippy_index_close", "znippy_interpret_footer", "znippy_write_manifest_bytes",
 ]
@@ -62,6 +62,7 @@ def lib():
         L.znippy_archive_close.argtypes = [vp]
         L.znippy_archive_extract_zip_entries.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, vp, C.c_size_t, vp, vp]
         L.znippy_archive_extract_tar_members.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp, vp]
+        L.znippy_archive_gunzip_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
         L.znippy_zip_end_of_directory.argtypes = [vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.znippy_zip_find_entry.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, vp]
         L.znippy_zip_local_data_offset.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64)]
@@ -284,6 +285,40 @@ class ZnippyArchive:
                 elif st[k] == _lib.E_DST_SMALL:
                     again.append(i)
             most = sum(min(int(scan_cap), 1032 * (self.file_size(paths[i]) or 0) + 512) for i in again)
+            if cap is not None or room >= most:
+                break
+            todo, room = again, min(8 * room, most)
+        return out, status
+
+    def gunzip_files(self, paths, cap=None):
+        """The whole content of every archived gzip file of `paths` (.gz logs, .tar.gz sdists, .crate files, BGZF files), all members
+        concatenated, inflated on the device in one batch: the files are gathered there whole, their rooms come from each file's ISIZE
+        (its last four bytes), members and flush segments are decoded in parallel and every member's CRC-32 and ISIZE are checked; a
+        file of several members goes through again with eight times the room.  cap: bytes of the result buffer of the one call made.
+        None: the first call gets four times the files' sizes + 1 MiB, and the files that did not fit (ZNIPPY_E_DST_SMALL) go through
+        the call again with eight times the room, until they fit or the room is what DEFLATE can expand them to.  Returns (list of
+        bytes, or None where the status is not 0; statuses)."""
+        paths = [str(p) for p in paths]
+        n = len(paths)
+        out, status = [None] * n, [0] * n
+        todo = list(range(n))
+        room = int(cap) if cap is not None else 4 * sum(self.file_size(p) or 0 for p in paths) + (1 << 20)
+        while todo:
+            m = len(todo)
+            arr = (C.c_char_p * m)(*[paths[i].encode() for i in todo])
+            buf = np.empty(max(room, 1), dtype=np.uint8)
+            off = np.zeros(m + 1, dtype=np.uint64)
+            st = np.zeros(m, dtype=np.int32)
+            _chk(lib().znippy_archive_gunzip_files(self.h, arr, m, buf.ctypes.data_as(vp), room, off.ctypes.data_as(vp), st.ctypes.data_as(vp)),
+                 "gunzip_files")
+            again = []
+            for k, i in enumerate(todo):
+                status[i] = int(st[k])
+                if st[k] == 0:
+                    out[i] = buf[int(off[k]):int(off[k + 1])].tobytes()
+                elif st[k] == _lib.E_DST_SMALL:
+                    again.append(i)
+            most = sum(1032 * (self.file_size(paths[i]) or 0) + 512 for i in again)
             if cap is not None or room >= most:
                 break
             todo, room = again, min(8 * room, most)
