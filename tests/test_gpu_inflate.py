@@ -1,7 +1,8 @@
 """znippy_inflate_batch: raw DEFLATE streams decoded on the device, against Python's zlib as arbiter.
 Every batch goes through one call; sources start at odd offsets; 0xA5 guard bytes stand around the destinations and are checked
-afterwards.  Hand-built streams come from the small bit writer below, and every one of them is first shown to zlib, which must
-accept or reject it as the case intends.  The expected status of any stream with expected length n is what zlib makes of it:
+afterwards.  Hand-built streams come from the small bit writer of tests/deflate_build.py, and every one of them is first shown to
+zlib, which must accept or reject it as the case intends.  The expected status of any stream with expected length n is what zlib
+makes of it:
   raises / does not reach eof / eof with fewer than n bytes -> ZNIPPY_E_CORRUPT;  an (n+1)-th byte -> ZNIPPY_E_DST_SMALL;
   eof with exactly n bytes -> 0 and zlib's bytes."""
 import ctypes as C
@@ -11,265 +12,13 @@ import numpy as np
 import pytest
 
 import gen
+from deflate_build import (TEXT, Bits, block_kind_cases, classify, deflate, fixed_block, flushed_stream, rejection_cases, stored_block,
+                           table_corner_cases, truncation_cases)
 
 pytestmark = pytest.mark.gpu
 
 OK, E_INVAL, E_DST_SMALL, E_CORRUPT, E_UNSUPPORTED, E_CHECKSUM = 0, -1, -4, -5, -6, -7
 GUARD = 0xA5
-
-
-# ---- the arbiter ---------------------------------------------------------------------------------------------------------------
-
-def classify(data, n):
-    """(expected status, expected bytes or None) of stream `data` with expected length n, from zlib's raw inflate"""
-    d = zlib.decompressobj(-15)
-    try:
-        out = d.decompress(bytes(data), n + 1)
-    except zlib.error:
-        return E_CORRUPT, None
-    if len(out) > n:
-        return E_DST_SMALL, None
-    if not d.eof or len(out) < n:
-        return E_CORRUPT, None
-    return OK, out
-
-
-def deflate(data, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
-    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
-    return c.compress(data) + c.flush()
-
-
-# ---- a bit writer and RFC 1951's codes -----------------------------------------------------------------------------------------
-
-LBASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
-LEXT = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
-DBASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
-DEXT = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
-CL_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
-FIXED_LL = [8] * 144 + [9] * 112 + [7] * 24 + [8] * 8
-FIXED_D = [5] * 32
-PLAIN_CL = [4] * 13 + [5] * 6          # a complete code over all 19 code-length symbols
-
-
-class Bits:
-    def __init__(self):
-        self.b = []
-
-    def put(self, v, n):                # a value, least significant bit first
-        self.b += [(v >> i) & 1 for i in range(n)]
-
-    def code(self, c):                  # a Huffman code (value, length), most significant bit first
-        v, n = c
-        self.b += [(v >> i) & 1 for i in reversed(range(n))]
-
-    def align(self):
-        self.b += [0] * (-len(self.b) % 8)
-
-    def raw(self, data):
-        assert len(self.b) % 8 == 0
-        for x in data:
-            self.put(x, 8)
-
-    def bytes(self):
-        return np.packbits(np.array(self.b, np.uint8), bitorder="little").tobytes()
-
-
-def canon(lens):
-    """symbol -> (code, length) of the canonical code with these lengths (complete or not)"""
-    count = [0] * 17
-    for n in lens:
-        count[n] += 1
-    count[0] = 0
-    nxt, code = [0] * 17, 0
-    for n in range(1, 16):
-        code = (code + count[n - 1]) << 1
-        nxt[n] = code
-    out = {}
-    for s, n in enumerate(lens):
-        if n:
-            out[s] = (nxt[n], n)
-            nxt[n] += 1
-    return out
-
-
-def put_ops(bw, ops, ll, dd, eob=True):
-    """ops: ints (literals), ('m', length, distance), ('ll', symbol) a bare literal/length symbol, ('sym', symbol, extra value,
-    distance symbol, extra value) a match given by its symbols"""
-    for op in ops:
-        if isinstance(op, int):
-            bw.code(ll[op])
-        elif op[0] == "ll":
-            bw.code(ll[op[1]])
-        elif op[0] == "sym":
-            _, ls, lx, ds, dx = op
-            bw.code(ll[ls]); bw.put(lx, LEXT[ls - 257] if ls <= 285 else 0)
-            bw.code(dd[ds]); bw.put(dx, DEXT[ds] if ds < 30 else 0)
-        else:
-            _, length, dist = op
-            i = max(k for k in range(29) if LBASE[k] <= length and (k == 28 or length < 258))
-            bw.code(ll[257 + i]); bw.put(length - LBASE[i], LEXT[i])
-            j = max(k for k in range(30) if DBASE[k] <= dist)
-            bw.code(dd[j]); bw.put(dist - DBASE[j], DEXT[j])
-    if eob:
-        bw.code(ll[256])
-
-
-def fixed_block(bw, ops, final=1, eob=True):
-    bw.put(final, 1); bw.put(1, 2)
-    put_ops(bw, ops, canon(FIXED_LL), canon(FIXED_D), eob)
-
-
-def stored_block(bw, data, final=1, nlen=None):
-    bw.put(final, 1); bw.put(0, 2); bw.align()
-    bw.put(len(data), 16); bw.put((len(data) ^ 0xFFFF) if nlen is None else nlen, 16)
-    bw.raw(data)
-
-
-def dynamic_block(bw, ll_lens, d_lens, ops, final=1, cl_lens=None, cl_syms=None, hlit=None, hdist=None, body=True, eob=True):
-    """cl_syms: the code-length symbols as (symbol, extra value) pairs; None: every length as a symbol of its own"""
-    cl_lens = PLAIN_CL if cl_lens is None else cl_lens
-    if cl_syms is None:
-        cl_syms = [(n, 0) for n in list(ll_lens) + list(d_lens)]
-    bw.put(final, 1); bw.put(2, 2)
-    bw.put((len(ll_lens) if hlit is None else hlit) - 257, 5)
-    bw.put((len(d_lens) if hdist is None else hdist) - 1, 5)
-    bw.put(19 - 4, 4)
-    for s in CL_ORDER:
-        bw.put(cl_lens[s], 3)
-    cc = canon(cl_lens)
-    for s, x in cl_syms:
-        bw.code(cc[s])
-        bw.put(x, {16: 2, 17: 3, 18: 7}.get(s, 0))
-    if body:
-        put_ops(bw, ops, canon(ll_lens), canon(d_lens), eob)
-
-
-def ll_lens_for(pairs, n=257):
-    lens = [0] * n
-    for s, k in pairs:
-        lens[s] = k
-    return lens
-
-
-TEXT = gen.pseudo_text(300_000, seed=7)
-
-
-# ---- cases ---------------------------------------------------------------------------------------------------------------------
-
-def block_kind_cases():
-    rnd = np.random.default_rng(11).integers(0, 256, 32768, dtype=np.uint8).tobytes()
-    cases = [("empty", bytes([3, 0]), 0), ("one byte", deflate(b"Z"), 1),
-             ("stored 70000", deflate((rnd * 3)[:70000], 0), 70000),
-             ("fixed text", deflate(TEXT[:5000], 6, zlib.Z_FIXED), 5000),
-             ("level 9 text", deflate(TEXT, 9), len(TEXT)),
-             ("rle zeros", deflate(bytes(300_000), 6, zlib.Z_RLE), 300_000),
-             ("huffman only", deflate(TEXT[:20000], 6, zlib.Z_HUFFMAN_ONLY), 20000)]
-    bw = Bits()
-    stored_block(bw, b"", final=0)
-    fixed_block(bw, list(b"behind an empty stored block"))
-    cases.append(("empty stored block first", bw.bytes(), 28))
-    for dist in (1, 2, 3, 63, 64, 65, 257, 258, 259, 32768):
-        bw = Bits()
-        head = rnd if dist == 32768 else rnd[:dist]
-        if dist == 32768:
-            stored_block(bw, head, final=0)
-            fixed_block(bw, [("m", 258, dist)])
-        else:
-            fixed_block(bw, list(head) + [("m", 258, dist)])
-        cases.append((f"match 258 at distance {dist}", bw.bytes(), len(head) + 258))
-    return cases
-
-
-def table_corner_cases():
-    cases = []
-    # literal/length codes of 15 bits, and a lone distance code of length 1
-    ll = ll_lens_for([(97 + k, k + 1) for k in range(13)] + [(257, 14), (110, 15), (256, 15)], 258)
-    bw = Bits()
-    dynamic_block(bw, ll, [1], list(b"abcdefghijklmnnmlkjihgfedcba") + [("m", 3, 1)] * 3 + [110])
-    cases.append(("15-bit codes, lone distance code", bw.bytes(), 28 + 9 + 1))
-    # HLIT 286 with HDIST 30
-    bw = Bits()
-    dynamic_block(bw, [8] * 226 + [9] * 60, [4] * 2 + [5] * 28, list(b"all 286 and all 30") + [("m", 258, 18), ("m", 100, 3), 255, 0])
-    cases.append(("HLIT 286, HDIST 30", bw.bytes(), 18 + 258 + 100 + 2))
-    # a code-16 repeat that crosses from the literal/length lengths into the distance lengths: 120 zeros, 1, 2, 134 zeros, a 4 for
-    # symbol 256, then "repeat it" 6 times — symbols 257, 258, 259 and the first three distance codes — and 13 more distance codes
-    ll = ll_lens_for([(120, 1), (121, 2), (256, 4), (257, 4), (258, 4), (259, 4)], 260)
-    syms = [(18, 120 - 11), (1, 0), (2, 0), (18, 134 - 11), (4, 0), (16, 6 - 3), (16, 6 - 3), (16, 6 - 3), (4, 0)]
-    bw = Bits()
-    dynamic_block(bw, ll, [4] * 16, [120, 121, 120, 120, ("m", 5, 4), ("m", 3, 7)], cl_syms=syms)
-    cases.append(("repeat across the two sets", bw.bytes(), 4 + 5 + 3))
-    # a dynamic block holding only end-of-block (its one code has one bit, and there is no distance code), then a fixed block
-    bw = Bits()
-    dynamic_block(bw, ll_lens_for([(256, 1)]), [0], [], final=0, cl_syms=[(18, 127), (18, 118 - 11), (1, 0), (0, 0)])
-    fixed_block(bw, list(b"after nothing"))
-    cases.append(("dynamic block of end-of-block only", bw.bytes(), 13))
-    # a stored block begun at bit 3 of a byte
-    bw = Bits()
-    fixed_block(bw, [200], final=0)
-    assert len(bw.b) % 8 == 3
-    stored_block(bw, b"stored from bit 3")
-    cases.append(("stored block at bit 3", bw.bytes(), 1 + 17))
-    return cases
-
-
-def rejection_cases():
-    """(what, stream, n): every one must classify as ZNIPPY_E_CORRUPT"""
-    out = []
-
-    def add(what, bw, n=10):
-        out.append((what, bw.bytes() + bytes(8), n))   # (zeros behind it: the error is the stream's, not a short input's)
-    bw = Bits(); bw.put(1, 1); bw.put(3, 2); add("block type 3", bw)
-    bw = Bits(); stored_block(bw, b"0123456789", nlen=10); add("LEN is not the complement of NLEN", bw)
-    ok_ll = ll_lens_for([(65, 1), (256, 1)])
-    for hlit in (287, 288):
-        bw = Bits(); dynamic_block(bw, [8] * 224 + [9] * 64, [1, 1], [], hlit=hlit, body=False); add(f"HLIT {hlit}", bw)
-    for hdist in (31, 32):
-        bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], hdist=hdist, body=False); add(f"HDIST {hdist}", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_syms=[(16, 0)], body=False); add("code 16 with no previous length", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_syms=[(18, 127), (18, 127)], body=False); add("repeat past HLIT + HDIST", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_syms=[(18, 127), (18, 107), (1, 0), (1, 0), (17, 0)], body=False); add("zeros past HLIT + HDIST", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_lens=[1, 1, 1] + [0] * 16, cl_syms=[], body=False); add("over-subscribed code-length set", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_lens=[2, 2, 2] + [0] * 16, cl_syms=[], body=False); add("incomplete code-length set", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1], [], cl_lens=[0] * 18 + [1], cl_syms=[], body=False); add("code-length set of one 1-bit code", bw)
-    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 1), (66, 1), (256, 1)]), [1, 1], [], body=False); add("over-subscribed literal/length set", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [1, 1, 1], [], body=False); add("over-subscribed distance set", bw)
-    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 2), (66, 2), (256, 2)]), [1, 1], [], body=False); add("incomplete literal/length set", bw)
-    bw = Bits(); dynamic_block(bw, ok_ll, [2, 2, 2], [], body=False); add("incomplete distance set", bw)
-    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 1), (66, 1)]), [1, 1], [], body=False); add("no end-of-block code", bw)
-    # a lone 1-bit literal/length code is allowed; the bit pattern it leaves unused is not
-    bw = Bits(); dynamic_block(bw, ll_lens_for([(256, 1)]), [0], [], body=False); bw.put(1, 1); add("unused code of an incomplete set", bw, 0)
-    # ... nor is any distance code where the block has none, or the unused one of a lone distance code
-    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 2), (256, 2), (257, 1)], 258), [0], [65, 65, 65, ("ll", 257)], eob=False); bw.put(0, 4); add("a match in a block without distance codes", bw)
-    bw = Bits(); dynamic_block(bw, ll_lens_for([(65, 2), (256, 2), (257, 1)], 258), [1], [65, 65, 65, ("ll", 257)], eob=False); bw.put(1, 4); add("unused code of a lone distance code", bw)
-    for s in (286, 287):
-        bw = Bits(); fixed_block(bw, [65, 66, ("ll", s)]); add(f"literal/length symbol {s}", bw)
-    for s in (30, 31):
-        bw = Bits(); fixed_block(bw, [65, 66, 67, ("sym", 257, 0, s, 0)]); add(f"distance symbol {s}", bw)
-    bw = Bits(); fixed_block(bw, [65, 66, 67, ("m", 3, 4)]); add("distance beyond the bytes produced", bw)
-    bw = Bits(); fixed_block(bw, [("m", 3, 1)]); add("a match as the first symbol", bw)
-    bw = Bits(); fixed_block(bw, list(b"0123456789"), final=0); out.append(("no final block", bw.bytes(), 10))
-    bw = Bits(); fixed_block(bw, list(b"01234")); add("end-of-block short of the expected length", bw)
-    return out
-
-
-def truncation_cases():
-    fixed = deflate(TEXT[:150], 6, zlib.Z_FIXED)
-    i = 150
-    while len(fixed) != 91:        # grow or shrink the input until the stream has the length the case names
-        i += 1 if len(fixed) < 91 else -1
-        fixed = deflate(TEXT[:i], 6, zlib.Z_FIXED)
-        assert 20 < i < 1000
-    nf = i
-    j = 400
-    dyn = deflate(TEXT[1000:1000 + j], 9)
-    seen = set()
-    while len(dyn) != 260:
-        assert j not in seen, "no input of this text deflates to 260 bytes"
-        seen.add(j)
-        j += 1 if len(dyn) < 260 else -1
-        dyn = deflate(TEXT[1000:1000 + j], 9)
-    assert dyn[0] & 6 == 4 and fixed[0] & 6 == 2
-    return [(f"fixed[:{k}]", fixed[:k], nf) for k in range(len(fixed))] + [(f"dynamic[:{k}]", dyn[:k], j) for k in range(len(dyn))], (fixed, nf), (dyn, j)
 
 
 def mutant_streams():
@@ -528,16 +277,6 @@ def test_sources_and_destinations_beyond_4_gib(gpu_ctx):
 
 
 # ---- 9. stored blocks in the middle of a stream: flush points ------------------------------------------------------------------
-
-def flushed_stream(data, piece, kinds, level=6, strategy=zlib.Z_DEFAULT_STRATEGY):
-    """`data` deflated with a flush of kinds[k % len] behind every `piece` bytes: each flush writes an empty stored block"""
-    c = zlib.compressobj(level, zlib.DEFLATED, -15, 9, strategy)
-    out = []
-    for k, at in enumerate(range(0, len(data), piece)):
-        out.append(c.compress(data[at:at + piece]))
-        out.append(c.flush(kinds[k % len(kinds)]))
-    return b"".join(out) + c.flush()
-
 
 def test_flush_points_all_over_the_input_window(gpu_ctx):
     """Z_SYNC_FLUSH and Z_FULL_FLUSH write an empty stored block wherever they are asked to: behind a Huffman block, at any byte
