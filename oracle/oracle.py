@@ -43,6 +43,9 @@ def lib():
         L.oracle_zstd_get_decompressed_size.restype = C.c_int
         L.oracle_zstd_decompress.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
         L.oracle_zstd_decompress.restype = C.c_int64
+        L.oracle_zstd_trace.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                        C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.oracle_zstd_trace.restype = C.c_int64
         L.oracle_have_libzstd.restype = C.c_int
         L.oracle_libzstd_compress_bound.argtypes = [C.c_size_t]
         L.oracle_libzstd_compress_bound.restype = C.c_size_t
@@ -98,6 +101,80 @@ def zstd_decompress(frame, cap=None) -> bytes:
     if r < 0:
         raise ValueError(f"oracle decompress: error {r}")
     return out[:r].tobytes()
+
+
+_TRACE_KINDS = ("ll", "of", "ml")
+
+
+def zstd_trace(frame, cap=None) -> dict:
+    """What the frame contains, as oracle_zstd_decompress reads it (the same decode, with a recorder).  Returns
+    {"content": the decoded bytes, "frames": [frame]}; a frame is a dict of fhd, fcs_bytes, header_bytes, has_size,
+    content_size, window, checksum, dict_id, regenerated, checksum_read, blocks; a block is a dict of type (0 raw, 1 RLE,
+    2 compressed), size, last, at (position of its first byte in the content) and, for a compressed block:
+      lits    type, size_format, streams (0 for raw and RLE literals), regen, comp, header_bytes, bytes (the literals)
+      huf     None or kind ("direct" / "fse"), desc_bytes, max_bits (the table's log), weights (as read, then the implied
+              last one), longest (the longest code: max_bits + 1 - the smallest weight)
+      nseq, nseq_bytes, modes (None without sequences)
+      tables  {"ll" / "of" / "ml": mode, log, rle_symbol (None unless RLE_Mode), norm (the counts as read, [] otherwise)}
+      seqs    uint64 array [nseq, 4]: literal length, match length, Offset_Value, resolved distance.
+    Skippable frames are listed under "skippable" as (magic, size).  Raises ValueError where the decoder does."""
+    a, p, n = _buf(frame)
+    if cap is None:
+        cap = zstd_decompressed_size(frame)
+    out = np.empty(max(cap, 1), dtype=np.uint8)
+    need = np.zeros(3, dtype=np.uint64)
+    ev, sq, lit = np.empty(4096, np.int64), np.empty((1024, 4), np.uint64), np.empty(max(cap, 1), np.uint8)
+    for _ in range(2):
+        r = lib().oracle_zstd_trace(out.ctypes.data_as(C.c_void_p), cap, p, n, ev.ctypes.data_as(C.c_void_p), len(ev),
+                                    sq.ctypes.data_as(C.c_void_p), len(sq), lit.ctypes.data_as(C.c_void_p), len(lit),
+                                    need.ctypes.data_as(C.c_void_p))
+        if r < 0:
+            raise ValueError(f"oracle trace: error {r}")
+        if need[0] <= len(ev) and need[1] <= len(sq) and need[2] <= len(lit):
+            break
+        ev, sq = np.empty(max(int(need[0]), 1), np.int64), np.empty((max(int(need[1]), 1), 4), np.uint64)
+        lit = np.empty(max(int(need[2]), 1), np.uint8)
+    else:
+        raise AssertionError("the recorder asked for more room twice")
+    content = out[:r].tobytes()
+    sq = sq[:int(need[1])]
+    frames, skippable, blk, i, end = [], [], None, 0, int(need[0])
+    evl = ev[:end].tolist()
+    while i < end:
+        tag, k = evl[i], evl[i + 1]
+        v = evl[i + 2:i + 2 + k]
+        i += 2 + k
+        if tag == 1:
+            frames.append(dict(zip(("fhd", "fcs_bytes", "header_bytes", "has_size", "content_size", "window", "checksum",
+                                    "dict_id"), v), blocks=[]))
+        elif tag == 2:
+            blk = dict(type=v[0], size=v[1], last=v[2], at=v[3])
+            if v[0] == 2:
+                blk.update(lits=None, huf=None, nseq=0, nseq_bytes=0, modes=None, tables={}, seqs=sq[:0], _sq=0)
+            frames[-1]["blocks"].append(blk)
+        elif tag == 3:
+            blk["lits"] = dict(type=v[0], size_format=v[1], streams=v[2], regen=v[3], comp=v[4], header_bytes=v[5],
+                               bytes=lit[v[6]:v[6] + v[3]].tobytes())
+        elif tag == 4:
+            w = v[4:] + [v[3]]
+            blk["huf"] = dict(kind="fse" if v[0] else "direct", desc_bytes=v[1], max_bits=v[2], weights=w,
+                              longest=v[2] + 1 - min(x for x in w if x))
+        elif tag == 5:
+            blk["nseq"], blk["nseq_bytes"], blk["_sq"] = v[0], v[1], v[2]
+        elif tag == 6:
+            blk["modes"] = v[0]
+        elif tag == 7:
+            blk["tables"][_TRACE_KINDS[v[0]]] = dict(mode=v[1], log=v[2], rle_symbol=v[3] if v[1] == 1 else None, norm=v[4:])
+        elif tag == 8:
+            skippable.append((v[0], v[1]))
+        elif tag == 9:
+            frames[-1]["regenerated"], frames[-1]["checksum_read"] = v[0], (None if v[1] < 0 else v[1])
+    for f in frames:
+        for b in f["blocks"]:
+            if b["type"] == 2:
+                b["seqs"] = sq[b["_sq"]:b["_sq"] + b["nseq"]]
+                del b["_sq"]
+    return dict(content=content, frames=frames, skippable=skippable)
 
 
 def have_libzstd() -> bool:

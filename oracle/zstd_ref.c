@@ -53,7 +53,39 @@ typedef struct {
     int valid;
 } zr_huf_t;
 
+/* ---------------- recorder (oracle_zstd_trace) ----------------
+ * What a frame contains, as the decoder below reads it.  The decode is the same code with or without a recorder; a NULL
+ * recorder (oracle_zstd_decompress, the row loop of loops_ref.c) records nothing and does no work for it.
+ *   ev:  records of int64: tag, count of values, the values.  `ev_n` counts every value that wanted to be written, so a
+ *        caller whose buffer was too small (ev_n > ev_cap) knows the size to come back with; nothing is stored past the cap.
+ *   sq:  four uint64 per sequence: literal length, match length, Offset_Value, the distance it resolved to.
+ *   lit: the regenerated literal bytes of every compressed block, one block behind the other (RLE literals expanded). */
+#define ZT_FRAME 1  /* FHD, FCS bytes, header bytes, has size, content size, window size, checksum flag, dictionary id */
+#define ZT_BLOCK 2  /* type, size, last, position of its first byte in the output */
+#define ZT_LITS 3   /* type, size format, streams, regenerated size, compressed size, header bytes, position in lit */
+#define ZT_HUF 4    /* 0 direct / 1 FSE, bytes of the description, the table's log, implied last weight, weights as read ... */
+#define ZT_NSEQ 5   /* count, bytes the count took, index of the block's first sequence in sq */
+#define ZT_MODES 6  /* the Compression_Modes byte */
+#define ZT_TABLE 7  /* 0 LL / 1 OF / 2 ML, mode, accuracy log (0: RLE), RLE symbol or -1, counts as read ... */
+#define ZT_SKIP 8   /* a skippable frame: magic, size */
+#define ZT_END 9    /* end of a frame: bytes it regenerated, checksum read or -1 */
 typedef struct {
+    int64_t *ev; size_t ev_cap, ev_n;
+    uint64_t *sq; size_t sq_cap, sq_n;     /* in sequences */
+    uint8_t *lit; size_t lit_cap, lit_n;
+} zr_trace_t;
+
+static void zt_put(zr_trace_t *t, int64_t tag, int n, const int64_t *v) {
+    int i;
+    if (t->ev_n + 2 + (size_t)n <= t->ev_cap) {
+        t->ev[t->ev_n] = tag; t->ev[t->ev_n + 1] = n;
+        for (i = 0; i < n; i++) t->ev[t->ev_n + 2 + i] = v[i];
+    }
+    t->ev_n += 2 + (size_t)n;
+}
+
+typedef struct {
+    zr_trace_t *tr;
     zr_huf_t huf;
     zr_fse_t ll, of, ml;
     int ll_valid, of_valid, ml_valid;
@@ -274,9 +306,9 @@ static int zr_huf_build(zr_huf_t *h, const uint8_t *weights, int nsym_given) {
     return ZR_OK;
 }
 
-static int zr_huf_read_tree(zr_huf_t *h, const uint8_t *src, size_t n, size_t *consumed) {
+static int zr_huf_read_tree(zr_huf_t *h, const uint8_t *src, size_t n, size_t *consumed, zr_trace_t *tr) {
     uint8_t weights[256];
-    int nw = 0;
+    int nw = 0, rc_build;
     uint8_t hb;
     if (n < 1) return ZR_ERR_SRC_TRUNC;
     hb = src[0];
@@ -328,7 +360,18 @@ static int zr_huf_read_tree(zr_huf_t *h, const uint8_t *src, size_t n, size_t *c
         }
         *consumed = (size_t)1 + hb;
     }
-    return zr_huf_build(h, weights, nw);
+    rc_build = zr_huf_build(h, weights, nw);
+    if (tr && !rc_build) {
+        int64_t v[4 + 256];
+        int i, lastw = 0;
+        uint32_t total = 0;
+        for (i = 0; i < nw; i++) total += weights[i] ? 1u << (weights[i] - 1) : 0;
+        lastw = zr_highbit((1u << h->log) - total) + 1;
+        v[0] = hb < 128; v[1] = (int64_t)*consumed; v[2] = h->log; v[3] = lastw;
+        for (i = 0; i < nw; i++) v[4 + i] = weights[i];
+        zt_put(tr, ZT_HUF, 4 + nw, v);
+    }
+    return rc_build;
 }
 
 static int zr_huf_decode_stream(const zr_huf_t *h, const uint8_t *src, size_t n, uint8_t *dst,
@@ -348,6 +391,19 @@ static int zr_huf_decode_stream(const zr_huf_t *h, const uint8_t *src, size_t n,
 
 /* ---------------- literals section ---------------- */
 typedef struct { const uint8_t *ptr; size_t len; int rle; uint8_t rle_byte; } zr_lits_t;
+
+static void zt_lits(zr_trace_t *t, int type, int sf, int streams, size_t regen, size_t comp, size_t hdr,
+                    const zr_lits_t *l) {
+    int64_t v[7];
+    v[0] = type; v[1] = sf; v[2] = streams; v[3] = (int64_t)regen; v[4] = (int64_t)comp; v[5] = (int64_t)hdr;
+    v[6] = (int64_t)t->lit_n;
+    zt_put(t, ZT_LITS, 7, v);
+    if (regen && t->lit_n + regen <= t->lit_cap) {
+        if (l->rle) memset(t->lit + t->lit_n, l->rle_byte, regen);
+        else memcpy(t->lit + t->lit_n, l->ptr, regen);
+    }
+    t->lit_n += regen;
+}
 
 static int zr_decode_literals(zr_frame_t *f, const uint8_t *src, size_t n, zr_lits_t *out,
                               size_t *consumed) {
@@ -370,6 +426,7 @@ static int zr_decode_literals(zr_frame_t *f, const uint8_t *src, size_t n, zr_li
             out->ptr = NULL; out->len = regen; out->rle = 1; out->rle_byte = src[hdr];
             *consumed = hdr + 1;
         }
+        if (f->tr) zt_lits(f->tr, type, sf, 0, regen, type == 0 ? regen : 1, hdr, out);
         return ZR_OK;
     }
     {
@@ -390,7 +447,7 @@ static int zr_decode_literals(zr_frame_t *f, const uint8_t *src, size_t n, zr_li
         remain = comp;
         if (type == 2) {
             size_t used;
-            rc = zr_huf_read_tree(&f->huf, p, remain, &used);
+            rc = zr_huf_read_tree(&f->huf, p, remain, &used, f->tr);
             if (rc) return rc;
             p += used; remain -= used;
         } else if (!f->huf.valid) {
@@ -414,13 +471,23 @@ static int zr_decode_literals(zr_frame_t *f, const uint8_t *src, size_t n, zr_li
         }
         out->ptr = f->lit; out->len = regen; out->rle = 0;
         *consumed = hdr + comp;
+        if (f->tr) zt_lits(f->tr, type, sf, streams, regen, comp, hdr, out);
         return ZR_OK;
     }
 }
 
 /* ---------------- sequences section ---------------- */
+static void zt_table(zr_trace_t *t, int kind, int mode, int log, int sym, const int16_t *norm, int nsym) {
+    int64_t v[4 + 64];
+    int i;
+    v[0] = kind; v[1] = mode; v[2] = log; v[3] = sym;
+    for (i = 0; i < nsym; i++) v[4 + i] = norm[i];
+    zt_put(t, ZT_TABLE, 4 + nsym, v);
+}
+
 static int zr_seq_table(zr_fse_t *t, int *valid, int mode, const uint8_t **pp, const uint8_t *end,
-                        const int16_t *def, int def_n, int def_log, int max_log, int max_sym) {
+                        const int16_t *def, int def_n, int def_log, int max_log, int max_sym,
+                        zr_trace_t *tr, int kind) {
     const uint8_t *p = *pp;
     int rc;
     switch (mode) {
@@ -428,6 +495,7 @@ static int zr_seq_table(zr_fse_t *t, int *valid, int mode, const uint8_t **pp, c
         rc = zr_fse_build(t, def, def_n, def_log);
         if (rc) return rc;
         *valid = 1;
+        if (tr) zt_table(tr, kind, 0, def_log, -1, NULL, 0);
         return ZR_OK;
     case 1:
         if (p >= end) return ZR_ERR_SRC_TRUNC;
@@ -435,6 +503,7 @@ static int zr_seq_table(zr_fse_t *t, int *valid, int mode, const uint8_t **pp, c
         zr_fse_rle(t, *p);
         *pp = p + 1;
         *valid = 1;
+        if (tr) zt_table(tr, kind, 1, 0, *p, NULL, 0);
         return ZR_OK;
     case 2: {
         int16_t norm[64];
@@ -446,9 +515,11 @@ static int zr_seq_table(zr_fse_t *t, int *valid, int mode, const uint8_t **pp, c
         if (rc) return rc;
         *pp = p + used;
         *valid = 1;
+        if (tr) zt_table(tr, kind, 2, log, -1, norm, nsym);
         return ZR_OK;
     }
     default:
+        if (tr && *valid) zt_table(tr, kind, 3, t->log, -1, NULL, 0);
         return *valid ? ZR_OK : ZR_ERR_CORRUPT;
     }
 }
@@ -465,6 +536,7 @@ static int zr_decode_block(zr_frame_t *f, const uint8_t *src, size_t n, uint8_t 
     memset(&lits, 0, sizeof lits);
     const uint8_t *p, *end = src + n;
     uint32_t nseq;
+    zr_trace_t *const tr = f->tr;
     int rc = zr_decode_literals(f, src, n, &lits, &used);
     if (rc) return rc;
     p = src + used;
@@ -473,6 +545,11 @@ static int zr_decode_block(zr_frame_t *f, const uint8_t *src, size_t n, uint8_t 
     else if (p[0] < 128) { nseq = p[0]; p += 1; }
     else if (p[0] < 255) { if (p + 2 > end) return ZR_ERR_SRC_TRUNC; nseq = ((uint32_t)(p[0] - 128) << 8) + p[1]; p += 2; }
     else { if (p + 3 > end) return ZR_ERR_SRC_TRUNC; nseq = (uint32_t)p[1] + ((uint32_t)p[2] << 8) + 0x7F00; p += 3; }
+    if (tr) {
+        int64_t v[3];
+        v[0] = nseq; v[1] = p - (src + used); v[2] = (int64_t)tr->sq_n;
+        zt_put(tr, ZT_NSEQ, 3, v);
+    }
     if (nseq) {
         uint8_t modes;
         zr_bwd_t b;
@@ -480,9 +557,10 @@ static int zr_decode_block(zr_frame_t *f, const uint8_t *src, size_t n, uint8_t 
         if (p >= end) return ZR_ERR_SRC_TRUNC;
         modes = *p++;
         if (modes & 3) return ZR_ERR_CORRUPT;
-        rc = zr_seq_table(&f->ll, &f->ll_valid, (modes >> 6) & 3, &p, end, ZR_LL_DEFAULT, 36, 6, ZR_LL_MAX_LOG, 35); if (rc) return rc;
-        rc = zr_seq_table(&f->of, &f->of_valid, (modes >> 4) & 3, &p, end, ZR_OF_DEFAULT, 29, 5, ZR_OF_MAX_LOG, 31); if (rc) return rc;
-        rc = zr_seq_table(&f->ml, &f->ml_valid, (modes >> 2) & 3, &p, end, ZR_ML_DEFAULT, 53, 6, ZR_ML_MAX_LOG, 52); if (rc) return rc;
+        if (tr) { int64_t v = modes; zt_put(tr, ZT_MODES, 1, &v); }
+        rc = zr_seq_table(&f->ll, &f->ll_valid, (modes >> 6) & 3, &p, end, ZR_LL_DEFAULT, 36, 6, ZR_LL_MAX_LOG, 35, tr, 0); if (rc) return rc;
+        rc = zr_seq_table(&f->of, &f->of_valid, (modes >> 4) & 3, &p, end, ZR_OF_DEFAULT, 29, 5, ZR_OF_MAX_LOG, 31, tr, 1); if (rc) return rc;
+        rc = zr_seq_table(&f->ml, &f->ml_valid, (modes >> 2) & 3, &p, end, ZR_ML_DEFAULT, 53, 6, ZR_ML_MAX_LOG, 52, tr, 2); if (rc) return rc;
         if (p >= end) return ZR_ERR_SRC_TRUNC;
         rc = zr_bwd_init(&b, p, (size_t)(end - p));
         if (rc) return rc;
@@ -516,6 +594,13 @@ static int zr_decode_block(zr_frame_t *f, const uint8_t *src, size_t n, uint8_t 
                     f->rep[1] = f->rep[0];
                     f->rep[0] = offset;
                 }
+            }
+            if (tr) {
+                if (tr->sq_n < tr->sq_cap) {
+                    uint64_t *q = tr->sq + 4 * tr->sq_n;
+                    q[0] = ll; q[1] = ml; q[2] = ov; q[3] = offset;
+                }
+                tr->sq_n++;
             }
             if (lit_at + ll > lits.len) return ZR_ERR_CORRUPT;
             if (out + ll + ml > dst_cap) return ZR_ERR_DST_SMALL;
@@ -599,8 +684,7 @@ int oracle_zstd_get_decompressed_size(const uint8_t *src, size_t n, uint64_t *ou
     return ZR_OK;
 }
 
-/* zl_decompress: returns bytes written (>=0) or a negative ZR_ERR_*. */
-int64_t oracle_zstd_decompress(uint8_t *dst, size_t cap, const uint8_t *src, size_t n) {
+static int64_t zr_decompress(uint8_t *dst, size_t cap, const uint8_t *src, size_t n, zr_trace_t *tr) {
     size_t out = 0;
     uint8_t *lit = (uint8_t *)malloc(ZR_BLOCK_MAX + 64);
     zr_frame_t *f = (zr_frame_t *)calloc(1, sizeof(zr_frame_t));
@@ -613,14 +697,23 @@ int64_t oracle_zstd_decompress(uint8_t *dst, size_t cap, const uint8_t *src, siz
         if (n >= 8 && (xrd32(src) & 0xFFFFFFF0u) == 0x184D2A50u) {
             uint32_t sz = xrd32(src + 4);
             if ((size_t)8 + sz > n) { result = ZR_ERR_SRC_TRUNC; goto done; }
+            if (tr) { int64_t v[2]; v[0] = xrd32(src); v[1] = sz; zt_put(tr, ZT_SKIP, 2, v); }
             src += 8 + sz; n -= 8 + sz;
             continue;
         }
         rc = zr_parse_header(src, n, &h);
         if (rc) { result = rc; goto done; }
         if (h.dict_id) { result = ZR_ERR_UNSUPPORTED; goto done; }
+        if (tr) {
+            int64_t v[8];
+            const int flag = src[4] >> 6;
+            v[0] = src[4]; v[1] = flag == 0 ? (src[4] >> 5) & 1 : 1 << flag; v[2] = (int64_t)h.hdr_len; v[3] = h.has_size;
+            v[4] = (int64_t)h.content_size; v[5] = (int64_t)h.window; v[6] = h.checksum; v[7] = h.dict_id;
+            zt_put(tr, ZT_FRAME, 8, v);
+        }
         src += h.hdr_len; n -= h.hdr_len;
         memset(f, 0, sizeof *f);
+        f->tr = tr;
         f->lit = lit;
         f->rep[0] = 1; f->rep[1] = 4; f->rep[2] = 8;
         while (!last) {
@@ -629,6 +722,11 @@ int64_t oracle_zstd_decompress(uint8_t *dst, size_t cap, const uint8_t *src, siz
             bh = src[0] | ((uint32_t)src[1] << 8) | ((uint32_t)src[2] << 16);
             last = bh & 1; btype = (bh >> 1) & 3; bsize = bh >> 3;
             src += 3; n -= 3;
+            if (tr) {
+                int64_t v[4];
+                v[0] = btype; v[1] = bsize; v[2] = last; v[3] = (int64_t)out;
+                zt_put(tr, ZT_BLOCK, 4, v);
+            }
             if (btype == 0) {
                 if (bsize > n) { result = ZR_ERR_SRC_TRUNC; goto done; }
                 if (out + bsize > cap) { result = ZR_ERR_DST_SMALL; goto done; }
@@ -660,9 +758,33 @@ int64_t oracle_zstd_decompress(uint8_t *dst, size_t cap, const uint8_t *src, siz
             if ((uint32_t)oracle_xxh64(dst + frame_start, out - frame_start, 0) != want) { result = ZR_ERR_CHECKSUM; goto done; }
             src += 4; n -= 4;
         }
+        if (tr) {
+            int64_t v[2];
+            v[0] = (int64_t)(out - frame_start); v[1] = h.checksum ? (int64_t)xrd32(src - 4) : -1;
+            zt_put(tr, ZT_END, 2, v);
+        }
     }
     result = (int64_t)out;
 done:
     free(lit); free(f);
     return result;
+}
+
+/* zl_decompress: returns bytes written (>=0) or a negative ZR_ERR_*. */
+int64_t oracle_zstd_decompress(uint8_t *dst, size_t cap, const uint8_t *src, size_t n) {
+    return zr_decompress(dst, cap, src, n, NULL);
+}
+
+/* The same decode with a recorder.  ev / sq / lit may be too small (or NULL with a cap of 0): the counts that come back in
+ * need[0..2] (values of ev, sequences, literal bytes) say what a second call needs; what did not fit is not stored. */
+int64_t oracle_zstd_trace(uint8_t *dst, size_t cap, const uint8_t *src, size_t n, int64_t *ev, size_t ev_cap,
+                          uint64_t *sq, size_t sq_cap, uint8_t *lit, size_t lit_cap, uint64_t *need) {
+    zr_trace_t t;
+    int64_t r;
+    t.ev = ev; t.ev_cap = ev_cap; t.ev_n = 0;
+    t.sq = sq; t.sq_cap = sq_cap; t.sq_n = 0;
+    t.lit = lit; t.lit_cap = lit_cap; t.lit_n = 0;
+    r = zr_decompress(dst, cap, src, n, &t);
+    need[0] = t.ev_n; need[1] = t.sq_n; need[2] = t.lit_n;
+    return r;
 }

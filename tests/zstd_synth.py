@@ -120,6 +120,21 @@ def execute(blocks):
     return bytes(out)
 
 
+def blocks_of_trace(frame_trace, content):
+    """The description (Raw / Rle / Comp with their literals and sequences) of one frame of oracle.zstd_trace's result:
+    what `execute` needs to say the frame's bytes again.  content: the trace's decoded bytes (raw and RLE blocks are read
+    from it)."""
+    out = []
+    for b in frame_trace["blocks"]:
+        if b["type"] == 0:
+            out.append(Raw(content[b["at"]:b["at"] + b["size"]]))
+        elif b["type"] == 1:
+            out.append(Rle(content[b["at"]], b["size"]))
+        else:
+            out.append(Comp(b["lits"]["bytes"], [(int(s[0]), int(s[1]), int(s[2])) for s in b["seqs"]]))
+    return out
+
+
 # ---- bit streams ------------------------------------------------------------------------------------------------------
 
 class _Bits:
