@@ -3246,9 +3246,19 @@ extern "C" int znippy_rounds_set_store_incompressible(znippy_rounds *r, int on) 
     return ZNIPPY_OK;
 }
 
+// ---- the DEFLATE batch calls: not runs, no table is involved -------------------------------------------
+// What each call works out on the host — which items pass, where they go, the lists the kernels read, what the kernels' answers mean
+// — is host/deflate_batch.{h,cc}, plain C++ that a stand-alone program tests.  Here: the argument checks, the allocations, the
+// copies and the launches, in stages over that plan.
+static_assert(DB_OK == ZNIPPY_OK && DB_E_INVAL == ZNIPPY_E_INVAL && DB_E_NOMEM == ZNIPPY_E_NOMEM && DB_E_DST_SMALL == ZNIPPY_E_DST_SMALL &&
+              DB_E_CORRUPT == ZNIPPY_E_CORRUPT && DB_E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED && DB_E_CHECKSUM == ZNIPPY_E_CHECKSUM,
+              "host/deflate_batch.h gives out the codes of znippy_hip.h");
+static_assert(gzp::OK == ZNIPPY_OK && gzp::E_DST_SMALL == ZNIPPY_E_DST_SMALL && gzp::E_CORRUPT == ZNIPPY_E_CORRUPT &&
+              gzp::E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED && gzp::E_CHECKSUM == ZNIPPY_E_CHECKSUM, "host/gz_plan.h gives out the codes of znippy_hip.h");
+
 // ---- raw DEFLATE of ZIP entries (znippy_inflate_batch) ---------------------------------------------
-// Not a run: no table is involved.  Every item is validated on the host; the items that pass are uploaded as one list, decoded by one
-// launch (wave = stream) and checksummed by a second one; status and CRC come back in one copy each.
+// The items that pass inflate_admit are uploaded as one list, decoded by one launch (wave = stream) and checksummed by a second one;
+// status and CRC come back in one copy each.
 static int inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len,
                          const uint8_t *method, void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_len,
                          const uint32_t *crc32, uint64_t n, int32_t *status, uint32_t *crc_out) {
@@ -3260,38 +3270,10 @@ static int inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, c
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
 
-    // 1) every item against the source region, the output region and the sizes and methods the kernel takes
-    std::vector<int32_t> st(n, 0);
-    std::vector<InflateItem> items;
-    std::vector<uint32_t> item_of;  // list entry -> item
-    uint64_t packed = 0;
-    bool packed_wrap = false;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t so = src_off[i], sl = src_len[i], ol = out_len[i];
-        const bool dst_known = out_off || !packed_wrap;
-        const uint64_t dst = out_off ? out_off[i] : packed;
-        if (!out_off) { packed_wrap |= packed + ol < packed; packed += ol; }
-        const unsigned m = method ? method[i] : 8u;
-        if (so > src_cap || sl > src_cap - so) { st[i] = ZNIPPY_E_INVAL; continue; }
-        if (!dst_known || ol > out_cap || dst > out_cap - ol) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
-        if (sl >= (1ull << 32) || ol >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
-        if (m != 0 && m != 8) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
-        if (m == 0 && sl != ol) { st[i] = ZNIPPY_E_CORRUPT; continue; }
-        InflateItem it;
-        it.src = (const uint8_t *)d_src + so;
-        it.dst = (uint8_t *)d_out + dst;
-        it.src_len = (uint32_t)sl; it.out_len = (uint32_t)ol;
-        it.method = m;
-        it.want_crc = crc32 ? crc32[i] : 0; it.has_crc = crc32 ? 1 : 0;
-        it.pad = 0;
-        items.push_back(it);
-        item_of.push_back((uint32_t)i);
-    }
-    const uint32_t n_items = (uint32_t)items.size();
-    std::vector<int32_t> h_st(n_items, 0);
-    std::vector<uint32_t> h_crc(n_items, 0);
-    if (n_items) {
-        // 2) every allocation, then the stream
+    InflateBatch b;
+    inflate_admit(InflateCall{(const uint8_t *)d_src, src_cap, src_off, src_len, method, (uint8_t *)d_out, out_cap, out_off, out_len, crc32, n}, b);
+    const uint32_t n_items = (uint32_t)b.items.size();
+    if (n_items) {  // every allocation, then the stream
         struct Guard {
             znippy_ctx *ctx;
             InflateItem *items = nullptr; int32_t *st = nullptr; uint32_t *crc = nullptr;
@@ -3300,21 +3282,16 @@ static int inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, c
         HIPCHK(ctx, tmalloc(ctx, &g.items, sizeof(InflateItem) * n_items));
         HIPCHK(ctx, tmalloc(ctx, &g.st, sizeof(int32_t) * n_items));
         HIPCHK(ctx, tmalloc(ctx, &g.crc, sizeof(uint32_t) * n_items));
-        HIPCHK(ctx, hipMemcpyAsync(g.items, items.data(), sizeof(InflateItem) * n_items, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(g.items, b.items.data(), sizeof(InflateItem) * n_items, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemsetAsync(g.crc, 0, sizeof(uint32_t) * n_items, s));
         timed(ctx, "inflate", s, [&] { launch_inflate(g.items, n_items, g.st, s); });
         timed(ctx, "inflate_crc", s, [&] { launch_inflate_crc(g.items, n_items, g.st, g.crc, s); });
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(h_st.data(), g.st, sizeof(int32_t) * n_items, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipMemcpyAsync(h_crc.data(), g.crc, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(b.h_st.data(), g.st, sizeof(int32_t) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(b.h_crc.data(), g.crc, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
     }
-    if (crc_out) memset(crc_out, 0, sizeof(uint32_t) * n);
-    for (uint32_t k = 0; k < n_items; k++) {
-        st[item_of[k]] = h_st[k];
-        if (crc_out) crc_out[item_of[k]] = h_crc[k];
-    }
-    if (status) memcpy(status, st.data(), sizeof(int32_t) * n);
+    inflate_scatter(b, n, status, crc_out);
     return ZNIPPY_OK;
 }
 
@@ -3325,9 +3302,9 @@ extern "C" int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t
 }
 
 // ---- one tar member out of gzip-compressed tars (znippy_targz_find_batch) ----------------------------
-// Not a run, like the call above: the items are validated on the host, the ones that pass get a slice of the context's range scratch
-// (sized before anything is queued) and are walked by one launch (wave = stream, targz.hip); status, place and length come back in one
-// copy; the members that were found and fit are packed into d_out by the range reads' gather.
+// The items that pass targz_admit get a slice of the context's range scratch (sized before anything is queued) and are walked by one
+// launch (wave = stream, targz.hip); status, place and length come back in one copy; the members that targz_pack finds in place and
+// fitting are packed into d_out by the range reads' gather.
 static int targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, const uint8_t *whole,
                             uint64_t n, const char *name_prefix, uint64_t prefix_len, const char *name_suffix, uint64_t suffix_len, uint64_t scan_cap,
                             void *d_out, uint64_t out_cap, uint64_t *out_off, uint64_t *out_len, int32_t *status, uint64_t *scanned) {
@@ -3341,38 +3318,14 @@ static int targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
 
-    // 1) every item against the source region; its slice of the scratch
-    std::vector<int32_t> st(n, 0);
-    std::vector<TargzItem> items;
-    std::vector<uint64_t> slice;    // list entry -> offset of its slice
-    std::vector<uint32_t> item_of;  // list entry -> item
-    uint64_t need = 0;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t so = src_off[i], sl = src_len[i];
-        out_off[i] = out_len[i] = 0;
-        if (scanned) scanned[i] = 0;
-        if (so > src_cap || sl > src_cap - so) { st[i] = ZNIPPY_E_INVAL; continue; }
-        if (sl >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
-        // no valid DEFLATE expands more than 1032 : 1, and one item walks at most 4 GiB - 16 bytes of tar
-        const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>(scan_cap, 1032 * sl + 512), 0xFFFFFFF0ull);
-        TargzItem it;
-        it.src = (const uint8_t *)d_src + so;
-        it.scratch = nullptr;
-        it.src_len = (uint32_t)sl; it.cap = (uint32_t)cap;
-        it.whole = whole ? whole[i] != 0 : 1; it.pad = 0;
-        items.push_back(it);
-        slice.push_back(need);
-        item_of.push_back((uint32_t)i);
-        need += (cap + 15) & ~15ull;
-        if (need > (1ull << 40)) return ZNIPPY_E_NOMEM;  // (far beyond the scratch's cap: the sum stays small)
-    }
-    const uint32_t n_items = (uint32_t)items.size();
-    std::vector<TargzResult> res(n_items);
-    if (n_items) {
-        // 2) every allocation, then the stream
-        int rc;
-        if ((rc = ensure_range_scratch(ctx, 0, need))) return rc;
-        for (uint32_t k = 0; k < n_items; k++) items[k].scratch = ctx->rr_pool[0] + slice[k];
+    const TargzCall call{(const uint8_t *)d_src, src_cap, src_off, src_len, whole, n, scan_cap, (uint8_t *)d_out, out_cap, out_off, out_len, scanned};
+    TargzBatch b;
+    int rc;
+    if ((rc = targz_admit(call, b))) return rc;
+    const uint32_t n_items = (uint32_t)b.items.size();
+    if (n_items) {  // every allocation, then the stream
+        if ((rc = ensure_range_scratch(ctx, 0, b.need))) return rc;
+        targz_bind(b, ctx->rr_pool[0]);
         struct Guard {
             znippy_ctx *ctx;
             TargzItem *items = nullptr; TargzResult *res = nullptr; uint8_t *filter = nullptr; RangePiece *pieces = nullptr;
@@ -3381,50 +3334,28 @@ static int targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
         std::vector<uint8_t> filter(prefix_len + suffix_len + 16, 0);
         if (prefix_len) memcpy(filter.data(), name_prefix, prefix_len);
         if (suffix_len) memcpy(filter.data() + prefix_len, name_suffix, suffix_len);
-        // the gather's list is cut once the results are known: at most one piece per RANGE_PIECE bytes of output and one more per item
-        const size_t max_pieces = (size_t)(out_cap / RANGE_PIECE) + 2 * (size_t)n_items;
-        if (max_pieces > RR_ITEMS_MAX) return ZNIPPY_E_NOMEM;
+        size_t max_pieces;  // the gather's list is cut once the results are known
+        if ((rc = targz_piece_bound(out_cap, n_items, &max_pieces))) return rc;
         HIPCHK(ctx, tmalloc(ctx, &g.items, sizeof(TargzItem) * n_items));
         HIPCHK(ctx, tmalloc(ctx, &g.res, sizeof(TargzResult) * n_items));
         HIPCHK(ctx, tmalloc(ctx, &g.filter, filter.size()));
         HIPCHK(ctx, tmalloc(ctx, &g.pieces, sizeof(RangePiece) * max_pieces));
-        std::vector<RangePiece> pieces;
-        pieces.reserve(2 * (size_t)n_items);
-        HIPCHK(ctx, hipMemcpyAsync(g.items, items.data(), sizeof(TargzItem) * n_items, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(g.items, b.items.data(), sizeof(TargzItem) * n_items, hipMemcpyHostToDevice, s));
         HIPCHK(ctx, hipMemcpyAsync(g.filter, filter.data(), filter.size(), hipMemcpyHostToDevice, s));
         timed(ctx, "targz_find", s, [&] { launch_targz_find(g.items, n_items, g.filter, (uint32_t)prefix_len, (uint32_t)suffix_len, g.res, s); });
         HIPCHK(ctx, hipGetLastError());
-        HIPCHK(ctx, hipMemcpyAsync(res.data(), g.res, sizeof(TargzResult) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(b.res.data(), g.res, sizeof(TargzResult) * n_items, hipMemcpyDeviceToHost, s));
         HIPCHK(ctx, hipStreamSynchronize(s));
-        // 3) the members found, back to back in array order; one that no longer fits takes no room, and those behind it may still fit
-        uint64_t packed = 0;
-        for (uint32_t k = 0; k < n_items; k++) {
-            const uint32_t i = item_of[k];
-            const TargzResult &r = res[k];
-            st[i] = r.status;
-            if (scanned) scanned[i] = r.scanned;
-            if (r.status != 0) continue;
-            if (r.off > items[k].cap || r.len > items[k].cap - r.off) { st[i] = ZNIPPY_E_CORRUPT; continue; }  // (the kernel's word is checked, not trusted)
-            if (r.len > out_cap - packed) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
-            out_off[i] = packed; out_len[i] = r.len;
-            const uint8_t *from = items[k].scratch + r.off;
-            uint8_t *to = (uint8_t *)d_out + packed;
-            for (uint64_t left = r.len; left;) {  // from the second piece of a member on, a destination starts on a 128-byte line
-                const uint64_t room = RANGE_PIECE - ((uintptr_t)to & 127), len = std::min(left, room);
-                pieces.push_back(RangePiece{from, to, (uint32_t)len, 0});
-                from += len; to += len; left -= len;
-            }
-            packed += r.len;
-        }
-        if (!pieces.empty()) {
-            if (pieces.size() > max_pieces) return ZNIPPY_E_NOMEM;  // (cannot happen: the bound above counts them)
-            HIPCHK(ctx, hipMemcpyAsync(g.pieces, pieces.data(), sizeof(RangePiece) * pieces.size(), hipMemcpyHostToDevice, s));
-            timed(ctx, "targz_gather", s, [&] { launch_range_gather(g.pieces, (uint32_t)pieces.size(), s); });
+        targz_pack(call, b);
+        if (!b.pieces.empty()) {
+            if (b.pieces.size() > max_pieces) return ZNIPPY_E_NOMEM;  // (cannot happen: the bound counts them)
+            HIPCHK(ctx, hipMemcpyAsync(g.pieces, b.pieces.data(), sizeof(RangePiece) * b.pieces.size(), hipMemcpyHostToDevice, s));
+            timed(ctx, "targz_gather", s, [&] { launch_range_gather(g.pieces, (uint32_t)b.pieces.size(), s); });
             HIPCHK(ctx, hipGetLastError());
             HIPCHK(ctx, hipStreamSynchronize(s));
         }
     }
-    if (status) memcpy(status, st.data(), sizeof(int32_t) * n);
+    if (status) memcpy(status, b.st.data(), sizeof(int32_t) * n);
     return ZNIPPY_OK;
 }
 
@@ -3437,13 +3368,90 @@ extern "C" int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint6
 }
 
 // ---- whole gzip files (znippy_gunzip_batch) ----------------------------------------------------------
-// Not a run, like the two calls above.  The items that pass the host's validation are scanned for candidate starts; the host keeps
-// candidates (host/gz_plan.h: keep_candidates), the probe leaves a record per kept candidate, plan_item turns an item's records into
-// runs and members, and the decode and CRC launches follow.  Items without a kept candidate behind byte 0, and items whose candidates did
-// not fit their slice of the list, take the single pass instead.  One device allocation, sized from the source lengths before
-// anything is queued, holds every list.
-static_assert(gzp::OK == ZNIPPY_OK && gzp::E_DST_SMALL == ZNIPPY_E_DST_SMALL && gzp::E_CORRUPT == ZNIPPY_E_CORRUPT &&
-              gzp::E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED && gzp::E_CHECKSUM == ZNIPPY_E_CHECKSUM, "host/gz_plan.h gives out the codes of znippy_hip.h");
+// The items that pass gz_admit are scanned for candidate starts; gz_candidates keeps candidates and says which items are probed and
+// which take the single pass (those without a kept candidate behind byte 0, and those whose candidates did not fit their slice of the
+// list); the probe leaves a record per kept candidate; gz_decode_plan turns records into runs and members, and the decode and CRC
+// launches follow; gz_verdict reads their answers.  One device allocation (gz_layout), sized from the source lengths before anything
+// is queued, holds every list.
+struct GzDev {  // the allocation, and where its lists are
+    uint8_t *p;
+    GzLayout at;
+    hipStream_t s;
+    template <typename T>
+    T *list(size_t off) const { return (T *)(p + off); }
+    const GzItem *items() const { return list<GzItem>(at.items); }
+};
+
+// items and chunks up; the scan; the counts back, then the raw list as far as gz_raw_end says
+static int gz_scan_stage(znippy_ctx *ctx, GzBatch &b, const GzDev &d) {
+    const uint32_t n_items = (uint32_t)b.items.size();
+    hipStream_t s = d.s;
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.items, b.items.data(), sizeof(GzItem) * n_items, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.chunks, b.chunks.data(), sizeof(GzScanChunk) * b.chunks.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(d.p + d.at.count, 0, sizeof(uint32_t) * n_items, s));
+    timed(ctx, "gunzip_scan", s, [&] {
+        launch_gunzip_scan(d.items(), d.list<const GzScanChunk>(d.at.chunks), (uint32_t)b.chunks.size(), d.list<uint32_t>(d.at.count), d.list<uint64_t>(d.at.raw), s);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    HIPCHK(ctx, hipMemcpyAsync(b.count.data(), d.p + d.at.count, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    if (const uint64_t raw_end = gz_raw_end(b)) {
+        b.raw.resize(raw_end);
+        HIPCHK(ctx, hipMemcpyAsync(b.raw.data(), d.p + d.at.raw, sizeof(uint64_t) * raw_end, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    return ZNIPPY_OK;
+}
+
+// the probe over the kept candidates, the single pass over the other items; records and results back
+static int gz_probe_stage(znippy_ctx *ctx, GzBatch &b, const GzDev &d) {
+    const uint32_t n_cands = (uint32_t)b.cands.size(), n_single = (uint32_t)b.single.size();
+    hipStream_t s = d.s;
+    if (n_cands) {
+        HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.cands, b.cands.data(), sizeof(GzCand) * n_cands, hipMemcpyHostToDevice, s));
+        if (!b.stops.empty()) HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.stops, b.stops.data(), sizeof(uint32_t) * b.stops.size(), hipMemcpyHostToDevice, s));
+        timed(ctx, "gunzip_probe", s, [&] {
+            launch_gunzip_probe(d.items(), d.list<const GzCand>(d.at.cands), n_cands, d.list<const uint32_t>(d.at.stops), d.list<GzProbe>(d.at.recs), s);
+        });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(b.recs.data(), d.p + d.at.recs, sizeof(GzProbe) * n_cands, hipMemcpyDeviceToHost, s));
+    }
+    if (n_single) {
+        HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.single_list, b.single.data(), sizeof(uint32_t) * n_single, hipMemcpyHostToDevice, s));
+        timed(ctx, "gunzip_single", s, [&] {
+            launch_gunzip_single(d.items(), d.list<const uint32_t>(d.at.single_list), n_single, d.list<GzSingle>(d.at.single_res), s);
+        });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(b.sres.data(), d.p + d.at.single_res, sizeof(GzSingle) * n_single, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    return ZNIPPY_OK;
+}
+
+// the decode launch over the non-empty runs; the CRC launch over them and over the first member of every item of the single pass
+static int gz_decode_stage(znippy_ctx *ctx, GzBatch &b, const GzDev &d) {
+    const uint32_t n_runs = (uint32_t)b.h_runs.size(), n_crc = (uint32_t)b.crc_items.size();
+    hipStream_t s = d.s;
+    if (n_runs) {
+        HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.runs, b.h_runs.data(), sizeof(GzRun) * n_runs, hipMemcpyHostToDevice, s));
+        timed(ctx, "gunzip_inflate", s, [&] { launch_gunzip_inflate(d.items(), d.list<const GzRun>(d.at.runs), n_runs, d.list<int32_t>(d.at.run_st), s); });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(b.run_st.data(), d.p + d.at.run_st, sizeof(int32_t) * n_runs, hipMemcpyDeviceToHost, s));
+    }
+    if (n_crc) {
+        HIPCHK(ctx, hipMemcpyAsync(d.p + d.at.crc_items, b.crc_items.data(), sizeof(InflateItem) * n_crc, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(d.p + d.at.crc_st, 0, sizeof(int32_t) * n_crc, s));
+        timed(ctx, "gunzip_crc", s, [&] {
+            launch_inflate_crc(d.list<const InflateItem>(d.at.crc_items), n_crc, d.list<int32_t>(d.at.crc_st), d.list<uint32_t>(d.at.crc_got), s);
+        });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(b.crc_st.data(), d.p + d.at.crc_st, sizeof(int32_t) * n_crc, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipMemcpyAsync(b.crc_got.data(), d.p + d.at.crc_got, sizeof(uint32_t) * n_crc, hipMemcpyDeviceToHost, s));
+    }
+    if (n_runs || n_crc) HIPCHK(ctx, hipStreamSynchronize(s));
+    return ZNIPPY_OK;
+}
+
 static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n, void *d_out,
                         uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len, int32_t *status,
                         uint32_t *members, uint32_t *segments) {
@@ -3452,7 +3460,6 @@ static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, co
     if (!n) return ZNIPPY_OK;
     if (!src_off || !src_len || !out_room || !out_len || !d_src || (out_cap && !d_out)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
     if (!seg_min) {
         seg_min = gzp::SEG_MIN_DEFAULT;
@@ -3462,213 +3469,27 @@ static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, co
         }
     }
 
-    // 1) every item against the source region and the output region; its slice of the candidate list and its chunks of the scan
-    std::vector<int32_t> st(n, 0);
-    std::vector<GzItem> items;
-    std::vector<uint32_t> item_of;  // list entry -> item
-    std::vector<GzScanChunk> chunks;
-    uint64_t packed = 0, cand_total = 0;
-    bool packed_wrap = false;
-    for (uint64_t i = 0; i < n; i++) {
-        const uint64_t so = src_off[i], sl = src_len[i], room = out_room[i];
-        const bool dst_known = out_off || !packed_wrap;
-        const uint64_t dst = out_off ? out_off[i] : packed;
-        if (!out_off) { packed_wrap |= packed + room < packed; packed += room; }
-        out_len[i] = 0;
-        if (members) members[i] = 0;
-        if (segments) segments[i] = 0;
-        if (so > src_cap || sl > src_cap - so) { st[i] = ZNIPPY_E_INVAL; continue; }
-        if (!dst_known || room > out_cap || dst > out_cap - room) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
-        if (sl >= (1ull << 32) || room >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
-        if (!sl) continue;  // no member at all: nothing, as gzip.decompress(b"") gives
-        GzItem it;
-        it.src = (const uint8_t *)d_src + so;
-        it.dst = (uint8_t *)d_out + dst;
-        it.src_len = (uint32_t)sl; it.room = (uint32_t)room;
-        it.cand_base = (uint32_t)cand_total; it.cand_cap = (uint32_t)(16 + sl / 256);
-        cand_total += it.cand_cap;
-        if (cand_total > (1ull << 30) || chunks.size() + sl / GZ_SCAN_CHUNK + 1 > (1ull << 30)) return ZNIPPY_E_NOMEM;
-        for (uint64_t off = 0; off < sl; off += GZ_SCAN_CHUNK) chunks.push_back(GzScanChunk{(uint32_t)items.size(), (uint32_t)off});
-        items.push_back(it);
-        item_of.push_back((uint32_t)i);
-    }
-    const uint32_t n_items = (uint32_t)items.size();
-    if (n_items) {
-        // 2) the one allocation, then the stream.  A kept candidate list is never longer than the raw one plus byte 0 of every item
-        const size_t n_kept_max = (size_t)cand_total + n_items;
-        size_t bytes = 0;
-        auto carve = [&](size_t sz) { const size_t at = bytes; bytes += (sz + 15) & ~(size_t)15; return at; };
-        const size_t o_items = carve(sizeof(GzItem) * n_items), o_chunks = carve(sizeof(GzScanChunk) * chunks.size()),
-                     o_count = carve(sizeof(uint32_t) * n_items), o_raw = carve(sizeof(uint64_t) * cand_total),
-                     o_cands = carve(sizeof(GzCand) * n_kept_max), o_stops = carve(sizeof(uint32_t) * cand_total),
-                     o_recs = carve(sizeof(GzProbe) * n_kept_max), o_runs = carve(sizeof(GzRun) * n_kept_max),
-                     o_run_st = carve(sizeof(int32_t) * n_kept_max), o_mem = carve(sizeof(InflateItem) * n_kept_max),
-                     o_mem_st = carve(sizeof(int32_t) * n_kept_max), o_mem_crc = carve(sizeof(uint32_t) * n_kept_max),
-                     o_list = carve(sizeof(uint32_t) * n_items), o_single = carve(sizeof(GzSingle) * n_items);
+    const GzCall call{(const uint8_t *)d_src, src_cap, src_off, src_len, n, (uint8_t *)d_out, out_cap, out_off, out_room, seg_min, out_len, members, segments};
+    GzBatch b;
+    int rc;
+    if ((rc = gz_admit(call, b))) return rc;
+    if (!b.items.empty()) {
         struct Guard {
             znippy_ctx *ctx;
             uint8_t *p = nullptr;
             ~Guard() { tfree(ctx, p); }
         } g{ctx};
-        HIPCHK(ctx, tmalloc(ctx, &g.p, bytes));
-        GzItem *const d_items = (GzItem *)(g.p + o_items);
-        uint32_t *const d_count = (uint32_t *)(g.p + o_count);
-        uint64_t *const d_raw = (uint64_t *)(g.p + o_raw);
-        HIPCHK(ctx, hipMemcpyAsync(d_items, items.data(), sizeof(GzItem) * n_items, hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemcpyAsync(g.p + o_chunks, chunks.data(), sizeof(GzScanChunk) * chunks.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(ctx, hipMemsetAsync(d_count, 0, sizeof(uint32_t) * n_items, s));
-        timed(ctx, "gunzip_scan", s, [&] { launch_gunzip_scan(d_items, (const GzScanChunk *)(g.p + o_chunks), (uint32_t)chunks.size(), d_count, d_raw, s); });
-        HIPCHK(ctx, hipGetLastError());
-        std::vector<uint32_t> count(n_items);
-        HIPCHK(ctx, hipMemcpyAsync(count.data(), d_count, sizeof(uint32_t) * n_items, hipMemcpyDeviceToHost, s));
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        // 3) the candidates kept; which items are probed and which take the single pass
-        std::vector<uint64_t> raw;
-        uint64_t raw_end = 0;  // the list is copied back as far as the last item that has candidates and room for them
-        for (uint32_t k = 0; k < n_items; k++)
-            if (count[k] && count[k] <= items[k].cand_cap) raw_end = (uint64_t)items[k].cand_base + count[k];
-        if (raw_end) {
-            raw.resize(raw_end);
-            HIPCHK(ctx, hipMemcpyAsync(raw.data(), d_raw, sizeof(uint64_t) * raw_end, hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipStreamSynchronize(s));
-        }
-        std::vector<GzCand> cands;
-        std::vector<uint32_t> stops, single, probed;  // probed: the items with records, in the order of their records
-        std::vector<size_t> first_cand;               // probed[j]'s first entry of cands
-        for (uint32_t k = 0; k < n_items; k++) {
-            size_t kept = 0;
-            if (count[k] && count[k] <= items[k].cand_cap) kept = gzp::keep_candidates(raw.data() + items[k].cand_base, count[k], seg_min);
-            if (!kept) { single.push_back(k); continue; }
-            const uint64_t *c = raw.data() + items[k].cand_base;
-            probed.push_back(k);
-            first_cand.push_back(cands.size());
-            const uint32_t stop_begin = (uint32_t)stops.size();
-            for (size_t j = 0; j < kept; j++)
-                if ((c[j] & 1) == gzp::K_FLUSH) stops.push_back((uint32_t)(c[j] >> 1));
-            const uint32_t stop_end = (uint32_t)stops.size();
-            cands.push_back(GzCand{k, 0, gzp::K_MEMBER, stop_begin, stop_end, 0});
-            uint32_t next_stop = stop_begin;  // the first flush candidate behind the position
-            for (size_t j = 0; j < kept; j++) {
-                const uint32_t pos = (uint32_t)(c[j] >> 1), kind = (uint32_t)(c[j] & 1);
-                while (next_stop < stop_end && stops[next_stop] <= pos) next_stop++;
-                cands.push_back(GzCand{k, pos, kind, next_stop, stop_end, 0});
-            }
-        }
-        first_cand.push_back(cands.size());
-        const uint32_t n_cands = (uint32_t)cands.size(), n_single = (uint32_t)single.size();
-        if (n_cands > n_kept_max || stops.size() > cand_total) return ZNIPPY_E_NOMEM;  // (cannot happen: the bound above counts them)
-        std::vector<GzProbe> recs(n_cands);
-        std::vector<GzSingle> sres(n_single);
-        if (n_cands) {
-            HIPCHK(ctx, hipMemcpyAsync(g.p + o_cands, cands.data(), sizeof(GzCand) * n_cands, hipMemcpyHostToDevice, s));
-            if (!stops.empty()) HIPCHK(ctx, hipMemcpyAsync(g.p + o_stops, stops.data(), sizeof(uint32_t) * stops.size(), hipMemcpyHostToDevice, s));
-            timed(ctx, "gunzip_probe", s, [&] {
-                launch_gunzip_probe(d_items, (const GzCand *)(g.p + o_cands), n_cands, (const uint32_t *)(g.p + o_stops), (GzProbe *)(g.p + o_recs), s);
-            });
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(recs.data(), g.p + o_recs, sizeof(GzProbe) * n_cands, hipMemcpyDeviceToHost, s));
-        }
-        if (n_single) {
-            HIPCHK(ctx, hipMemcpyAsync(g.p + o_list, single.data(), sizeof(uint32_t) * n_single, hipMemcpyHostToDevice, s));
-            timed(ctx, "gunzip_single", s, [&] { launch_gunzip_single(d_items, (const uint32_t *)(g.p + o_list), n_single, (GzSingle *)(g.p + o_single), s); });
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(sres.data(), g.p + o_single, sizeof(GzSingle) * n_single, hipMemcpyDeviceToHost, s));
-        }
-        HIPCHK(ctx, hipStreamSynchronize(s));
-        // 4) the plan of every probed item; the decode launch; the CRC launch over every non-empty run and over the first member of
-        //    every item of the single pass (the CRCs of a member's runs are combined on the host: a long member is many workgroups)
-        std::vector<int32_t> item_st(n_items, 0);
-        std::vector<InflateItem> crc_items;
-        std::vector<uint32_t> crc_item_of;  // CRC launch entry -> item, for the entries that carry the CRC to compare with
-        auto crc_item = [&](uint8_t *dst, uint64_t len, bool has, uint32_t want) {
-            InflateItem it;
-            it.src = nullptr; it.dst = dst; it.src_len = 0; it.out_len = (uint32_t)len;
-            it.method = 8; it.want_crc = want; it.has_crc = has ? 1 : 0; it.pad = 0;
-            crc_items.push_back(it);
-        };
-        for (uint32_t e = 0; e < n_single; e++) {
-            const uint32_t k = single[e];
-            const GzSingle &r = sres[e];
-            item_st[k] = r.status;
-            if (r.status == 0 && (r.out_len > items[k].room || r.len0 > r.out_len)) item_st[k] = ZNIPPY_E_CORRUPT;  // (the kernel's word is checked, not trusted)
-            if (item_st[k] != 0) continue;
-            crc_item(items[k].dst, r.len0, true, r.crc0);
-            crc_item_of.push_back(k);
-        }
-        const size_t n_first = crc_items.size();
-        std::vector<gzp::Run> runs;
-        std::vector<gzp::Member> mems;
-        std::vector<gzp::ItemPlan> plans(probed.size());
-        std::vector<gzp::Probe> pr;
-        for (size_t j = 0; j < probed.size(); j++) {
-            const uint32_t k = probed[j];
-            pr.clear();
-            for (size_t c = first_cand[j]; c < first_cand[j + 1]; c++) {
-                const GzProbe &r = recs[c];
-                pr.push_back(gzp::Probe{cands[c].pos, cands[c].kind, r.data_start, r.end_kind, r.end_pos, r.status, r.out, r.reach, r.crc, r.isize, r.next});
-            }
-            gzp::plan_item(pr.data(), pr.size(), k, items[k].src_len, items[k].room, runs, mems, &plans[j]);
-            item_st[k] = plans[j].status;
-        }
-        std::vector<GzRun> h_runs;
-        std::vector<uint32_t> run_item;
-        std::vector<size_t> crc_of_run(runs.size(), 0);  // run -> its entry of the CRC launch (non-empty runs)
-        for (size_t r = 0; r < runs.size(); r++)
-            if (runs[r].out_len) {
-                h_runs.push_back(GzRun{runs[r].item, runs[r].src_start, (uint32_t)runs[r].out_off, (uint32_t)runs[r].out_len});
-                run_item.push_back(runs[r].item);
-                crc_of_run[r] = crc_items.size();
-                crc_item(items[runs[r].item].dst + runs[r].out_off, runs[r].out_len, false, 0);
-            }
-        const uint32_t n_runs = (uint32_t)h_runs.size(), n_crc = (uint32_t)crc_items.size();
-        if (n_runs > n_kept_max || n_crc > n_kept_max) return ZNIPPY_E_NOMEM;  // (cannot happen: a run per record, a first member per item at most)
-        std::vector<int32_t> run_st(n_runs, 0), crc_st(n_crc, 0);
-        std::vector<uint32_t> crc_got(n_crc, 0);
-        if (n_runs) {
-            HIPCHK(ctx, hipMemcpyAsync(g.p + o_runs, h_runs.data(), sizeof(GzRun) * n_runs, hipMemcpyHostToDevice, s));
-            timed(ctx, "gunzip_inflate", s, [&] { launch_gunzip_inflate(d_items, (const GzRun *)(g.p + o_runs), n_runs, (int32_t *)(g.p + o_run_st), s); });
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(run_st.data(), g.p + o_run_st, sizeof(int32_t) * n_runs, hipMemcpyDeviceToHost, s));
-        }
-        if (n_crc) {
-            HIPCHK(ctx, hipMemcpyAsync(g.p + o_mem, crc_items.data(), sizeof(InflateItem) * n_crc, hipMemcpyHostToDevice, s));
-            HIPCHK(ctx, hipMemsetAsync(g.p + o_mem_st, 0, sizeof(int32_t) * n_crc, s));
-            timed(ctx, "gunzip_crc", s, [&] {
-                launch_inflate_crc((const InflateItem *)(g.p + o_mem), n_crc, (int32_t *)(g.p + o_mem_st), (uint32_t *)(g.p + o_mem_crc), s);
-            });
-            HIPCHK(ctx, hipGetLastError());
-            HIPCHK(ctx, hipMemcpyAsync(crc_st.data(), g.p + o_mem_st, sizeof(int32_t) * n_crc, hipMemcpyDeviceToHost, s));
-            HIPCHK(ctx, hipMemcpyAsync(crc_got.data(), g.p + o_mem_crc, sizeof(uint32_t) * n_crc, hipMemcpyDeviceToHost, s));
-        }
-        if (n_runs || n_crc) HIPCHK(ctx, hipStreamSynchronize(s));
-        for (uint32_t r = 0; r < n_runs; r++)
-            if (run_st[r] != 0) item_st[run_item[r]] = ZNIPPY_E_CORRUPT;
-        for (size_t c = 0; c < n_first; c++)
-            if (crc_st[c] != 0 && item_st[crc_item_of[c]] == 0) item_st[crc_item_of[c]] = ZNIPPY_E_CHECKSUM;
-        for (const gzp::Member &m : mems) {
-            uint32_t crc = 0;
-            for (size_t r = m.run0; r < m.run1; r++)
-                if (runs[r].out_len) crc = gzp::crc32_combine(crc, crc_got[crc_of_run[r]], runs[r].out_len);
-            if (crc != m.crc && item_st[m.item] == 0) item_st[m.item] = ZNIPPY_E_CHECKSUM;
-        }
-        for (uint32_t e = 0; e < n_single; e++) {
-            const uint32_t k = single[e], i = item_of[k];
-            st[i] = item_st[k];
-            if (st[i] != 0) continue;
-            out_len[i] = sres[e].out_len;
-            if (members) members[i] = sres[e].members;
-            if (segments) segments[i] = 1;
-        }
-        for (size_t j = 0; j < probed.size(); j++) {
-            const uint32_t k = probed[j], i = item_of[k];
-            st[i] = item_st[k];
-            if (st[i] != 0) continue;
-            out_len[i] = plans[j].out_len;
-            if (members) members[i] = plans[j].members;
-            if (segments) segments[i] = plans[j].segments;
-        }
+        const GzLayout at = gz_layout(b);
+        HIPCHK(ctx, tmalloc(ctx, &g.p, at.bytes));
+        const GzDev d{g.p, at, ctx->stream};
+        if ((rc = gz_scan_stage(ctx, b, d))) return rc;
+        if ((rc = gz_candidates(b, seg_min))) return rc;
+        if ((rc = gz_probe_stage(ctx, b, d))) return rc;
+        if ((rc = gz_decode_plan(b))) return rc;
+        if ((rc = gz_decode_stage(ctx, b, d))) return rc;
+        gz_verdict(call, b);
     }
-    if (status) memcpy(status, st.data(), sizeof(int32_t) * n);
+    if (status) memcpy(status, b.st.data(), sizeof(int32_t) * n);
     return ZNIPPY_OK;
 }
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "host/deflate_batch.h"  // the lists of the DEFLATE batch calls
 #include "host/range_plan.h"
 #include "host/rows_plan.h"  // Tile, BigUnit and the constants the read side's host plan shares with the kernels
 
@@ -293,76 +294,26 @@ struct TreeUnit {
 void launch_round_block_entries(const TreeUnit *units, uint32_t n_units, uint32_t n_entries, const uint32_t *tile_cv, uint32_t *tree, hipStream_t s);
 
 
-// Raw DEFLATE of ZIP entries (inflate.hip, znippy_inflate_batch): one item the host has validated, decoded by one wave
-struct InflateItem {
-    const uint8_t *src;  // the compressed bytes, any alignment
-    uint8_t *dst;
-    uint32_t src_len, out_len;  // both below 4 GiB
-    uint32_t method;            // 8: DEFLATE; 0: a copy (src_len == out_len)
-    uint32_t want_crc, has_crc;
-    uint32_t pad;
-};
+// The DEFLATE batch calls (inflate.hip, targz.hip, gunzip.hip): InflateItem, TargzItem, TargzResult, GzItem, GzScanChunk, GzCand,
+// GzProbe, GzRun, GzSingle and GZ_SCAN_CHUNK are in host/deflate_batch.h, beside the host code that builds and reads the lists of them
+// (host/deflate_batch.cc), for the reason given at RangePiece above.
+// Raw DEFLATE of ZIP entries (znippy_inflate_batch): one wave per item the host has validated.
 // status[i] = 0 or ZNIPPY_E_* for every item; no byte outside [dst, dst + out_len) of any item is written
 void launch_inflate(const InflateItem *items, uint32_t n_items, int32_t *status, hipStream_t s);
 // for every item with status 0: crc_out[i] = CRC-32 of its out_len bytes; status[i] = ZNIPPY_E_CHECKSUM where has_crc and it is not want_crc
 void launch_inflate_crc(const InflateItem *items, uint32_t n_items, int32_t *status, uint32_t *crc_out, hipStream_t s);
 
-// One tar member out of gzip-compressed tars (targz.hip, znippy_targz_find_batch): one item the host has validated, decoded by one
-// wave only as far as the tar has to be read
-struct TargzItem {
-    const uint8_t *src;  // the gzip member, any alignment
-    uint8_t *scratch;    // where the tar is inflated to: 16-byte aligned, cap rounded up to 16 bytes long
-    uint32_t src_len;    // below 4 GiB
-    uint32_t cap;        // inflated bytes the item may take: 512 .. 4 GiB - 16
-    uint32_t whole;      // src is the whole file: input that ends inside the stream is damage, not "more"
-    uint32_t pad;
-};
-struct TargzResult {
-    int32_t status;    // 0 or ZNIPPY_E_*
-    uint32_t pad;
-    uint64_t off, len;  // status 0: the member is scratch[off .. off + len)
-    uint64_t scanned;   // bytes inflated
-};
+// One tar member out of gzip-compressed tars (znippy_targz_find_batch): one wave per item, decoding only as far as the tar has to be read.
 // filter: name_prefix then name_suffix, in device memory.  res[i] for every item; no byte outside [scratch, scratch + cap) is written
 void launch_targz_find(const TargzItem *items, uint32_t n_items, const uint8_t *filter, uint32_t prefix_len, uint32_t suffix_len, TargzResult *res,
                        hipStream_t s);
 
-// Whole gzip files (gunzip.hip, znippy_gunzip_batch): one item the host has validated
-struct GzItem {
-    const uint8_t *src;  // the file, any alignment
-    uint8_t *dst;        // its room
-    uint32_t src_len, room;  // both below 4 GiB
-    uint32_t cand_base, cand_cap;  // its slice of the scan's candidate list
-};
-constexpr uint32_t GZ_SCAN_CHUNK = 4096;
-struct GzScanChunk { uint32_t item, off; };  // bytes [off, off + GZ_SCAN_CHUNK) of the item: one wave of the scan
+// Whole gzip files (znippy_gunzip_batch).
 // count[i] = candidates found in item i (byte 0 not among them); the first cand_cap of them, in no order, as pos << 1 | kind
 // (0: behind 00 00 FF FF, 1: at 1F 8B 08) in cands[cand_base ..]
 void launch_gunzip_scan(const GzItem *items, const GzScanChunk *chunks, uint32_t n_chunks, uint32_t *count, uint64_t *cands, hipStream_t s);
-struct GzCand {  // one kept candidate: one wave of the probe
-    uint32_t item, pos, kind;
-    uint32_t stop0, stop1;  // stops[stop0 .. stop1): the kept flush candidates of its item behind pos, ascending
-    uint32_t pad;
-};
-struct GzProbe {  // gzp::Probe without the candidate
-    uint32_t data_start, end_kind, end_pos;
-    int32_t status;
-    uint64_t out;
-    uint32_t reach, crc, isize;
-    int32_t next;
-};
 void launch_gunzip_probe(const GzItem *items, const GzCand *cands, uint32_t n_cands, const uint32_t *stops, GzProbe *recs, hipStream_t s);
-struct GzRun {  // one wave of the decode launch
-    uint32_t item, src_start;  // the first DEFLATE byte, relative to the item's source
-    uint32_t out_off, out_len; // relative to the item's room; out_len > 0, and exact
-};
 void launch_gunzip_inflate(const GzItem *items, const GzRun *runs, uint32_t n_runs, int32_t *status, hipStream_t s);
-struct GzSingle {  // what the single pass says about an item
-    int32_t status;       // ZNIPPY_E_CHECKSUM here: an ISIZE, or the CRC-32 of a member behind the first
-    uint32_t out_len, members;
-    uint32_t crc0, len0;  // the first member's CRC-32 as its trailer has it, and its length: left to the CRC launch
-    uint32_t pad;
-};
 // list[k]: an item decoded from its first byte to its last by one wave, its members one after the other, trailers and padding checked
 void launch_gunzip_single(const GzItem *items, const uint32_t *list, uint32_t n_list, GzSingle *res, hipStream_t s);
 

@@ -194,6 +194,15 @@ uint64_t range_plan_decoded(const RrTable &t, const RangePlan &p, uint64_t dec_b
     return dec;
 }
 
+void range_cut_pieces(const uint8_t *src, uint8_t *dst, uint64_t len, std::vector<RangePiece> &pieces) {
+    uint64_t step = std::min<uint64_t>(len, RANGE_PIECE - ((uintptr_t)dst & 127));  // every later piece starts on a 128-byte line of the output
+    while (len) {
+        pieces.push_back(RangePiece{src, dst, (uint32_t)step, 0});
+        src += step; dst += step; len -= step;
+        step = std::min<uint64_t>(len, RANGE_PIECE);
+    }
+}
+
 void range_plan_pieces(const RrTable &t, const RrCall &c, RangePlan &p, const uint8_t *const pools[2], const uint8_t *d_blobs, uint8_t *d_out,
                        std::vector<RangePiece> &pieces) {
     for (uint64_t i = 0; i < c.n_ranges; i++) {
@@ -206,14 +215,7 @@ void range_plan_pieces(const RrTable &t, const RrCall &c, RangePlan &p, const ui
             if (bad) { p.st[i] = RP_E_DIGEST; continue; }
         }
         const uint8_t *src = w.comp ? pools[w.pool] + w.slot + (c.begin[i] - w.first) : d_blobs + (t.h_blob_off[w.row] - c.blob_base) + c.begin[i];
-        uint8_t *to = d_out + p.dst[i];
-        uint64_t left = c.len[i];
-        uint64_t step = std::min<uint64_t>(left, RANGE_PIECE - ((uintptr_t)to & 127));  // every later piece starts on a 128-byte line of the output
-        while (left) {
-            pieces.push_back(RangePiece{src, to, (uint32_t)step, 0});
-            src += step; to += step; left -= step;
-            step = std::min<uint64_t>(left, RANGE_PIECE);
-        }
+        range_cut_pieces(src, d_out + p.dst[i], c.len[i], pieces);
     }
 }
 

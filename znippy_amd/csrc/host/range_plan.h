@@ -122,8 +122,10 @@ uint64_t range_plan_block_items(const RrTable &t, RangePlan &p, const uint8_t *p
                                 std::vector<BlockCvItem> &items, std::vector<std::pair<uint32_t, uint32_t>> &item_of);
 // dec_blocks plus the length of every row decoded whole
 uint64_t range_plan_decoded(const RrTable &t, const RangePlan &p, uint64_t dec_blocks);
-// Failed rows and bad blocks into p.st; every good range cut into pieces of at most RANGE_PIECE bytes whose destinations, from the
-// second piece of a range on, start on a 128-byte line.
+// `len` bytes from src to dst, cut into pieces of at most RANGE_PIECE bytes whose destinations, from the second piece on, start on a
+// 128-byte line; appended to `pieces` (also the gather of znippy_targz_find_batch: deflate_batch.cc)
+void range_cut_pieces(const uint8_t *src, uint8_t *dst, uint64_t len, std::vector<RangePiece> &pieces);
+// Failed rows and bad blocks into p.st; every good range cut into pieces (range_cut_pieces).
 void range_plan_pieces(const RrTable &t, const RrCall &c, RangePlan &p, const uint8_t *const pools[2], const uint8_t *d_blobs, uint8_t *d_out,
                        std::vector<RangePiece> &pieces);
 
