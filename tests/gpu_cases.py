@@ -395,6 +395,19 @@ def write_case(oracle):
     return entries, skip, [oracle.blake3(e) for e in entries]
 
 
+def ragged_rounds():
+    """(offsets, sizes, staging bytes): many rounds of ragged sizes at unaligned offsets in one staging buffer — several chunks
+    per wave, big-unit slices, the merge kernel."""
+    rng = np.random.default_rng(5)
+    sizes = [0, 1, 5, 64, 1000, 1024, 1025, 4096, 10240, 10240, 10240, 33333, 65536, 65537, 70000, 300000,
+             0, 2, 1 << 20, 3, 999, 5 << 20, 17, 64 * 1024 * 3 + 5] + [int(x) for x in rng.integers(0, 20000, 400)]
+    offs, pos = [], 3
+    for s in sizes:
+        offs.append(pos)
+        pos += s + int(rng.integers(0, 7))
+    return offs, sizes, np.frombuffer(gen.incompressible(99, pos + 16), dtype=np.uint8)
+
+
 def periodic(period, n, seed):
     rng = np.random.default_rng(seed)
     p = rng.integers(32, 127, size=period, dtype=np.uint8).tobytes()

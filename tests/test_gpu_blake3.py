@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import gen
+from gpu_cases import ragged_rounds
 
 pytestmark = pytest.mark.gpu
 
@@ -36,14 +37,7 @@ def test_rounds_mixed_sizes_unaligned(gpu_ctx, oracle):
     packing (several chunks per wave), big-unit slices and the merge kernel."""
     import torch
     from znippy_amd import hip
-    rng = np.random.default_rng(5)
-    sizes = [0, 1, 5, 64, 1000, 1024, 1025, 4096, 10240, 10240, 10240, 33333, 65536, 65537, 70000, 300000,
-             0, 2, 1 << 20, 3, 999, 5 << 20, 17, 64 * 1024 * 3 + 5] + [int(x) for x in rng.integers(0, 20000, 400)]
-    offs, pos = [], 3
-    for s in sizes:
-        offs.append(pos)
-        pos += s + int(rng.integers(0, 7))
-    buf = np.frombuffer(gen.incompressible(99, pos + 16), dtype=np.uint8)
+    offs, sizes, buf = ragged_rounds()
     d = torch.from_numpy(buf.copy()).cuda()
     rt = hip.RoundTable(gpu_ctx, offs, sizes)
     got = rt.hash(d)

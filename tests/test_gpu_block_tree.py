@@ -13,6 +13,7 @@ import b3_tree
 import gen
 import test_gpu_ranges as tr
 from gpu_cases import foreign_archive
+from range_checks import verified_and_check
 
 pytestmark = pytest.mark.gpu
 
@@ -205,29 +206,6 @@ def test_set_authenticates(gpu_ctx, auth_rows):
 
 
 # ---- 3. verified reads return the unverified call's bytes -----------------------------------------------------------------
-
-def verified_and_check(rt, d_blobs, rows, ranges, tag, guard=37, packed=False, want=None, **kw):
-    """tr.read_and_check for the verified call: exact bytes, the sentinel everywhere else, status 0; (decoded, hashed)."""
-    lens = np.array([n for _, _, n in ranges], np.uint64)
-    at = (np.cumsum(lens) - lens).astype(np.uint64)
-    total = int(lens.sum())
-    region = tr.sentinel(guard + total + 101)
-    rr, rb = [r for r, _, _ in ranges], [b for _, b, _ in ranges]
-    if packed:
-        status, decoded, hashed = rt.read_ranges_verified(d_blobs, rr, rb, lens, region[guard:], out_cap=total, **kw)
-    else:
-        status, decoded, hashed = rt.read_ranges_verified(d_blobs, rr, rb, lens, region, out_offsets=at + np.uint64(guard), **kw)
-    assert (status == 0).all(), (tag, status)
-    expect = np.full(guard + total + 101, SENTINEL, np.uint8)
-    for (row, begin, n), a in zip(ranges, at):
-        expect[guard + int(a):guard + int(a) + n] = np.frombuffer(rows[row][begin:begin + n], np.uint8)
-    got = region.cpu().numpy()
-    if not np.array_equal(got, expect):
-        raise AssertionError((tag, "first differing byte", int(np.nonzero(got != expect)[0][0])))
-    if want is not None:
-        assert (decoded, hashed) == want, (tag, decoded, hashed, want)
-    return decoded, hashed
-
 
 @pytest.fixture(scope="module")
 def own_rows(oracle):

@@ -144,7 +144,10 @@ struct znippy_ctx {
         int store_g = 0;         // ZNIPPY_STORE_G: tiles per wave of the store path kernel (0 = from the tile count)
         bool edbg = false, no_fused_store = false, no_fork_verify = false, no_run_lanes = false, nohash = false, fz_only = false, tdbg = false, no_fuse_hash = false, trace = false, no_pack = false;
         int ktime = 2;  // per-kernel HIP events: 2 = every kernel, 1 = the dominant read kernels only, 0 = none
+        bool poison = false;  // ZNIPPY_POISON (test hook): recycled and pooled memory is filled with poison_byte before it is handed out
+        int poison_byte = 0;
     } sw;
+    int poison_hold = 0;  // ZNIPPY_POISON: > 0 inside an entry point that has refilled the pools itself (poison_enter, PoisonHold)
     int cus = 256;
     // A lean run's verify is queued on the auxiliary stream, beside the next run's role-split kernel (run_verify): decided at
     // creation from what the two kernels take of a CU — a verify that cannot be resident beside that persistent kernel would
@@ -219,6 +222,23 @@ static void read_switches(znippy_ctx *ctx) {
     ctx->sw.fz_only = on("ZNIPPY_FZ_ONLY");  // test hook: no serial fallback behind the two-phase path (what it leaves shows up as corrupt rows)
     if (const char *e = getenv("ZNIPPY_ROLES_MIN")) ctx->sw.roles_min = (unsigned)atoi(e);
     if (const char *e = getenv("ZNIPPY_KTIME")) ctx->sw.ktime = atoi(e);
+    if (const char *e = getenv("ZNIPPY_POISON")) {  // test hook: a fill byte, 0 .. 255 (decimal or 0x..; zero is a fill byte like any other), unset = off
+        char *end = nullptr;
+        const long v = strtol(e, &end, e[0] == '0' && (e[1] == 'x' || e[1] == 'X') ? 16 : 10);
+        if (*e && end && !*end && v >= 0 && v <= 255) { ctx->sw.poison = true; ctx->sw.poison_byte = (int)v; }
+    }
+}
+
+// ---- ZNIPPY_POISON (test hook) ---------------------------------------------------------------------------
+// With the switch on, no buffer reaches its user holding what its last user — or nobody — left in it: every buffer of the
+// recyclers below and every pool of the context is filled with the switch's byte first.  A result that changes with the byte,
+// or differs from a context without the switch, read something before anything wrote it.  Off: one bool tested per site.
+// The fill of a device buffer is queued on the main stream — everything that used the buffer before is ordered there by the
+// time it comes back to a recycler — and waited for: uploads into it are plain hipMemcpy, which nothing orders behind a stream.
+static hipError_t poison_dev(znippy_ctx *ctx, void *p, size_t bytes) {
+    if (!p || !bytes) return hipSuccess;
+    const hipError_t e = hipMemsetAsync(p, ctx->sw.poison_byte, bytes, ctx->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
 }
 
 static void *pinned_take(znippy_ctx *ctx, size_t bytes, size_t *cap) {
@@ -232,11 +252,13 @@ static void *pinned_take(znippy_ctx *ctx, size_t bytes, size_t *cap) {
         *cap = ctx->pinned_pool[best].first;
         ctx->pinned_pool_bytes -= *cap;
         ctx->pinned_pool.erase(ctx->pinned_pool.begin() + best);
+        if (ctx->sw.poison) memset(p, ctx->sw.poison_byte, *cap);  // (given back only once nothing queued still writes it: pinned_give's callers)
         return p;
     }
     void *p = nullptr;
     if (hipHostMalloc(&p, bytes) != hipSuccess) return nullptr;
     *cap = bytes;
+    if (ctx->sw.poison) memset(p, ctx->sw.poison_byte, *cap);
     return p;
 }
 static void pinned_give(znippy_ctx *ctx, void *p, size_t cap) {
@@ -290,7 +312,7 @@ static inline bool ctx_enter(znippy_ctx *ctx, EnterKind kind = ENTER_WORK) {
 // Device memory of the tables (index columns, plans, per-run scratch) comes from a per-context pool: a table is
 // built and torn down per hand-off in the host pipelines, and ~15 hipMalloc + hipFree pairs cost more than the
 // kernels of a small hand-off.  Nothing in a table relies on fresh memory: every array is either uploaded, reset by
-// the run (memset) or written before it is read.
+// the run (memset) or written before it is read (DESIGN.md §3a lists which, array by array; ZNIPPY_POISON tests it).
 template <class T>
 static hipError_t tmalloc(znippy_ctx *ctx, T **out, size_t bytes) {
     bytes = std::max<size_t>(bytes, 16);
@@ -304,14 +326,14 @@ static hipError_t tmalloc(znippy_ctx *ctx, T **out, size_t bytes) {
         ctx->dev_sizes[*out] = ctx->dev_pool[best].first;
         ctx->dev_pool_bytes -= ctx->dev_pool[best].first;
         ctx->dev_pool.erase(ctx->dev_pool.begin() + best);
-        return hipSuccess;
+        return ctx->sw.poison ? poison_dev(ctx, *out, ctx->dev_sizes[*out]) : hipSuccess;  // (the whole capacity, not only `bytes`)
     }
     void *p = nullptr;
     const hipError_t e = hipMalloc(&p, bytes);
     if (e != hipSuccess) return e;
     *out = (T *)p;
     ctx->dev_sizes[p] = bytes;
-    return hipSuccess;
+    return ctx->sw.poison ? poison_dev(ctx, p, bytes) : hipSuccess;
 }
 static void tfree(znippy_ctx *ctx, void *p) {
     if (!p) return;
@@ -642,6 +664,14 @@ static int dev_upload(znippy_ctx *ctx, T **d, const T *h, size_t n) {
 static int ensure_decoder(znippy_ctx *ctx) {
     if (ctx->lit_scratch) return ZNIPPY_OK;
     if (hipMalloc(&ctx->lit_scratch, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
+    if (ctx->sw.poison) (void)poison_dev(ctx, ctx->lit_scratch, decode_lit_scratch_bytes(ctx->decode_grid));
+    return ZNIPPY_OK;
+}
+// the block-item launches' literal scratch (they run beside the general decoder): made by the first run or range call that has block items
+static int ensure_decoder_b(znippy_ctx *ctx) {
+    if (ctx->lit_scratch_b) return ZNIPPY_OK;
+    if (hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) { (void)hipGetLastError(); ctx->lit_scratch_b = nullptr; return ZNIPPY_E_NOMEM; }
+    if (ctx->sw.poison) (void)poison_dev(ctx, ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid));
     return ZNIPPY_OK;
 }
 // One grow-only pool of the context (sizes: host/rows_plan.h): when `want` is more than it holds, the main stream is waited for
@@ -662,6 +692,8 @@ static bool pool_grow(znippy_ctx *ctx, std::initializer_list<PoolBuf> bufs, uint
             return false;
         }
     *cap = want;
+    if (ctx->sw.poison)
+        for (const PoolBuf &b : bufs) (void)poison_dev(ctx, *b.p, b.bytes);
     return true;
 }
 // the two-phase path's pools; without one of them the serial decoder keeps the frames
@@ -710,8 +742,48 @@ static int ensure_encoder(znippy_ctx *ctx) {
         if (ctx->enc_tabs) { (void)hipFree(ctx->enc_tabs); ctx->enc_tabs = nullptr; }
         return ZNIPPY_E_NOMEM;
     }
+    if (ctx->sw.poison) (void)poison_dev(ctx, ctx->enc_seq, (size_t)ctx->encode_grid * MAX_SEQ * 3 * 4);
     return ZNIPPY_OK;
 }
+
+// ZNIPPY_POISON: every pool and scratch buffer of the context filled again, at the start of an entry point that queues a run or a
+// batch call — after everything the context has queued anywhere has ended (a debug mode: the runs of a pipeline no longer
+// overlap; their results may not change).  A call made from inside another one (the private runs of a range read, the runs
+// behind the single-chunk shims' staging) finds the hold set and leaves the pools as the outer call has them.
+// Kept, because they are written once and read by every later run:
+//  - the predefined tables at the head of bx_fse_pool (BX_POOL_FIRST cells, uploaded when the pool is made or grown);
+//  - enc_tabs (uploaded when the encoder's scratch is made) — not in the list at all;
+//  - shim_in / shim_out: the single-chunk shims stage the caller's bytes there BEFORE the run they queue (filled when allocated only);
+//  - clk_buf and diag[]: diagnostics that add up over launches, zeroed where they are made.
+// Everything else a run or call finds in a pool it must have written itself (DESIGN.md §3a lists who does).
+static int poison_pools(znippy_ctx *ctx) {
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, lanes_sync(ctx));
+    if (ctx->aux) HIPCHK(ctx, hipStreamSynchronize(ctx->aux));
+    if (ctx->copy) HIPCHK(ctx, hipStreamSynchronize(ctx->copy));
+    const size_t lit = decode_lit_scratch_bytes(ctx->decode_grid), head = sizeof(uint16_t) * BX_POOL_FIRST;
+    const struct { void *p; size_t from, bytes; } pools[] = {
+        {ctx->lit_scratch, 0, lit}, {ctx->lit_scratch_b, 0, lit},
+        {ctx->fz_lit_pool, 0, (size_t)ctx->fz_lit_cap}, {ctx->fz_seq_pool, 0, (size_t)ctx->fz_seq_cap * 8},
+        {ctx->bx_fse_pool, head, (size_t)ctx->bx_fse_cap * 2}, {ctx->bx_huf_pool, 0, (size_t)ctx->bx_huf_cap * 2},
+        {ctx->rx_pool, 0, (size_t)ctx->rx_cap * 4}, {ctx->rx_chunk, 0, (size_t)(ctx->rx_cap / 1024) * 4}, {ctx->rx_cdone, 0, (size_t)(ctx->rx_cap / 1024)},
+        {ctx->vs_pool, 0, (size_t)ctx->vs_cap}, {ctx->rr_pool[0], 0, (size_t)ctx->rr_cap[0]}, {ctx->rr_pool[1], 0, (size_t)ctx->rr_cap[1]},
+        {ctx->enc_seq, 0, (size_t)ctx->encode_grid * MAX_SEQ * 3 * 4}, {ctx->enc_prov, 0, ctx->enc_prov_cap}, {ctx->ldm, 0, 4 * ctx->ldm_cap},
+        {ctx->cursor, 0, 64},
+    };
+    for (const auto &b : pools)
+        if (b.p && b.bytes > b.from) HIPCHK(ctx, hipMemsetAsync((uint8_t *)b.p + b.from, ctx->sw.poison_byte, b.bytes - b.from, ctx->stream));
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return ZNIPPY_OK;
+}
+static inline int poison_enter(znippy_ctx *ctx) { return ctx->sw.poison && !ctx->poison_hold ? poison_pools(ctx) : ZNIPPY_OK; }
+struct PoisonHold {  // the scope of an entry point whose inner calls must find the pools as it left them
+    znippy_ctx *ctx;
+    explicit PoisonHold(znippy_ctx *c) : ctx(c->sw.poison ? c : nullptr) { if (ctx) ctx->poison_hold++; }
+    ~PoisonHold() { if (ctx) ctx->poison_hold--; }
+    PoisonHold(const PoisonHold &) = delete;
+    PoisonHold &operator=(const PoisonHold &) = delete;
+};
 
 // rows of a front-to-back table arrive as two 32-bit size columns (zn_rows_pack32): the four 64-bit columns the kernels read
 // are made here — sizes widened, offsets = first offset + running sum (per 1,024 rows: sums, their scan, fill)
@@ -946,6 +1018,7 @@ int znippy_ctx_create(int device, void *hip_stream, znippy_ctx **out) {
         znippy_ctx_destroy(ctx);
         return ZNIPPY_E_NOMEM;
     }
+    if (ctx->sw.poison) (void)poison_dev(ctx, ctx->cursor, 64);
     {
         hipDeviceProp_t p;
         int cus = hipGetDeviceProperties(&p, device) == hipSuccess ? p.multiProcessorCount : 256;
@@ -1514,6 +1587,11 @@ static int run_clear(znippy_ctx *ctx, znippy_rows *r, const RunPlan &p, const Ro
     else HIPCHK(ctx, hipMemsetAsync(r->ctl, 0, r->ctl_bytes, s));
     // (the second hash pass looks at small tiles only when rows were handed over)
     if (p.small_off) HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)r->hand(H_FUSED), (int)r->shape.n, 1, s));
+    // ZNIPPY_FZ_ONLY (test hook): a row the parallel paths leave is never decoded and never hashed, and k_verify compares whatever its
+    // digest slot holds — in a recycled buffer, or in memory a context of the same process gave back, that can be the row's own right
+    // digest of an earlier table, and the row came back verified.  Cleared, the slot never equals a checksum: the row is corrupt, as
+    // the hook promises.  (With the serial decoder in place every row with a status >= 0 is hashed: nothing to clear.)
+    if (ctx->sw.fz_only && r->shape.n) HIPCHK(ctx, hipMemsetAsync(r->digests, 0, 32 * (size_t)r->shape.n, s));
     return ZNIPPY_OK;
 }
 
@@ -1907,7 +1985,7 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
         if (!rc && ctx->batch_checksums && !r->bx_cand_ck && tmalloc(ctx, &r->bx_cand_ck, 4 * (size_t)r->shape.bx_slots) != hipSuccess) rc = ZNIPPY_E_NOMEM;
     }
     if (rc) return rc;
-    if (r->shape.n_cand && !ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) return ZNIPPY_E_NOMEM;
+    if (r->shape.n_cand && ensure_decoder_b(ctx)) return ZNIPPY_E_NOMEM;
     if (r->run_seq && rows_route_hint(r->hints, plain) < 0 && r->shape.n) {  // a run of this table has finished meanwhile?
         const unsigned last = (unsigned)((r->run_seq - 1) & 1);
         const bool last_plain = r->run_args[last].plain;  // (a decode-only run teaches the table's own hints nothing)
@@ -1946,6 +2024,7 @@ static int rows_launch(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uin
 static void rows_abandon(znippy_ctx *ctx, znippy_rows *r);
 static int rows_queue(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs, uint64_t blob_base, void *d_out, uint64_t out_cap, bool verify, bool plain = false) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
     bool queued = false;
     const int rc = rows_launch(ctx, r, d_blobs, blob_base, d_out, out_cap, (unsigned)(r->run_seq & 1), verify, plain, &queued);
     if (rc && queued) rows_abandon(ctx, r);
@@ -2028,6 +2107,7 @@ static int rows_settle(znippy_ctx *ctx, znippy_rows *r, unsigned slot) {
     HIPCHK(ctx, lanes_sync(ctx));                 // the latest run's kernel may be queued there
     HIPCHK(ctx, hipStreamSynchronize(ctx->aux));  // the latest run's verify may be queued there
     rows_force_full(r->hints);
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
     const unsigned latest = (unsigned)((r->run_seq - 1) & 1);
     const unsigned order[2] = {slot, latest};
     for (int i = 0; i < (slot == latest ? 1 : 2); i++) {
@@ -2265,7 +2345,7 @@ struct RangeBufs {  // the buffers of one call; every return gives them back
 static int range_slab_make(znippy_ctx *ctx, const RrTable &t, const RangePlan &p, RangeBufs &b) {
     const size_t bytes = range_slab_layout(p, &b.up_bytes);
     if (!(b.h_slab = (uint8_t *)pinned_take(ctx, bytes + 64, &b.h_cap)) || tmalloc(ctx, &b.slab, bytes) != hipSuccess) return ZNIPPY_E_NOMEM;
-    if (!ctx->lit_scratch_b && hipMalloc(&ctx->lit_scratch_b, decode_lit_scratch_bytes(ctx->decode_grid)) != hipSuccess) { (void)hipGetLastError(); ctx->lit_scratch_b = nullptr; return ZNIPPY_E_NOMEM; }
+    if (ensure_decoder_b(ctx)) return ZNIPPY_E_NOMEM;
     range_slab_bind(b.h_slab, p, b.h);
     range_slab_bind(b.slab, p, b.d);
     range_slab_fill(t, p, b.h_slab);
@@ -2347,6 +2427,8 @@ static int rows_read_ranges(znippy_ctx *ctx, znippy_rows *r, const void *d_blobs
     if (!rc && verified) rc = rows_host_checksum(ctx, r);
     if (rc) return rc;
     ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
+    const PoisonHold hold(ctx);  // (the private runs below decode into the range scratch beside what the block pass left there)
 
     // the plan: every range validated, the distinct rows, their routes and slots — then the scratch and the block pass's slab
     const RrTable t = rows_table_view(r);
@@ -2426,6 +2508,8 @@ static int rows_block_tree_build(znippy_ctx *ctx, znippy_rows *r, const void *d_
     if (!n_entries) return ZNIPPY_OK;
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
+    const PoisonHold hold(ctx);
 
     // 1) the rows with entries against the blob region; a slot in the scratch for every compressed one — sized before anything is queued
     const RrTable t = rows_table_view(r);
@@ -2714,6 +2798,7 @@ int znippy_hash_rounds(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, uin
     if (!ctx || !r || r->ctx != ctx || !digests || (r->n && !d_src)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
     const ResSlab res = r->dev(r->slot);
     int rc = hash_rounds_async(ctx, r, res, d_src);
     if (rc) return rc;
@@ -2730,6 +2815,7 @@ static int shim_reserve(znippy_ctx *ctx, size_t in_need, size_t out_need) {
         size_t cap = std::max<size_t>(in_need + 64, 1 << 16);
         HIPCHK(ctx, hipMalloc(&ctx->shim_in, cap));
         ctx->shim_in_cap = cap;
+        if (ctx->sw.poison) HIPCHK(ctx, poison_dev(ctx, ctx->shim_in, cap));
     }
     if (out_need > ctx->shim_out_cap || !ctx->shim_out) {
         if (ctx->shim_out) (void)hipFree(ctx->shim_out);
@@ -2737,6 +2823,7 @@ static int shim_reserve(znippy_ctx *ctx, size_t in_need, size_t out_need) {
         size_t cap = std::max<size_t>(out_need + 64, 1 << 16);
         HIPCHK(ctx, hipMalloc(&ctx->shim_out, cap));
         ctx->shim_out_cap = cap;
+        if (ctx->sw.poison) HIPCHK(ctx, poison_dev(ctx, ctx->shim_out, cap));
     }
     return ZNIPPY_OK;
 }
@@ -2813,6 +2900,7 @@ static bool ensure_ldm(znippy_ctx *ctx, znippy_rounds *r) {
         ctx->ldm = nullptr; ctx->ldm_cap = 0;
         if (hipMalloc(&ctx->ldm, 4 * r->ldm_entries) != hipSuccess) { (void)hipGetLastError(); ctx->ldm = nullptr; return false; }
         ctx->ldm_cap = r->ldm_entries;
+        if (ctx->sw.poison) (void)poison_dev(ctx, ctx->ldm, 4 * r->ldm_entries);
     }
     if (!r->d_ldm) {
         std::vector<uint64_t> desc(r->n, LDM_NONE);
@@ -2987,6 +3075,7 @@ static int rounds_launch(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, v
         ctx->enc_prov = nullptr; ctx->enc_prov_cap = 0;
         HIPCHK(ctx, hipMalloc(&ctx->enc_prov, r->prov_bytes + 64));
         ctx->enc_prov_cap = r->prov_bytes + 64;
+        if (ctx->sw.poison) HIPCHK(ctx, poison_dev(ctx, ctx->enc_prov, ctx->enc_prov_cap));
     }
     const EncPlan p = enc_plan(rounds_shape(r), env);
     // the alignment and the tree switch are this run's values: a later znippy_rounds_set_blob_align / _emit_block_tree does not reach it
@@ -3018,6 +3107,7 @@ static void rounds_abandon(znippy_ctx *ctx, znippy_rounds *r, unsigned slot) {
 }
 static int rounds_queue(znippy_ctx *ctx, znippy_rounds *r, const void *d_src, void *d_blob_out, uint64_t blob_cap) {
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
     const unsigned slot = (unsigned)(r->run_seq & 1);
     bool queued = false;
     const int rc = rounds_launch(ctx, r, d_src, d_blob_out, blob_cap, slot, &queued);
@@ -3269,6 +3359,7 @@ static int inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, c
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
 
     InflateBatch b;
     inflate_admit(InflateCall{(const uint8_t *)d_src, src_cap, src_off, src_len, method, (uint8_t *)d_out, out_cap, out_off, out_len, crc32, n}, b);
@@ -3317,6 +3408,7 @@ static int targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
     HIPCHK(ctx, hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
 
     const TargzCall call{(const uint8_t *)d_src, src_cap, src_off, src_len, whole, n, scan_cap, (uint8_t *)d_out, out_cap, out_off, out_len, scanned};
     TargzBatch b;
@@ -3461,6 +3553,7 @@ static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, co
     if (!src_off || !src_len || !out_room || !out_len || !d_src || (out_cap && !d_out)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
     if (!seg_min) {
         seg_min = gzp::SEG_MIN_DEFAULT;
         if (const char *e = getenv("ZNIPPY_GZ_SEG_MIN")) {
