@@ -27,6 +27,8 @@
  *                                over a batch of tarballs       the tar to the first .../Cargo.toml); sdists: znippy-plugin-python/src/native.rs:L17-21
  *   znippy_gunzip_batch          lgz::decompress_gz             znippy-common/src/plugins/wasm_loader.rs (host_decompress codec 1,
  *                                over a batch of files          tar_gz_list_entries): the gunzip of a whole file
+ *   znippy_bunzip2_batch         lbzip2 (host_decompress 2)     znippy-common/src/plugins/wasm_loader.rs:L18-31,L213-221 (codec 2),
+ *                                over a batch of files          L410-441 (tar.bz2): the bunzip2 of a whole file
  *
  * Codec wire format: one standard Zstandard frame (RFC 8878) per chunk.  (The reference's
  * OpenZL framing cannot be reproduced or checked offline — see DESIGN.md "Oracle".)
@@ -397,8 +399,8 @@ int znippy_inflate_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, c
  * the first .../Cargo.toml; znippy-plugin-python/src/native.rs:L17-21 lists .tar.gz sdists beside wheels).  Such files sit in the archive as
  * stored gzip streams.  A tar has no directory — where a member lies is known only while the stream is inflated — so this call decodes
  * each stream only until the tar it produces answers the question: "the filter happens before any decompression work"
- * (TODO_NOW.md:L200-213) becomes "stop the moment the answer is known".  Plain .tar, bzip2 / xz tarballs and multi-member gzip are out of
- * scope.
+ * (TODO_NOW.md:L200-213) becomes "stop the moment the answer is known".  Plain .tar, xz tarballs and multi-member gzip are out of
+ * scope; a bzip2 tarball is decompressed whole by znippy_bunzip2_batch, which finds no member.
  *   d_src, src_cap     DEVICE: the region that holds the files; item i is the gzip member d_src[src_off[i] .. + src_len[i])
  *   whole              HOST, optional (NULL: every item is whole): 0 = item i is only the head of its file
  *   name_prefix/suffix the filter, compared as bytes as in znippy_zip_find_entry: the first regular member (typeflag '0', '\0', '7') in
@@ -486,10 +488,81 @@ int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
  * items launches no probe.  The same wave takes, member by member, an item whose candidates outnumber its slice of the list
  * (16 + src_len / 256), so that no result depends on which candidates could be kept.
  * Out of scope: decoding dependent pieces in parallel from their predecessors' last 32 KiB, guessing block boundaries inside streams
- * without flush points, bzip2 and xz, and listing tar members. */
+ * without flush points, xz, and listing tar members.  bzip2 files: znippy_bunzip2_batch below. */
 int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
                         void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len,
                         int32_t *status, uint32_t *members, uint32_t *segments);
+
+/* ---- whole bzip2 files the engine already holds --------------------------------------------------------------------------------
+ * The bunzip2 of the reference's ingest side: host_decompress codec 2 and the tar.bz2 archive format of host_archive_open
+ * (znippy-common/src/plugins/wasm_loader.rs:L18-31, L213-221, L410-441; design.md: "Bzip2 | lbzip2-rs | workers per core"): .bz2
+ * files, .tar.bz2 / .tbz / .tbz2 source tarballs and older sdists, planet.osm.bz2 (TODO_NOW.md:L158, L400-407), all of which sit in the
+ * archive as stored rows.  bzip2 blocks are independent: lbzip2 finds them by their 48-bit magic at any bit offset and decodes them
+ * in parallel, and so does this call, a wave or a workgroup per block.
+ *   d_src, src_cap     DEVICE: the region that holds the files; item i is the whole file d_src[src_off[i] .. + src_len[i])
+ *   d_out, out_cap     DEVICE: item i's content goes to d_out[out_off[i] .. + out_room[i]), its room
+ *   out_off            HOST, optional (NULL: the rooms lie back to back in array order)
+ *   out_room           HOST: the bytes item i may produce.  bzip2 names the content's size nowhere: measure mode says it
+ *   slot_cap           the most candidate blocks decoded per pass (below).  0 = the default: what fits a scratch budget of 1 GiB,
+ *                      which ZNIPPY_BZ_SCRATCH_MB (a decimal number of MiB) replaces for every call.  A slot holds one block in front
+ *                      of and behind the inverse BWT and its successor array: about 5 x level x 100,000 bytes are in use, and since the
+ *                      level of a candidate ahead of the chain is not known when it is decoded every slot is sized for level 9
+ *                      (6 x 900,000 bytes).  If not one slot fits the budget the call returns ZNIPPY_E_NOMEM with nothing queued.
+ *                      No result depends on slot_cap.
+ *   out_len            HOST out: bytes produced; 0 for every status but 0
+ *   status             HOST, optional: per item, see below
+ *   streams            HOST out, optional: bzip2 streams decoded (status 0)
+ *   blocks             HOST out, optional: blocks decoded (status 0)
+ * Measure mode: with d_out NULL and out_cap 0 nothing is written and out_room is not read; out_len[i] is the size the content has
+ * (reported for status 0 only).  Statuses are as below, except that no CRC is checked and ZNIPPY_E_DST_SMALL cannot occur.
+ * Per item, with Python's bz2.decompress as arbiter for everything it accepts: the content of all streams, concatenated; an item of
+ * no bytes has no stream and no content (status 0).
+ * Streams: the first must start with "BZh" and a digit 1-9, else ZNIPPY_E_CORRUPT.  Behind a stream's end (the end magic
+ * 0x177245385090, the combined CRC, padding to a byte) a rest that starts with the three bytes "BZh" is another stream and is judged
+ * like the first; any other rest, zeros included, is ignored, as the bzip2 tool and the arbiter do.  One stated deviation: the
+ * arbiter silently drops a damaged later stream; this call reports it.
+ * Blocks: a randomised block is ZNIPPY_E_UNSUPPORTED (no writer has set that bit since 0.9.5).  ZNIPPY_E_CORRUPT: input that ends
+ * early; origPtr >= the block length; nGroups outside 2..6; nSelectors 0; a selector MTF index >= nGroups; a code length outside
+ * 1..20 during the delta walk; an over-subscribed code, or a bit pattern no code has; a run (RUNA/RUNB) or a symbol count beyond
+ * level x 100,000; a block of no symbols (or no used byte); the selectors running out; a block not followed by either magic.
+ * nSelectors above 18002 is accepted, as bzip2 1.0.8 does: the surplus is read and discarded.  A block whose last bytes are four
+ * equal ones without their count is accepted (the arbiter refuses it; no writer produces it).
+ * Room and checksums: more content than out_room is ZNIPPY_E_DST_SMALL.  Every block's CRC (the bzip2 CRC-32: polynomial 0x04C11DB7,
+ * MSB first), computed on the device from the bytes written, is compared with its header, and every stream's combined CRC
+ * (c = rotl(c, 1) ^ block_crc) with its trailer: a mismatch on an otherwise clean item is ZNIPPY_E_CHECKSUM.  The first failure in
+ * stream order decides the status.
+ * Host validation and ZNIPPY_E_INVAL exactly as znippy_gunzip_batch (required: src_off, src_len, out_len, and out_room unless in
+ * measure mode; d_src, and d_out when out_cap > 0); a room not inside out_cap is ZNIPPY_E_DST_SMALL; a src_len or room of 4 GiB or
+ * more is ZNIPPY_E_UNSUPPORTED.  n == 0 is ZNIPPY_OK.  The call returns ZNIPPY_OK whatever the items report.
+ * Writes: no byte of d_out outside the room of an item is written; inside the room of an item whose status is not 0 the bytes are
+ * unspecified; rooms must not overlap (not checked).  A damaged file is a status, never a fault, a hang or a stray write.
+ * Not a run, and synchronous on the context's stream, exactly as znippy_gunzip_batch; no table is touched; both allocations (the
+ * lists: about 1.5 bytes per source byte; the slots) are made before the first stream operation, and ZNIPPY_POISON fills both.
+ * Stages (csrc/bunzip2.hip, csrc/host/bz_plan.h; znippy_last_kernel_times: bunzip2_scan, bunzip2_decode, bunzip2_walk,
+ * bunzip2_expand, bunzip2_crc — only those that were launched; decode to crc once per pass):
+ *   scan     a wave covers 4 KiB of source: every bit position where the block magic 0x314159265359 starts goes to the candidate
+ *            list.  The magic overlaps itself only at a shift of 45 bits, so an item holds at most 8 x src_len / 45 + 1 of them:
+ *            the list is that long and has no overflow path.
+ *   decode   one wave per job of the pass.  A stream header: "BZh", the level, the magic behind it.  A candidate block: CRC, origPtr,
+ *            used-byte map, selectors, code lengths, then the symbols in groups of 50 (Huffman, RUNA/RUNB, MTF) into the slot; it
+ *            records the length, the bit where the block ended, the magic there and, behind an end magic, the combined CRC and the
+ *            byte behind the padding.  The chain of symbols is serial.
+ *   walk     one workgroup per block that decoded: the successor array by a stable counting sort over 32 slices; the chain from
+ *            origPtr followed sublist by sublist (splitter list ranking: every node whose index is a multiple of the spacing, 256,
+ *            which ZNIPPY_BZ_SPLIT replaces, starts a sublist); a chain that closes early (periodic input) is walked once and
+ *            repeated; then the lengths of the final run-length step, slice by slice.
+ *   plan     (host) walks each item's chain of records from the first stream header: a candidate counts only if the block in front
+ *            of it ended exactly at its bit, an end magic leads to the next stream header or to the end.  Candidates the chain has
+ *            passed are dropped undecoded.  No record is trusted: each is checked against the item and the chain.  It assigns the
+ *            output offsets, folds the combined CRC and chooses the next pass's up to slot_cap candidates in position order.
+ *   expand   one workgroup per block landed on: four equal bytes, then a count of 0..251 — into its final place, never beyond the
+ *            block's exact byte count.  The state does not cross blocks.
+ *   crc      one workgroup per block landed on, over the bytes written.
+ * Out of scope: finding or listing tar members inside .tar.bz2, parallel Huffman decoding inside a block, randomised blocks, any
+ * bzip2 encoder, xz. */
+int znippy_bunzip2_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
+                         void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t slot_cap, uint64_t *out_len,
+                         int32_t *status, uint32_t *streams, uint32_t *blocks);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,

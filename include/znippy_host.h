@@ -211,6 +211,21 @@ int znippy_archive_extract_tar_members(znippy_archive *a, const char *const *rel
  * ZNIPPY_E_INVAL. */
 int znippy_archive_gunzip_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap,
                                 uint64_t *entry_off /* n_files + 1 */, int32_t *status);
+/* For every archived file of relative_paths (each a bzip2 file: a .bz2, a .tar.bz2 / .tbz / .tbz2 source tarball or older sdist): its
+ * whole content, all streams concatenated — what the reference's host_decompress (codec 2) does per file through lbzip2
+ * (znippy-common/src/plugins/wasm_loader.rs:L18-31, L213-221), on the read side and for all files at once.  The files are gathered
+ * whole on the device — one range-read pass whose result is not copied to the host.  bzip2 names the content's size nowhere, so the
+ * znippy_bunzip2_batch of include/znippy_hip.h runs twice on them there: in measure mode, which gives every file's room, then into
+ * those rooms, blocks decoded in parallel, every block CRC and combined CRC checked.  Only the contents come back to the host.
+ * Results as in znippy_archive_gunzip_files: file i at dst[entry_off[i] .. entry_off[i + 1]), of length 0 when its status is not 0.
+ * status (optional), per file: 0; ZNIPPY_E_INVAL an unknown path; ZNIPPY_E_UNSUPPORTED a file or a content of 4 GiB or more; the
+ * per-item codes of that call (ZNIPPY_E_CORRUPT — a file that is no bzip2 file too —, ZNIPPY_E_CHECKSUM, ZNIPPY_E_UNSUPPORTED);
+ * ZNIPPY_E_DST_SMALL when cap does not hold it (the files in front of it are unaffected); a chunk's decode error.  An empty file has
+ * no stream and no content.  With dst NULL and cap 0 only the measuring call is made: entry_off holds the offsets the clean files
+ * would get, so entry_off[n_files] is the cap that holds them all, and no CRC has been looked at.  The call returns ZNIPPY_OK
+ * whatever the files report; NULL arguments give ZNIPPY_E_INVAL.  Members of the tar inside a .tar.bz2 are not listed or found. */
+int znippy_archive_bunzip2_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap,
+                                 uint64_t *entry_off /* n_files + 1 */, int32_t *status);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

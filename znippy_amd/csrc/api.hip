@@ -3591,3 +3591,142 @@ extern "C" int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t 
                                    int32_t *status, uint32_t *members, uint32_t *segments) {
     ZN_NO_THROW(gunzip_batch(ctx, d_src, src_cap, src_off, src_len, n, d_out, out_cap, out_off, out_room, seg_min, out_len, status, members, segments))
 }
+
+// ---- whole bzip2 files (znippy_bunzip2_batch) ---------------------------------------------------------
+// The items that pass bz_admit are scanned for block magics; bz_start sorts the candidates into the items' chains; then passes of at
+// most n_slots jobs: bzp::choose names them, decode and walk leave a record each, bzp::advance walks the chains over the records,
+// and the blocks landed on are expanded into the rooms and checksummed (not in measure mode) before the next pass reuses the slots.
+// Two device allocations, both sized from the source lengths and the slot count and made before anything is queued: the lists, and
+// the slots.
+static_assert(BZ_OK == ZNIPPY_OK && BZ_E_INVAL == ZNIPPY_E_INVAL && BZ_E_NOMEM == ZNIPPY_E_NOMEM && BZ_E_DST_SMALL == ZNIPPY_E_DST_SMALL &&
+              BZ_E_CORRUPT == ZNIPPY_E_CORRUPT && BZ_E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED && BZ_E_CHECKSUM == ZNIPPY_E_CHECKSUM,
+              "host/bz_plan.h gives out the codes of znippy_hip.h");
+
+struct BzDev {  // the list allocation and where its lists are, and the slots
+    uint8_t *p;
+    size_t items, chunks, count, raw, jobs, recs, lands, crc, bytes;
+    size_t jobs_cap, n_slots;  // entries of jobs and recs; of lands, crc and the slots
+    uint8_t *slots;
+    template <typename T>
+    T *list(size_t off) const { return (T *)(p + off); }
+};
+
+static int bz_scan_stage(znippy_ctx *ctx, BzBatch &b, const BzDev &d, hipStream_t s) {
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.items, b.items.data(), sizeof(BzItem) * b.items.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.chunks, b.chunks.data(), sizeof(BzChunk) * b.chunks.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(d.p + d.count, 0, 16, s));
+    timed(ctx, "bunzip2_scan", s, [&] {
+        launch_bunzip2_scan(d.list<const BzItem>(d.items), d.list<const BzChunk>(d.chunks), (uint32_t)b.chunks.size(), d.list<uint32_t>(d.count),
+                            d.list<uint64_t>(d.raw), (uint32_t)b.cand_total, s);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    uint32_t count = 0;
+    HIPCHK(ctx, hipMemcpyAsync(&count, d.p + d.count, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    const size_t n_raw = (size_t)std::min<uint64_t>(count, b.cand_total);
+    b.raw.resize(n_raw);
+    if (n_raw) {
+        HIPCHK(ctx, hipMemcpyAsync(b.raw.data(), d.p + d.raw, sizeof(uint64_t) * n_raw, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+    }
+    bz_start(b, n_raw);
+    return ZNIPPY_OK;
+}
+
+// one pass: the jobs up, decode and walk, the records back; the chains; what landed expanded and checksummed
+static int bz_pass(znippy_ctx *ctx, BzBatch &b, const BzDev &d, uint32_t split, hipStream_t s) {
+    const uint32_t n_jobs = (uint32_t)b.jobs.size();
+    if (b.jobs.size() > d.jobs_cap) return ZNIPPY_E_NOMEM;  // (cannot happen: bzp::choose gives out n_slots block jobs and a header job per item at the most)
+    for (const BzJob &j : b.jobs)
+        if (j.slot >= d.n_slots) return ZNIPPY_E_NOMEM;     // (likewise)
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.jobs, b.jobs.data(), sizeof(BzJob) * n_jobs, hipMemcpyHostToDevice, s));
+    timed(ctx, "bunzip2_decode", s, [&] { launch_bunzip2_decode(d.list<const BzItem>(d.items), d.list<const BzJob>(d.jobs), n_jobs, d.list<BzRec>(d.recs), d.slots, s); });
+    HIPCHK(ctx, hipGetLastError());
+    timed(ctx, "bunzip2_walk", s, [&] { launch_bunzip2_walk(d.list<const BzJob>(d.jobs), n_jobs, d.list<BzRec>(d.recs), d.slots, split, s); });
+    HIPCHK(ctx, hipGetLastError());
+    b.recs.resize(n_jobs);
+    HIPCHK(ctx, hipMemcpyAsync(b.recs.data(), d.p + d.recs, sizeof(BzRec) * n_jobs, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    b.lands.clear();
+    bzp::advance(b.chains, b.jobs, b.first_job, b.recs.data(), b.lands);
+    const uint32_t n_lands = (uint32_t)b.lands.size();
+    if (n_lands > d.n_slots) return ZNIPPY_E_NOMEM;  // (cannot happen: a chain lands on a block job of the pass at most once)
+    if (n_lands) {  // (never in measure mode)
+        HIPCHK(ctx, hipMemcpyAsync(d.p + d.lands, b.lands.data(), sizeof(BzLand) * n_lands, hipMemcpyHostToDevice, s));
+        timed(ctx, "bunzip2_expand", s, [&] { launch_bunzip2_expand(d.list<const BzItem>(d.items), d.list<const BzLand>(d.lands), n_lands, d.slots, s); });
+        HIPCHK(ctx, hipGetLastError());
+        timed(ctx, "bunzip2_crc", s, [&] { launch_bunzip2_crc(d.list<const BzItem>(d.items), d.list<const BzLand>(d.lands), n_lands, d.list<uint32_t>(d.crc), s); });
+        HIPCHK(ctx, hipGetLastError());
+        b.got_crc.resize(n_lands);
+        HIPCHK(ctx, hipMemcpyAsync(b.got_crc.data(), d.p + d.crc, sizeof(uint32_t) * n_lands, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        bzp::fold_crc(b.chains, b.lands, b.got_crc.data());
+    }
+    return ZNIPPY_OK;
+}
+
+static int bunzip2_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n, void *d_out,
+                         uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t slot_cap, uint64_t *out_len, int32_t *status,
+                         uint32_t *streams, uint32_t *blocks) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
+    if (!n) return ZNIPPY_OK;
+    const bool measure = !d_out && !out_cap;
+    if (!src_off || !src_len || (!measure && !out_room) || !out_len || !d_src || (out_cap && !d_out)) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
+    uint64_t budget = BZ_SCRATCH_DEFAULT;
+    if (const char *e = getenv("ZNIPPY_BZ_SCRATCH_MB")) {
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (v) budget = std::min<unsigned long long>(v, 1ull << 30) << 20;
+    }
+    uint32_t split = BZ_SPLIT_DEFAULT;
+    if (const char *e = getenv("ZNIPPY_BZ_SPLIT")) {
+        const unsigned long long v = strtoull(e, nullptr, 10);
+        if (v) split = (uint32_t)std::min<unsigned long long>(v, 0xFFFFFFFFull);
+    }
+
+    const BzCall call{(const uint8_t *)d_src, src_cap, src_off, src_len, n, (uint8_t *)d_out, out_cap, out_off, out_room, out_len, streams, blocks};
+    BzBatch b;
+    int rc;
+    if ((rc = bz_admit(call, b))) return rc;
+    if (!b.items.empty()) {
+        const size_t n_slots = bz_slots(b, slot_cap, budget);
+        if (!n_slots) return ZNIPPY_E_NOMEM;  // not one slot fits the budget: nothing has been queued
+        struct Guard {
+            znippy_ctx *ctx;
+            uint8_t *p = nullptr, *slots = nullptr;
+            ~Guard() { tfree(ctx, p); tfree(ctx, slots); }
+        } g{ctx};
+        BzDev d{};
+        auto carve = [&d](size_t sz) { const size_t at = d.bytes; d.bytes += (sz + 15) & ~(size_t)15; return at; };
+        d.items = carve(sizeof(BzItem) * b.items.size());
+        d.chunks = carve(sizeof(BzChunk) * b.chunks.size());
+        d.count = carve(16);
+        d.raw = carve(sizeof(uint64_t) * b.cand_total);
+        d.jobs_cap = bz_jobs_max(b, n_slots);
+        d.jobs = carve(sizeof(BzJob) * d.jobs_cap);
+        d.recs = carve(sizeof(BzRec) * d.jobs_cap);
+        d.lands = carve(sizeof(BzLand) * n_slots);
+        d.crc = carve(sizeof(uint32_t) * n_slots);
+        HIPCHK(ctx, tmalloc(ctx, &g.p, d.bytes));
+        HIPCHK(ctx, tmalloc(ctx, &g.slots, n_slots * BZ_SLOT_BYTES));
+        d.p = g.p;
+        d.slots = g.slots;
+        d.n_slots = n_slots;
+        hipStream_t s = ctx->stream;
+        if ((rc = bz_scan_stage(ctx, b, d, s))) return rc;
+        while (bzp::choose(b.chains, n_slots, b.jobs, b.first_job))
+            if ((rc = bz_pass(ctx, b, d, split, s))) return rc;
+        bz_verdict(call, b);
+    }
+    if (status) memcpy(status, b.st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" int znippy_bunzip2_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
+                                    void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t slot_cap, uint64_t *out_len,
+                                    int32_t *status, uint32_t *streams, uint32_t *blocks) {
+    ZN_NO_THROW(bunzip2_batch(ctx, d_src, src_cap, src_off, src_len, n, d_out, out_cap, out_off, out_room, slot_cap, out_len, status, streams, blocks))
+}

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include "host/bz_plan.h"        // the lists of znippy_bunzip2_batch
 #include "host/deflate_batch.h"  // the lists of the DEFLATE batch calls
 #include "host/range_plan.h"
 #include "host/rows_plan.h"  // Tile, BigUnit and the constants the read side's host plan shares with the kernels
@@ -316,5 +317,18 @@ void launch_gunzip_probe(const GzItem *items, const GzCand *cands, uint32_t n_ca
 void launch_gunzip_inflate(const GzItem *items, const GzRun *runs, uint32_t n_runs, int32_t *status, hipStream_t s);
 // list[k]: an item decoded from its first byte to its last by one wave, its members one after the other, trailers and padding checked
 void launch_gunzip_single(const GzItem *items, const uint32_t *list, uint32_t n_list, GzSingle *res, hipStream_t s);
+
+// Whole bzip2 files (znippy_bunzip2_batch, bunzip2.hip): BzItem, BzChunk, BzJob, BzRec, BzLand, BzSlice and the layout of a slot are
+// in host/bz_plan.h.  `scratch` is n_slots x BZ_SLOT_BYTES; a job or landed block names its slot.
+// *count = starts of the block magic found; each as item << 36 | bit in cands[0 .. min(*count, cap)), in no order
+void launch_bunzip2_scan(const BzItem *items, const BzChunk *chunks, uint32_t n_chunks, uint32_t *count, uint64_t *cands, uint32_t cap, hipStream_t s);
+// recs[j] for every job (all of it but out_len); a block's bytes in front of the inverse BWT into its slot
+void launch_bunzip2_decode(const BzItem *items, const BzJob *jobs, uint32_t n_jobs, BzRec *recs, uint8_t *scratch, hipStream_t s);
+// for every block job with status 0: the inverse BWT into the slot's out area, the slice table and recs[j].out_len
+void launch_bunzip2_walk(const BzJob *jobs, uint32_t n_jobs, BzRec *recs, uint8_t *scratch, uint32_t split, hipStream_t s);
+// every landed block's final run-length step into its place; no byte outside [dst + out_off, dst + out_off + out_len) is written
+void launch_bunzip2_expand(const BzItem *items, const BzLand *lands, uint32_t n_lands, const uint8_t *scratch, hipStream_t s);
+// crc[l] = the bzip2 CRC-32 of the bytes of landed block l
+void launch_bunzip2_crc(const BzItem *items, const BzLand *lands, uint32_t n_lands, uint32_t *crc, hipStream_t s);
 
 }  // namespace zn

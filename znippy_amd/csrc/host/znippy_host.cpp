@@ -1773,7 +1773,99 @@ static int znippy_archive_gunzip_files_impl(znippy_archive *a, const char *const
     return ZNIPPY_OK;
 }
 
+// ---- the content of archived bzip2 files (znippy_archive_bunzip2_files) --------------------------
+// The files are gathered whole on the device (one range read, no copy to the host).  bzip2 names no size anywhere, so
+// znippy_bunzip2_batch runs twice there: in measure mode, which gives every file's room, then into those rooms.  Only the contents
+// come back to the host.
+static int znippy_archive_bunzip2_files_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
+                                             int32_t *status) {
+    if (!a || !entry_off || (n_files && !paths) || (cap && !dst)) return fail(ZNIPPY_E_INVAL, "null argument");
+    const size_t n = (size_t)n_files;
+    const bool sizes_only = !dst && !cap;  // the sizes of the contents alone: entry_off as if every clean file had been written
+    std::vector<int32_t> st(n, 0);
+    std::vector<FileRange> req;
+    std::vector<size_t> who;
+    std::vector<uint64_t> fsize(n, 0), measured(n, 0);
+    const IndexView view = a->ix.view();
+    for (size_t i = 0; i < n; i++) {
+        auto it = paths[i] ? a->files.find(paths[i]) : a->files.end();
+        if (it == a->files.end()) { st[i] = ZNIPPY_E_INVAL; continue; }
+        for (uint64_t r : it->second) fsize[i] += view.row_len(r);
+        if (fsize[i] >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
+        who.push_back(i);
+        req.push_back(FileRange{&it->second, 0, fsize[i]});
+    }
+    int rc = archive_ctx(a);
+    if (rc) return rc;
+    std::vector<std::vector<uint8_t>> content(n);
+    if (!who.empty()) {
+        std::vector<uint64_t> at;
+        std::vector<int32_t> rst;
+        uint64_t total = 0;
+        if ((rc = read_file_ranges(a, req, nullptr, &at, &rst, &total))) return rc;
+        ReadBufs &bufs = a->bufs;
+        std::vector<size_t> todo;  // indexes into who
+        std::vector<uint64_t> s_off, s_len;
+        for (size_t k = 0; k < who.size(); k++) {
+            if (rst[k]) { st[who[k]] = rst[k]; continue; }
+            todo.push_back(k);
+            s_off.push_back(at[k]); s_len.push_back(fsize[who[k]]);
+        }
+        std::vector<uint64_t> o_room(todo.size(), 0), o_len(todo.size(), 0);
+        std::vector<int32_t> ist(todo.size(), 0);
+        uint64_t out_total = 0;
+        if (!todo.empty()) {
+            rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), nullptr, 0, nullptr, nullptr, 0, o_room.data(),
+                                      ist.data(), nullptr, nullptr);
+            if (rc) return fail(rc, std::string("bunzip2 (measure) failed: ") + znippy_last_error(a->ctx));
+            for (size_t j = 0; j < todo.size(); j++) {
+                if (ist[j] != 0) { st[who[todo[j]]] = ist[j]; o_room[j] = 0; }  // (this status stands; the file takes no room in the second call)
+                if (o_room[j] >= (1ull << 32)) { st[who[todo[j]]] = ZNIPPY_E_UNSUPPORTED; o_room[j] = 0; }
+                out_total += o_room[j];
+            }
+            if (sizes_only) {
+                for (size_t j = 0; j < todo.size(); j++) measured[who[todo[j]]] = o_room[j];
+                todo.clear();
+            }
+        }
+        if (!todo.empty()) {
+            if (!bufs.d_blobs.reserve(out_total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");  // (the chunks in it have been gathered from)
+            rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), bufs.d_blobs.p, out_total, nullptr, o_room.data(), 0,
+                                      o_len.data(), ist.data(), nullptr, nullptr);
+            if (rc) return fail(rc, std::string("bunzip2 failed: ") + znippy_last_error(a->ctx));
+            if (!bufs.blob_pin.reserve(out_total + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+            if (out_total && hipMemcpy(bufs.blob_pin.p, bufs.d_blobs.p, out_total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+            uint64_t o = 0;
+            for (size_t j = 0; j < todo.size(); j++) {
+                const size_t i = who[todo[j]];
+                if (st[i] == 0) st[i] = ist[j];
+                if (st[i] == 0) content[i].assign(bufs.blob_pin.p + o, bufs.blob_pin.p + o + o_len[j]);
+                o += o_room[j];
+            }
+        }
+    }
+    // the contents, packed in file order; one that does not fit is left out and the ones behind it may still fit
+    uint64_t cursor = 0;
+    for (size_t i = 0; i < n; i++) {
+        entry_off[i] = cursor;
+        if (st[i]) continue;
+        if (sizes_only) { cursor += measured[i]; continue; }
+        const uint64_t len = content[i].size();
+        if (len > cap - cursor) { st[i] = ZNIPPY_E_DST_SMALL; continue; }
+        if (len) std::memcpy((uint8_t *)dst + cursor, content[i].data(), (size_t)len);
+        cursor += len;
+    }
+    entry_off[n] = cursor;
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
 extern "C" {
+
+int znippy_archive_bunzip2_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
+                                 int32_t *status) {
+    return guarded([&] { return znippy_archive_bunzip2_files_impl(a, relative_paths, n_files, dst, cap, entry_off, status); });
+}
 
 int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
                                        const char *name_suffix, void *dst, size_t cap, uint64_t *entry_off, int32_t *status) {

@@ -229,6 +229,41 @@ class Context:
                                              np_ptr(mem), np_ptr(seg)), "znippy_gunzip_batch")
         return status[:n], oo[:n], ol[:n], mem[:n], seg[:n]
 
+    # ---- whole bzip2 files held in device memory ----
+    def bunzip2_batch(self, d_src, src_off, src_len, d_out, out_room, out_off=None, slot_cap=0, src_cap=None, out_cap=None):
+        """znippy_bunzip2_batch: item i is the whole bzip2 file d_src[src_off[i] .. + src_len[i]); the content of all its streams goes
+        to d_out + out_off[i] (None: the rooms lie back to back in array order) and may take out_room[i] bytes (bunzip2_sizes says
+        how many it needs).  Blocks are found by their magic and decoded in parallel, at most slot_cap per pass (0: what fits the
+        scratch budget); every block CRC and combined CRC is checked.  Synchronous and not a run.  Returns (status per item: 0 or
+        ZNIPPY_E_*, out_off, out_len — 0 unless the status is 0 —, streams, blocks)."""
+        so, sl, room = as_np(src_off, np.uint64), as_np(src_len, np.uint64), as_np(out_room, np.uint64)
+        n = len(so)
+        assert len(sl) == n and len(room) == n and (out_off is None or len(out_off) == n), "item arrays differ in length"
+        oo = as_np(out_off, np.uint64) if out_off is not None else np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.uint64)
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ol = np.zeros(max(n, 1), dtype=np.uint64)
+        streams, blocks = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        self._chk(self.L.znippy_bunzip2_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), n, _dptr(d_out), int(out_cap),
+                                              np_ptr(oo) if out_off is not None else None, np_ptr(room), int(slot_cap), np_ptr(ol), np_ptr(status),
+                                              np_ptr(streams), np_ptr(blocks)), "znippy_bunzip2_batch")
+        return status[:n], oo[:n], ol[:n], streams[:n], blocks[:n]
+
+    def bunzip2_sizes(self, d_src, src_off, src_len, slot_cap=0, src_cap=None):
+        """znippy_bunzip2_batch in measure mode (no output buffer): nothing is written and no CRC is checked.  Returns (status per
+        item, the size each item's content has — 0 unless the status is 0 —, streams, blocks)."""
+        so, sl = as_np(src_off, np.uint64), as_np(src_len, np.uint64)
+        n = len(so)
+        assert len(sl) == n, "item arrays differ in length"
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ol = np.zeros(max(n, 1), dtype=np.uint64)
+        streams, blocks = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        self._chk(self.L.znippy_bunzip2_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), n, None, 0, None, None, int(slot_cap),
+                                              np_ptr(ol), np_ptr(status), np_ptr(streams), np_ptr(blocks)), "znippy_bunzip2_batch")
+        return status[:n], ol[:n], streams[:n], blocks[:n]
+
 
 def get_decompressed_size(frame) -> int:
     a = np.frombuffer(frame, dtype=np.uint8)

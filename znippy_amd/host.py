@@ -29,7 +29,7 @@ class _ME(C.Structure):
 HOST_EXPORTS = [
     "znippy_host_last_error", "znippy_compress_stream", "znippy_stream_send", "znippy_stream_send_packed", "znippy_stream_finish",
     "znippy_compress_dir", "znippy_decompress_archive", "znippy_archive_open", "znippy_archive_file_count", "znippy_archive_file_size",
-    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
+    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_archive_bunzip2_files", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
     "znippy_index_manifest_len", "znippy_index_manifest_entry", "znippy_index_row", "znippy_index_metadata",
     "znippy_index_close", "znippy_interpret_footer", "znippy_write_manifest_bytes",
 ]
@@ -63,6 +63,8 @@ def lib():
         L.znippy_archive_extract_zip_entries.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, vp, C.c_size_t, vp, vp]
         L.znippy_archive_extract_tar_members.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, vp, C.c_size_t, vp, vp]
         L.znippy_archive_gunzip_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
+        if hasattr(L, "znippy_archive_bunzip2_files"):  # (a library built before the call existed still loads)
+            L.znippy_archive_bunzip2_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
         L.znippy_zip_end_of_directory.argtypes = [vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.znippy_zip_find_entry.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, vp]
         L.znippy_zip_local_data_offset.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64)]
@@ -323,6 +325,27 @@ class ZnippyArchive:
                 break
             todo, room = again, min(8 * room, most)
         return out, status
+
+    def bunzip2_files(self, paths, cap=None):
+        """The whole content of every archived bzip2 file of `paths` (.bz2, .tar.bz2, .tbz, .tbz2), all streams concatenated,
+        decoded on the device in one batch: the files are gathered there whole, a measuring pass gives their rooms (bzip2 names no
+        size), then their blocks are decoded in parallel and every block CRC and combined CRC is checked.  cap: bytes of the result
+        buffer.  None: the sizes are measured first (a call without a buffer) and the buffer holds exactly the clean files.  Returns
+        (list of bytes, or None where the status is not 0; statuses)."""
+        paths = [str(p) for p in paths]
+        n = len(paths)
+        arr = (C.c_char_p * n)(*[p.encode() for p in paths])
+        off = np.zeros(n + 1, dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        if cap is None:
+            _chk(lib().znippy_archive_bunzip2_files(self.h, arr, n, None, 0, off.ctypes.data_as(vp), st.ctypes.data_as(vp)), "bunzip2_files")
+            cap = int(off[n])
+        room = int(cap)
+        buf = np.empty(max(room, 1), dtype=np.uint8)
+        _chk(lib().znippy_archive_bunzip2_files(self.h, arr, n, buf.ctypes.data_as(vp), room, off.ctypes.data_as(vp),
+                                                st.ctypes.data_as(vp)), "bunzip2_files")
+        out = [buf[int(off[i]):int(off[i + 1])].tobytes() if st[i] == 0 else None for i in range(n)]
+        return out, [int(v) for v in st[:n]]
 
     def block_tree_stats(self):
         """[entries loaded from the sidecar `<path>.b3t` at open, chunks whose sidecar entries were accepted, chunks whose
