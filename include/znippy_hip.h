@@ -488,7 +488,7 @@ int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
  * items launches no probe.  The same wave takes, member by member, an item whose candidates outnumber its slice of the list
  * (16 + src_len / 256), so that no result depends on which candidates could be kept.
  * Out of scope: decoding dependent pieces in parallel from their predecessors' last 32 KiB, guessing block boundaries inside streams
- * without flush points, xz, and listing tar members.  bzip2 files: znippy_bunzip2_batch below. */
+ * without flush points, xz.  bzip2 files: znippy_bunzip2_batch below; listing the members of the tar inside: znippy_tar_list_batch. */
 int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
                         void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len,
                         int32_t *status, uint32_t *members, uint32_t *segments);
@@ -558,11 +558,75 @@ int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, co
  *   expand   one workgroup per block landed on: four equal bytes, then a count of 0..251 — into its final place, never beyond the
  *            block's exact byte count.  The state does not cross blocks.
  *   crc      one workgroup per block landed on, over the bytes written.
- * Out of scope: finding or listing tar members inside .tar.bz2, parallel Huffman decoding inside a block, randomised blocks, any
- * bzip2 encoder, xz. */
+ * Out of scope: parallel Huffman decoding inside a block, randomised blocks, any bzip2 encoder, xz.  The members of the tar inside a
+ * .tar.bz2 are listed by znippy_tar_list_batch below, from the decompressed bytes. */
 int znippy_bunzip2_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
                          void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t slot_cap, uint64_t *out_len,
                          int32_t *status, uint32_t *streams, uint32_t *blocks);
+
+/* ---- the members of tars held in device memory ------------------------------------------ */
+#ifndef ZNIPPY_TAR_MEMBER_DEFINED
+#define ZNIPPY_TAR_MEMBER_DEFINED
+/* one regular member of a tar (znippy_tar_list_batch, znippy_tar_list_members) */
+typedef struct {
+    uint64_t header_off, data_off, size; /* relative to the tar's first byte: its header, its bytes */
+    uint64_t name_off;                   /* its name: name_len bytes at this offset of the names buffer, not terminated */
+    uint64_t out_off;                    /* its bytes in the packed output */
+    uint32_t name_len, typeflag;         /* typeflag: '0', 0 or '7' */
+} znippy_tar_member;
+#endif
+/* Every regular member of n tars — what the reference's tar_entries_from_bytes (wasm_loader.rs, host_archive_open formats 1 and 2)
+ * returns for a decompressed .tar.gz / .tar.bz2 — listed and, where wanted, extracted on the device.
+ * Item i is the tar d_tar[tar_off[i] .. + tar_len[i]) (DEVICE, any alignment; below 4 GiB each): a plain tar, or what
+ * znippy_gunzip_batch / znippy_bunzip2_batch made of a compressed one.  Listed are the members of typeflag '0', '\0' (unless the name
+ * field ends with '/': a V7 directory) and '7', in stream order, whose name starts with name_prefix and ends with name_suffix (bytes,
+ * compared as such; empty = all; the filter of znippy_targz_find_batch).  The name is the pending GNU 'L' name or pax path= (of several
+ * in front of one member the first), else prefix "/" name, else name.  'g' and 'K' entries are stepped over; one zero block is stepped
+ * over, two end the tar, and so does the end of the item's bytes at a header boundary with no name pending (csrc/tar_list_rules.h).
+ *   members      HOST, members_cap entries.  The matching members of item i are members[member_first[i] .. member_first[i + 1]);
+ *                header_off, data_off and size are relative to the item's first byte.
+ *   names        HOST, names_cap bytes: the names, packed in member order, not terminated
+ *   d_out        DEVICE, out_cap bytes, or NULL with out_cap 0: the members' bytes, packed in member order at out_off (without d_out,
+ *                out_off says where they would stand)
+ *   member_first HOST, n + 1.   names_bytes, out_bytes: HOST, the bytes of names and of d_out the listed members take
+ *   status       HOST, optional: 0 or ZNIPPY_E_* per item
+ * Measure mode: members NULL with members_cap 0 (names and d_out NULL as well).  Nothing is written but member_first, *names_bytes
+ * and *out_bytes, which are what a full call with caps that hold everything reports.
+ * Per item: ZNIPPY_E_CORRUPT — a block on the chain from byte 0 that is neither zero nor a valid header (checksum, unsigned or
+ * signed), a size field that is no number, a header, payload or member (with its padding) that crosses the item's end, a pending
+ * name with no member behind it, a malformed pax record.  ZNIPPY_E_UNSUPPORTED — a GNU sparse member, an 'L' / 'x' payload above
+ * 8 KiB, an item of 4 GiB or more, and the two deviations from `tarfile`: (1) a pax size= record that differs from the size field
+ * of the member behind it (one that equals it is accepted; writers emit a differing one only for members of 8 GiB and more);
+ * (2) more than 64 extended headers ('L', 'x', 'X', 'g', 'K') in a row with no member or zero block between them (writers emit
+ * four at most; the bound keeps the emit stage's look back short whatever the input is).  A wrong offset is never listed.  ZNIPPY_E_DST_SMALL — the item's members, names or contents no longer fit a cap: the item takes no room,
+ * and items behind it may still fit.  ZNIPPY_E_INVAL — the item does not lie inside tar_cap.  An item with a status lists no member
+ * (the reference's `.ok()?`).  A tar nested in a member, headers behind the two zero blocks and member data that looks like a header
+ * are judged and never reached: they add nothing.
+ * The call returns ZNIPPY_OK whatever the items report; n == 0 is ZNIPPY_OK.  ZNIPPY_E_INVAL: NULL member_first, names_bytes,
+ * out_bytes, tar_off, tar_len or d_tar, a cap without its buffer, a filter string of 64 KiB or more, measure mode with names or d_out.
+ * Writes: no entry of members, byte of names or byte of d_out outside what member_first, *names_bytes and *out_bytes report.
+ * Not a run, and synchronous on the context's stream, exactly as znippy_gunzip_batch; no table is touched; the allocations (the
+ * per-block lists: about 37 bytes per 512-byte block; staging for records, names and gather pieces, bounded by the caps) are made
+ * before the first stream operation, and ZNIPPY_POISON fills them.
+ * Stages (csrc/tar_list.hip, csrc/host/tar_list_plan.h; znippy_last_kernel_times: tar_scan, tar_chain, tar_emit, tar_emit_write,
+ * tar_gather — only those that were launched):
+ *   scan     a half-wave per 512-byte block, 16 bytes a lane: zero test and checksum by a reduction, and for a block whose checksum
+ *            holds the header's kind, size and successor (an 'L' / 'x' / 'X' header with its payload).  A dense record per block:
+ *            no overflow path.  Terminals — the first of two zero blocks, no header, unsupported, a step past the end — lead to
+ *            themselves.
+ *   chain    rounds of pointer doubling over all blocks of all items: a marked block marks the target of its jump pointer, and the
+ *            jump pointers square.  The number of rounds is ceil(log2(blocks of the largest item + 1)), whatever the tars hold.
+ *   emit     every marked member header looks back over the extended headers directly in front of it for its name and for a
+ *            differing size=; the first failing block in stream order is the item's status; members that pass the filter are counted
+ *            (prefix sums over chunks of 256 blocks).  The host turns the totals into statuses and room (caps), and a second launch
+ *            writes records and names to staging lists.  The host checks every record against its item before it reaches the caller
+ *            or becomes a piece of the gather: no device record is trusted.
+ *   gather   the contents, by the range reads' gather, only with d_out. */
+int znippy_tar_list_batch(znippy_ctx *ctx, const void *d_tar, uint64_t tar_cap, const uint64_t *tar_off, const uint64_t *tar_len, uint64_t n,
+                          const char *name_prefix, uint64_t prefix_len, const char *name_suffix, uint64_t suffix_len,
+                          znippy_tar_member *members, uint64_t members_cap, char *names, uint64_t names_cap,
+                          void *d_out, uint64_t out_cap, uint64_t *member_first /* n + 1 */, uint64_t *names_bytes, uint64_t *out_bytes,
+                          int32_t *status);
 
 /* ---- (2)+(4) batch encode + hash over Rounds -------------------------------------------- */
 /* A Round is (offset,len,skip) into one staging buffer (slotpool.rs:L39-47,

@@ -223,9 +223,42 @@ int znippy_archive_gunzip_files(znippy_archive *a, const char *const *relative_p
  * ZNIPPY_E_DST_SMALL when cap does not hold it (the files in front of it are unaffected); a chunk's decode error.  An empty file has
  * no stream and no content.  With dst NULL and cap 0 only the measuring call is made: entry_off holds the offsets the clean files
  * would get, so entry_off[n_files] is the cap that holds them all, and no CRC has been looked at.  The call returns ZNIPPY_OK
- * whatever the files report; NULL arguments give ZNIPPY_E_INVAL.  Members of the tar inside a .tar.bz2 are not listed or found. */
+ * whatever the files report; NULL arguments give ZNIPPY_E_INVAL.  The members of the tar inside a .tar.bz2 are listed and extracted
+ * by znippy_archive_list_tar_members below. */
 int znippy_archive_bunzip2_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap,
                                  uint64_t *entry_off /* n_files + 1 */, int32_t *status);
+#ifndef ZNIPPY_TAR_MEMBER_DEFINED
+#define ZNIPPY_TAR_MEMBER_DEFINED
+/* one regular member of a tar (include/znippy_hip.h: znippy_tar_list_batch) */
+typedef struct {
+    uint64_t header_off, data_off, size; /* relative to the tar's first byte: its header, its bytes */
+    uint64_t name_off;                   /* its name: name_len bytes at this offset of the names buffer, not terminated */
+    uint64_t out_off;                    /* its bytes in the packed output */
+    uint32_t name_len, typeflag;         /* typeflag: '0', 0 or '7' */
+} znippy_tar_member;
+#endif
+/* For every archived file of relative_paths (a .tar, a .tar.gz / .tgz / .crate, a .tar.bz2 / .tbz2): every regular member of the tar
+ * in it whose name starts with name_prefix and ends with name_suffix (either may be NULL or empty) — what the reference's
+ * host_archive_open formats 1 and 2 (wasm_loader.rs: tar_gz_list_entries, tar_bz2_list_entries) return through
+ * tar_entries_from_bytes and host_archive_list / host_archive_entry then serve, for all files at once.  The files are gathered whole
+ * on the device — one range-read pass whose result is not copied to the host; only the first three and the last four bytes of each
+ * come back at this point.  Each goes by its first bytes: 1f 8b through
+ * znippy_gunzip_batch, with rooms from ISIZE and the retry rule of znippy_archive_gunzip_files; "BZh" through znippy_bunzip2_batch,
+ * in measure mode and then for the decode; anything else is taken as a plain tar.  One znippy_tar_list_batch of include/znippy_hip.h then
+ * lists all the tars there.  Only the member tables and the names come back to the host, and the members' contents when dst is given.
+ * Results as in that call: the members of file i are members[member_first[i] .. member_first[i + 1]) (member_first: n_files + 1
+ * values; offsets relative to the decompressed tar), their names packed in names, their contents packed in dst at out_off;
+ * *names_bytes and *out_bytes say how much of names and dst they take.  With members NULL and members_cap 0 (names and dst NULL too)
+ * the tars are only measured: member_first, *names_bytes and *out_bytes are what a call with caps that hold everything reports.
+ * status (optional), per file: 0; ZNIPPY_E_INVAL an unknown path; ZNIPPY_E_UNSUPPORTED a file or a tar of 4 GiB or more; the
+ * decoders' codes (ZNIPPY_E_CORRUPT, ZNIPPY_E_CHECKSUM, ZNIPPY_E_UNSUPPORTED); the codes of znippy_tar_list_batch: ZNIPPY_E_CORRUPT —
+ * a file that is no tar too —, ZNIPPY_E_UNSUPPORTED, ZNIPPY_E_DST_SMALL when a cap does not hold the file's members, names or
+ * contents: the files in front of it are unaffected and the ones behind it may still fit; a chunk's decode error.  A file with a
+ * status lists no member.  The two deviations from `tarfile` are that call's (include/znippy_hip.h).  The call returns ZNIPPY_OK whatever the files report; NULL arguments give ZNIPPY_E_INVAL. */
+int znippy_archive_list_tar_members(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,
+                                    const char *name_suffix, znippy_tar_member *members, uint64_t members_cap, char *names,
+                                    uint64_t names_cap, void *dst, size_t cap, uint64_t *member_first /* n_files + 1 */,
+                                    uint64_t *names_bytes, uint64_t *out_bytes, int32_t *status);
 void znippy_archive_close(znippy_archive *a);
 
 /* ---- index / container ---- */

@@ -3730,3 +3730,115 @@ extern "C" int znippy_bunzip2_batch(znippy_ctx *ctx, const void *d_src, uint64_t
                                     int32_t *status, uint32_t *streams, uint32_t *blocks) {
     ZN_NO_THROW(bunzip2_batch(ctx, d_src, src_cap, src_off, src_len, n, d_out, out_cap, out_off, out_room, slot_cap, out_len, status, streams, blocks))
 }
+
+// ---- the members of tars (znippy_tar_list_batch) -------------------------------------------------------
+// The items that pass tl_admit are scanned block by block, the chains from their first blocks are marked in tl_rounds rounds, and
+// the marked members are judged and counted; tl_place turns the totals into statuses and room; the write launch leaves records and
+// names in staging lists, which tl_accept checks record by record on their way to the caller; the gather moves the contents.  One
+// device allocation (tl_layout) and the staging lists, all sized from the item lengths and the caps and made before anything is queued.
+static_assert(TL_OK == ZNIPPY_OK && TL_E_INVAL == ZNIPPY_E_INVAL && TL_E_NOMEM == ZNIPPY_E_NOMEM && TL_E_DST_SMALL == ZNIPPY_E_DST_SMALL &&
+              TL_E_CORRUPT == ZNIPPY_E_CORRUPT && TL_E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED, "host/tar_list_plan.h gives out the codes of znippy_hip.h");
+
+static int tar_list_batch(znippy_ctx *ctx, const void *d_tar, uint64_t tar_cap, const uint64_t *tar_off, const uint64_t *tar_len, uint64_t n,
+                          const char *name_prefix, uint64_t prefix_len, const char *name_suffix, uint64_t suffix_len, znippy_tar_member *members,
+                          uint64_t members_cap, char *names, uint64_t names_cap, void *d_out, uint64_t out_cap, uint64_t *member_first,
+                          uint64_t *names_bytes, uint64_t *out_bytes, int32_t *status) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
+    if (!member_first || !names_bytes || !out_bytes || (prefix_len && !name_prefix) || (suffix_len && !name_suffix) || prefix_len >= TL_FILTER_MAX ||
+        suffix_len >= TL_FILTER_MAX || (members_cap && !members) || (names_cap && !names) || (out_cap && !d_out))
+        return ZNIPPY_E_INVAL;
+    const bool measure = !members;
+    if (measure && (names || d_out)) return ZNIPPY_E_INVAL;
+    if (!n) { member_first[0] = 0; *names_bytes = *out_bytes = 0; return ZNIPPY_OK; }
+    if (!tar_off || !tar_len || !d_tar) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
+
+    const TlCall call{(const uint8_t *)d_tar, tar_cap, tar_off, tar_len, n, members, members_cap, names, names_cap, (uint8_t *)d_out, out_cap,
+                      member_first, names_bytes, out_bytes};
+    TlBatch b;
+    int rc;
+    if ((rc = tl_admit(call, b))) return rc;
+    const uint32_t n_items = (uint32_t)b.items.size(), n_chunks = (uint32_t)b.chunks.size(), n_nodes = (uint32_t)b.n_nodes;
+    if (n_items) {
+        struct Guard {
+            znippy_ctx *ctx;
+            uint8_t *p = nullptr; znippy_tar_member *recs = nullptr; char *names = nullptr; RangePiece *pieces = nullptr;
+            ~Guard() { tfree(ctx, p); tfree(ctx, recs); tfree(ctx, names); tfree(ctx, pieces); }
+        } g{ctx};
+        const TlLayout at = tl_layout(b, prefix_len + suffix_len);
+        size_t cap_recs, cap_names, cap_pieces;
+        if ((rc = tl_staging(call, b, &cap_recs, &cap_names, &cap_pieces))) return rc;
+        std::vector<uint8_t> filter(prefix_len + suffix_len + 16, 0);
+        if (prefix_len) memcpy(filter.data(), name_prefix, prefix_len);
+        if (suffix_len) memcpy(filter.data() + prefix_len, name_suffix, suffix_len);
+        std::vector<znippy_tar_member> h_recs;
+        std::vector<char> h_names;
+        // every allocation, then the stream
+        HIPCHK(ctx, tmalloc(ctx, &g.p, at.bytes));
+        if (!measure) {
+            HIPCHK(ctx, tmalloc(ctx, &g.recs, sizeof(znippy_tar_member) * cap_recs));
+            HIPCHK(ctx, tmalloc(ctx, &g.names, cap_names));
+            if (cap_pieces) HIPCHK(ctx, tmalloc(ctx, &g.pieces, sizeof(RangePiece) * cap_pieces));
+            h_recs.resize(cap_recs);
+            h_names.resize(cap_names);
+        }
+        auto list = [&g](size_t off) { return g.p + off; };
+        const TlItem *d_items = (const TlItem *)list(at.items);
+        const TlChunk *d_chunks = (const TlChunk *)list(at.chunks);
+        TlNode *d_nodes = (TlNode *)list(at.nodes);
+        uint32_t *jump[2] = {(uint32_t *)list(at.jump_a), (uint32_t *)list(at.jump_b)};
+        HIPCHK(ctx, hipMemcpyAsync(list(at.items), b.items.data(), sizeof(TlItem) * n_items, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(list(at.chunks), b.chunks.data(), sizeof(TlChunk) * n_chunks, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemcpyAsync(list(at.filter), filter.data(), filter.size(), hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(list(at.totals), 0xFF, sizeof(TlTotal) * n_items, s));  // the keys: TL_KEY_NONE
+        timed(ctx, "tar_scan", s, [&] { launch_tar_scan(d_items, d_chunks, n_chunks, d_nodes, list(at.mark), jump[0], s); });
+        HIPCHK(ctx, hipGetLastError());
+        const uint32_t rounds = tl_rounds(b.max_nodes);
+        timed(ctx, "tar_chain", s, [&] {
+            for (uint32_t r = 0; r < rounds; r++) launch_tar_chain(jump[r & 1], jump[~r & 1], list(at.mark), n_nodes, s);
+        });
+        HIPCHK(ctx, hipGetLastError());
+        timed(ctx, "tar_emit", s, [&] {
+            launch_tar_emit(d_items, n_items, d_chunks, n_chunks, d_nodes, list(at.mark), (uint32_t *)list(at.pred), n_nodes, list(at.filter), (uint32_t)prefix_len,
+                            (uint32_t)suffix_len, (uint32_t *)list(at.pick), (uint32_t *)list(at.src), (TlSum *)list(at.sums), (TlTotal *)list(at.totals), s);
+        });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(b.totals.data(), list(at.totals), sizeof(TlTotal) * n_items, hipMemcpyDeviceToHost, s));
+        HIPCHK(ctx, hipStreamSynchronize(s));
+        tl_place(call, b);
+        if (!measure && b.take_members) {
+            if (b.take_members > cap_recs || b.take_names > cap_names) return ZNIPPY_E_NOMEM;  // (cannot happen: tl_place keeps to the caps and the item sizes)
+            HIPCHK(ctx, hipMemcpyAsync(list(at.bases), b.bases.data(), sizeof(TlBase) * n_items, hipMemcpyHostToDevice, s));
+            timed(ctx, "tar_emit_write", s, [&] {
+                launch_tar_emit_write(d_items, d_chunks, n_chunks, d_nodes, (const uint32_t *)list(at.pick), (const uint32_t *)list(at.src),
+                                      (const TlSum *)list(at.sums), (const TlBase *)list(at.bases), g.recs, b.take_members, g.names, b.take_names, s);
+            });
+            HIPCHK(ctx, hipGetLastError());
+            HIPCHK(ctx, hipMemcpyAsync(h_recs.data(), g.recs, sizeof(znippy_tar_member) * b.take_members, hipMemcpyDeviceToHost, s));
+            if (b.take_names) HIPCHK(ctx, hipMemcpyAsync(h_names.data(), g.names, b.take_names, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            tl_accept(call, b, h_recs.data(), b.take_members, h_names.data(), b.take_names);
+            if (!b.pieces.empty()) {
+                if (b.pieces.size() > cap_pieces) return ZNIPPY_E_NOMEM;  // (cannot happen: tl_staging counts them)
+                HIPCHK(ctx, hipMemcpyAsync(g.pieces, b.pieces.data(), sizeof(RangePiece) * b.pieces.size(), hipMemcpyHostToDevice, s));
+                timed(ctx, "tar_gather", s, [&] { launch_range_gather(g.pieces, (uint32_t)b.pieces.size(), s); });
+                HIPCHK(ctx, hipGetLastError());
+                HIPCHK(ctx, hipStreamSynchronize(s));
+            }
+        }
+    }
+    if (status) memcpy(status, b.st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" int znippy_tar_list_batch(znippy_ctx *ctx, const void *d_tar, uint64_t tar_cap, const uint64_t *tar_off, const uint64_t *tar_len, uint64_t n,
+                                     const char *name_prefix, uint64_t prefix_len, const char *name_suffix, uint64_t suffix_len,
+                                     znippy_tar_member *members, uint64_t members_cap, char *names, uint64_t names_cap, void *d_out, uint64_t out_cap,
+                                     uint64_t *member_first, uint64_t *names_bytes, uint64_t *out_bytes, int32_t *status) {
+    ZN_NO_THROW(tar_list_batch(ctx, d_tar, tar_cap, tar_off, tar_len, n, name_prefix, prefix_len, name_suffix, suffix_len, members, members_cap, names,
+                               names_cap, d_out, out_cap, member_first, names_bytes, out_bytes, status))
+}

@@ -8,6 +8,7 @@
 #include "host/deflate_batch.h"  // the lists of the DEFLATE batch calls
 #include "host/range_plan.h"
 #include "host/rows_plan.h"  // Tile, BigUnit and the constants the read side's host plan shares with the kernels
+#include "host/tar_list_plan.h"  // the lists of znippy_tar_list_batch
 
 namespace zn {
 
@@ -330,5 +331,21 @@ void launch_bunzip2_walk(const BzJob *jobs, uint32_t n_jobs, BzRec *recs, uint8_
 void launch_bunzip2_expand(const BzItem *items, const BzLand *lands, uint32_t n_lands, const uint8_t *scratch, hipStream_t s);
 // crc[l] = the bzip2 CRC-32 of the bytes of landed block l
 void launch_bunzip2_crc(const BzItem *items, const BzLand *lands, uint32_t n_lands, uint32_t *crc, hipStream_t s);
+
+// The members of tars (znippy_tar_list_batch, tar_list.hip): TlItem, TlChunk, TlNode, TlSum, TlTotal and TlBase are in
+// host/tar_list_plan.h.  Every per-node list has an entry for every node of every item.
+// nodes[g], jump[g] = nodes[g].succ and mark[g] = (g is node 0 of its item) for every node
+void launch_tar_scan(const TlItem *items, const TlChunk *chunks, uint32_t n_chunks, TlNode *nodes, uint8_t *mark, uint32_t *jump, hipStream_t s);
+// one round of pointer doubling: a marked node marks jump_in's target; jump_out[g] = jump_in[jump_in[g]]
+void launch_tar_chain(const uint32_t *jump_in, uint32_t *jump_out, uint8_t *mark, uint32_t n_nodes, hipStream_t s);
+// pred, judge, prefix: pick[g] (bit 31: a listed member; below it its name's length), src[g] (where a pending name starts, or ~0),
+// sums[0 .. n_chunks] as prefix sums and totals[k] (the keys have been reset to TL_KEY_NONE) for every item
+void launch_tar_emit(const TlItem *items, uint32_t n_items, const TlChunk *chunks, uint32_t n_chunks, const TlNode *nodes, const uint8_t *mark, uint32_t *pred,
+                     uint32_t n_nodes, const uint8_t *filter, uint32_t prefix_len, uint32_t suffix_len, uint32_t *pick, uint32_t *src, TlSum *sums,
+                     TlTotal *totals, hipStream_t s);
+// the records and names of the items with bases[k].take, at the places the bases name; nothing at or behind the caps
+void launch_tar_emit_write(const TlItem *items, const TlChunk *chunks, uint32_t n_chunks, const TlNode *nodes, const uint32_t *pick, const uint32_t *src,
+                           const TlSum *sums, const TlBase *bases, znippy_tar_member *members, uint64_t members_cap, char *names, uint64_t names_cap,
+                           hipStream_t s);
 
 }  // namespace zn

@@ -26,7 +26,7 @@
 // produces a byte, a failed check sets a status and loops end through their conditions.
 //
 // Not done here: decoding dependent pieces in parallel from their predecessors' last 32 KiB, guessing block boundaries inside streams
-// without flush points, xz, listing tar members.  (bzip2 files: bunzip2.hip.)
+// without flush points, xz.  (bzip2 files: bunzip2.hip; listing the members of the tar inside: tar_list.hip.)
 #include "inflate_dev.h"
 #include "tar_rules.h"
 

@@ -1860,7 +1860,197 @@ static int znippy_archive_bunzip2_files_impl(znippy_archive *a, const char *cons
     return ZNIPPY_OK;
 }
 
+// ---- the members of archived tars (znippy_archive_list_tar_members) ------------------------------
+// The files are gathered whole on the device (one range read, no copy to the host); the first three and the last four bytes of each
+// come back (copies queued together, one wait) and say which way it goes and, for a gzip file, its room: gzip files go through
+// znippy_gunzip_batch (rooms from ISIZE, the retry rule of znippy_archive_gunzip_files), bzip2 files through znippy_bunzip2_batch
+// (measured, then decoded), the others are copied as they are — all into one device region, the tars, over which one
+// znippy_tar_list_batch runs; where every file is a plain tar the listing runs on the gathered files themselves.  Member tables and
+// names come back, and the contents when dst is given.
+static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, const char *name_prefix, const char *name_suffix,
+                                                znippy_tar_member *members, uint64_t members_cap, char *names, uint64_t names_cap, void *dst, size_t cap,
+                                                uint64_t *member_first, uint64_t *names_bytes, uint64_t *out_bytes, int32_t *status) {
+    if (!a || !member_first || !names_bytes || !out_bytes || (n_files && !paths) || (members_cap && !members) || (names_cap && !names) || (cap && !dst))
+        return fail(ZNIPPY_E_INVAL, "null argument");
+    const bool measure = !members;
+    if (measure && (names || dst)) return fail(ZNIPPY_E_INVAL, "a measuring call takes no buffers");
+    const char *prefix = name_prefix ? name_prefix : "", *suffix = name_suffix ? name_suffix : "";
+    const size_t n = (size_t)n_files;
+    std::vector<int32_t> st(n, 0);
+    std::vector<FileRange> req;
+    std::vector<size_t> who;
+    std::vector<uint64_t> fsize(n, 0);
+    const IndexView view = a->ix.view();
+    for (size_t i = 0; i <= n; i++) member_first[i] = 0;
+    *names_bytes = *out_bytes = 0;
+    for (size_t i = 0; i < n; i++) {
+        auto it = paths[i] ? a->files.find(paths[i]) : a->files.end();
+        if (it == a->files.end()) { st[i] = ZNIPPY_E_INVAL; continue; }
+        for (uint64_t r : it->second) fsize[i] += view.row_len(r);
+        if (fsize[i] >= (1ull << 32)) { st[i] = ZNIPPY_E_UNSUPPORTED; continue; }
+        who.push_back(i);
+        req.push_back(FileRange{&it->second, 0, fsize[i]});
+    }
+    int rc = archive_ctx(a);
+    if (rc) return rc;
+    enum { PLAIN, GZ, BZ };
+    struct Tar { size_t file; uint64_t src, len; int kind; uint64_t room, off, tar_len; };
+    std::vector<Tar> tars;  // in file order
+    if (!who.empty()) {
+        // the files, whole, on the device
+        std::vector<uint64_t> at;
+        std::vector<int32_t> rst;
+        uint64_t total = 0;
+        if ((rc = read_file_ranges(a, req, nullptr, &at, &rst, &total))) return rc;
+        ReadBufs &bufs = a->bufs;
+        auto most = [&](const Tar &t) { return std::min<uint64_t>(1032 * t.len + 512, 0xFFFFFFF0ull); };
+        // 1) which way each file goes, and the rooms of the gzip files: the first three and the last four bytes of every file come
+        // to page-locked memory, eight bytes a file, by copies that are all queued before the one wait for them
+        if (!bufs.blob_pin.reserve(8 * who.size() + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
+        uint8_t *const ends = bufs.blob_pin.p;
+        std::memset(ends, 0, 8 * who.size());
+        for (size_t k = 0; k < who.size(); k++) {
+            const uint64_t len = fsize[who[k]];
+            if (rst[k] || !len) continue;
+            const uint8_t *const src = bufs.d_out.p + at[k];
+            if (hipMemcpyAsync(ends + 8 * k, src, (size_t)std::min<uint64_t>(len, 3), hipMemcpyDeviceToHost, nullptr) != hipSuccess ||
+                (len >= 4 && hipMemcpyAsync(ends + 8 * k + 4, src + len - 4, 4, hipMemcpyDeviceToHost, nullptr) != hipSuccess))
+                return fail(ZNIPPY_E_HIP, "D2H failed");
+        }
+        if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+        for (size_t k = 0; k < who.size(); k++) {
+            if (rst[k]) { st[who[k]] = rst[k]; continue; }
+            Tar t{who[k], at[k], fsize[who[k]], PLAIN, 0, 0, 0};
+            const uint8_t *const head = ends + 8 * k, *const tail = head + 4;
+            if (t.len >= 2 && head[0] == 0x1f && head[1] == 0x8b) t.kind = GZ;
+            else if (t.len >= 3 && head[0] == 'B' && head[1] == 'Z' && head[2] == 'h') t.kind = BZ;
+            if (t.kind == GZ && t.len >= 4)
+                t.room = std::min<uint64_t>((uint64_t)tail[0] | (uint64_t)tail[1] << 8 | (uint64_t)tail[2] << 16 | (uint64_t)tail[3] << 24, most(t));
+            if (t.kind == PLAIN) t.room = t.tar_len = t.len;
+            tars.push_back(t);
+        }
+        // 2) the rooms of the bzip2 files
+        std::vector<size_t> bz, gz;
+        for (size_t j = 0; j < tars.size(); j++) {
+            if (tars[j].kind == BZ) bz.push_back(j);
+            else if (tars[j].kind == GZ) gz.push_back(j);
+        }
+        std::vector<uint64_t> s_off, s_len, o_off, o_room, o_len;
+        std::vector<int32_t> ist;
+        auto lists = [&](const std::vector<size_t> &sel) {
+            s_off.clear(); s_len.clear(); o_off.clear(); o_room.clear();
+            for (size_t j : sel) { s_off.push_back(tars[j].src); s_len.push_back(tars[j].len); o_off.push_back(tars[j].off); o_room.push_back(tars[j].room); }
+            o_len.assign(sel.size(), 0);
+            ist.assign(sel.size(), 0);
+        };
+        if (!bz.empty()) {
+            lists(bz);
+            rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), bz.size(), nullptr, 0, nullptr, nullptr, 0, o_len.data(), ist.data(),
+                                      nullptr, nullptr);
+            if (rc) return fail(rc, std::string("bunzip2 (measure) failed: ") + znippy_last_error(a->ctx));
+            for (size_t q = 0; q < bz.size(); q++) {
+                Tar &t = tars[bz[q]];
+                if (ist[q]) st[t.file] = ist[q];
+                else if (o_len[q] >= (1ull << 32)) st[t.file] = ZNIPPY_E_UNSUPPORTED;
+                else t.room = o_len[q];
+            }
+        }
+        // 3) the region of the tars: every file's room, on a 16-byte boundary.  With plain tars alone there is nothing to decode and
+        // the listing runs where the files were gathered.  Device-to-device copies do not wait on the host and the context's stream
+        // is not ordered behind the null stream, so the copies are queued there and waited for before a batch call reads the region.
+        DevBuf region;
+        uint64_t region_len = 0;
+        const bool in_place = bz.empty() && gz.empty();
+        auto give_room = [&](Tar &t) { t.off = region_len; region_len = (region_len + t.room + 15) & ~15ull; };
+        if (in_place) {
+            for (Tar &t : tars) t.off = t.src;
+            region_len = total;
+        } else {
+            for (Tar &t : tars)
+                if (st[t.file] == 0) give_room(t);
+            if (!region.reserve(region_len + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+            for (Tar &t : tars)
+                if (t.kind == PLAIN && t.len && hipMemcpyAsync(region.p + t.off, bufs.d_out.p + t.src, t.len, hipMemcpyDeviceToDevice, nullptr) != hipSuccess)
+                    return fail(ZNIPPY_E_HIP, "D2D failed");
+            if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2D failed");
+        }
+        {
+            std::vector<size_t> sel;
+            for (size_t j : bz)
+                if (st[tars[j].file] == 0) sel.push_back(j);
+            if (!sel.empty()) {
+                lists(sel);
+                rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), sel.size(), region.p, region_len, o_off.data(), o_room.data(), 0,
+                                          o_len.data(), ist.data(), nullptr, nullptr);
+                if (rc) return fail(rc, std::string("bunzip2 failed: ") + znippy_last_error(a->ctx));
+                for (size_t q = 0; q < sel.size(); q++) { st[tars[sel[q]].file] = ist[q]; tars[sel[q]].tar_len = o_len[q]; }
+            }
+        }
+        while (!gz.empty()) {
+            lists(gz);
+            rc = znippy_gunzip_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), gz.size(), region.p, region_len, o_off.data(), o_room.data(), 0,
+                                     o_len.data(), ist.data(), nullptr, nullptr);
+            if (rc) return fail(rc, std::string("gunzip failed: ") + znippy_last_error(a->ctx));
+            std::vector<size_t> again;
+            for (size_t q = 0; q < gz.size(); q++) {
+                Tar &t = tars[gz[q]];
+                st[t.file] = ist[q];
+                t.tar_len = o_len[q];
+                if (ist[q] == ZNIPPY_E_DST_SMALL && t.room < most(t)) {  // several members: ISIZE names only the last
+                    st[t.file] = 0;
+                    t.room = std::min<uint64_t>(std::max<uint64_t>(8 * t.room, 4096), most(t));
+                    again.push_back(gz[q]);
+                }
+            }
+            if (!again.empty()) {  // a larger region with what there is in front, the new rooms behind
+                const uint64_t keep = region_len;
+                for (size_t j : again) give_room(tars[j]);
+                DevBuf larger;
+                if (!larger.reserve(region_len + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");
+                if (keep && (hipMemcpyAsync(larger.p, region.p, keep, hipMemcpyDeviceToDevice, nullptr) != hipSuccess || hipStreamSynchronize(nullptr) != hipSuccess))
+                    return fail(ZNIPPY_E_HIP, "D2D failed");
+                std::swap(region.p, larger.p);
+                std::swap(region.cap, larger.cap);
+            }
+            gz.swap(again);
+        }
+        // 4) one listing over all of them
+        std::vector<size_t> sel;
+        uint64_t bytes = 0;
+        for (size_t j = 0; j < tars.size(); j++)
+            if (st[tars[j].file] == 0) { sel.push_back(j); bytes += tars[j].tar_len; }
+        if (!sel.empty()) {
+            std::vector<uint64_t> t_off, t_len, first(sel.size() + 1, 0);
+            for (size_t j : sel) { t_off.push_back(tars[j].off); t_len.push_back(tars[j].tar_len); }
+            ist.assign(sel.size(), 0);
+            const uint64_t out_cap = dst ? std::min<uint64_t>(cap, bytes) : 0;
+            if (dst && !bufs.d_blobs.reserve(out_cap + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");  // (the chunks in it have been gathered from)
+            rc = znippy_tar_list_batch(a->ctx, in_place ? bufs.d_out.p : region.p, region_len, t_off.data(), t_len.data(), sel.size(), prefix, strlen(prefix), suffix, strlen(suffix), members,
+                                       members_cap, names, names_cap, dst ? bufs.d_blobs.p : nullptr, out_cap, first.data(), names_bytes, out_bytes, ist.data());
+            if (rc) return fail(rc, std::string("tar listing failed: ") + znippy_last_error(a->ctx));
+            if (dst && *out_bytes && hipMemcpy(dst, bufs.d_blobs.p, *out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
+            size_t q = 0;
+            for (size_t i = 0; i < n; i++) {  // (sel is in file order)
+                member_first[i] = first[q];
+                if (q < sel.size() && tars[sel[q]].file == i) st[i] = ist[q++];
+            }
+            member_first[n] = first[sel.size()];
+        }
+    }
+    if (status) std::memcpy(status, st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
 extern "C" {
+
+int znippy_archive_list_tar_members(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix, const char *name_suffix,
+                                    znippy_tar_member *members, uint64_t members_cap, char *names, uint64_t names_cap, void *dst, size_t cap,
+                                    uint64_t *member_first, uint64_t *names_bytes, uint64_t *out_bytes, int32_t *status) {
+    return guarded([&] {
+        return znippy_archive_list_tar_members_impl(a, relative_paths, n_files, name_prefix, name_suffix, members, members_cap, names, names_cap, dst, cap,
+                                                    member_first, names_bytes, out_bytes, status);
+    });
+}
 
 int znippy_archive_bunzip2_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
                                  int32_t *status) {

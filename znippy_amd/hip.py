@@ -10,6 +10,11 @@ from . import _lib
 from ._lib import VerifyCounters, ZnippyError, as_np, np_ptr, vp
 
 
+# znippy_tar_member of include/znippy_hip.h
+TAR_MEMBER = np.dtype([("header_off", "<u8"), ("data_off", "<u8"), ("size", "<u8"), ("name_off", "<u8"), ("out_off", "<u8"), ("name_len", "<u4"),
+                       ("typeflag", "<u4")])
+
+
 def _pinned(shape, dtype):
     """Host result buffer; pinned when torch can (direct DMA on D2H), reused across calls."""
     try:
@@ -263,6 +268,41 @@ class Context:
         self._chk(self.L.znippy_bunzip2_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), n, None, 0, None, None, int(slot_cap),
                                               np_ptr(ol), np_ptr(status), np_ptr(streams), np_ptr(blocks)), "znippy_bunzip2_batch")
         return status[:n], ol[:n], streams[:n], blocks[:n]
+
+    # ---- the members of tars held in device memory ----
+    def tar_list_batch(self, d_tar, tar_off, tar_len, suffix=b"", prefix=b"", d_out=None, members_cap=None, names_cap=None, tar_cap=None, out_cap=None,
+                       measure=False):
+        """znippy_tar_list_batch: item i is the (decompressed) tar d_tar[tar_off[i] .. + tar_len[i]).  Every regular member whose name
+        starts with `prefix` and ends with `suffix` (bytes; empty = all) is listed, in stream order; with d_out their contents are
+        packed into it.  members_cap / names_cap None: a measuring call first, and caps that hold everything.  measure=True: the
+        measuring call alone.  Synchronous and not a run.  Returns (status per item: 0 or ZNIPPY_E_*, member_first — n + 1 —,
+        members: a structured array (TAR_MEMBER; offsets relative to the item), names: bytes, names_bytes, out_bytes)."""
+        to, tl = as_np(tar_off, np.uint64), as_np(tar_len, np.uint64)
+        n = len(to)
+        assert len(tl) == n, "item arrays differ in length"
+        prefix, suffix = bytes(prefix), bytes(suffix)
+        tar_cap = d_tar.numel() if tar_cap is None else tar_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        nb, ob = C.c_uint64(0), C.c_uint64(0)
+
+        def call(members, m_cap, names, n_cap, out, o_cap):
+            self._chk(self.L.znippy_tar_list_batch(self.h, _dptr(d_tar), int(tar_cap), np_ptr(to), np_ptr(tl), n, prefix, len(prefix), suffix, len(suffix),
+                                                   np_ptr(members) if members is not None else None, int(m_cap),
+                                                   np_ptr(names) if names is not None else None, int(n_cap), _dptr(out) if out is not None else None,
+                                                   int(o_cap), np_ptr(first), C.byref(nb), C.byref(ob), np_ptr(status)), "znippy_tar_list_batch")
+
+        if measure or members_cap is None or names_cap is None:
+            call(None, 0, None, 0, None, 0)
+            if measure:
+                return status[:n], first, np.zeros(0, dtype=TAR_MEMBER), b"", nb.value, ob.value
+            members_cap = int(first[n]) if members_cap is None else members_cap
+            names_cap = nb.value if names_cap is None else names_cap
+        members = np.zeros(max(int(members_cap), 1), dtype=TAR_MEMBER)
+        names = np.zeros(max(int(names_cap), 1), dtype=np.uint8)
+        out_cap = (d_out.numel() if d_out is not None else 0) if out_cap is None else out_cap
+        call(members, members_cap, names, names_cap, d_out, out_cap)
+        return status[:n], first, members[:int(first[n])], names[:nb.value].tobytes(), nb.value, ob.value
 
 
 def get_decompressed_size(frame) -> int:

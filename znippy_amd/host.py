@@ -29,7 +29,7 @@ class _ME(C.Structure):
 HOST_EXPORTS = [
     "znippy_host_last_error", "znippy_compress_stream", "znippy_stream_send", "znippy_stream_send_packed", "znippy_stream_finish",
     "znippy_compress_dir", "znippy_decompress_archive", "znippy_archive_open", "znippy_archive_file_count", "znippy_archive_file_size",
-    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_archive_bunzip2_files", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
+    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_archive_bunzip2_files", "znippy_archive_list_tar_members", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
     "znippy_index_manifest_len", "znippy_index_manifest_entry", "znippy_index_row", "znippy_index_metadata",
     "znippy_index_close", "znippy_interpret_footer", "znippy_write_manifest_bytes",
 ]
@@ -65,6 +65,9 @@ def lib():
         L.znippy_archive_gunzip_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
         if hasattr(L, "znippy_archive_bunzip2_files"):  # (a library built before the call existed still loads)
             L.znippy_archive_bunzip2_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
+        if hasattr(L, "znippy_archive_list_tar_members"):  # (likewise)
+            L.znippy_archive_list_tar_members.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, vp, C.c_uint64, vp, C.c_uint64, vp,
+                                                          C.c_size_t, vp, vp, vp, vp]
         L.znippy_zip_end_of_directory.argtypes = [vp, C.c_size_t, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.znippy_zip_find_entry.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, vp]
         L.znippy_zip_local_data_offset.argtypes = [vp, C.c_size_t, C.POINTER(C.c_uint64)]
@@ -346,6 +349,40 @@ class ZnippyArchive:
                                                 st.ctypes.data_as(vp)), "bunzip2_files")
         out = [buf[int(off[i]):int(off[i + 1])].tobytes() if st[i] == 0 else None for i in range(n)]
         return out, [int(v) for v in st[:n]]
+
+    def list_tar_members(self, paths, suffix=b"", prefix=b"", contents=False, cap=None):
+        """Every regular member of the tar in every archived file of `paths` (.tar, .tar.gz / .tgz / .crate, .tar.bz2) whose name starts
+        with `prefix` and ends with `suffix` (bytes without NUL; empty = all), listed on the device in one batch: the files are gathered
+        there whole, gzip and bzip2 files are decompressed there (chosen by their first bytes), and one znippy_tar_list_batch walks all
+        the tars.  contents: the members' bytes come back as well.  cap: bytes of the buffer for the contents.  None: the tars are
+        measured first (a call without buffers) and the buffers hold exactly what is listed.  Returns, per file,
+        (status, [(name, size, bytes | None), ...]); a file whose status is not 0 lists nothing."""
+        from .hip import TAR_MEMBER
+        paths = [str(p) for p in paths]
+        n = len(paths)
+        arr = (C.c_char_p * n)(*[p.encode() for p in paths])
+        prefix, suffix = bytes(prefix), bytes(suffix)
+        first = np.zeros(n + 1, dtype=np.uint64)
+        st = np.zeros(max(n, 1), dtype=np.int32)
+        nb, ob = C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda a: a.ctypes.data_as(vp)  # noqa: E731
+        _chk(lib().znippy_archive_list_tar_members(self.h, arr, n, prefix, suffix, None, 0, None, 0, None, 0, ptr(first), C.byref(nb), C.byref(ob), ptr(st)),
+             "list_tar_members")
+        members = np.zeros(max(int(first[n]), 1), dtype=TAR_MEMBER)
+        names = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        room = (ob.value if cap is None else int(cap)) if contents else 0
+        buf = np.empty(max(room, 1), dtype=np.uint8) if contents else None
+        _chk(lib().znippy_archive_list_tar_members(self.h, arr, n, prefix, suffix, ptr(members), int(first[n]), ptr(names), nb.value,
+                                                   ptr(buf) if contents else None, room, ptr(first), C.byref(nb), C.byref(ob), ptr(st)), "list_tar_members")
+        nm = names.tobytes()
+        out = []
+        for i in range(n):
+            ms = []
+            for m in members[int(first[i]):int(first[i + 1])]:
+                no, oo, size = int(m["name_off"]), int(m["out_off"]), int(m["size"])
+                ms.append((nm[no:no + int(m["name_len"])], size, buf[oo:oo + size].tobytes() if contents else None))
+            out.append((int(st[i]), ms))
+        return out
 
     def block_tree_stats(self):
         """[entries loaded from the sidecar `<path>.b3t` at open, chunks whose sidecar entries were accepted, chunks whose
