@@ -487,11 +487,69 @@ int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
  * inflates it with the room as its limit and checks trailer and padding (single), its CRC goes to the crc launch, and a batch of such
  * items launches no probe.  The same wave takes, member by member, an item whose candidates outnumber its slice of the list
  * (16 + src_len / 256), so that no result depends on which candidates could be kept.
- * Out of scope: decoding dependent pieces in parallel from their predecessors' last 32 KiB, guessing block boundaries inside streams
- * without flush points, xz.  bzip2 files: znippy_bunzip2_batch below; listing the members of the tar inside: znippy_tar_list_batch. */
+ * Opt-in (znippy_ctx_set_gunzip_cut below): block starts found inside streams without flush points, and the pieces between them
+ * decoded in parallel from their predecessors' last 32 KiB.  Out of scope: xz.  bzip2 files: znippy_bunzip2_batch below; listing the members of the tar inside: znippy_tar_list_batch. */
 int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
                         void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len,
                         int32_t *status, uint32_t *members, uint32_t *segments);
+
+/* Cutting gzip files at block starts: opt-in, off by default.  A file whose writer left no cut points (a crate, an sdist, plain gzip
+ * or zlib output, a log) can only be cut where a DEFLATE block starts, and block starts have to be found: at any bit offset, by
+ * testing for a valid header; and a piece cut there reaches into bytes that do not exist yet.  With a value set, later
+ * znippy_gunzip_batch calls of the context run these stages between scan and probe (znippy_last_kernel_times: gunzip_find,
+ * gunzip_cut_probe, gunzip_decode, gunzip_tails, gunzip_apply, gunzip_cut_crc):
+ *   find     every item of at least 2 * cut_bytes source bytes is tested at every bit position, a lane per position.  A position
+ *            passes exactly when a non-final dynamic block (BFINAL 0, BTYPE 2) whose header satisfies the dynamic-block rules written
+ *            at znippy_inflate_batch, up to its first body symbol, starts there inside the input (csrc/gz_cut_rules.h, one text for
+ *            the kernel and for a host test).  The item's source is divided into windows of cut_bytes bytes counted from its byte 0;
+ *            the lowest passing position of a window is its kept block candidate, so an item has ceil(src_len / cut_bytes) slots and
+ *            the list cannot overflow.
+ *   probe    one wave per candidate of an item the search kept a candidate in — byte 0, the kept block candidates, and the member and
+ *            kept flush candidates of the scan —, as the probe above, with a piece starting at any bit and ending in front of the
+ *            first block whose header starts at a kept candidate, flush or block; positions are 64-bit bit positions.
+ *   plan     (host, csrc/host/gz_cut_plan.{h,cc}) the chain rule, member by member: only candidates the chain from byte 0 lands on
+ *            count, so a false candidate changes no result.  A piece that reaches back does not join the piece in front: it becomes
+ *            a marker piece — unless its symbols alone exceed the scratch budget: then it joins the run in front, as above.  A
+ *            member's first piece and pieces that reach nowhere are decoded straight into place.  A reach beyond the member's first
+ *            byte is "too far back".  Offsets are prefix sums of the probe's exact counts; consecutive pieces form passes whose
+ *            marker pieces fit the scratch budget.  Nothing in a record is trusted.  The plan answers for files that are clean, and
+ *            hands every other file — an error, a room too small, a wrong ISIZE, a reach too far back, garbage behind a trailer, any
+ *            contradiction — to the stages behind, untouched, which decode it as with the value 0 and report what it is.
+ *   decode   one wave per piece.  A marker piece goes to scratch as 16-bit symbols, 2 bytes per content byte: a value below 256 is
+ *            a byte, 0x8000 | k names byte k of the 32,768 in front of the piece's first byte; matches inside the piece copy
+ *            symbols, markers included, overlapping ones too.
+ *   tails    one workgroup per item and pass takes the item's pieces in chain order and turns the last 32 KiB of each marker piece
+ *            into bytes at their final place, reading markers from the final bytes in front of the piece.  The only serial loop runs
+ *            inside one workgroup and is bounded by the piece count; no workgroup waits for another; a pass starts from the bytes
+ *            earlier passes left.
+ *   apply    every remaining symbol of every marker piece becomes a byte, a lane per symbol.
+ *   crc      the CRC launch over the pieces, combined per item on the host and compared with the trailer; an item whose pieces or
+ *            CRC are not clean is decoded again by the stages behind.
+ * The contract is equivalence: out_len, status, members and, for status 0, the bytes in the room are those of the value 0, for every
+ * input, damaged ones included.  segments keeps its meaning — the pieces of the item that a wave of its own decoded — and so grows
+ * for a file that is cut; a file with flush points or members keeps every cut point it has with the value 0.  The lists of these
+ * stages (about 180 bytes per slot and per entry of the scan's list) and the symbol scratch are three further allocations, made with
+ * the first before the first stream operation.  A call whose searched items would need more than 2^30 slots, or whose further
+ * allocations the device has no memory for, runs as with the value 0.
+ *   cut_bytes   0 = off; 64 .. 2^30; anything else is ZNIPPY_E_INVAL.  ZNIPPY_GZ_CUT (0, or 64 ..) in the environment of
+ *               znippy_ctx_create sets the initial value; a value that is not valid there is ignored.  znippy_ctx_gunzip_cut returns
+ *               the value (0 for a NULL or closed context).  ZNIPPY_GZ_CUT_DEFAULT is the value the tools turn the switch on with: the largest of the
+ *               best values swept at 8 and 64 MiB (4, 8 and 16 KiB are equal, 32 KiB and more slower; on one 512 MiB file, where
+ *               the tails stage is four fifths of the call, 128 KiB is 1.8 times faster: profiles/gunzip_cut_report.log).
+ *   ZNIPPY_GZ_CUT_SCRATCH_MB (read per call, default 1024, at least 1): the symbol scratch of one pass, never more than twice the
+ *               rooms of the searched items.
+ * znippy_ctx_gunzip_cut_stats describes the context's last znippy_gunzip_batch call (all zero after a call with the value 0):
+ *   out[0]  bit positions tested: 8 * src_len of every searched item
+ *   out[1]  positions that passed the whole header test
+ *   out[2]  block candidates kept: windows with a passing position
+ *   out[3]  kept candidates the chain landed on, block or flush, in the items that were cut
+ *   out[4]  pieces decoded with markers        out[5]  pieces decoded straight into place
+ *   out[6]  marker symbols resolved (3 to 6: of the items these stages finished)            out[7]  passes
+ * Not done: cuts inside a block, stored-block or fixed-block candidates, the same for znippy_inflate_batch and ZIP entries. */
+#define ZNIPPY_GZ_CUT_DEFAULT 16384ull
+int znippy_ctx_set_gunzip_cut(znippy_ctx *ctx, uint64_t cut_bytes);
+uint64_t znippy_ctx_gunzip_cut(const znippy_ctx *ctx);
+int znippy_ctx_gunzip_cut_stats(znippy_ctx *ctx, uint64_t out[8]);
 
 /* ---- whole bzip2 files the engine already holds --------------------------------------------------------------------------------
  * The bunzip2 of the reference's ingest side: host_decompress codec 2 and the tar.bz2 archive format of host_archive_open

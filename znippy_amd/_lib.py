@@ -56,6 +56,7 @@ EXPORTS = [
     "znippy_rounds_emit_block_tree", "znippy_rounds_block_tree_layout", "znippy_rounds_block_tree",
     "znippy_inflate_batch", "znippy_targz_find_batch", "znippy_gunzip_batch", "znippy_roles_wait_stats",
     "znippy_bunzip2_batch", "znippy_tar_list_batch",
+    "znippy_ctx_set_gunzip_cut", "znippy_ctx_gunzip_cut", "znippy_ctx_gunzip_cut_stats",
 ]
 
 
@@ -161,6 +162,11 @@ def lib():
                                               vp, C.c_uint64, vp, vp, vp, vp]
     if hasattr(L, "znippy_gunzip_batch"):  # (likewise)
         L.znippy_gunzip_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]
+    if hasattr(L, "znippy_ctx_set_gunzip_cut"):  # (likewise)
+        L.znippy_ctx_set_gunzip_cut.argtypes = [vp, C.c_uint64]
+        L.znippy_ctx_gunzip_cut.argtypes = [vp]
+        L.znippy_ctx_gunzip_cut.restype = C.c_uint64
+        L.znippy_ctx_gunzip_cut_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     if hasattr(L, "znippy_bunzip2_batch"):  # (likewise)
         L.znippy_bunzip2_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, C.c_uint64, vp, vp, vp, vp]
     if hasattr(L, "znippy_tar_list_batch"):  # (likewise)

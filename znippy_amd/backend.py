@@ -28,6 +28,19 @@ class HipBackend:
         """Frames with a content checksum through the batch path of later read runs (0 = off; znippy_ctx_set_batch_checksums)."""
         self.ctx.set_batch_checksums(on)
 
+    def set_gunzip_cut(self, cut_bytes):
+        """Later gunzip calls cut files without flush points at found block starts (0 = off, 64 .. 2^30 source bytes per kept
+        candidate; znippy_ctx_set_gunzip_cut)."""
+        self.ctx.set_gunzip_cut(cut_bytes)
+
+    @property
+    def gunzip_cut(self):
+        return self.ctx.gunzip_cut
+
+    def gunzip_cut_stats(self):
+        """The counters of the context's last gunzip call (znippy_ctx_gunzip_cut_stats)."""
+        return self.ctx.gunzip_cut_stats()
+
     def set_blob_align(self, align):
         """Blob offsets of later encode_hash calls are multiples of `align` inside their region (a power of two, 1 .. 4096;
         znippy_rounds_set_blob_align on every table built from here on)."""

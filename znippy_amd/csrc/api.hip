@@ -91,6 +91,8 @@ struct znippy_ctx {
     int gen_share = 3;  // workgroups per CU the general decoder takes while block items / foreign frames run beside it (4 = the whole register file)
     int level = 19;  // CompressCtx::new(compression_level), codec.rs:L16-28; CONFIG.compression_level is 19 (common_config.rs:L37)
     int window_log = 0;  // cross-block window of the higher effort tier (znippy_ctx_set_window_log); 0 = self-contained blocks
+    uint64_t gz_cut = 0;  // znippy_ctx_set_gunzip_cut: the window of the block-start search of znippy_gunzip_batch in source bytes; 0 = no search
+    uint64_t gz_cut_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // znippy_ctx_gunzip_cut_stats: the last gunzip call
     int batch_checksums = 0;  // the batch path takes frames with a content checksum and checks it itself (znippy_ctx_set_batch_checksums); read at the start of every run
     uint32_t *ldm = nullptr;  // far window index (grow-only, entries)
     size_t ldm_cap = 0;
@@ -217,6 +219,11 @@ static void read_switches(znippy_ctx *ctx) {
     if (const char *e = getenv("ZNIPPY_BX_BIG")) { ctx->sw.bx_big = (unsigned)atoi(e); ctx->sw.bx_big_set = true; }  // A/B: foreign frames through the round-2 paths (serial decoder + wave-per-block two-phase path)
     if (const char *lv = getenv("ZNIPPY_LEVEL")) { const int v = atoi(lv); if (v >= 1 && v <= 22) ctx->level = v; }  // initial level of every context (tests, A/B runs)
     if (const char *wl = getenv("ZNIPPY_WINDOW_LOG")) { const int v = atoi(wl); if (v == 0 || (v >= WINDOW_LOG_MIN && v <= WINDOW_LOG_MAX)) ctx->window_log = v; }  // initial window of every context (host layer, tools)
+    if (const char *gc = getenv("ZNIPPY_GZ_CUT")) {  // initial value of every context (host layer, tools)
+        char *end = nullptr;
+        const unsigned long long v = strtoull(gc, &end, 10);
+        if (*gc >= '0' && *gc <= '9' && end && !*end && gzcut::cut_valid(v)) ctx->gz_cut = v;
+    }
     if (const char *bc = getenv("ZNIPPY_BX_CHECKSUM")) { const int v = atoi(bc); if (v == 0 || v == 1) ctx->batch_checksums = v; }  // initial switch of every context (host layer, tools)
     if (const char *gs = getenv("ZNIPPY_GEN_SHARE")) { const int v = atoi(gs); if (v >= 1 && v <= 4) ctx->gen_share = v; }  // A/B
     ctx->sw.fz_only = on("ZNIPPY_FZ_ONLY");  // test hook: no serial fallback behind the two-phase path (what it leaves shows up as corrupt rows)
@@ -1175,6 +1182,22 @@ int znippy_ctx_set_window_log(znippy_ctx *ctx, int window_log) {
 }
 
 int znippy_ctx_window_log(const znippy_ctx *ctx) { return ctx && !ctx->closing ? ctx->window_log : ZNIPPY_E_INVAL; }
+
+int znippy_ctx_set_gunzip_cut(znippy_ctx *ctx, uint64_t cut_bytes) {
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
+    if (!ctx || !gzcut::cut_valid(cut_bytes)) return ZNIPPY_E_INVAL;
+    ctx->gz_cut = cut_bytes;
+    return ZNIPPY_OK;
+}
+
+uint64_t znippy_ctx_gunzip_cut(const znippy_ctx *ctx) { return ctx && !ctx->closing ? ctx->gz_cut : 0; }
+
+int znippy_ctx_gunzip_cut_stats(znippy_ctx *ctx, uint64_t out[8]) {
+    if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
+    if (!ctx || !out) return ZNIPPY_E_INVAL;
+    memcpy(out, ctx->gz_cut_stats, sizeof ctx->gz_cut_stats);
+    return ZNIPPY_OK;
+}
 
 int znippy_ctx_set_kernel_timing(znippy_ctx *ctx, int level) {
     if (!ctx_enter(ctx, ENTER_HOST)) return ZNIPPY_E_INVAL;
@@ -3544,6 +3567,202 @@ static int gz_decode_stage(znippy_ctx *ctx, GzBatch &b, const GzDev &d) {
     return ZNIPPY_OK;
 }
 
+// The block-start search (znippy_ctx_set_gunzip_cut): the searched items and their chunks up, the slots set to NONE and the count of
+// passing positions to 0, the search, slots and count back; what they say goes to the context's statistics
+struct GzFindDev {
+    uint8_t *p;
+    size_t items, chunks, slots, passed, bytes;
+};
+static GzFindDev gz_find_layout(const gzcut::FindPlan &f) {
+    GzFindDev d{};
+    auto carve = [&d](size_t sz) { const size_t at = d.bytes; d.bytes += (sz + 15) & ~(size_t)15; return at; };
+    d.items = carve(sizeof(gzcut::FindItem) * f.items.size());
+    d.chunks = carve(sizeof(gzcut::FindChunk) * f.chunks.size());
+    d.slots = carve(sizeof(uint64_t) * f.n_slots);
+    d.passed = carve(sizeof(uint64_t));
+    return d;
+}
+static int gz_find_stage(znippy_ctx *ctx, const gzcut::FindPlan &f, const GzFindDev &d, uint64_t cut, std::vector<uint64_t> &slots, hipStream_t s) {
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.items, f.items.data(), sizeof(gzcut::FindItem) * f.items.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(d.p + d.chunks, f.chunks.data(), sizeof(gzcut::FindChunk) * f.chunks.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(d.p + d.slots, 0xFF, sizeof(uint64_t) * f.n_slots, s));
+    HIPCHK(ctx, hipMemsetAsync(d.p + d.passed, 0, sizeof(uint64_t), s));
+    timed(ctx, "gunzip_find", s, [&] {
+        launch_gunzip_find((const gzcut::FindItem *)(d.p + d.items), (const gzcut::FindChunk *)(d.p + d.chunks), (uint32_t)f.chunks.size(), (uint32_t)cut,
+                           (unsigned long long *)(d.p + d.slots), (unsigned long long *)(d.p + d.passed), s);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    slots.resize((size_t)f.n_slots);
+    uint64_t passed = 0;
+    HIPCHK(ctx, hipMemcpyAsync(slots.data(), d.p + d.slots, sizeof(uint64_t) * f.n_slots, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(&passed, d.p + d.passed, sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    ctx->gz_cut_stats[0] = f.tested;
+    ctx->gz_cut_stats[1] = passed;
+    ctx->gz_cut_stats[2] = gzcut::count_kept(f, slots.data(), cut);
+    return ZNIPPY_OK;
+}
+
+// The cut at the block starts found (host/gz_cut_plan.h): one more allocation for its lists (entries: a candidate per slot, one per searched
+// item and one per entry of its slice of the scan's list at the most, and so records, pieces, groups and CRC entries) and one for the symbols of a pass
+struct GzCutDev {
+    uint8_t *p;
+    size_t cands, stops, recs, pieces, groups, status, crc_items, crc_st, crc_got, resolved, bytes;
+    size_t entries;
+    uint16_t *scratch;
+    uint64_t budget_syms;
+};
+static GzCutDev gz_cut_layout(const gzcut::FindPlan &f, const GzBatch &b, uint64_t budget_bytes) {
+    GzCutDev d{};
+    auto carve = [&d](size_t sz) { const size_t at = d.bytes; d.bytes += (sz + 15) & ~(size_t)15; return at; };
+    d.entries = (size_t)f.n_slots + f.items.size();
+    for (const uint32_t k : f.item_of) d.entries += b.items[k].cand_cap;  // (the scan's member and flush candidates)
+    d.cands = carve(sizeof(gzcut::CutCand) * d.entries);
+    d.stops = carve(sizeof(uint64_t) * d.entries);
+    d.recs = carve(sizeof(gzcut::CutRec) * d.entries);
+    d.pieces = carve(sizeof(gzcut::CutPiece) * d.entries);
+    d.groups = carve(sizeof(gzcut::CutGroup) * d.entries);
+    d.status = carve(sizeof(int32_t) * d.entries);
+    d.crc_items = carve(sizeof(InflateItem) * d.entries);
+    d.crc_st = carve(sizeof(int32_t) * d.entries);
+    d.crc_got = carve(sizeof(uint32_t) * d.entries);
+    d.resolved = carve(sizeof(uint64_t) * d.entries);  // per piece
+    uint64_t rooms = 0;  // no pass holds more symbols than the searched items have room for
+    for (const uint32_t k : f.item_of) rooms += b.items[k].room;
+    d.budget_syms = std::max<uint64_t>(1, std::min<uint64_t>(budget_bytes / 2, rooms));
+    return d;
+}
+
+// Probe, plan, and pass by pass decode, tails and apply; then the CRC of every piece.  Items whose plan stands and whose pieces and
+// CRC are clean get their results here (b.cut_done, cut_res); every other item is left to the stages behind, untouched but for bytes
+// inside its own room.
+struct GzCutResult { uint32_t item; uint32_t members, segments; uint64_t out_len; };
+static int gz_cut_stage(znippy_ctx *ctx, GzBatch &b, const GzDev &d, const gzcut::FindPlan &f, const GzCutDev &c, const uint64_t *slots, uint64_t cut,
+                        uint64_t seg_min, std::vector<GzCutResult> &done) {
+    hipStream_t s = d.s;
+    std::vector<gzcut::CutCand> cands;
+    std::vector<uint64_t> stops, kept, raw;
+    std::vector<std::pair<uint64_t, uint32_t>> all;  // (bit, member) of one item
+    std::vector<size_t> first_cand;  // per find item, and one more
+    for (size_t fi = 0; fi < f.items.size(); fi++) {
+        first_cand.push_back(cands.size());
+        gzcut::kept_of(f, fi, slots, cut, kept);
+        if (kept.empty()) continue;  // (nothing to cut at that the stages behind do not cut at themselves)
+        const uint32_t k = f.item_of[fi];
+        all.clear();
+        all.emplace_back(0, 1u);
+        for (const uint64_t v : kept) all.emplace_back(v, 0u);
+        if (b.count[k] && b.count[k] <= b.items[k].cand_cap) {  // the scan's candidates, kept as gz_candidates keeps them
+            raw.assign(b.raw.begin() + b.items[k].cand_base, b.raw.begin() + b.items[k].cand_base + b.count[k]);
+            const size_t n_kept = gzp::keep_candidates(raw.data(), raw.size(), seg_min);
+            for (size_t j = 0; j < n_kept; j++)
+                if ((raw[j] >> 1) < b.items[k].src_len) all.emplace_back((raw[j] >> 1) * 8, (uint32_t)(raw[j] & 1));
+        }
+        std::sort(all.begin(), all.end());
+        all.erase(std::unique(all.begin(), all.end()), all.end());
+        const uint32_t base = (uint32_t)stops.size();
+        for (const auto &c : all)
+            if (!c.second) stops.push_back(c.first);
+        const uint32_t end = (uint32_t)stops.size();
+        uint32_t next_stop = base;  // the first stop behind the position
+        for (const auto &c : all) {
+            while (next_stop < end && stops[next_stop] <= c.first) next_stop++;
+            cands.push_back(gzcut::CutCand{k, c.second, c.first, next_stop, end});
+        }
+    }
+    first_cand.push_back(cands.size());
+    if (cands.empty()) return ZNIPPY_OK;
+    if (cands.size() > c.entries || stops.size() > c.entries) return ZNIPPY_E_NOMEM;  // (cannot happen: gz_cut_layout counts them)
+    const uint32_t n_cands = (uint32_t)cands.size();
+    HIPCHK(ctx, hipMemcpyAsync(c.p + c.cands, cands.data(), sizeof(gzcut::CutCand) * n_cands, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(c.p + c.stops, stops.data(), sizeof(uint64_t) * stops.size(), hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemsetAsync(c.p + c.resolved, 0, sizeof(uint64_t) * c.entries, s));
+    timed(ctx, "gunzip_cut_probe", s, [&] {
+        launch_gunzip_cut_probe(d.items(), (const gzcut::CutCand *)(c.p + c.cands), n_cands, (const uint64_t *)(c.p + c.stops), (gzcut::CutRec *)(c.p + c.recs), s);
+    });
+    HIPCHK(ctx, hipGetLastError());
+    std::vector<gzcut::CutRec> recs(n_cands);
+    HIPCHK(ctx, hipMemcpyAsync(recs.data(), c.p + c.recs, sizeof(gzcut::CutRec) * n_cands, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    std::vector<gzcut::CutPiece> pieces;
+    std::vector<gzcut::CutItemPlan> plans;
+    std::vector<gzcut::CutMember> mems;
+    for (size_t fi = 0; fi < f.items.size(); fi++) {
+        const size_t c0 = first_cand[fi], c1 = first_cand[fi + 1];
+        if (c0 == c1) continue;
+        const uint32_t k = f.item_of[fi];
+        gzcut::plan_cut(cands.data() + c0, recs.data() + c0, c1 - c0, k, b.items[k].src_len, b.items[k].room, c.budget_syms, pieces, mems, plans);
+    }
+    if (plans.empty()) return ZNIPPY_OK;
+    std::vector<gzcut::CutPass> passes;
+    std::vector<gzcut::CutGroup> groups;
+    gzcut::make_passes(pieces, c.budget_syms, passes, groups);
+    const uint32_t n_pieces = (uint32_t)pieces.size();
+    if (pieces.size() > c.entries || groups.size() > c.entries) return ZNIPPY_E_NOMEM;  // (cannot happen: a piece per candidate at the most)
+    for (const gzcut::CutPiece &pc : pieces)
+        if (pc.marker && (pc.sym_off > c.budget_syms || pc.out_len > c.budget_syms - pc.sym_off)) return ZNIPPY_E_NOMEM;  // (likewise: make_passes places them inside)
+    HIPCHK(ctx, hipMemcpyAsync(c.p + c.pieces, pieces.data(), sizeof(gzcut::CutPiece) * n_pieces, hipMemcpyHostToDevice, s));
+    HIPCHK(ctx, hipMemcpyAsync(c.p + c.groups, groups.data(), sizeof(gzcut::CutGroup) * groups.size(), hipMemcpyHostToDevice, s));
+    const gzcut::CutPiece *const d_pieces = (const gzcut::CutPiece *)(c.p + c.pieces);
+    unsigned long long *const d_resolved = (unsigned long long *)(c.p + c.resolved);
+    for (const gzcut::CutPass &ps : passes) {  // (ordered by the stream: a pass starts from the bytes the passes before it left)
+        const uint32_t np = (uint32_t)(ps.piece1 - ps.piece0), ng = (uint32_t)(ps.group1 - ps.group0);
+        timed(ctx, "gunzip_decode", s, [&] { launch_gunzip_cut_decode(d.items(), d_pieces + ps.piece0, np, c.scratch, (int32_t *)(c.p + c.status) + ps.piece0, s); });
+        HIPCHK(ctx, hipGetLastError());
+        timed(ctx, "gunzip_tails", s, [&] { launch_gunzip_cut_tails(d.items(), d_pieces, (const gzcut::CutGroup *)(c.p + c.groups) + ps.group0, ng, c.scratch, d_resolved, s); });
+        HIPCHK(ctx, hipGetLastError());
+        timed(ctx, "gunzip_apply", s, [&] { launch_gunzip_cut_apply(d.items(), d_pieces + ps.piece0, np, c.scratch, d_resolved + ps.piece0, s); });
+        HIPCHK(ctx, hipGetLastError());
+    }
+    // the CRC of every non-empty piece, combined per item on the host
+    std::vector<InflateItem> crc_items;
+    std::vector<size_t> crc_of(pieces.size(), (size_t)-1);
+    for (size_t p = 0; p < pieces.size(); p++) {
+        if (!pieces[p].out_len) continue;
+        InflateItem it;
+        it.src = nullptr; it.dst = b.items[pieces[p].item].dst + pieces[p].out_off; it.src_len = 0; it.out_len = pieces[p].out_len;
+        it.method = 8; it.want_crc = 0; it.has_crc = 0; it.pad = 0;
+        crc_of[p] = crc_items.size();
+        crc_items.push_back(it);
+    }
+    const uint32_t n_crc = (uint32_t)crc_items.size();
+    std::vector<int32_t> piece_st(n_pieces);
+    std::vector<uint32_t> crc_got(n_crc);
+    std::vector<uint64_t> resolved(n_pieces);
+    if (n_crc) {
+        HIPCHK(ctx, hipMemcpyAsync(c.p + c.crc_items, crc_items.data(), sizeof(InflateItem) * n_crc, hipMemcpyHostToDevice, s));
+        HIPCHK(ctx, hipMemsetAsync(c.p + c.crc_st, 0, sizeof(int32_t) * n_crc, s));
+        timed(ctx, "gunzip_cut_crc", s, [&] { launch_inflate_crc((const InflateItem *)(c.p + c.crc_items), n_crc, (int32_t *)(c.p + c.crc_st), (uint32_t *)(c.p + c.crc_got), s); });
+        HIPCHK(ctx, hipGetLastError());
+        HIPCHK(ctx, hipMemcpyAsync(crc_got.data(), c.p + c.crc_got, sizeof(uint32_t) * n_crc, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(ctx, hipMemcpyAsync(piece_st.data(), c.p + c.status, sizeof(int32_t) * n_pieces, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipMemcpyAsync(resolved.data(), c.p + c.resolved, sizeof(uint64_t) * n_pieces, hipMemcpyDeviceToHost, s));
+    HIPCHK(ctx, hipStreamSynchronize(s));
+    b.cut_done.assign(b.items.size(), 0);
+    for (const gzcut::CutItemPlan &pl : plans) {
+        bool ok = true;
+        for (size_t p = pl.piece0; p < pl.piece1; p++)
+            if (piece_st[p] != 0) ok = false;
+        for (size_t m = pl.member0; m < pl.member1 && ok; m++) {
+            uint32_t crc = 0;
+            for (size_t p = mems[m].piece0; p < mems[m].piece1; p++)
+                if (pieces[p].out_len) crc = gzp::crc32_combine(crc, crc_got[crc_of[p]], pieces[p].out_len);
+            if (crc != mems[m].crc) ok = false;
+        }
+        if (!ok) continue;  // (the stages behind decode the item again and say what it is)
+        b.cut_done[pl.item] = 1;
+        done.push_back(GzCutResult{pl.item, pl.members, (uint32_t)(pl.piece1 - pl.piece0), pl.out_len});
+        ctx->gz_cut_stats[3] += pl.piece1 - pl.piece0 - pl.members;
+        for (size_t p = pl.piece0; p < pl.piece1; p++) {
+            ctx->gz_cut_stats[pieces[p].marker ? 4 : 5]++;
+            ctx->gz_cut_stats[6] += resolved[p];
+        }
+    }
+    ctx->gz_cut_stats[7] = passes.size();
+    return ZNIPPY_OK;
+}
+
 static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n, void *d_out,
                         uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len, int32_t *status,
                         uint32_t *members, uint32_t *segments) {
@@ -3553,6 +3772,7 @@ static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, co
     if (!src_off || !src_len || !out_room || !out_len || !d_src || (out_cap && !d_out)) return ZNIPPY_E_INVAL;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     ctx->n_ktimes = 0;
+    memset(ctx->gz_cut_stats, 0, sizeof ctx->gz_cut_stats);
     { const int prc = poison_enter(ctx); if (prc) return prc; }
     if (!seg_min) {
         seg_min = gzp::SEG_MIN_DEFAULT;
@@ -3569,18 +3789,51 @@ static int gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, co
     if (!b.items.empty()) {
         struct Guard {
             znippy_ctx *ctx;
-            uint8_t *p = nullptr;
-            ~Guard() { tfree(ctx, p); }
+            uint8_t *p = nullptr, *find = nullptr, *cut = nullptr;
+            uint16_t *syms = nullptr;
+            ~Guard() { tfree(ctx, p); tfree(ctx, find); tfree(ctx, cut); tfree(ctx, syms); }
         } g{ctx};
+        const uint64_t cut = ctx->gz_cut;
+        gzcut::FindPlan fp;
+        if (cut && gzcut::find_plan(b.items.data(), b.items.size(), cut, fp) != gzcut::OK) fp = gzcut::FindPlan{};  // (beyond the slot limit: as with the value 0)
+        GzFindDev fd = gz_find_layout(fp);
         const GzLayout at = gz_layout(b);
         HIPCHK(ctx, tmalloc(ctx, &g.p, at.bytes));
+        GzCutDev cd{};
+        if (!fp.items.empty()) {
+            uint64_t budget = 1024ull << 20;
+            if (const char *e = getenv("ZNIPPY_GZ_CUT_SCRATCH_MB")) {
+                const unsigned long long v = strtoull(e, nullptr, 10);
+                if (v) budget = std::min<unsigned long long>(v, 1ull << 20) << 20;
+            }
+            cd = gz_cut_layout(fp, b, budget);
+            // (memory the value 0 does not take: where the device has none left for it, the call runs as with the value 0)
+            if (tmalloc(ctx, &g.find, fd.bytes) != hipSuccess || tmalloc(ctx, &g.cut, cd.bytes) != hipSuccess ||
+                tmalloc(ctx, &g.syms, (size_t)cd.budget_syms * 2) != hipSuccess) {
+                (void)hipGetLastError();
+                fp = gzcut::FindPlan{};
+            }
+        }
+        fd.p = g.find;
+        cd.p = g.cut;
+        cd.scratch = g.syms;
         const GzDev d{g.p, at, ctx->stream};
         if ((rc = gz_scan_stage(ctx, b, d))) return rc;
+        std::vector<uint64_t> cut_slots;
+        std::vector<GzCutResult> cut_res;
+        if (!fp.items.empty() && (rc = gz_find_stage(ctx, fp, fd, cut, cut_slots, ctx->stream))) return rc;
+        if (!fp.items.empty() && (rc = gz_cut_stage(ctx, b, d, fp, cd, cut_slots.data(), cut, seg_min, cut_res))) return rc;
         if ((rc = gz_candidates(b, seg_min))) return rc;
         if ((rc = gz_probe_stage(ctx, b, d))) return rc;
         if ((rc = gz_decode_plan(b))) return rc;
         if ((rc = gz_decode_stage(ctx, b, d))) return rc;
         gz_verdict(call, b);
+        for (const GzCutResult &r : cut_res) {  // (status 0, as gz_admit left it)
+            const uint32_t i = b.item_of[r.item];
+            out_len[i] = r.out_len;
+            if (members) members[i] = r.members;
+            if (segments) segments[i] = r.segments;
+        }
     }
     if (status) memcpy(status, b.st.data(), sizeof(int32_t) * n);
     return ZNIPPY_OK;

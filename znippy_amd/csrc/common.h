@@ -6,6 +6,7 @@
 #include <stddef.h>
 #include "host/bz_plan.h"        // the lists of znippy_bunzip2_batch
 #include "host/deflate_batch.h"  // the lists of the DEFLATE batch calls
+#include "host/gz_cut_plan.h"    // the lists of the block-start search of znippy_gunzip_batch
 #include "host/range_plan.h"
 #include "host/rows_plan.h"  // Tile, BigUnit and the constants the read side's host plan shares with the kernels
 #include "host/tar_list_plan.h"  // the lists of znippy_tar_list_batch
@@ -316,6 +317,19 @@ void launch_targz_find(const TargzItem *items, uint32_t n_items, const uint8_t *
 void launch_gunzip_scan(const GzItem *items, const GzScanChunk *chunks, uint32_t n_chunks, uint32_t *count, uint64_t *cands, hipStream_t s);
 void launch_gunzip_probe(const GzItem *items, const GzCand *cands, uint32_t n_cands, const uint32_t *stops, GzProbe *recs, hipStream_t s);
 void launch_gunzip_inflate(const GzItem *items, const GzRun *runs, uint32_t n_runs, int32_t *status, hipStream_t s);
+// The block-start search (host/gz_cut_plan.h): slots[] starts as NONE everywhere and *passed as 0.  Every bit position of every
+// searched item is tested (gz_cut_rules.h); a position that passes is counted and lowers the slot of its window of `cut` bytes.
+void launch_gunzip_find(const gzcut::FindItem *items, const gzcut::FindChunk *chunks, uint32_t n_chunks, uint32_t cut, unsigned long long *slots,
+                        unsigned long long *passed, hipStream_t s);
+// The cut at the block starts found (host/gz_cut_plan.h): a record per candidate; the pieces of a pass decoded (status[k] of piece k:
+// 0 or a ZNIPPY_E_*), marker pieces into scratch; then their last 32 KiB, group by group, and the rest of them made bytes.  The
+// pieces and groups given are those of one pass; *resolved is added to.
+void launch_gunzip_cut_probe(const GzItem *items, const gzcut::CutCand *cands, uint32_t n_cands, const uint64_t *stops, gzcut::CutRec *recs, hipStream_t s);
+void launch_gunzip_cut_decode(const GzItem *items, const gzcut::CutPiece *pieces, uint32_t n_pieces, uint16_t *scratch, int32_t *status, hipStream_t s);
+void launch_gunzip_cut_tails(const GzItem *items, const gzcut::CutPiece *pieces, const gzcut::CutGroup *groups, uint32_t n_groups, const uint16_t *scratch,
+                             unsigned long long *resolved, hipStream_t s);
+void launch_gunzip_cut_apply(const GzItem *items, const gzcut::CutPiece *pieces, uint32_t n_pieces, const uint16_t *scratch, unsigned long long *resolved,
+                             hipStream_t s);
 // list[k]: an item decoded from its first byte to its last by one wave, its members one after the other, trailers and padding checked
 void launch_gunzip_single(const GzItem *items, const uint32_t *list, uint32_t n_list, GzSingle *res, hipStream_t s);
 

@@ -170,6 +170,7 @@ uint64_t gz_raw_end(const GzBatch &b) {
 
 int gz_candidates(GzBatch &b, uint64_t seg_min) {
     for (uint32_t k = 0; k < b.items.size(); k++) {
+        if (k < b.cut_done.size() && b.cut_done[k]) continue;  // (decoded already, at block starts: api.hip, host/gz_cut_plan.h)
         if (!gz_has_raw(b, k)) { b.single.push_back(k); continue; }  // (its slice of raw was not copied back, or holds nothing)
         uint64_t *const c = b.raw.data() + b.items[k].cand_base;
         const size_t kept = gzp::keep_candidates(c, b.count[k], seg_min);

@@ -191,6 +191,9 @@ struct GzBatch {
     // the scan's answer (sized by gz_admit / to gz_raw_end, filled by api.hip)
     std::vector<uint32_t> count;      // [k]
     std::vector<uint64_t> raw;
+    // the cut at block starts (znippy_ctx_set_gunzip_cut; filled by api.hip, empty with the switch off): [k] != 0: the item is
+    // decoded and checked already, and gz_candidates gives it neither a probe nor the single pass
+    std::vector<uint8_t> cut_done;
     // gz_candidates
     std::vector<GzCand> cands;        // [c]
     std::vector<uint32_t> stops;      // kept flush positions, per probed item ascending

@@ -234,6 +234,24 @@ class Context:
                                              np_ptr(mem), np_ptr(seg)), "znippy_gunzip_batch")
         return status[:n], oo[:n], ol[:n], mem[:n], seg[:n]
 
+    GUNZIP_CUT_STATS = ("tested", "passed", "kept", "landed", "marker_pieces", "direct_pieces", "markers_resolved", "passes")
+
+    def set_gunzip_cut(self, cut_bytes):
+        """Opt-in: later gunzip_batch calls cut files at DEFLATE block starts found on the device, beside their members and flush points,
+        and decode the pieces in parallel.  0 (default, off) or 64 .. 2^30, the window in source bytes that keeps one block candidate.
+        Status, content and members are those of the value 0; segments counts the pieces.  See znippy_ctx_set_gunzip_cut in znippy_hip.h."""
+        self._chk(self.L.znippy_ctx_set_gunzip_cut(self.h, int(cut_bytes)), "znippy_ctx_set_gunzip_cut")
+
+    @property
+    def gunzip_cut(self):
+        return int(self.L.znippy_ctx_gunzip_cut(self.h))
+
+    def gunzip_cut_stats(self):
+        """The eight counters of the last gunzip_batch call (znippy_ctx_gunzip_cut_stats), in the order of GUNZIP_CUT_STATS."""
+        st = (C.c_uint64 * 8)()
+        self._chk(self.L.znippy_ctx_gunzip_cut_stats(self.h, st), "znippy_ctx_gunzip_cut_stats")
+        return [int(v) for v in st]
+
     # ---- whole bzip2 files held in device memory ----
     def bunzip2_batch(self, d_src, src_off, src_len, d_out, out_room, out_off=None, slot_cap=0, src_cap=None, out_cap=None):
         """znippy_bunzip2_batch: item i is the whole bzip2 file d_src[src_off[i] .. + src_len[i]); the content of all its streams goes
