@@ -29,6 +29,8 @@
  *                                over a batch of files          tar_gz_list_entries): the gunzip of a whole file
  *   znippy_bunzip2_batch         lbzip2 (host_decompress 2)     znippy-common/src/plugins/wasm_loader.rs:L18-31,L213-221 (codec 2),
  *                                over a batch of files          L410-441 (tar.bz2): the bunzip2 of a whole file
+ *   znippy_unxz_batch            nothing: the reference has no   .xz / .tar.xz / .txz are in its skip lists and stay stored rows; its ecosystem
+ *                                xz decoder, it skips the files  list (TODO_NOW.md, "Holger ecosystem") names an LZMA-family decoder, lzip
  *
  * Codec wire format: one standard Zstandard frame (RFC 8878) per chunk.  (The reference's
  * OpenZL framing cannot be reproduced or checked offline — see DESIGN.md "Oracle".)
@@ -488,7 +490,7 @@ int znippy_targz_find_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap
  * items launches no probe.  The same wave takes, member by member, an item whose candidates outnumber its slice of the list
  * (16 + src_len / 256), so that no result depends on which candidates could be kept.
  * Opt-in (znippy_ctx_set_gunzip_cut below): block starts found inside streams without flush points, and the pieces between them
- * decoded in parallel from their predecessors' last 32 KiB.  Out of scope: xz.  bzip2 files: znippy_bunzip2_batch below; listing the members of the tar inside: znippy_tar_list_batch. */
+ * decoded in parallel from their predecessors' last 32 KiB.  bzip2 files: znippy_bunzip2_batch below; xz files: znippy_unxz_batch; listing the members of the tar inside: znippy_tar_list_batch. */
 int znippy_gunzip_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
                         void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t seg_min, uint64_t *out_len,
                         int32_t *status, uint32_t *members, uint32_t *segments);
@@ -616,11 +618,89 @@ int znippy_ctx_gunzip_cut_stats(znippy_ctx *ctx, uint64_t out[8]);
  *   expand   one workgroup per block landed on: four equal bytes, then a count of 0..251 — into its final place, never beyond the
  *            block's exact byte count.  The state does not cross blocks.
  *   crc      one workgroup per block landed on, over the bytes written.
- * Out of scope: parallel Huffman decoding inside a block, randomised blocks, any bzip2 encoder, xz.  The members of the tar inside a
+ * Out of scope: parallel Huffman decoding inside a block, randomised blocks, any bzip2 encoder.  xz files: znippy_unxz_batch below.  The members of the tar inside a
  * .tar.bz2 are listed by znippy_tar_list_batch below, from the decompressed bytes. */
 int znippy_bunzip2_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
                          void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t slot_cap, uint64_t *out_len,
                          int32_t *status, uint32_t *streams, uint32_t *blocks);
+
+/* ---- whole xz files the engine already holds -----------------------------------------------------------------------------------
+ * .xz, .tar.xz and .txz — kernel and toolchain tarballs, distro packages, many source releases — are in the reference's skip lists
+ * (and in index.py's and znippy_host.cpp's), so they sit in the archive as stored rows, and the reference has no decoder for them: its
+ * ecosystem list (TODO_NOW.md, "Holger ecosystem") only names an LZMA-family decoder, lzip, beside lgz and lbzip2.  The arbiter here
+ * is liblzma 5.2, through Python's lzma.decompress.  An xz file names the compressed and the uncompressed size of every block in the
+ * index at the end of each stream, so every block's source range and output offset are known before a byte is decoded: all blocks of
+ * all items are decoded in one launch, a wave per block, straight into place.  Inside a block LZMA2 is an adaptive range coder and
+ * strictly serial: the call pays off for batches of files and for multi-block files (xz -T, pixz); a lone single-block file is one
+ * wave's work and far slower than a CPU thread (profiles/unxz_report.log).
+ *   d_src, src_cap     DEVICE: the region that holds the files; item i is the whole file d_src[src_off[i] .. + src_len[i])
+ *   d_out, out_cap     DEVICE: item i's content goes to d_out[out_off[i] .. + out_room[i]), its room
+ *   out_off            HOST, optional (NULL: the rooms lie back to back in array order)
+ *   out_room           HOST: the bytes item i may produce; measure mode says how many its indexes claim
+ *   out_len            HOST out: bytes produced; 0 for every status but 0
+ *   status             HOST, optional: per item, see below
+ *   streams, blocks    HOST out, optional: streams and blocks decoded (status 0)
+ *   unverified         HOST out, optional: the blocks of the item (status 0) whose integrity check was not verified, see Checks
+ * Measure mode: with d_out NULL and out_cap 0 nothing is written and out_room is not read; out_len[i] is the sum of the uncompressed
+ * sizes in the item's indexes.  No block header and no block data is read: the statuses come from the container walk alone, and
+ * ZNIPPY_E_DST_SMALL cannot occur.  This is the file's claim, which a full call verifies block by block.
+ * Container (xz file format 1.1.0).  An item is a sequence of streams, each optionally followed by stream padding (zero bytes, a
+ * multiple of four); an item of no bytes has no stream and no content (status 0).  It is walked from its end, as xz --list does: the
+ * footer (magic "YZ", CRC32 over backward size and flags), the index the backward size points at (indicator 0x00, record count,
+ * unpadded / uncompressed size pairs as VLIs, zero padding, CRC32), the stream header at index start - sum of the padded block sizes
+ * - 12, whose flags must equal the footer's, then the stream in front of that.  ZNIPPY_E_CORRUPT: any magic, CRC32 or padding that
+ * is not as said, a VLI longer than 9 bytes or with a needless trailing zero byte, a record with an unpadded size below 5, a record
+ * count the index bytes cannot hold, sizes that do not add up to the item, header and footer flags that differ, stream padding in
+ * front of the first stream, bytes behind the last stream that are not stream padding.  ZNIPPY_E_UNSUPPORTED: a reserved flag bit,
+ * content of 4 GiB or more.  ZNIPPY_E_DST_SMALL: more content than the room; nothing of that item is decoded.
+ * Two deviations from lzma.decompress, both towards the xz tool: lzma.decompress drops whatever follows stream padding
+ * (lzma.decompress(a + bytes(4) + b) is a's content alone), refuses padding behind the last stream, and ignores trailing bytes that
+ * are no stream; the xz tool decodes both streams, accepts the padding and refuses the garbage, and so does this call.
+ * Blocks.  The header: size byte, flags, optional compressed and uncompressed size, the filter list, zero padding, CRC32 (checked
+ * first: a damaged header is ZNIPPY_E_CORRUPT whatever its fields say); sizes that are present must be the index's.  Exactly one
+ * filter, LZMA2 (id 0x21, one property byte <= 40), is decoded; BCJ and delta filters, a filter chain, an unknown filter, a larger
+ * property byte and a reserved header flag are ZNIPPY_E_UNSUPPORTED.  LZMA2 chunks: control 0x00 ends the block, 0x01 / 0x02 are
+ * uncompressed chunks with / without a dictionary reset, 0x80-0xFF LZMA chunks (nothing / state reset / state reset + new properties
+ * / + dictionary reset), 0x03-0x7F are corrupt.  The first chunk must reset the dictionary; the first LZMA chunk behind a dictionary
+ * reset must bring properties; lc + lp <= 4 and a property byte <= 224.  An uncompressed chunk changes neither the LZMA state nor
+ * what the next chunk must bring: behind 0x02 an LZMA chunk may go on with no reset at all (liblzma's rule, found with hand-built
+ * chunk sequences).  The first byte of a chunk's range coder must be zero (liblzma checks it).  A chunk must consume exactly its
+ * compressed and produce exactly its uncompressed size, the 0x00 must stand exactly at the end of the block's compressed size, the
+ * output must be the index's uncompressed size, block padding must be zero.  An end marker inside LZMA2, a match that reaches in
+ * front of the last dictionary reset and one beyond the declared dictionary size are corrupt: liblzma 5.2 draws both lines at the
+ * same byte (its buffer is the declared size), so there is no deviation here.  All of these are ZNIPPY_E_CORRUPT.
+ * Checks.  CRC32 (id 1) and CRC64 (id 4, ECMA-182 reflected, polynomial 0xC96C5795D7870F42) are computed on the device over the bytes
+ * written and compared with the block's check field: a mismatch on an otherwise clean item is ZNIPPY_E_CHECKSUM.  With no check
+ * (id 0), SHA-256 (id 10) and the reserved ids the content is delivered with status 0 and the block counts in `unverified`, as the xz
+ * tool delivers it with a warning.  The first failure in stream order decides an item's status.
+ * Host validation and ZNIPPY_E_INVAL exactly as znippy_bunzip2_batch (required: src_off, src_len, out_len, and out_room unless in
+ * measure mode; d_src, and d_out when out_cap > 0); a room not inside out_cap is ZNIPPY_E_DST_SMALL; a src_len or room of 4 GiB or
+ * more is ZNIPPY_E_UNSUPPORTED.  n == 0 is ZNIPPY_OK.  The call returns ZNIPPY_OK whatever the items report.
+ * Writes: no byte of d_out outside the room of an item is written; inside the room of an item whose status is not 0 the bytes are
+ * unspecified; rooms must not overlap (not checked).  A damaged file is a status, never a fault, a hang or a stray write.
+ * Not a run, and synchronous on the context's stream, exactly as znippy_bunzip2_batch; no table is touched.  There is no scratch slot
+ * per block, hence no slot_cap.  The tail stage's lists and staging buffer (72 bytes and at most 1,040 staged bytes per item) are
+ * allocated before the first stream operation; a later round that asks for more, a long index, takes a larger staging buffer
+ * (index bytes <= source bytes: a round never stages more than the source holds); the job lists (72 bytes per block), whose size
+ * only the walk gives, are allocated when the rounds are over and the stream is idle.  ZNIPPY_POISON fills them all.
+ * Stages (csrc/unxz.hip, csrc/host/xz_plan.h; znippy_last_kernel_times: unxz_tail once per round, unxz_decode, unxz_check — only
+ * those that were launched):
+ *   tail     a wave per byte range the host's container walk asks for; one copy back per round.  The first round brings every
+ *            item's last 1 KiB and its first 12 bytes, which hold footer, index and header of most one-stream files: a batch of
+ *            those takes one round; a stream in front of another, a longer index or long padding takes a round more each.
+ *   plan     (host) all parsing, every container rule, the block job list (source range, output offset, declared sizes, check id)
+ *            and the judgement of the decode records.  No byte and no record from the device is trusted: each is checked against
+ *            the item and the index.
+ *   decode   one wave per block: its own block header, the LZMA2 chunks, the range decoder in wave-uniform control flow (range,
+ *            code, state and rep0-3 in scalars, probabilities as 16-bit cells in LDS, input through an LDS window), literals stored
+ *            64 at a time, matches and uncompressed chunks copied by all lanes.  28,560 bytes of LDS per wave: five blocks per CU.
+ *   check    one workgroup per block with check id 1 or 4, over the bytes written.
+ * Out of scope: any xz or LZMA encoder, .lzma (LZMA-alone) and .lz (lzip) files, BCJ and delta filters, SHA-256 verification,
+ * parallelism inside a block.  The members of the tar inside a .tar.xz are listed by znippy_tar_list_batch below, from the
+ * decompressed bytes. */
+int znippy_unxz_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
+                      void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t *out_len, int32_t *status,
+                      uint32_t *streams, uint32_t *blocks, uint32_t *unverified);
 
 /* ---- the members of tars held in device memory ------------------------------------------ */
 #ifndef ZNIPPY_TAR_MEMBER_DEFINED

@@ -227,6 +227,18 @@ int znippy_archive_gunzip_files(znippy_archive *a, const char *const *relative_p
  * by znippy_archive_list_tar_members below. */
 int znippy_archive_bunzip2_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap,
                                  uint64_t *entry_off /* n_files + 1 */, int32_t *status);
+/* For every archived file of relative_paths (each an xz file: a .xz, a .tar.xz / .txz source tarball or package): its whole content,
+ * all streams concatenated.  The reference has no xz decoder: such files are in its skip lists, stay stored rows, and a user takes
+ * them to liblzma on the host.  The files are gathered whole on the device — one range-read pass whose result is not copied to the
+ * host — and the znippy_unxz_batch of include/znippy_hip.h runs twice on them there: in measure mode, which reads the sizes the
+ * files' indexes claim and gives every file's room, then into those rooms, every block of every file in one launch, CRC32 and CRC64
+ * checks verified.  Only the contents come back to the host.
+ * Results, statuses, the sizes-only call (dst NULL, cap 0) and the return value exactly as znippy_archive_bunzip2_files, with the
+ * per-item codes of that call (ZNIPPY_E_CORRUPT — a file that is no xz file too —, ZNIPPY_E_CHECKSUM, ZNIPPY_E_UNSUPPORTED:
+ * BCJ and delta filters, reserved flags).  Blocks whose check is none, SHA-256 or a reserved id are delivered unverified, as the xz
+ * tool delivers them.  The members of the tar inside a .tar.xz are listed and extracted by znippy_archive_list_tar_members below. */
+int znippy_archive_unxz_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap,
+                              uint64_t *entry_off /* n_files + 1 */, int32_t *status);
 #ifndef ZNIPPY_TAR_MEMBER_DEFINED
 #define ZNIPPY_TAR_MEMBER_DEFINED
 /* one regular member of a tar (include/znippy_hip.h: znippy_tar_list_batch) */
@@ -237,14 +249,15 @@ typedef struct {
     uint32_t name_len, typeflag;         /* typeflag: '0', 0 or '7' */
 } znippy_tar_member;
 #endif
-/* For every archived file of relative_paths (a .tar, a .tar.gz / .tgz / .crate, a .tar.bz2 / .tbz2): every regular member of the tar
+/* For every archived file of relative_paths (a .tar, a .tar.gz / .tgz / .crate, a .tar.bz2 / .tbz2, a .tar.xz / .txz): every regular member of the tar
  * in it whose name starts with name_prefix and ends with name_suffix (either may be NULL or empty) — what the reference's
  * host_archive_open formats 1 and 2 (wasm_loader.rs: tar_gz_list_entries, tar_bz2_list_entries) return through
  * tar_entries_from_bytes and host_archive_list / host_archive_entry then serve, for all files at once.  The files are gathered whole
  * on the device — one range-read pass whose result is not copied to the host; only the first three and the last four bytes of each
  * come back at this point.  Each goes by its first bytes: 1f 8b through
  * znippy_gunzip_batch, with rooms from ISIZE and the retry rule of znippy_archive_gunzip_files; "BZh" through znippy_bunzip2_batch,
- * in measure mode and then for the decode; anything else is taken as a plain tar.  One znippy_tar_list_batch of include/znippy_hip.h then
+ * in measure mode and then for the decode; fd 37 7a ("\3757z", an xz file) through znippy_unxz_batch in the same two steps; anything
+ * else is taken as a plain tar.  One znippy_tar_list_batch of include/znippy_hip.h then
  * lists all the tars there.  Only the member tables and the names come back to the host, and the members' contents when dst is given.
  * Results as in that call: the members of file i are members[member_first[i] .. member_first[i + 1]) (member_first: n_files + 1
  * values; offsets relative to the decompressed tar), their names packed in names, their contents packed in dst at out_off;

@@ -55,7 +55,7 @@ EXPORTS = [
     "znippy_rows_read_ranges_verified",
     "znippy_rounds_emit_block_tree", "znippy_rounds_block_tree_layout", "znippy_rounds_block_tree",
     "znippy_inflate_batch", "znippy_targz_find_batch", "znippy_gunzip_batch", "znippy_roles_wait_stats",
-    "znippy_bunzip2_batch", "znippy_tar_list_batch",
+    "znippy_bunzip2_batch", "znippy_tar_list_batch", "znippy_unxz_batch",
     "znippy_ctx_set_gunzip_cut", "znippy_ctx_gunzip_cut", "znippy_ctx_gunzip_cut_stats",
 ]
 
@@ -172,6 +172,8 @@ def lib():
     if hasattr(L, "znippy_tar_list_batch"):  # (likewise)
         L.znippy_tar_list_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, C.c_char_p, C.c_uint64, C.c_char_p, C.c_uint64, vp, C.c_uint64,
                                             vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp]
+    if hasattr(L, "znippy_unxz_batch"):  # (likewise)
+        L.znippy_unxz_batch.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64, vp, C.c_uint64, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "znippy_roles_wait_stats"):  # (likewise)
         L.znippy_roles_wait_stats.argtypes = [vp, C.POINTER(C.c_uint32), vp, C.c_uint64, C.POINTER(C.c_uint64)]
     _lib = L

@@ -4095,3 +4095,94 @@ extern "C" int znippy_tar_list_batch(znippy_ctx *ctx, const void *d_tar, uint64_
     ZN_NO_THROW(tar_list_batch(ctx, d_tar, tar_cap, tar_off, tar_len, n, name_prefix, prefix_len, name_suffix, suffix_len, members, members_cap, names,
                                names_cap, d_out, out_cap, member_first, names_bytes, out_bytes, status))
 }
+
+// ---- whole xz files (znippy_unxz_batch) ----------------------------------------------------------------
+// The items that pass xz_admit are walked from their ends: a round brings the byte ranges the walks ask for to the host
+// (xz_wants, the tail launch, one copy back, xz_give) until every walk is done — one round for one-stream files whose footer and
+// index lie in the last XZ_TAIL bytes.  xz_plan_jobs then knows every block; one decode launch and one check launch serve them
+// all, and xz_verdict judges the records.  Device memory: the tail stage's lists and staging buffer, sized from the item count
+// and the first round's ranges and made before the first stream operation (a later round that asks for more, a long index,
+// gets a larger staging buffer: never more than the source bytes); the job lists, whose size only the walk gives, once the rounds
+// are over and the stream is idle.
+static_assert(XZ_OK == ZNIPPY_OK && XZ_E_INVAL == ZNIPPY_E_INVAL && XZ_E_NOMEM == ZNIPPY_E_NOMEM && XZ_E_DST_SMALL == ZNIPPY_E_DST_SMALL &&
+              XZ_E_CORRUPT == ZNIPPY_E_CORRUPT && XZ_E_UNSUPPORTED == ZNIPPY_E_UNSUPPORTED && XZ_E_CHECKSUM == ZNIPPY_E_CHECKSUM,
+              "host/xz_plan.h gives out the codes of znippy_hip.h");
+
+static int unxz_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n, void *d_out,
+                      uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t *out_len, int32_t *status, uint32_t *streams,
+                      uint32_t *blocks, uint32_t *unverified) {
+    if (!ctx_enter(ctx)) return ZNIPPY_E_INVAL;
+    if (!ctx || n >= 0xFFFFFFF0ull) return ZNIPPY_E_INVAL;
+    if (!n) return ZNIPPY_OK;
+    const bool measure = !d_out && !out_cap;
+    if (!src_off || !src_len || (!measure && !out_room) || !out_len || !d_src || (out_cap && !d_out)) return ZNIPPY_E_INVAL;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->n_ktimes = 0;
+    { const int prc = poison_enter(ctx); if (prc) return prc; }
+
+    const XzCall call{(const uint8_t *)d_src, src_cap, src_off, src_len, n, (uint8_t *)d_out, out_cap, out_off, out_room, out_len, streams, blocks, unverified};
+    XzBatch b;
+    int rc;
+    if ((rc = xz_admit(call, b))) return rc;
+    if (!b.items.empty()) {
+        struct Guard {
+            znippy_ctx *ctx;
+            uint8_t *lists = nullptr, *stage = nullptr, *jobs = nullptr;
+            ~Guard() { tfree(ctx, lists); tfree(ctx, stage); tfree(ctx, jobs); }
+        } g{ctx};
+        hipStream_t s = ctx->stream;
+        const size_t n_items = b.items.size();
+        const size_t items_bytes = (sizeof(XzItem) * n_items + 15) & ~(size_t)15;
+        uint64_t need = xz_wants(b), stage_cap = need;
+        HIPCHK(ctx, tmalloc(ctx, &g.lists, items_bytes + 2 * sizeof(XzRange) * n_items));
+        HIPCHK(ctx, tmalloc(ctx, &g.stage, (size_t)stage_cap));
+        const XzItem *d_items = (const XzItem *)g.lists;
+        XzRange *d_ranges = (XzRange *)(g.lists + items_bytes);
+        HIPCHK(ctx, hipMemcpyAsync(g.lists, b.items.data(), sizeof(XzItem) * n_items, hipMemcpyHostToDevice, s));
+        while (need) {
+            if (need > stage_cap) {  // (the stream is idle: the round before ended with a wait)
+                tfree(ctx, g.stage);
+                g.stage = nullptr;
+                HIPCHK(ctx, tmalloc(ctx, &g.stage, (size_t)need));
+                stage_cap = need;
+            }
+            const uint32_t n_ranges = (uint32_t)b.ranges.size();  // (at most two per item)
+            HIPCHK(ctx, hipMemcpyAsync(d_ranges, b.ranges.data(), sizeof(XzRange) * n_ranges, hipMemcpyHostToDevice, s));
+            timed(ctx, "unxz_tail", s, [&] { launch_unxz_tail(d_items, d_ranges, n_ranges, g.stage, s); });
+            HIPCHK(ctx, hipGetLastError());
+            b.stage.resize((size_t)need);
+            HIPCHK(ctx, hipMemcpyAsync(b.stage.data(), g.stage, (size_t)need, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+            xz_give(b);
+            need = xz_wants(b);
+        }
+        if ((rc = xz_plan_jobs(call, b))) return rc;
+        const size_t n_jobs = b.jobs.size();
+        if (n_jobs) {  // (never in measure mode)
+            const size_t jobs_bytes = (sizeof(XzJob) * n_jobs + 15) & ~(size_t)15, recs_bytes = sizeof(XzRec) * n_jobs;
+            HIPCHK(ctx, tmalloc(ctx, &g.jobs, jobs_bytes + recs_bytes + sizeof(uint64_t) * n_jobs));
+            const XzJob *d_jobs = (const XzJob *)g.jobs;
+            XzRec *d_recs = (XzRec *)(g.jobs + jobs_bytes);
+            uint64_t *d_sums = (uint64_t *)(g.jobs + jobs_bytes + recs_bytes);
+            HIPCHK(ctx, hipMemcpyAsync(g.jobs, b.jobs.data(), sizeof(XzJob) * n_jobs, hipMemcpyHostToDevice, s));
+            timed(ctx, "unxz_decode", s, [&] { launch_unxz_decode(d_items, d_jobs, (uint32_t)n_jobs, d_recs, s); });
+            HIPCHK(ctx, hipGetLastError());
+            timed(ctx, "unxz_check", s, [&] { launch_unxz_check(d_items, d_jobs, (uint32_t)n_jobs, d_sums, s); });
+            HIPCHK(ctx, hipGetLastError());
+            b.recs.resize(n_jobs);
+            b.sums.resize(n_jobs);
+            HIPCHK(ctx, hipMemcpyAsync(b.recs.data(), d_recs, recs_bytes, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipMemcpyAsync(b.sums.data(), d_sums, sizeof(uint64_t) * n_jobs, hipMemcpyDeviceToHost, s));
+            HIPCHK(ctx, hipStreamSynchronize(s));
+        }
+        xz_verdict(call, b);
+    }
+    if (status) memcpy(status, b.st.data(), sizeof(int32_t) * n);
+    return ZNIPPY_OK;
+}
+
+extern "C" int znippy_unxz_batch(znippy_ctx *ctx, const void *d_src, uint64_t src_cap, const uint64_t *src_off, const uint64_t *src_len, uint64_t n,
+                                 void *d_out, uint64_t out_cap, const uint64_t *out_off, const uint64_t *out_room, uint64_t *out_len, int32_t *status,
+                                 uint32_t *streams, uint32_t *blocks, uint32_t *unverified) {
+    ZN_NO_THROW(unxz_batch(ctx, d_src, src_cap, src_off, src_len, n, d_out, out_cap, out_off, out_room, out_len, status, streams, blocks, unverified))
+}

@@ -9,6 +9,7 @@
 #include "host/gz_cut_plan.h"    // the lists of the block-start search of znippy_gunzip_batch
 #include "host/range_plan.h"
 #include "host/rows_plan.h"  // Tile, BigUnit and the constants the read side's host plan shares with the kernels
+#include "host/xz_plan.h"    // the lists of znippy_unxz_batch
 #include "host/tar_list_plan.h"  // the lists of znippy_tar_list_batch
 
 namespace zn {
@@ -361,5 +362,13 @@ void launch_tar_emit(const TlItem *items, uint32_t n_items, const TlChunk *chunk
 void launch_tar_emit_write(const TlItem *items, const TlChunk *chunks, uint32_t n_chunks, const TlNode *nodes, const uint32_t *pick, const uint32_t *src,
                            const TlSum *sums, const TlBase *bases, znippy_tar_member *members, uint64_t members_cap, char *names, uint64_t names_cap,
                            hipStream_t s);
+
+// Whole xz files (znippy_unxz_batch, unxz.hip): XzItem, XzRange, XzJob and XzRec are in host/xz_plan.h.
+// the bytes of every range to stage + at
+void launch_unxz_tail(const XzItem *items, const XzRange *ranges, uint32_t n_ranges, uint8_t *stage, hipStream_t s);
+// recs[j] for every job; a block's content into its place in the item's room, never a byte outside [out_off, out_off + out_len)
+void launch_unxz_decode(const XzItem *items, const XzJob *jobs, uint32_t n_jobs, XzRec *recs, hipStream_t s);
+// sums[j] = the CRC32 (check id 1) or CRC64 (check id 4) of the bytes of job j's place, 0 for every other check id
+void launch_unxz_check(const XzItem *items, const XzJob *jobs, uint32_t n_jobs, uint64_t *sums, hipStream_t s);
 
 }  // namespace zn

@@ -21,6 +21,7 @@
 #include <cstdio>
 #include <cstring>
 #include <fcntl.h>
+#include <functional>
 #include <map>
 #include <memory>
 #include <sched.h>
@@ -1773,12 +1774,14 @@ static int znippy_archive_gunzip_files_impl(znippy_archive *a, const char *const
     return ZNIPPY_OK;
 }
 
-// ---- the content of archived bzip2 files (znippy_archive_bunzip2_files) --------------------------
-// The files are gathered whole on the device (one range read, no copy to the host).  bzip2 names no size anywhere, so
-// znippy_bunzip2_batch runs twice there: in measure mode, which gives every file's room, then into those rooms.  Only the contents
-// come back to the host.
-static int znippy_archive_bunzip2_files_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
-                                             int32_t *status) {
+// ---- the content of archived bzip2 and xz files (znippy_archive_bunzip2_files, znippy_archive_unxz_files) -----------------------
+// The files are gathered whole on the device (one range read, no copy to the host).  The batch call of the format
+// (znippy_bunzip2_batch, znippy_unxz_batch) runs twice there: in measure mode, which gives every file's room (bzip2 names no size
+// anywhere; an xz file names it in its indexes), then into those rooms.  Only the contents come back to the host.
+// batch(src, src_cap, src_off, src_len, n, out, out_cap, out_room, out_len, status) is that call on the archive's context.
+typedef std::function<int(const void *, uint64_t, const uint64_t *, const uint64_t *, uint64_t, void *, uint64_t, const uint64_t *, uint64_t *, int32_t *)> MeasuredBatch;
+static int archive_measured_files_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
+                                       int32_t *status, const char *what, const MeasuredBatch &batch) {
     if (!a || !entry_off || (n_files && !paths) || (cap && !dst)) return fail(ZNIPPY_E_INVAL, "null argument");
     const size_t n = (size_t)n_files;
     const bool sizes_only = !dst && !cap;  // the sizes of the contents alone: entry_off as if every clean file had been written
@@ -1815,9 +1818,8 @@ static int znippy_archive_bunzip2_files_impl(znippy_archive *a, const char *cons
         std::vector<int32_t> ist(todo.size(), 0);
         uint64_t out_total = 0;
         if (!todo.empty()) {
-            rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), nullptr, 0, nullptr, nullptr, 0, o_room.data(),
-                                      ist.data(), nullptr, nullptr);
-            if (rc) return fail(rc, std::string("bunzip2 (measure) failed: ") + znippy_last_error(a->ctx));
+            rc = batch(bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), nullptr, 0, nullptr, o_room.data(), ist.data());
+            if (rc) return fail(rc, std::string(what) + " (measure) failed: " + znippy_last_error(a->ctx));
             for (size_t j = 0; j < todo.size(); j++) {
                 if (ist[j] != 0) { st[who[todo[j]]] = ist[j]; o_room[j] = 0; }  // (this status stands; the file takes no room in the second call)
                 if (o_room[j] >= (1ull << 32)) { st[who[todo[j]]] = ZNIPPY_E_UNSUPPORTED; o_room[j] = 0; }
@@ -1830,9 +1832,8 @@ static int znippy_archive_bunzip2_files_impl(znippy_archive *a, const char *cons
         }
         if (!todo.empty()) {
             if (!bufs.d_blobs.reserve(out_total + 64)) return fail(ZNIPPY_E_NOMEM, "device allocation failed");  // (the chunks in it have been gathered from)
-            rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), bufs.d_blobs.p, out_total, nullptr, o_room.data(), 0,
-                                      o_len.data(), ist.data(), nullptr, nullptr);
-            if (rc) return fail(rc, std::string("bunzip2 failed: ") + znippy_last_error(a->ctx));
+            rc = batch(bufs.d_out.p, total, s_off.data(), s_len.data(), todo.size(), bufs.d_blobs.p, out_total, o_room.data(), o_len.data(), ist.data());
+            if (rc) return fail(rc, std::string(what) + " failed: " + znippy_last_error(a->ctx));
             if (!bufs.blob_pin.reserve(out_total + 64)) return fail(ZNIPPY_E_NOMEM, "page-locked allocation failed");
             if (out_total && hipMemcpy(bufs.blob_pin.p, bufs.d_blobs.p, out_total, hipMemcpyDeviceToHost) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2H failed");
             uint64_t o = 0;
@@ -1864,7 +1865,7 @@ static int znippy_archive_bunzip2_files_impl(znippy_archive *a, const char *cons
 // The files are gathered whole on the device (one range read, no copy to the host); the first three and the last four bytes of each
 // come back (copies queued together, one wait) and say which way it goes and, for a gzip file, its room: gzip files go through
 // znippy_gunzip_batch (rooms from ISIZE, the retry rule of znippy_archive_gunzip_files), bzip2 files through znippy_bunzip2_batch
-// (measured, then decoded), the others are copied as they are — all into one device region, the tars, over which one
+// and xz files through znippy_unxz_batch (both measured, then decoded), the others are copied as they are — all into one device region, the tars, over which one
 // znippy_tar_list_batch runs; where every file is a plain tar the listing runs on the gathered files themselves.  Member tables and
 // names come back, and the contents when dst is given.
 static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *const *paths, uint64_t n_files, const char *name_prefix, const char *name_suffix,
@@ -1893,7 +1894,7 @@ static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *c
     }
     int rc = archive_ctx(a);
     if (rc) return rc;
-    enum { PLAIN, GZ, BZ };
+    enum { PLAIN, GZ, BZ, XZ };
     struct Tar { size_t file; uint64_t src, len; int kind; uint64_t room, off, tar_len; };
     std::vector<Tar> tars;  // in file order
     if (!who.empty()) {
@@ -1924,15 +1925,17 @@ static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *c
             const uint8_t *const head = ends + 8 * k, *const tail = head + 4;
             if (t.len >= 2 && head[0] == 0x1f && head[1] == 0x8b) t.kind = GZ;
             else if (t.len >= 3 && head[0] == 'B' && head[1] == 'Z' && head[2] == 'h') t.kind = BZ;
+            else if (t.len >= 3 && head[0] == 0xFD && head[1] == '7' && head[2] == 'z') t.kind = XZ;
             if (t.kind == GZ && t.len >= 4)
                 t.room = std::min<uint64_t>((uint64_t)tail[0] | (uint64_t)tail[1] << 8 | (uint64_t)tail[2] << 16 | (uint64_t)tail[3] << 24, most(t));
             if (t.kind == PLAIN) t.room = t.tar_len = t.len;
             tars.push_back(t);
         }
-        // 2) the rooms of the bzip2 files
-        std::vector<size_t> bz, gz;
+        // 2) the rooms of the bzip2 and xz files
+        std::vector<size_t> bz, xz, gz;
         for (size_t j = 0; j < tars.size(); j++) {
             if (tars[j].kind == BZ) bz.push_back(j);
+            else if (tars[j].kind == XZ) xz.push_back(j);
             else if (tars[j].kind == GZ) gz.push_back(j);
         }
         std::vector<uint64_t> s_off, s_len, o_off, o_room, o_len;
@@ -1943,13 +1946,22 @@ static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *c
             o_len.assign(sel.size(), 0);
             ist.assign(sel.size(), 0);
         };
-        if (!bz.empty()) {
-            lists(bz);
-            rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), bz.size(), nullptr, 0, nullptr, nullptr, 0, o_len.data(), ist.data(),
-                                      nullptr, nullptr);
-            if (rc) return fail(rc, std::string("bunzip2 (measure) failed: ") + znippy_last_error(a->ctx));
-            for (size_t q = 0; q < bz.size(); q++) {
-                Tar &t = tars[bz[q]];
+        // the batch call of a kind over the lists: measure mode without `out`
+        auto measured_batch = [&](int kind, size_t n_sel, uint8_t *out, uint64_t out_cap) {
+            const uint64_t *off = out ? o_off.data() : nullptr, *room = out ? o_room.data() : nullptr;
+            return kind == BZ ? znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), n_sel, out, out_cap, off, room, 0, o_len.data(),
+                                                     ist.data(), nullptr, nullptr)
+                              : znippy_unxz_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), n_sel, out, out_cap, off, room, o_len.data(), ist.data(),
+                                                  nullptr, nullptr, nullptr);
+        };
+        for (int kind : {BZ, XZ}) {
+            const std::vector<size_t> &of_kind = kind == BZ ? bz : xz;
+            if (of_kind.empty()) continue;
+            lists(of_kind);
+            rc = measured_batch(kind, of_kind.size(), nullptr, 0);
+            if (rc) return fail(rc, std::string(kind == BZ ? "bunzip2" : "unxz") + " (measure) failed: " + znippy_last_error(a->ctx));
+            for (size_t q = 0; q < of_kind.size(); q++) {
+                Tar &t = tars[of_kind[q]];
                 if (ist[q]) st[t.file] = ist[q];
                 else if (o_len[q] >= (1ull << 32)) st[t.file] = ZNIPPY_E_UNSUPPORTED;
                 else t.room = o_len[q];
@@ -1960,7 +1972,7 @@ static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *c
         // is not ordered behind the null stream, so the copies are queued there and waited for before a batch call reads the region.
         DevBuf region;
         uint64_t region_len = 0;
-        const bool in_place = bz.empty() && gz.empty();
+        const bool in_place = bz.empty() && xz.empty() && gz.empty();
         auto give_room = [&](Tar &t) { t.off = region_len; region_len = (region_len + t.room + 15) & ~15ull; };
         if (in_place) {
             for (Tar &t : tars) t.off = t.src;
@@ -1974,15 +1986,14 @@ static int znippy_archive_list_tar_members_impl(znippy_archive *a, const char *c
                     return fail(ZNIPPY_E_HIP, "D2D failed");
             if (hipStreamSynchronize(nullptr) != hipSuccess) return fail(ZNIPPY_E_HIP, "D2D failed");
         }
-        {
+        for (int kind : {BZ, XZ}) {
             std::vector<size_t> sel;
-            for (size_t j : bz)
+            for (size_t j : kind == BZ ? bz : xz)
                 if (st[tars[j].file] == 0) sel.push_back(j);
             if (!sel.empty()) {
                 lists(sel);
-                rc = znippy_bunzip2_batch(a->ctx, bufs.d_out.p, total, s_off.data(), s_len.data(), sel.size(), region.p, region_len, o_off.data(), o_room.data(), 0,
-                                          o_len.data(), ist.data(), nullptr, nullptr);
-                if (rc) return fail(rc, std::string("bunzip2 failed: ") + znippy_last_error(a->ctx));
+                rc = measured_batch(kind, sel.size(), region.p, region_len);
+                if (rc) return fail(rc, std::string(kind == BZ ? "bunzip2" : "unxz") + " failed: " + znippy_last_error(a->ctx));
                 for (size_t q = 0; q < sel.size(); q++) { st[tars[sel[q]].file] = ist[q]; tars[sel[q]].tar_len = o_len[q]; }
             }
         }
@@ -2054,7 +2065,24 @@ int znippy_archive_list_tar_members(znippy_archive *a, const char *const *relati
 
 int znippy_archive_bunzip2_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
                                  int32_t *status) {
-    return guarded([&] { return znippy_archive_bunzip2_files_impl(a, relative_paths, n_files, dst, cap, entry_off, status); });
+    return guarded([&] {
+        return archive_measured_files_impl(a, relative_paths, n_files, dst, cap, entry_off, status, "bunzip2",
+                                           [&](const void *src, uint64_t src_cap, const uint64_t *s_off, const uint64_t *s_len, uint64_t n, void *out, uint64_t out_cap,
+                                               const uint64_t *room, uint64_t *len, int32_t *st) {
+                                               return znippy_bunzip2_batch(a->ctx, src, src_cap, s_off, s_len, n, out, out_cap, nullptr, room, 0, len, st, nullptr, nullptr);
+                                           });
+    });
+}
+
+int znippy_archive_unxz_files(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, void *dst, size_t cap, uint64_t *entry_off,
+                              int32_t *status) {
+    return guarded([&] {
+        return archive_measured_files_impl(a, relative_paths, n_files, dst, cap, entry_off, status, "unxz",
+                                           [&](const void *src, uint64_t src_cap, const uint64_t *s_off, const uint64_t *s_len, uint64_t n, void *out, uint64_t out_cap,
+                                               const uint64_t *room, uint64_t *len, int32_t *st) {
+                                               return znippy_unxz_batch(a->ctx, src, src_cap, s_off, s_len, n, out, out_cap, nullptr, room, len, st, nullptr, nullptr, nullptr);
+                                           });
+    });
 }
 
 int znippy_archive_extract_zip_entries(znippy_archive *a, const char *const *relative_paths, uint64_t n_files, const char *name_prefix,

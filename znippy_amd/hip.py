@@ -287,6 +287,41 @@ class Context:
                                               np_ptr(ol), np_ptr(status), np_ptr(streams), np_ptr(blocks)), "znippy_bunzip2_batch")
         return status[:n], ol[:n], streams[:n], blocks[:n]
 
+    # ---- whole xz files held in device memory ----
+    def unxz_batch(self, d_src, src_off, src_len, d_out, out_room, out_off=None, src_cap=None, out_cap=None):
+        """znippy_unxz_batch: item i is the whole xz file d_src[src_off[i] .. + src_len[i]); the content of all its streams goes to
+        d_out + out_off[i] (None: the rooms lie back to back in array order) and may take out_room[i] bytes (unxz_sizes says how
+        many the file claims).  Every block of every item is decoded in one launch, a wave per block, straight into its place; CRC32
+        and CRC64 checks are verified.  Synchronous and not a run.  Returns (status per item: 0 or ZNIPPY_E_*, out_off, out_len — 0
+        unless the status is 0 —, streams, blocks, unverified: the blocks whose check is none, SHA-256 or a reserved id)."""
+        so, sl, room = as_np(src_off, np.uint64), as_np(src_len, np.uint64), as_np(out_room, np.uint64)
+        n = len(so)
+        assert len(sl) == n and len(room) == n and (out_off is None or len(out_off) == n), "item arrays differ in length"
+        oo = as_np(out_off, np.uint64) if out_off is not None else np.concatenate([[0], np.cumsum(room)[:-1]]).astype(np.uint64)
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        out_cap = d_out.numel() if out_cap is None else out_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ol = np.zeros(max(n, 1), dtype=np.uint64)
+        streams, blocks, unverified = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        self._chk(self.L.znippy_unxz_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), n, _dptr(d_out), int(out_cap),
+                                           np_ptr(oo) if out_off is not None else None, np_ptr(room), np_ptr(ol), np_ptr(status),
+                                           np_ptr(streams), np_ptr(blocks), np_ptr(unverified)), "znippy_unxz_batch")
+        return status[:n], oo[:n], ol[:n], streams[:n], blocks[:n], unverified[:n]
+
+    def unxz_sizes(self, d_src, src_off, src_len, src_cap=None):
+        """znippy_unxz_batch in measure mode (no output buffer): the container walk alone — no block is read, nothing is written.
+        Returns (status per item, the size each file's indexes claim — 0 unless the status is 0 —, streams, blocks, unverified)."""
+        so, sl = as_np(src_off, np.uint64), as_np(src_len, np.uint64)
+        n = len(so)
+        assert len(sl) == n, "item arrays differ in length"
+        src_cap = d_src.numel() if src_cap is None else src_cap
+        status = np.zeros(max(n, 1), dtype=np.int32)
+        ol = np.zeros(max(n, 1), dtype=np.uint64)
+        streams, blocks, unverified = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        self._chk(self.L.znippy_unxz_batch(self.h, _dptr(d_src), int(src_cap), np_ptr(so), np_ptr(sl), n, None, 0, None, None, np_ptr(ol),
+                                           np_ptr(status), np_ptr(streams), np_ptr(blocks), np_ptr(unverified)), "znippy_unxz_batch")
+        return status[:n], ol[:n], streams[:n], blocks[:n], unverified[:n]
+
     # ---- the members of tars held in device memory ----
     def tar_list_batch(self, d_tar, tar_off, tar_len, suffix=b"", prefix=b"", d_out=None, members_cap=None, names_cap=None, tar_cap=None, out_cap=None,
                        measure=False):

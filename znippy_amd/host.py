@@ -29,7 +29,7 @@ class _ME(C.Structure):
 HOST_EXPORTS = [
     "znippy_host_last_error", "znippy_compress_stream", "znippy_stream_send", "znippy_stream_send_packed", "znippy_stream_finish",
     "znippy_compress_dir", "znippy_decompress_archive", "znippy_archive_open", "znippy_archive_file_count", "znippy_archive_file_size",
-    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_archive_bunzip2_files", "znippy_archive_list_tar_members", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
+    "znippy_archive_extract_file", "znippy_archive_extract_file_verified", "znippy_archive_read_range", "znippy_archive_read_range_verified", "znippy_archive_block_tree_stats", "znippy_archive_extract_zip_entries", "znippy_archive_extract_tar_members", "znippy_archive_gunzip_files", "znippy_archive_bunzip2_files", "znippy_archive_unxz_files", "znippy_archive_list_tar_members", "znippy_zip_end_of_directory", "znippy_zip_find_entry", "znippy_zip_local_data_offset", "znippy_archive_close", "znippy_index_open", "znippy_index_rows",
     "znippy_index_manifest_len", "znippy_index_manifest_entry", "znippy_index_row", "znippy_index_metadata",
     "znippy_index_close", "znippy_interpret_footer", "znippy_write_manifest_bytes",
 ]
@@ -65,6 +65,8 @@ def lib():
         L.znippy_archive_gunzip_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
         if hasattr(L, "znippy_archive_bunzip2_files"):  # (a library built before the call existed still loads)
             L.znippy_archive_bunzip2_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
+        if hasattr(L, "znippy_archive_unxz_files"):  # (likewise)
+            L.znippy_archive_unxz_files.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, vp, C.c_size_t, vp, vp]
         if hasattr(L, "znippy_archive_list_tar_members"):  # (likewise)
             L.znippy_archive_list_tar_members.argtypes = [vp, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_char_p, vp, C.c_uint64, vp, C.c_uint64, vp,
                                                           C.c_size_t, vp, vp, vp, vp]
@@ -335,25 +337,35 @@ class ZnippyArchive:
         size), then their blocks are decoded in parallel and every block CRC and combined CRC is checked.  cap: bytes of the result
         buffer.  None: the sizes are measured first (a call without a buffer) and the buffer holds exactly the clean files.  Returns
         (list of bytes, or None where the status is not 0; statuses)."""
+        return self._measured_files(lib().znippy_archive_bunzip2_files, "bunzip2_files", paths, cap)
+
+    def unxz_files(self, paths, cap=None):
+        """The whole content of every archived xz file of `paths` (.xz, .tar.xz, .txz), all streams concatenated, decoded on the
+        device in one batch: the files are gathered there whole, a measuring pass reads the sizes their indexes claim, then every
+        block of every file is decoded in one launch, a wave per block, and CRC32 and CRC64 checks are verified (blocks with no
+        check or SHA-256 are delivered unverified).  cap: as in bunzip2_files.  Returns (list of bytes, or None where the status
+        is not 0; statuses)."""
+        return self._measured_files(lib().znippy_archive_unxz_files, "unxz_files", paths, cap)
+
+    def _measured_files(self, call, what, paths, cap):
         paths = [str(p) for p in paths]
         n = len(paths)
         arr = (C.c_char_p * n)(*[p.encode() for p in paths])
         off = np.zeros(n + 1, dtype=np.uint64)
         st = np.zeros(max(n, 1), dtype=np.int32)
         if cap is None:
-            _chk(lib().znippy_archive_bunzip2_files(self.h, arr, n, None, 0, off.ctypes.data_as(vp), st.ctypes.data_as(vp)), "bunzip2_files")
+            _chk(call(self.h, arr, n, None, 0, off.ctypes.data_as(vp), st.ctypes.data_as(vp)), what)
             cap = int(off[n])
         room = int(cap)
         buf = np.empty(max(room, 1), dtype=np.uint8)
-        _chk(lib().znippy_archive_bunzip2_files(self.h, arr, n, buf.ctypes.data_as(vp), room, off.ctypes.data_as(vp),
-                                                st.ctypes.data_as(vp)), "bunzip2_files")
+        _chk(call(self.h, arr, n, buf.ctypes.data_as(vp), room, off.ctypes.data_as(vp), st.ctypes.data_as(vp)), what)
         out = [buf[int(off[i]):int(off[i + 1])].tobytes() if st[i] == 0 else None for i in range(n)]
         return out, [int(v) for v in st[:n]]
 
     def list_tar_members(self, paths, suffix=b"", prefix=b"", contents=False, cap=None):
-        """Every regular member of the tar in every archived file of `paths` (.tar, .tar.gz / .tgz / .crate, .tar.bz2) whose name starts
+        """Every regular member of the tar in every archived file of `paths` (.tar, .tar.gz / .tgz / .crate, .tar.bz2, .tar.xz / .txz) whose name starts
         with `prefix` and ends with `suffix` (bytes without NUL; empty = all), listed on the device in one batch: the files are gathered
-        there whole, gzip and bzip2 files are decompressed there (chosen by their first bytes), and one znippy_tar_list_batch walks all
+        there whole, gzip, bzip2 and xz files are decompressed there (chosen by their first bytes), and one znippy_tar_list_batch walks all
         the tars.  contents: the members' bytes come back as well.  cap: bytes of the buffer for the contents.  None: the tars are
         measured first (a call without buffers) and the buffers hold exactly what is listed.  Returns, per file,
         (status, [(name, size, bytes | None), ...]); a file whose status is not 0 lists nothing."""
