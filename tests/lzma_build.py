@@ -94,6 +94,13 @@ class Writer:
         self.states = []          # the LZMA state in front of every operation
         self.lit_states = set()   # and in front of the literals
         self.carry_run = 0
+        # bookkeeping for coverage conditions (tests/test_lzma_random_cpu.py): what the operations coded so far have reached
+        self.op_states = set()    # (kind: lit, match, rep0..rep3, shortrep; the state in front of it)
+        self.len_ps = set()       # ("match" or "rep", length class 0 / 1 / 2, pos-state, pb)
+        self.slots = set()        # distance slots
+        self.aligns = set()       # the four align bits of the distances of slot 14 and above
+        self.matched_lits = set() # literals coded in matched mode: "eq" (the match byte itself) or the highest bit in which they differ from it
+        self.chunks = []          # (control: 0xE0 / 0xC0 / 0xA0 / 0x80 / 1 / 2, content offset, offset of the dictionary's start, lc, lp, pb)
         self.reset_state()
 
     def reset_state(self):
@@ -103,6 +110,7 @@ class Writer:
 
     def _len(self, rc, base, ps, length):
         v = length - 2
+        self.len_ps.add(("match" if base == P_LEN else "rep", min(v >> 3, 2), ps, self.pb))
         if v < 8:
             rc.bit(self.probs, base + LEN_CHOICE, 0)
             rc.tree(self.probs, base + LEN_LOW + ps * 8, 3, v)
@@ -125,6 +133,7 @@ class Writer:
         P, st = self.probs, self.state
         ps = len(self.hist) & ((1 << self.pb) - 1)
         self.states.append(st)
+        self.op_states.add((op[0] + str(op[1]) if op[0] == "rep" else op[0], st))
         if op[0] == "lit":
             self.lit_states.add(st)
             byte = op[1]
@@ -139,6 +148,7 @@ class Writer:
                     sym = sym << 1 | b
             else:
                 m = self.hist[-self.reps[0] - 1] if self.reps[0] < len(self.hist) else 0
+                self.matched_lits.add((m ^ byte).bit_length() - 1 if m != byte else "eq")
                 offs = 0x100
                 for i in reversed(range(8)):
                     m <<= 1
@@ -157,6 +167,10 @@ class Writer:
             rc.bit(P, P_IS_REP + st, 0)
             self._len(rc, P_LEN, ps, length)
             slot = dist_slot(d)
+            if op[0] == "match":
+                self.slots.add(slot)
+                if slot >= 14:
+                    self.aligns.add(d & 15)
             rc.tree(P, P_SLOT + (min(length - 2, 3) << 6), 6, slot)
             if slot >= 4:
                 nd = (slot >> 1) - 1
@@ -203,6 +217,7 @@ class Writer:
             self.reset_state()
         rc = RangeEncoder()
         start = len(self.content)
+        self.chunks.append((control & 0xE0, start, start - len(self.hist), self.lc, self.lp, self.pb))
         for op in ops:
             self._op(rc, op)
         rc.flush()
@@ -221,6 +236,7 @@ class Writer:
         assert 1 <= len(data) <= 1 << 16
         if reset_dict:
             self.hist = bytearray()
+        self.chunks.append((1 if reset_dict else 2, len(self.content), len(self.content) - len(self.hist), self.lc, self.lp, self.pb))
         self.raw += bytes([1 if reset_dict else 2]) + struct.pack(">H", len(data) - 1) + data
         self.hist += data
         self.content += data

@@ -15,6 +15,7 @@ FILLS = (0x00, 0xA5, 0xFF)
 @pytest.fixture(scope="module")
 def batches():
     valid = [(c[1], c[2]) for c in K.small_shapes()] + [(c[1], c[2]) for c in K.containers()] + [(c[1], c[2]) for c in K.scripted()]
+    valid += [K.literal_runs()[:2]] + [(c[1], c[2]) for c in K.window_edges()]
     cases, good, content = K.damaged()
     status = [good] + [c[1] for c in cases] + [good]
     return [v[0] for v in valid], [len(v[1]) for v in valid], [v[1] for v in valid], status, len(content) + 8

@@ -105,3 +105,67 @@ def test_damaged_cases_are_refused():
 def test_mutant_base():
     f, content = K.mutant_base()
     assert 250 <= len(f) <= 400 and lzma.decompress(f) == content and len(K.mutants()) == 8 * len(f)
+
+
+# ---- the deterministic sweeps -------------------------------------------------------------------------------------------------------
+
+def test_match_geometry_sweep():
+    cases = K.match_geometry()
+    assert [c[0] for c in cases] == ["lc 3", "lc 4"]
+    for name, f, content, blocks in cases:
+        assert lzma.decompress(f) == content, name
+        assert blocks == sum(len(K.match_lengths(d)) for d in K.MATCH_DISTANCES) >= 23 * 8
+    assert K.match_lengths(1) == [2, 3, 258, 259, 272, 273] and K.match_lengths(64) == [2, 3, 63, 64, 65, 127, 128, 129, 258, 259, 272, 273]
+    assert K.match_lengths(274) == [2, 3, 258, 259, 272, 273] and K.match_lengths(200)[2:5] == [199, 200, 201]
+
+
+def test_literal_run_sweep():
+    f, content, cases = K.literal_runs()
+    assert lzma.decompress(f) == content
+    assert set(cases) == {(k, how) for k in K.LITERAL_RUNS for how in K.RUN_FOLLOWERS} - {(0, "b")}
+    assert {62, 63, 64, 65, 127, 128, 129} <= set(K.LITERAL_RUNS)
+
+
+def test_window_edge_sweep():
+    """every case puts what it names where it says, by the model of the decoder's input window"""
+    cases = K.window_edges()
+    for name, f, content, block, what, at, want in cases:
+        assert lzma.decompress(f) == content, name
+        offs = K.window_offsets(block)
+        assert offs[at] == want, (name, offs[at], want)
+        raw_at = len(block.header)
+        if what == "control":   # the header, the property byte and the five start bytes follow the control byte
+            c, _, off, n = X.chunks_of(block.raw)[1]
+            assert c == 0xC0 and raw_at + off == at and [offs[at + i] for i in range(11)] == [(want + i) % 256 for i in range(11)]
+        elif what == "last":
+            c, _, off, n = X.chunks_of(block.raw)[1]
+            assert raw_at + off + n - 1 == at and block.raw[at - raw_at + 1] == 0
+        else:
+            assert len(block.check_bytes) == 8 and [offs[at + i] for i in range(8)] == [(want + i) % 256 for i in range(8)]
+    got = {(what, want) for _, _, _, _, what, _, want in cases}
+    assert got >= {("control", r) for r in range(245, 256)} | {("control", 0)} | {("last", r) for r in (255, 0, 1)}
+    assert got >= {("check", r % 256) for r in range(248, 257)}
+    assert cases[-1][4:] == ("check", cases[-1][5], 248)     # the last item's block ends where the window does
+
+
+def test_check_length_sweep():
+    for name, f, content in K.check_lengths():
+        assert lzma.decompress(f) == content and len(content) == sum(K.CHECK_LENGTHS), name
+    assert set(range(521)) | {65535, 65536, 65537} == set(K.CHECK_LENGTHS)
+    damage = K.check_damage()
+    assert len(damage) == 2 * (1 + 4 * 3) + 5 * (4 + 8)
+    for name, f, room in damage:
+        assert arbiter(f) is None, name
+
+
+def test_mutants_without_a_check():
+    """liblzma's verdict on every single-bit mutant of the LZMA2 bytes of a file without a check: the GPU test asks for the same"""
+    f, content, at, n = K.nocheck_base()
+    assert 120 <= len(f) <= 180 and lzma.decompress(f) == content and f[at + n - 1] == 0 and f[at] == 0xE0
+    kinds = [c[0] for c in X.chunks_of(f[at:at + n])]
+    assert kinds == [0xE0, 2, 0x80, 0]
+    mutants = K.nocheck_mutants()
+    verdicts = [arbiter(m) for m in mutants]
+    accepted = [v for v in verdicts if v is not None]
+    assert len(mutants) == 8 * n and 10 <= len(accepted) < len(mutants) / 5, (len(mutants), len(accepted))
+    assert all(len(v) == len(content) for v in accepted)

@@ -257,3 +257,220 @@ def mutant_base():
 def mutants():
     f, _ = mutant_base()
     return [f[:i // 8] + bytes([f[i // 8] ^ (1 << (i % 8))]) + f[i // 8 + 1:] for i in range(8 * len(f))]
+
+
+# ---- deterministic sweeps: every case a small block of its own ---------------------------------------------------------------------
+
+MATCH_DISTANCES = (1, 2, 3, 4, 5, 7, 8, 15, 16, 17, 31, 32, 33, 63, 64, 65, 127, 128, 129, 200, 272, 273, 274)
+LITERAL_RUNS = (0, 1, 62, 63, 64, 65, 66, 126, 127, 128, 129, 130, 191, 192, 193)
+RUN_FOLLOWERS = ("a", "b", "c", "d", "e")
+
+
+def match_lengths(dist):
+    want = (2, 3, dist - 1, dist, dist + 1, 2 * dist - 1, 2 * dist, 2 * dist + 1, 258, 259, 272, 273)
+    return sorted({min(max(n, 2), 273) for n in want})
+
+
+def _blocks_file(writers, check=X.CHECK_CRC32, prop=PROP_1M):
+    outs = [w.out() for w in writers]
+    return X.stream([X.Block(content, check, raw=raw, prop=prop) for raw, content in outs], check), b"".join(c for _, c in outs)
+
+
+def _match_byte(w):
+    return w.hist[-w.reps[0] - 1]
+
+
+def _geometry_ops(w, rnd, lead, dist, length, bit):
+    """(a generator: the Writer draws one operation at a time, so w.hist holds the bytes produced so far)"""
+    for _ in range(lead):
+        yield ("lit", rnd.randrange(256))
+    yield ("match", dist, length)
+    yield ("lit", _match_byte(w))               # matched mode: the byte the match would go on with
+    yield ("rep", 0, length)
+    yield ("lit", _match_byte(w) ^ (1 << bit))  # matched mode: it leaves the match byte at `bit`
+    yield ("rep", 0, length)
+    yield ("shortrep",)
+    yield ("lit", rnd.randrange(256))
+
+
+@functools.lru_cache(None)
+def match_geometry():
+    """[(name, file, content, blocks)], once with lc = 3 and once with lc = 4 (lp = 0).  A block is random literals that cover the
+    distance, the match, the literal the match would go on with, the same distance and length again as a rep0, a literal that differs
+    from the match byte, the rep0 once more, a short rep and a literal behind it: four times the byte at rep0 and the last byte behind
+    an overlapping or plain copy decide which probabilities the next symbol takes."""
+    out = []
+    for lc in (3, 4):
+        rnd, writers = random.Random(lc), []
+        for dist in MATCH_DISTANCES:
+            for k, length in enumerate(match_lengths(dist)):
+                w = L.Writer(lc=lc, lp=0, pb=2)
+                writers.append(w.lzma(_geometry_ops(w, rnd, dist + k % 3, dist, length, (k + dist) % 8)))
+        f, content = _blocks_file(writers)
+        out.append((f"lc {lc}", f, content, len(writers)))
+    return out
+
+
+def _run_head(rnd, k):
+    """three literals and a match, which stores them, then the k literals"""
+    return [("lit", c) for c in b"xyz"] + [("match", 2, 3)] + [("lit", rnd.randrange(256)) for _ in range(k)]
+
+
+def _matched_lit(w, flip):
+    yield ("lit", _match_byte(w) ^ flip)
+    yield ("shortrep",)
+    yield ("lit", _match_byte(w))
+    yield ("lit", 0x2E)
+
+
+@functools.lru_cache(None)
+def literal_runs():
+    """(file, content, [(k, follower)]): k literals behind the last store of the 64-literal buffer, followed by
+    a  a match of distance 1;
+    b  a match of distance k, whose source are the literals themselves (k > 0);
+    c  the chunk's end and a 0x80 chunk that opens with a match of distance k (1 for k = 0);
+    d  the chunk's end, a 0x02 chunk and a 0x80 chunk that opens with a literal — in matched mode for k = 0, the only run that leaves
+       the state at 7 or above —, a short rep and a literal that is in matched mode for every k;
+    e  a match of distance k (1 for k = 0) and the chunk's end, a 0x02 chunk and a 0x80 chunk that opens with a matched-mode literal."""
+    rnd, writers, cases = random.Random(64), [], []
+    for k in LITERAL_RUNS:
+        for how in RUN_FOLLOWERS:
+            w, head, d = L.Writer(), _run_head(rnd, k), max(k, 1)
+            if how == "a":
+                w.lzma(head + [("match", 1, 5), ("lit", 0x41)])
+            elif how == "b":
+                if k == 0:
+                    continue
+                w.lzma(head + [("match", k, min(k + 2, 273)), ("lit", 0x42)])
+            elif how == "c":
+                w.lzma(head).lzma([("match", d, 4), ("lit", 0x43)], control=0x80)
+            elif how == "d":
+                w.lzma(head).stored(b"-0123-", False).lzma(_matched_lit(w, 0x10), control=0x80)
+            else:
+                w.lzma(head + [("match", d, 3)]).stored(b"-4567-", False).lzma(_matched_lit(w, 1 << k % 8), control=0x80)
+            writers.append(w)
+            cases.append((k, how))
+    f, content = _blocks_file(writers)
+    return f, content, cases
+
+
+def window_offsets(block):
+    """A model of the decoder's 256-byte input window (unxz.hip, XzIn): {offset in the block: offset in the window when that byte is
+    read}.  The window is loaded at the block's start and again whenever a byte 256 or more past its base is asked for; the bytes of
+    an uncompressed chunk are copied, not read, so a long one moves the base to the control byte behind it."""
+    reads, at = [], len(block.header)
+    for c, _, off, n in X.chunks_of(block.raw):
+        reads += range(at + off, at + off + (3 if c in (1, 2) else n))
+    end = at + len(block.raw)
+    reads += range(end, end + len(block.padding) + min(8, len(block.check_bytes)))
+    out, base = {}, 0
+    for q in reads:
+        if q - base >= 256:
+            base = q
+        out[q] = q - base
+    return out
+
+
+def _edge_block(n_lead, n_lits, check):
+    """an uncompressed chunk of n_lead bytes (its last byte is fixed, so the LZMA chunk behind it does not depend on n_lead), then
+    an LZMA chunk with properties: n_lits random literals and a match"""
+    lead = random.Random(n_lead).randbytes(n_lead - 1) + b"\x55"
+    rnd = random.Random(7)
+    w = L.Writer().stored(lead, True).lzma([("lit", rnd.randrange(256)) for _ in range(n_lits)] + [("match", 3, 4)], control=0xC0)
+    raw, content = w.out()
+    return X.Block(content, check, raw=raw, prop=PROP_1M)
+
+
+@functools.lru_cache(None)
+def window_edges():
+    """[(name, file, content, block, what, block offset of it, offset in the window it is meant to have)].  The control byte of an
+    LZMA chunk at window offsets 245..260, so that the header, the property byte and the five bytes that start the range coder each
+    lie across a reload; a chunk's last byte at 255, 0 and 1; the eight bytes of a CRC64 at 248..256 (248: the field, and with it
+    the block, ends exactly where the window does — the last item)."""
+    out = []
+
+    def add(name, b, check, what, at, want):
+        out.append((name, X.stream([b], check), b.content, b, what, at, want))
+
+    for r in range(245, 261):
+        b = _edge_block(r - 15, 20, X.CHECK_CRC32)       # 12 bytes of block header, 3 of the uncompressed chunk's
+        add(f"control byte at {r}", b, X.CHECK_CRC32, "control", r, r if r < 256 else 0)   # (beyond 256 the uncompressed chunk moves the base there)
+    for r in (255, 0, 1):
+        size = len(_edge_block(1, 300, X.CHECK_CRC32).raw) - 1 - 4        # the LZMA chunk with its header
+        n = (r - (15 + size - 1)) % 256 or 256
+        assert n <= 240, n                                               # (no jump: the bases stay multiples of 256)
+        b = _edge_block(n, 300, X.CHECK_CRC32)
+        add(f"last byte of a chunk at {r}", b, X.CHECK_CRC32, "last", 15 + n + size - 1, r)
+    for r in (256, 255, 254, 253, 252, 251, 250, 249, 248):
+        for n_lits in range(190, 300):
+            size = len(_edge_block(1, n_lits, X.CHECK_CRC64).raw) - 4
+            fits = [n for n in range(256, 260) if (-(-(15 + n + size) // 4) * 4 - (15 + n)) % 256 == r % 256]
+            if fits:
+                break
+        b = _edge_block(fits[0], n_lits, X.CHECK_CRC64)
+        add(f"check field at {r}", b, X.CHECK_CRC64, "check", len(b.header) + len(b.raw) + len(b.padding), r % 256)
+    return out
+
+
+def stored_raw(data):
+    """`data` as uncompressed LZMA2 chunks, the end byte included"""
+    out = b""
+    for at in range(0, len(data), 65536):
+        part = data[at:at + 65536]
+        out += bytes([2 if at else 1, (len(part) - 1) >> 8, (len(part) - 1) & 255]) + part
+    return out + b"\x00"
+
+
+CHECK_LENGTHS = tuple(range(521)) + (65535, 65536, 65537)
+CHECK_DAMAGE_LENGTHS = (1, 255, 256, 257, 513)
+
+
+@functools.lru_cache(None)
+def check_lengths():
+    """[(name, file, content)]: a block of uncompressed chunks for every content length of CHECK_LENGTHS, once under CRC32 and once
+    under CRC64: the check kernel cuts a block into 256 segments, most of them empty below 256 bytes"""
+    rnd, out = random.Random(256), []
+    parts = [rnd.randbytes(n) for n in CHECK_LENGTHS]
+    for check, name in ((X.CHECK_CRC32, "CRC32"), (X.CHECK_CRC64, "CRC64")):
+        out.append((name, X.stream([X.Block(p, check, raw=stored_raw(p), prop=0) for p in parts], check), b"".join(parts)))
+    return out
+
+
+@functools.lru_cache(None)
+def check_damage():
+    """[(name, file, room)]: blocks of CHECK_DAMAGE_LENGTHS bytes whose check no longer fits: one content byte flipped at the first,
+    the middle and the last position with the check field kept, and one bit flipped in each byte of the check field"""
+    rnd, out = random.Random(257), []
+    for check, name in ((X.CHECK_CRC32, "CRC32"), (X.CHECK_CRC64, "CRC64")):
+        for n in CHECK_DAMAGE_LENGTHS:
+            p = rnd.randbytes(n)
+            field = X.check_field(check, p)
+            for at in sorted({0, n // 2, n - 1}):
+                q = p[:at] + bytes([p[at] ^ 0xFF]) + p[at + 1:]
+                out.append((f"{name}, {n} bytes, content byte {at}", X.stream([X.Block(q, check, raw=stored_raw(q), prop=0, check_bytes=field)], check), n))
+            for at in range(len(field)):
+                bad = field[:at] + bytes([field[at] ^ (1 << (at + n) % 8)]) + field[at + 1:]
+                out.append((f"{name}, {n} bytes, check byte {at}", X.stream([X.Block(p, check, raw=stored_raw(p), prop=0, check_bytes=bad)], check), n))
+    return out
+
+
+# ---- mutants of a file without a check: the verdict is the decoder's alone ----------------------------------------------------------
+
+@functools.lru_cache(None)
+def nocheck_base():
+    """(file, content, offset of the LZMA2 bytes in the file, their count): every kind of operation, and a 0x02 chunk between two
+    LZMA chunks"""
+    lits = lambda s: [("lit", c) for c in s]
+    w = L.Writer()
+    w.lzma(lits(b"The quick brown fox ") + [("match", 4, 3), ("match", 11, 5), ("match", 2, 2), ("match", 17, 9)] + lits(b"jumps") +
+           [("rep", 0, 4), ("shortrep",), ("lit", 0x6F), ("rep", 1, 3), ("rep", 2, 12), ("rep", 3, 2)] + lits(b" over"))
+    w.stored(b"the lazy", False)
+    w.lzma(lits(b" dog") + [("rep", 1, 5), ("shortrep",), ("match", 30, 20), ("lit", 0x2E), ("rep", 3, 6), ("rep", 2, 3), ("lit", 0x0A)], control=0x80)
+    f, content = scripted_file(w, check=X.CHECK_NONE)
+    raw = w.out()[0]
+    return f, content, f.index(raw), len(raw)
+
+
+def nocheck_mutants():
+    f, _, at, n = nocheck_base()
+    return [f[:i // 8] + bytes([f[i // 8] ^ (1 << (i % 8))]) + f[i // 8 + 1:] for i in range(8 * at, 8 * (at + n))]
